@@ -13,9 +13,13 @@ per GPU, rendezvous on 127.0.0.1 and a free port); under `python -m torch.distri
 --gpus N` the ranks come from the environment.  `--scaling strong` shards the SAME 64-sentence batch (64/N rows per
 rank, SURVEY 8e parity mode) instead of giving every rank its own 64 sentences.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-timed live with HIP events on the launch stream) and `cpu_baseline` (the reference step's operator sequence on
-PyTorch-CPU operators, oracle/torch_cpu_step.py, timed on this host's cores, rank 0 / N=1 only).
+Prints ONE JSON line on rank 0: `metric`, `value` (sentences/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one
+timed step), the workload in `config`, `final_loss`.  A plain run does nothing else: set-up, `--warmup` steps, `--steps` timed
+steps, the line.  `--full` adds what takes work of its own: `roofline` (dominant kernel, timed live with HIP events on the launch
+stream over extra instrumented steps), `box` (clocks and power during the timed region), the host API / slow-host probes and
+comparison processes (`process_runs`), `secondary` (BASELINE configs[2..4], tools/bench_secondary.py) and `cpu_baseline` (the
+reference step's operator sequence on PyTorch-CPU operators, oracle/torch_cpu_step.py, timed on this host's cores, rank 0 / N=1
+only).  `--dump-outputs DIR` writes what the last timed step returned and left behind (loss, gradient norm, parameters) as .npy.
 """
 import argparse
 import json
@@ -210,6 +214,23 @@ class BoxSampler:
         return dict(pci=self.bus, sysfs_card_found=self.matched, sclk_mhz_p50=med(0), mclk_mhz_p50=med(1), board_w_p50=med(2), samples=len(self.rows))
 
 
+DUMP_SAMPLE = 1 << 16     # elements kept of a larger parameter: 45 day layers + 10 GRU matrices -> ~15 MB in all
+
+
+def dump_outputs(out_dir, loss, gnorm, model):
+    """--dump-outputs: what the last timed step handed its caller -- the mean loss, the pre-clip gradient norm -- and the parameters
+    AdamW left, as float32 DIR/<name>.npy.  A parameter of more than DUMP_SAMPLE elements is stored as a fixed sample of its flat
+    elements (the same seeded indices in every run), so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(float(loss), dtype=np.float32))
+    np.save(os.path.join(out_dir, "grad_norm.npy"), np.asarray(float(gnorm), dtype=np.float32))
+    for name, p in model.named_parameters():
+        v = p.detach().reshape(-1).to(torch.float32).cpu().numpy()
+        if v.size > DUMP_SAMPLE:
+            v = v[np.sort(np.random.RandomState(0).choice(v.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, f"param.{name}.npy"), v)
+
+
 def free_port():
     import socket
     with socket.socket() as s_:
@@ -286,10 +307,13 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--gru-mode", type=int, default=int(os.environ.get("B2T_GRU_MODE", "-1")))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline, box clocks, host probes and comparison processes, secondary, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing check without a GPU (tests): gloo rendezvous, argument handling, max-over-ranks; measures nothing")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2..4] numbers reported under `secondary`")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the configs[2..4] numbers reported under `secondary`")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: 64 sentences per rank (default); strong: the same 64-sentence batch split 64/N rows per rank")
     a = ap.parse_args()
@@ -355,7 +379,8 @@ def main():
         for i in range(a.warmup):
             step(i)
         fence()
-        TrainStep.HOST_T["on"] = True; TrainStep.HOST_T["acc"] = {}     # host time per segment of the step, over the timed steps only
+        if a.full:
+            TrainStep.HOST_T["on"] = True; TrainStep.HOST_T["acc"] = {}     # host time per segment of the step, over the timed steps only
         t0 = time.perf_counter()
         for i in range(a.steps):
             loss, gn = step(a.warmup + i)
@@ -365,13 +390,13 @@ def main():
         dt = time.perf_counter() - t0
         ts.check_status()          # a hand-off timeout inside a persistent sweep would invalidate the run (raises)
         model._ws.check_sync()
-        return loss, dt, t_enq
+        return loss, gn, dt, t_enq
 
     if ts.reducer is not None and os.environ.get("B2T_DP_DEFERRED", "0") == "1":
         ts.reducer.deferred = True                 # measurement knob: all-reduce behind the backward pass (the post-refusal fallback)
-    sampler = BoxSampler(dev) if (world == 1 and os.environ.get("B2T_BENCH_NO_SAMPLER") != "1") else None
+    sampler = BoxSampler(dev) if (a.full and world == 1 and os.environ.get("B2T_BENCH_NO_SAMPLER") != "1") else None
     host_api = None                                               # this process's runtime-call latencies (slow-host mode signature)
-    if world == 1 and os.environ.get("B2T_BENCH_NO_PROBE") != "1":
+    if a.full and world == 1 and os.environ.get("B2T_BENCH_NO_PROBE") != "1":
         try:
             host_api = ops.host_api_probe()
         except Exception as e:      # noqa: BLE001 -- a diagnostic must never take the bench line down
@@ -379,7 +404,7 @@ def main():
     try:
         if sampler:
             sampler.start()
-        loss, dt, t_enq = timed_run()
+        loss, gn, dt, t_enq = timed_run()
     except RuntimeError as e:
         # The pipelined plan keeps several persistent sweeps in flight; if one of them ever reports a hand-off
         # timeout the measurement is discarded and repeated with the layers strictly in sequence (no side streams)
@@ -393,17 +418,20 @@ def main():
             if buf.dtype == torch.int32:
                 buf.zero_()
         ts.stat.zero_()
-        loss, dt, t_enq = timed_run()
+        loss, gn, dt, t_enq = timed_run()
     box = sampler.stop() if sampler else None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, gn, model)
     # A process on this pool sometimes comes up in a mode in which every HIP call is 2.5-3x slower for the whole life of the
     # process (NOTES.md 5 / R5: host enqueue 4-7 ms per step instead of 1.1-2.2, the GPU then waits on the plan's cross-queue hops
     # and the step is 1-2 ms slower).  The HEADLINE (`value`, `ms_per_step`) is always the FIRST process's measurement; a one-GPU
     # run that finds itself in the slow mode additionally starts over, at most twice, so that the line can show what other
     # processes on the same box measure: every process run is listed in `process_runs`, the fastest one in `best_process_ms`
-    # -- beside the headline, never instead of it (B2T_BENCH_NO_RESTART=1: never start over).
-    # (the chain of processes is one pid -- execv keeps it --: a CHILD process that inherits these variables, e.g. a secondary run
-    #  spawned by a re-started parent, starts its own chain)
-    chained = os.environ.get("B2T_BENCH_CHAIN") == str(os.getpid())
+    # -- beside the headline, never instead of it (B2T_BENCH_NO_RESTART=1: never start over).  --full only.
+    # (each further process is a fresh child of the one before, which waits for it and exits with its status; B2T_BENCH_CHAIN names
+    #  the parent's pid: a process further down that inherits these variables, e.g. a secondary run spawned by a re-started child,
+    #  starts its own chain)
+    chained = os.environ.get("B2T_BENCH_CHAIN") == str(os.getppid())
     restarts = int(os.environ.get("B2T_BENCH_RESTARTS", "0")) if chained else 0
     slow_ms = float(os.environ.get("B2T_BENCH_SLOW_ENQ_MS", "3.0"))
     runs = json.loads(os.environ.get("B2T_BENCH_PROCESS_RUNS", "[]")) if chained else []
@@ -414,22 +442,23 @@ def main():
     # Round 6: a process that finds itself slow measures the cross-queue hop and its own scheduling state IN this process (the
     # driver's bench lease is where the mode shows up reliably); the result rides in `config`, which the driver's parser keeps.
     slow_probe = json.loads(os.environ.get("B2T_BENCH_SLOW_PROBE", "null")) if chained else None
-    if world == 1 and not force_dp and (t_enq / a.steps * 1e3 > slow_ms or os.environ.get("B2T_BENCH_FORCE_SLOW_PROBE") == "1") and slow_probe is None:
+    if (a.full and world == 1 and not force_dp and (t_enq / a.steps * 1e3 > slow_ms or os.environ.get("B2T_BENCH_FORCE_SLOW_PROBE") == "1")
+            and slow_probe is None):
         try:
             slow_probe = ops.slow_mode_probe()
             slow_probe["in_process"] = restarts + 1
             os.environ["B2T_BENCH_SLOW_PROBE"] = json.dumps(slow_probe)
         except Exception as e:      # noqa: BLE001 -- a diagnostic must never take the bench line down
             slow_probe = dict(error=f"{type(e).__name__}: {e}")
-    if (world == 1 and not force_dp and t_enq / a.steps * 1e3 > slow_ms and restarts < 2
+    if (a.full and world == 1 and not force_dp and t_enq / a.steps * 1e3 > slow_ms and restarts < 2
             and os.environ.get("B2T_BENCH_NO_RESTART") is None):
-        os.environ["B2T_BENCH_PROCESS_RUNS"] = json.dumps(runs)
-        os.environ["B2T_BENCH_RESTARTS"] = str(restarts + 1)
-        os.environ["B2T_BENCH_CHAIN"] = str(os.getpid())
+        import subprocess
+        env = dict(os.environ, B2T_BENCH_PROCESS_RUNS=json.dumps(runs), B2T_BENCH_RESTARTS=str(restarts + 1), B2T_BENCH_CHAIN=str(os.getpid()))
         sys.stderr.write(f"[bench] slow-process mode (host enqueue {t_enq / a.steps * 1e3:.2f} ms per step, {dt / a.steps * 1e3:.3f} ms per step): one more "
                          f"process for comparison ({restarts + 1} of 2); the headline stays the first process's\n")
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, [sys.executable] + sys.argv)
+        rc = subprocess.run([sys.executable] + sys.argv, env=env).returncode
+        sys.exit(rc if rc >= 0 else 128 - rc)
     if box is not None:
         box["process_restarts"] = restarts
         box["host_api_us"] = host_api
@@ -445,77 +474,80 @@ def main():
     lossv = float(loss)
     assert np.isfinite(lossv), "non-finite loss in the bench step"
 
-    # ---- live per-kernel timing (HIP events on the launch stream) over 4 extra instrumented steps ----
-    # (GEMMs and sweeps are bracketed by the C++ executor on the streams it launches them on, b2t_exec_profile; the
-    # augmentation and CTC kernels by ops._Prof on torch's current stream, which is the stream they are launched on)
-    prof = ops.PROFILE
-    prof["on"] = True; prof["ev"] = []
-    model._ws.profile(True)
-    NPROF = 4
-    for i in range(NPROF):
-        step(a.warmup + a.steps + i)
-    torch.cuda.synchronize()
-    prof["on"] = False
-    recs = model._ws.profile_read()
-    model._ws.profile(False)
-    recs += [(name, flops, nlaunch, e0.elapsed_time(e1) * 1e-3) for name, flops, nlaunch, e0, e1 in prof["ev"]]
-    agg = {}
-    for name, flops, nlaunch, t in recs:
-        r = agg.setdefault(name, [0.0, 0.0, 0])
-        r[0] += t; r[1] += flops; r[2] += nlaunch
-    dom = max(agg.items(), key=lambda kv: kv[1][0])
-    dname, (dtime, dflops, dlaunch) = dom
-    achieved = dflops / dtime if dtime > 0 else 0.0
-    # `traffic`: memory-side bytes per launch of the dominant kernel from the committed rocprofv3 --pmc passes
-    # (profiles/pmc_latest.json; PMC cannot be collected from inside this process).  Only valid for the plan it was
-    # measured on (same number of time chunks), else null.
-    traffic, traffic_src = None, None
-    try:
-        with open(os.path.join(ROOT, "profiles", "pmc_latest.json")) as f:
-            pmc = json.load(f)
-        if dname in pmc and pmc.get("time_chunks") == ops.PIPELINE["chunks"] and pmc.get("time_chunks_bwd") == ops.PIPELINE["chunks_bwd"]:
-            traffic, traffic_src = round(pmc[dname]["bytes_per_launch"] / 1e9, 4), pmc["source"]
-    except OSError:
-        pass
-    ms_this = dt_this / a.steps * 1e3                  # the process the per-kernel timings below were taken in
-    roofline = dict(bound="mfma", kernel=dname, achieved=round(achieved / 1e12, 3), peak=round(PEAK_F32_MFMA / 1e12, 1),
-                    unit="TFLOP/s", frac=round(achieved / PEAK_F32_MFMA, 4), traffic=traffic, traffic_unit="GB/launch",
-                    traffic_source=traffic_src,
-                    avg_launch_us=round(dtime / max(1, dlaunch) * 1e6, 2), launches_per_step=dlaunch // NPROF,
-                    summed_stream_time_over_step=round(dtime / NPROF / (ms_this * 1e-3), 3),   # >1: launches overlap on side streams
-                    step_flops_frac=round(FLOPS_PER_STEP * rows / B / (ms * 1e-3) / PEAK_F32_MFMA, 4),   # per GPU
-                    step_hbm_frac=round(ALG_BYTES_PER_STEP * rows / B / (ms * 1e-3) / PEAK_HBM, 4),
-                    breakdown_ms={k: round(v[0] / NPROF * 1e3, 3) for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0])})
+    roofline = None
+    if a.full:
+        # ---- live per-kernel timing (HIP events on the launch stream) over 4 extra instrumented steps ----
+        # (GEMMs and sweeps are bracketed by the C++ executor on the streams it launches them on, b2t_exec_profile; the
+        # augmentation and CTC kernels by ops._Prof on torch's current stream, which is the stream they are launched on)
+        prof = ops.PROFILE
+        prof["on"] = True; prof["ev"] = []
+        model._ws.profile(True)
+        NPROF = 4
+        for i in range(NPROF):
+            step(a.warmup + a.steps + i)
+        torch.cuda.synchronize()
+        prof["on"] = False
+        recs = model._ws.profile_read()
+        model._ws.profile(False)
+        recs += [(name, flops, nlaunch, e0.elapsed_time(e1) * 1e-3) for name, flops, nlaunch, e0, e1 in prof["ev"]]
+        agg = {}
+        for name, flops, nlaunch, t in recs:
+            r = agg.setdefault(name, [0.0, 0.0, 0])
+            r[0] += t; r[1] += flops; r[2] += nlaunch
+        dom = max(agg.items(), key=lambda kv: kv[1][0])
+        dname, (dtime, dflops, dlaunch) = dom
+        achieved = dflops / dtime if dtime > 0 else 0.0
+        # `traffic`: memory-side bytes per launch of the dominant kernel from the committed rocprofv3 --pmc passes
+        # (profiles/pmc_latest.json; PMC cannot be collected from inside this process).  Only valid for the plan it was
+        # measured on (same number of time chunks), else null.
+        traffic, traffic_src = None, None
+        try:
+            with open(os.path.join(ROOT, "profiles", "pmc_latest.json")) as f:
+                pmc = json.load(f)
+            if dname in pmc and pmc.get("time_chunks") == ops.PIPELINE["chunks"] and pmc.get("time_chunks_bwd") == ops.PIPELINE["chunks_bwd"]:
+                traffic, traffic_src = round(pmc[dname]["bytes_per_launch"] / 1e9, 4), pmc["source"]
+        except OSError:
+            pass
+        ms_this = dt_this / a.steps * 1e3                  # the process the per-kernel timings below were taken in
+        roofline = dict(bound="mfma", kernel=dname, achieved=round(achieved / 1e12, 3), peak=round(PEAK_F32_MFMA / 1e12, 1),
+                        unit="TFLOP/s", frac=round(achieved / PEAK_F32_MFMA, 4), traffic=traffic, traffic_unit="GB/launch",
+                        traffic_source=traffic_src,
+                        avg_launch_us=round(dtime / max(1, dlaunch) * 1e6, 2), launches_per_step=dlaunch // NPROF,
+                        summed_stream_time_over_step=round(dtime / NPROF / (ms_this * 1e-3), 3),   # >1: launches overlap on side streams
+                        step_flops_frac=round(FLOPS_PER_STEP * rows / B / (ms * 1e-3) / PEAK_F32_MFMA, 4),   # per GPU
+                        step_hbm_frac=round(ALG_BYTES_PER_STEP * rows / B / (ms * 1e-3) / PEAK_HBM, 4),
+                        breakdown_ms={k: round(v[0] / NPROF * 1e3, 3) for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0])})
 
     if rank == 0:
+        config = dict(workload="BASELINE.json configs[1]: 5-layer GRU-512 + CTC, synthetic [B=64,T=500,F=512] -> 41 "
+                               "phonemes, fp32, full training step incl. on-GPU augmentation, clip and AdamW",
+                      global_batch=rows * world, rows_per_rank=rows, seq_len=T, parallelism=f"dp{world}",
+                      world_size_seen=world_seen, collective=("RCCL all-reduce, bucketed, overlapped with backward"
+                                                              + (" (deferred after a refused step)" if getattr(ts.reducer, "deferred", False) else "")
+                                                              if ts.reducer is not None else None),
+                      gru_mode=ops.gru_mode_for(B, H), time_chunks=ops.PIPELINE["chunks"],
+                      time_chunks_bwd=ops.PIPELINE["chunks_bwd"] or ops.PIPELINE["chunks"],
+                      host_enqueue_ms_per_step=runs[0]["host_enqueue_ms_per_step"] if runs else round(t_enq / a.steps * 1e3, 3))
         out = dict(metric="GRU+CTC train sentences/sec", value=round(value, 2), unit="sentences/s", n_gpus=world,
                    steps=a.steps, warmup=a.warmup, ms_per_step=round(ms, 3), higher_is_better=True, scaling=a.scaling,
                    vs_baseline=None, dtype=("f32" if not ops.AMP["on"] else "bf16 matmul operands, f32 accumulate/sweeps (B2T_AMP)"), data="synthetic",
-                   config=dict(workload="BASELINE.json configs[1]: 5-layer GRU-512 + CTC, synthetic [B=64,T=500,F=512] -> 41 "
-                                        "phonemes, fp32, full training step incl. on-GPU augmentation, clip and AdamW",
-                               global_batch=rows * world, rows_per_rank=rows, seq_len=T, parallelism=f"dp{world}",
-                               world_size_seen=world_seen, collective=("RCCL all-reduce, bucketed, overlapped with backward"
-                                                                       + (" (deferred after a refused step)" if getattr(ts.reducer, "deferred", False) else "")
-                                                                       if ts.reducer is not None else None),
-                               gru_mode=ops.gru_mode_for(B, H), time_chunks=ops.PIPELINE["chunks"],
-                               time_chunks_bwd=ops.PIPELINE["chunks_bwd"] or ops.PIPELINE["chunks"],
-                               # (round 6: the driver's parser keeps `config`, `roofline`, `cpu_baseline` only -- the per-process evidence lives here)
-                               process_runs=runs, best_process_ms=min(r["ms_per_step"] for r in runs) if runs else round(ms, 3),
-                               host_enqueue_ms_per_step=runs[0]["host_enqueue_ms_per_step"] if runs else round(t_enq / a.steps * 1e3, 3),
-                               host_api_us=host_api, slow_mode_probe=slow_probe,
-                               # where the host's time per step goes (Python + ctypes + the executor's enqueue), timed steps only: a slow
-                               # process's extra 3-6 ms are NOT in the executor's runtime calls (NOTES.md R6.1) -- this says which segment holds them
-                               step_host_ms={k: round(v / max(1, a.steps) * 1e3, 3) for k, v in TrainStep.HOST_T["acc"].items()},
-                               dp_collective_call_host_ms_per_step=(round(ts.reducer.host_s / max(1, a.steps + a.warmup + 4) * 1e3, 3) if ts.reducer is not None else None),
-                               host=dict(loadavg=[round(v, 2) for v in os.getloadavg()], cores_usable=usable_cores(),
-                                         exec_host_delay_us=int(os.environ.get("B2T_EXEC_HOST_DELAY_US", "0")))),
-                   roofline=roofline, final_loss=round(lossv, 4),
-                   host_enqueue_ms_per_step=runs[0]["host_enqueue_ms_per_step"] if runs else round(t_enq / a.steps * 1e3, 3),
-                   process_runs=runs, best_process_ms=min(r["ms_per_step"] for r in runs) if runs else round(ms, 3),
-                   headline_is="the first process's measurement (later processes, started only when the first one came up in the "
-                               "slow-host mode, are listed in process_runs; roofline kernel timings are from the last process)", box=box)
+                   config=config, final_loss=round(lossv, 4),
+                   host_enqueue_ms_per_step=runs[0]["host_enqueue_ms_per_step"] if runs else round(t_enq / a.steps * 1e3, 3))
+        if a.full:
+            # (round 6: the driver's parser keeps `config`, `roofline`, `cpu_baseline` only -- the per-process evidence lives in `config`)
+            config.update(process_runs=runs, best_process_ms=min(r["ms_per_step"] for r in runs) if runs else round(ms, 3),
+                          host_api_us=host_api, slow_mode_probe=slow_probe,
+                          # where the host's time per step goes (Python + ctypes + the executor's enqueue), timed steps only: a slow
+                          # process's extra 3-6 ms are NOT in the executor's runtime calls (NOTES.md R6.1) -- this says which segment holds them
+                          step_host_ms={k: round(v / max(1, a.steps) * 1e3, 3) for k, v in TrainStep.HOST_T["acc"].items()},
+                          dp_collective_call_host_ms_per_step=(round(ts.reducer.host_s / max(1, a.steps + a.warmup + 4) * 1e3, 3) if ts.reducer is not None else None),
+                          host=dict(loadavg=[round(v, 2) for v in os.getloadavg()], cores_usable=usable_cores(),
+                                    exec_host_delay_us=int(os.environ.get("B2T_EXEC_HOST_DELAY_US", "0"))))
+            out.update(roofline=roofline, process_runs=runs, best_process_ms=min(r["ms_per_step"] for r in runs) if runs else round(ms, 3),
+                       headline_is="the first process's measurement (later processes, started only when the first one came up in the "
+                                   "slow-host mode, are listed in process_runs; roofline kernel timings are from the last process)", box=box)
         sys.stderr.write("[bench] headline done: " + json.dumps(out)[:200] + "\n"); sys.stderr.flush()
-        if world == 1 and not a.no_secondary:
+        if a.full and world == 1 and not a.no_secondary:
             # BASELINE configs[2..4] measured by the same process, reported beside (never instead of) the headline
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_secondary
@@ -524,7 +556,7 @@ def main():
             out["roofline"]["bf16"] = {k: dict(ms_per_step=v.get("ms_per_step"), sentences_per_s=v.get("sentences_per_s"), window_ms=v.get("window_ms"),
                                                **(v.get("roofline") or {}), **(v.get("sweeps") or {}))
                                        for k, v in out["secondary"].items() if k in ("c3_amp", "c2_amp", "trainer_loop_c3_amp") and isinstance(v, dict) and "ms_per_step" in v}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             sys.stderr.write("[bench] cpu baseline ...\n"); sys.stderr.flush()
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))

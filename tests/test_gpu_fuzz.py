@@ -89,7 +89,9 @@ def test_passes_replayed_as_graphs_follow_the_eager_plan():
     mode guarantees -- passes really are replayed, the trajectory follows the eager plan's to 1e-4 relative -- and PRINTS whether
     this process was bit-identical."""
     def probe(g):
-        env = dict(os.environ, B2T_EXEC_GRAPH=g)
+        # b2t_native only defaults GPU_MAX_HW_QUEUES to 16: an environment that already says 4 leaves the replayed graph's branches
+        # sharing hardware queues with the plan's, and a persistent sweep queued in front of the kernel it waits for times out
+        env = dict(os.environ, B2T_EXEC_GRAPH=g, GPU_MAX_HW_QUEUES="16")
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "r4_graph_probe.py"), "12"], capture_output=True, text=True, timeout=600, env=env)
         lines = [l for l in r.stdout.splitlines() if l.startswith("graph=")]
         return r.returncode, (lines[-1] if lines else ""), r.stdout[-1500:] + r.stderr[-1500:]

@@ -298,7 +298,7 @@ def dp_forced_one_rank(steps: int = 30):
     the dense 47 MB day bucket.  Child processes (a process group cannot be torn down and re-made inside this one)."""
     import json, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "6", "--no-cpu-baseline", "--no-secondary"]
+    base = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", str(steps), "--warmup", "6", "--no-cpu-baseline", "--no-secondary"]
 
     def run(extra):
         env = dict(os.environ, **extra)

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 O=gpurun_out/r6_first
 mkdir -p $O
 export B2T_BENCH_NO_RESTART=1
-B="python bench.py --no-secondary --no-cpu-baseline --steps 30 --warmup 5"
+B="python bench.py --full --no-secondary --no-cpu-baseline --steps 30 --warmup 5"
 run() { tag=$1; shift; env "$@" $B > $O/bench_$tag.json 2> $O/bench_$tag.err; echo "$tag $(python - <<PY
 import json
 try:

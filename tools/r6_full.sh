@@ -5,7 +5,7 @@ O=gpurun_out/r6_full; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q --durations=25 > $O/pytest_gpu.txt 2>&1; echo "pytest gpu rc $?" | tee $O/summary.txt
 tail -40 $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc $?" | tee -a $O/summary.txt; tail -2 $O/smoke.txt
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/summary.txt
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?" | tee -a $O/summary.txt
 python - <<'PY' | tee -a $O/summary.txt
 import json
 try:

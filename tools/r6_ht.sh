@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/r6_ht; mkdir -p $O
 export B2T_BENCH_NO_RESTART=1 B2T_EXEC_HOST_TIMING=1
-B="python bench.py --no-secondary --no-cpu-baseline --steps 40 --warmup 6"
+B="python bench.py --full --no-secondary --no-cpu-baseline --steps 40 --warmup 6"
 run() { tag=$1; shift; env "$@" $B > $O/b.json 2> $O/b.err; python - <<PY | tee -a $O/summary.txt
 import json
 try:

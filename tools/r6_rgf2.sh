@@ -17,7 +17,7 @@ for shape, rgf, dirs, chunks in (("c2", "1", "f", "1,1"), ("c2", "1", "fb", "1,1
 PY
 timeout 900 python /tmp/ab.py 2>$O/ab.err | grep R6AMP | tee -a $O/summary.txt; tail -3 $O/ab.err
 export B2T_BENCH_NO_RESTART=1 B2T_STEP_HOST_TIMING=1
-for i in 1 2 3 4 5 6; do python bench.py --no-secondary --no-cpu-baseline --steps 40 --warmup 6 > $O/b.json 2> $O/b.err; python - <<PY | tee -a $O/summary.txt
+for i in 1 2 3 4 5 6; do python bench.py --full --no-secondary --no-cpu-baseline --steps 40 --warmup 6 > $O/b.json 2> $O/b.err; python - <<PY | tee -a $O/summary.txt
 import json
 try:
     d=json.loads([l for l in open('$O/b.json') if l.startswith('{')][-1]); print('HOSTSEG', d['ms_per_step'], 'enq', d['config']['host_enqueue_ms_per_step'], d['config'].get('step_host_ms'))
