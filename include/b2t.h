@@ -596,6 +596,43 @@ int b2t_lattice_rescore_nbest_host(int n_states, int start, int n_arcs, const in
 int b2t_nbest_convert_to_inputs(const int32_t* ali, const int32_t* a_off, int n, const int32_t* mapping, int F,
                                 int32_t* out_inputs, int32_t* out_times, int32_t* out_off, int cap);
 
+
+/* ---- causal LM scoring (the n-best rescoring LLM, language-model-standalone.py:92-162) ------------------------------
+ * Scoring-only forward of a pre-LayerNorm OPT decoder (OPTForCausalLM with ReLU, word_embed_proj_dim == hidden_size), csrc/causal_lm.hip.
+ * Weights are fp16 DEVICE arrays in this layout (nejm-brain-to-text_amd/llm_rescore.py builds it once at load time):
+ *   rows of every nn.Linear weight [N][K] zero-padded to a multiple of 256; K (= d_model or ffn_dim) a multiple of 64;
+ *   qkv_w = [q_proj; k_proj; v_proj] rows, qkv_b the three biases; embed_tokens [round_up(vocab, 256)][d] (zero rows beyond
+ *   vocab) is also the LM head (tied); embed_positions [max_pos + 2][d] (OPT's learned positions, offset 2).
+ * Head dim d_model / n_heads must be 64, 80 or 128. */
+typedef struct {
+  const void *ln1_w, *ln1_b;     /* fp16 [d] self_attn_layer_norm */
+  const void *qkv_w, *qkv_b;     /* fp16 [round_up(3d, 256)][d], [3d] */
+  const void *out_w, *out_b;     /* fp16 [round_up(d, 256)][d], [d] */
+  const void *ln2_w, *ln2_b;     /* fp16 [d] final_layer_norm of the layer */
+  const void *fc1_w, *fc1_b;     /* fp16 [round_up(ffn, 256)][d], [ffn] */
+  const void *fc2_w, *fc2_b;     /* fp16 [round_up(d, 256)][ffn], [d] */
+} b2t_clm_layer_t;
+
+typedef struct {
+  int n_layers, d_model, n_heads, ffn_dim, vocab, max_pos;
+  const void* embed_tokens;            /* fp16 [round_up(vocab, 256)][d] */
+  const void* embed_positions;         /* fp16 [max_pos + 2][d] */
+  const void *final_ln_w, *final_ln_b; /* fp16 [d] */
+  const b2t_clm_layer_t* layers_host;  /* HOST array of n_layers entries (device pointers inside) */
+} b2t_clm_t;
+
+/* Workspace bytes of b2t_clm_score_f16 for n_tokens tokens in n_seq sequences (0 if the sizes are invalid). */
+size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, int n_seq);
+/* Log-probability of packed sequences: sequence s is ids_host[seq_off_host[s] .. seq_off_host[s+1]) (HOST int32 arrays,
+ * seq_off_host[0] = 0, every length 1..max_pos, every id < vocab).  scores_out[s] (fp32, device) = sum over t = 1..n-1 of
+ * log softmax(logits[t-1])[id[t]] -- the reference's score before its length penalty (rescore_with_gpt2, :153-159);
+ * tok_logp_out (optional, fp32 [n_tokens], device) = the per-token terms, 0 at the first token of each sequence.
+ * Numerics: fp16 operands, fp32 accumulation, residual stream, LayerNorm, softmax and sums in fp32; a sequence's result does
+ * not depend on the other sequences of the batch.  Bad input (ids, lengths, head dim, workspace size) returns an error before
+ * any launch.  The index arrays are uploaded on `stream`, which the call synchronises once for that copy. */
+int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                      float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

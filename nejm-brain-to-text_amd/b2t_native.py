@@ -95,6 +95,19 @@ class LexLmDesc(C.Structure):
                 ("alpha", C.c_float), ("beta", C.c_float), ("unk_logp", C.c_float)]
 
 
+class ClmLayer(C.Structure):
+    """Mirror of b2t_clm_layer_t (include/b2t.h): fp16 device weights of one OPT decoder layer."""
+    _fields_ = [(n, VP) for n in ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc1_w", "fc1_b",
+                                  "fc2_w", "fc2_b")]
+
+
+class ClmDesc(C.Structure):
+    """Mirror of b2t_clm_t (include/b2t.h)."""
+    _fields_ = [(n, C.c_int) for n in ("n_layers", "d_model", "n_heads", "ffn_dim", "vocab", "max_pos")] + \
+               [(n, VP) for n in ("embed_tokens", "embed_positions", "final_ln_w", "final_ln_b")] + \
+               [("layers_host", C.POINTER(ClmLayer))]
+
+
 _SIGNATURES = {
     "b2t_version": (C.c_int, []),
     "b2t_last_error": (C.c_char_p, []),
@@ -198,6 +211,8 @@ _SIGNATURES = {
     "b2t_prefix_beam_search_lm_f32": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, C.c_int,
                                                 C.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
                                                 C.c_float, C.c_float, C.c_float, VP, VP]),
+    "b2t_clm_ws_bytes": (C.c_size_t, [C.POINTER(ClmDesc), LL, C.c_int]),
+    "b2t_clm_score_f16": (C.c_int, [C.POINTER(ClmDesc), VP, VP, C.c_int, VP, VP, VP, C.c_size_t, VP]),
 }
 
 

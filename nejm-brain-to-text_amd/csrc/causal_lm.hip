@@ -1,0 +1,527 @@
+// causal_lm.hip — scoring-only OPT decoder forward (the n-best rescoring LLM of language-model-standalone.py:127-162) for gfx950.
+// Input: packed variable-length sequences (token ids + per-sequence offsets; no padding, no KV cache).  Output: per sequence the
+// sum over t = 1..n-1 of log p(id[t] | id[0..t-1]), and optionally every per-token log-prob.
+//
+// Numerics contract:
+//   - weights are stored fp16 (as the checkpoint and the reference's torch_dtype=float16 hold them);
+//   - GEMM operands are fp16, accumulation fp32 (v_mfma_f32_32x32x16_f16);
+//   - the residual stream, LayerNorm statistics, softmax / log-softmax and the per-sequence sums are fp32;
+//   - the LayerNorm, attention and fc1 outputs (the next GEMM's operands) and q / k / v are rounded to fp16.
+//   Every output element is computed by one thread in a fixed order that depends only on its own row: a sequence's score is
+//   bit-identical alone or anywhere in any batch.
+//
+// Kernels, per layer (pre-LN OPT): LayerNorm -> QKV GEMM (+bias, q * head_dim^-0.5, fp16) -> causal attention -> out_proj GEMM
+// (+bias, added into the fp32 residual) -> LayerNorm -> fc1 GEMM (+bias, ReLU, fp16) -> fc2 GEMM (+bias, residual add).  Then the
+// final LayerNorm of every position but the last of each sequence, and the LM head (tied to embed_tokens) fused with
+// log-softmax and the gather: the tile epilogue emits per (row, 64-column group) the max and the sum of exp, and the logit of
+// the row's target token; a combine kernel forms logp = logit[target] - logsumexp.  The [tokens x vocab] logits never exist.
+//
+// GEMM: the packed tile design of gemm_bf16p.hip (k-contiguous operands read as 16-byte rows straight into double-buffered
+// LDS with 144-byte rows, one barrier per 64-k tile) as a sibling fp16 kernel, 128 x 128 (4 waves) and 256 x 256 (8 waves)
+// tiles.  Operands are never packed at run time: the LayerNorm / attention / fc1 kernels write the k-contiguous, row-padded
+// fp16 A operand directly, and nn.Linear weights ([N][K], k-contiguous) are padded once at load time to 256 rows.
+#include <math.h>
+#include <vector>
+
+#include "common.h"
+
+namespace b2t {
+namespace {
+
+using f32x16 = float __attribute__((ext_vector_type(16)));
+using half8 = _Float16 __attribute__((ext_vector_type(8)));
+
+constexpr int CK = 64, CPITCH = CK + 8;      // k tile; LDS row pitch in fp16 elements (144 B)
+constexpr int ROWPAD = 256;                   // A operands and weights are padded to this many rows
+
+enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3 };
+
+struct ClmGemm {
+  const _Float16* A;      // [round_up(M, 256)][K]
+  const _Float16* B;      // [round_up(N, 256)][K]
+  int M, N, K;            // K % 64 == 0
+  const _Float16* bias;   // [N] or null
+  _Float16* out16;        // EP_F16 / EP_RELU: [M][ldo]
+  float* resid;           // EP_RESID: [M][ldo] += C
+  int ldo;
+  float qscale; int qcols;   // EP_F16: columns < qcols are multiplied by qscale after the bias (OPT's q scaling)
+  float* pmax; float* psum;  // EP_HEAD: [M][ncg] per 64-column group max / sum exp(v - max)
+  float* tlogit; const int* tgt; int ncg;   // EP_HEAD: tlogit[r] = C[r][tgt[r]]
+};
+
+__device__ __forceinline__ float warp32_max(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float warp32_sum(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.
+template <int BM, int BN, int WGM, int WGN, int EP>
+__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
+  constexpr int T = 64 * WGM * WGN, WTM = BM / WGM, WTN = BN / WGN, FM = WTM / 32, FN = WTN / 32, RS = T / 8;
+  static_assert(WTN == 64, "the head epilogue reduces over 64-column wave slices");
+  static_assert(BM * 8 == 4 * T && BN * 8 == 4 * T, "four 16-byte loads per operand and thread per k tile");
+  extern __shared__ __attribute__((aligned(16))) _Float16 clm_lds[];
+  _Float16* As = clm_lds;
+  _Float16* Bs = clm_lds + 2 * BM * CPITCH;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WGN, wn = wave % WGN;
+  const int li = lane & 31, hh = lane >> 5;
+  int m0, n0;
+  {   // tiles column-major (consecutive tiles share the weight panel), a contiguous range of tiles per XCD
+    const int mt = (g.M + BM - 1) / BM, nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
+    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
+    m0 = (tile % mt) * BM; n0 = (tile / mt) * BN;
+  }
+  const int K = g.K, nk = K / CK;
+  const _Float16* ag = g.A + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
+  const _Float16* bg = g.B + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
+  const long long rstep = (long long)RS * K;
+  uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
+#define CLM_FETCH(k0)                                                                                                   \
+  ra0 = *reinterpret_cast<const uint4*>(ag + (k0)); ra1 = *reinterpret_cast<const uint4*>(ag + rstep + (k0));             \
+  ra2 = *reinterpret_cast<const uint4*>(ag + 2 * rstep + (k0)); ra3 = *reinterpret_cast<const uint4*>(ag + 3 * rstep + (k0)); \
+  rb0 = *reinterpret_cast<const uint4*>(bg + (k0)); rb1 = *reinterpret_cast<const uint4*>(bg + rstep + (k0));             \
+  rb2 = *reinterpret_cast<const uint4*>(bg + 2 * rstep + (k0)); rb3 = *reinterpret_cast<const uint4*>(bg + 3 * rstep + (k0));
+#define CLM_STASH(buf)                                                                                                  \
+  { _Float16* ad = As + (buf) * BM * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
+    _Float16* bd = Bs + (buf) * BN * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
+    *reinterpret_cast<uint4*>(ad) = ra0; *reinterpret_cast<uint4*>(ad + RS * CPITCH) = ra1;                             \
+    *reinterpret_cast<uint4*>(ad + 2 * RS * CPITCH) = ra2; *reinterpret_cast<uint4*>(ad + 3 * RS * CPITCH) = ra3;       \
+    *reinterpret_cast<uint4*>(bd) = rb0; *reinterpret_cast<uint4*>(bd + RS * CPITCH) = rb1;                             \
+    *reinterpret_cast<uint4*>(bd + 2 * RS * CPITCH) = rb2; *reinterpret_cast<uint4*>(bd + 3 * RS * CPITCH) = rb3; }
+  f32x16 acc[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  CLM_FETCH(0)
+  CLM_STASH(0)
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) { CLM_FETCH((kt + 1) * CK) }
+    const _Float16* ap = As + cur * BM * CPITCH + (wm * WTM + li) * CPITCH + 8 * hh;
+    const _Float16* bp = Bs + cur * BN * CPITCH + (wn * WTN + li) * CPITCH + 8 * hh;
+#pragma unroll
+    for (int kk = 0; kk < CK; kk += 16) {
+      half8 a[FM], b[FN];
+#pragma unroll
+      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const half8*>(ap + i * 32 * CPITCH + kk);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const half8*>(bp + j * 32 * CPITCH + kk);
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    if (kt + 1 < nk) { CLM_STASH(cur ^ 1) }
+    __syncthreads();
+  }
+#undef CLM_FETCH
+#undef CLM_STASH
+  // epilogue: C/D layout of the 32x32 MFMAs: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+  const int colw = n0 + wn * WTN;
+  if (EP == EP_HEAD) {
+    if (colw >= g.N) return;   // a 64-column group entirely beyond the vocabulary (wave-uniform)
+    const int cg = colw / 64;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        float v[FN];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          v[j] = colw + j * 32 + li < g.N ? acc[i][j][e] : -INFINITY;
+          mx = fmaxf(mx, v[j]);
+        }
+        mx = warp32_max(mx);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < FN; ++j) s += __expf(v[j] - mx);
+        s = warp32_sum(s);
+        if (row < g.M) {
+          if (li == 0) { g.pmax[(long long)row * g.ncg + cg] = mx; g.psum[(long long)row * g.ncg + cg] = s; }
+          const int t = g.tgt[row];
+#pragma unroll
+          for (int j = 0; j < FN; ++j)
+            if (colw + j * 32 + li == t) g.tlogit[row] = v[j];
+        }
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < FN; ++j) {
+    const int col = colw + j * 32 + li;
+    if (col >= g.N) continue;
+    const float bv = g.bias ? (float)g.bias[col] : 0.f;
+    const float sc = col < g.qcols ? g.qscale : 1.f;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        if (row >= g.M) continue;
+        float v = acc[i][j][e] + bv;
+        const long long off = (long long)row * g.ldo + col;
+        if (EP == EP_RESID) {
+          g.resid[off] += v;
+        } else {
+          if (EP == EP_RELU) v = fmaxf(v, 0.f);
+          else v *= sc;
+          g.out16[off] = (_Float16)v;
+        }
+      }
+    }
+  }
+}
+
+constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * sizeof(_Float16); }
+
+template <int EP>
+int launch_gemm(const ClmGemm& g, hipStream_t s) {
+  const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
+  if ((long long)m256 * n256 >= 256) {   // the 256-tiles fill the chip's 256 CUs: one 8-wave workgroup per CU
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<256, 256, 2, 4, EP>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
+    B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));
+    hipLaunchKernelGGL((clm_gemm_kernel<256, 256, 2, 4, EP>), dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
+  } else {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<128, 128, 2, 2, EP>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128));
+    B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(128, 128));
+    const int m128 = (g.M + 127) / 128, n128 = (g.N + 127) / 128;
+    hipLaunchKernelGGL((clm_gemm_kernel<128, 128, 2, 2, EP>), dim3(m128 * n128), dim3(256), lds_bytes(128, 128), s, g);
+  }
+  B2T_CHECK_LAUNCH("clm_gemm_kernel");
+  return 0;
+}
+
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float block_max256(float v, float* red) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// resid[t] = embed_tokens[id[t]] + embed_positions[pos[t] + 2] (fp32)
+__global__ __launch_bounds__(256) void clm_embed_kernel(const int* ids, const int* pos, const _Float16* et, const _Float16* ep,
+                                                        float* resid, int d) {
+  const int t = blockIdx.x;
+  const _Float16* a = et + (long long)ids[t] * d;
+  const _Float16* b = ep + (long long)(pos[t] + 2) * d;
+  float* o = resid + (long long)t * d;
+  for (int c = threadIdx.x; c < d; c += 256) o[c] = (float)a[c] + (float)b[c];
+}
+
+// out[r] = fp16(LayerNorm(x[rowmap ? rowmap[r] : r])) for r < rows; zeros for rows <= r < gridDim.x (the operand's padding)
+__global__ __launch_bounds__(256) void clm_layernorm_kernel(const float* x, const int* rowmap, int rows, const _Float16* w,
+                                                            const _Float16* b, _Float16* out, int d) {
+  __shared__ float red[4];
+  const int r = blockIdx.x;
+  _Float16* o = out + (long long)r * d;
+  if (r >= rows) {
+    for (int c = threadIdx.x; c < d; c += 256) o[c] = (_Float16)0.f;
+    return;
+  }
+  const float* xr = x + (long long)(rowmap ? rowmap[r] : r) * d;
+  float s = 0.f;
+  for (int c = threadIdx.x; c < d; c += 256) s += xr[c];
+  const float mean = block_sum256(s, red) / d;
+  float v = 0.f;
+  for (int c = threadIdx.x; c < d; c += 256) { const float q = xr[c] - mean; v += q * q; }
+  const float rstd = 1.0f / sqrtf(block_sum256(v, red) / d + 1e-5f);
+  for (int c = threadIdx.x; c < d; c += 256) o[c] = (_Float16)((xr[c] - mean) * rstd * (float)w[c] + (float)b[c]);
+}
+
+// Causal attention, one workgroup per (sequence, head), 4 waves; a wave takes 32 query rows at a time.  The score tile is
+// computed transposed, S^T = K . Q^T (v_mfma_f32_32x32x16_f16: A = 32 keys, B = 32 queries), so a lane owns one query column:
+// its online-softmax state (m, l) is per lane and the row reductions are in-lane plus one swap of the lane halves.  P^T is
+// then the B operand of O^T = V^T . P^T with no data movement (registers 8s..8s+7 of the accumulator are k-step s, keys in
+// the order 16s + 8(j >> 2) + 4h + (j & 3)), and O^T's rescale by exp(m_old - m_new) is per lane too.
+template <int D>
+__global__ __launch_bounds__(256) void clm_attn_kernel(const _Float16* qkv, _Float16* out, const int* seq_off, int d) {
+  constexpr int KS = D / 16, NF = (D + 31) / 32;
+  const int sq = blockIdx.x, h = blockIdx.y;
+  const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
+  const long long RS = 3LL * d;
+  const _Float16* Qb = qkv + (long long)t0 * RS + h * D;
+  const _Float16* Kb = Qb + d;
+  const _Float16* Vb = Qb + 2 * d;
+  const int nqb = (L + 31) / 32;
+  for (int qb = wave; qb < nqb; qb += 4) {
+    const int q0 = qb * 32, q = q0 + li;
+    const _Float16* qp = Qb + (long long)min(q, L - 1) * RS + 8 * hh;
+    half8 qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const half8*>(qp + 16 * ks);
+    float m = -INFINITY, l = 0.f;
+    f32x16 o[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) o[f][e] = 0.f;
+    for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
+      const int k0 = kb * 32;
+      const _Float16* kp = Kb + (long long)min(k0 + li, L - 1) * RS + 8 * hh;
+      f32x16 sacc;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(kp + 16 * ks), qf[ks], sacc, 0, 0, 0);
+      float mx = -INFINITY;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = k0 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        if (key > q || key >= L) sacc[e] = -INFINITY;
+        mx = fmaxf(mx, sacc[e]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float mnew = fmaxf(m, mx);
+      const float alpha = __expf(m - mnew);
+      float ps = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) { const float p = __expf(sacc[e] - mnew); sacc[e] = p; ps += p; }
+      ps += __shfl_xor(ps, 32);
+      l = l * alpha + ps;
+      m = mnew;
+      half8 pb[2];
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pb[s2][j] = (_Float16)sacc[8 * s2 + j];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[f][e] *= alpha;
+        const int dim = 32 * f + li;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          half8 va;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int key = k0 + 16 * s2 + 8 * (j >> 2) + 4 * hh + (j & 3);
+            va[j] = (dim < D && key < L) ? Vb[(long long)key * RS + dim] : (_Float16)0.f;
+          }
+          o[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb[s2], o[f], 0, 0, 0);
+        }
+      }
+    }
+    if (q < L) {
+      const float inv = 1.0f / l;
+      _Float16* op = out + (long long)(t0 + q) * d + h * D;
+#pragma unroll
+      for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int dim = 32 * f + (e & 3) + 8 * (e >> 2) + 4 * hh;
+          if (dim < D) op[dim] = (_Float16)(o[f][e] * inv);
+        }
+    }
+  }
+}
+
+// logp[r] = tlogit[r] - logsumexp over the row's 64-column groups
+__global__ __launch_bounds__(256) void clm_head_combine_kernel(const float* pmax, const float* psum, const float* tlogit, int ncg,
+                                                               float* logp) {
+  __shared__ float red[4];
+  const int r = blockIdx.x;
+  const float* pm = pmax + (long long)r * ncg;
+  const float* ps = psum + (long long)r * ncg;
+  float mx = -INFINITY;
+  for (int c = threadIdx.x; c < ncg; c += 256) mx = fmaxf(mx, pm[c]);
+  mx = block_max256(mx, red);
+  float s = 0.f;
+  for (int c = threadIdx.x; c < ncg; c += 256) s += ps[c] * expf(pm[c] - mx);
+  s = block_sum256(s, red);
+  if (threadIdx.x == 0) logp[r] = tlogit[r] - (mx + logf(s));
+}
+
+// scores[s] = sum of the sequence's log-probs in token order; tok_logp (optional) = per token, 0 at each sequence's first token
+__global__ __launch_bounds__(64) void clm_seq_sum_kernel(const float* logp, const int* seq_off, const int* head_off, float* scores,
+                                                         float* tok_logp) {
+  const int s = blockIdx.x, h0 = head_off[s], n = head_off[s + 1] - h0, t0 = seq_off[s];
+  if (tok_logp) {
+    if (threadIdx.x == 0) tok_logp[t0] = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) tok_logp[t0 + 1 + i] = logp[h0 + i];
+  }
+  if (threadIdx.x == 0) {
+    float acc = 0.f;
+    for (int i = 0; i < n; ++i) acc += logp[h0 + i];
+    scores[s] = acc;
+  }
+}
+
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline long long rup(long long x, long long m) { return (x + m - 1) / m * m; }
+
+struct ClmLayout {
+  size_t ints, resid, x16, qkv, hbuf, pmax, psum, tlogit, logp, total;
+  long long M, Mh, Mp, ncg;
+};
+
+ClmLayout clm_layout(const b2t_clm_t* m, long long M, int n_seq) {
+  ClmLayout L{};
+  const long long d = m->d_model, Mh = M - n_seq;
+  L.M = M; L.Mh = Mh; L.Mp = rup(M > 0 ? M : 1, ROWPAD); L.ncg = (m->vocab + 63) / 64;
+  size_t off = 0;
+  L.ints = off;   off += al256(sizeof(int) * (size_t)(2 * M + 2 * (Mh > 0 ? Mh : 0) + 2 * (n_seq + 1)));
+  L.resid = off;  off += al256(sizeof(float) * (size_t)(M * d));
+  L.x16 = off;    off += al256(sizeof(_Float16) * (size_t)(L.Mp * d));
+  L.qkv = off;    off += al256(sizeof(_Float16) * (size_t)(M * 3 * d));
+  L.hbuf = off;   off += al256(sizeof(_Float16) * (size_t)(L.Mp * m->ffn_dim));
+  L.pmax = off;   off += al256(sizeof(float) * (size_t)(Mh * L.ncg));
+  L.psum = off;   off += al256(sizeof(float) * (size_t)(Mh * L.ncg));
+  L.tlogit = off; off += al256(sizeof(float) * (size_t)Mh);
+  L.logp = off;   off += al256(sizeof(float) * (size_t)Mh);
+  L.total = off;
+  return L;
+}
+
+int check_model(const b2t_clm_t* m) {
+  B2T_REQUIRE(m, "b2t_clm: null model");
+  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 && m->max_pos > 0,
+              "b2t_clm: bad dimensions (layers %d, d %d, heads %d, ffn %d, vocab %d, max_pos %d)", m->n_layers, m->d_model,
+              m->n_heads, m->ffn_dim, m->vocab, m->max_pos);
+  B2T_REQUIRE(m->d_model % m->n_heads == 0, "b2t_clm: d_model %d is not a multiple of n_heads %d", m->d_model, m->n_heads);
+  const int hd = m->d_model / m->n_heads;
+  B2T_REQUIRE(hd == 64 || hd == 80 || hd == 128, "b2t_clm: unsupported head dim %d (64, 80 or 128)", hd);
+  B2T_REQUIRE(m->d_model % 64 == 0 && m->ffn_dim % 64 == 0, "b2t_clm: d_model %d and ffn_dim %d must be multiples of 64",
+              m->d_model, m->ffn_dim);
+  B2T_REQUIRE(m->embed_tokens && m->embed_positions && m->final_ln_w && m->final_ln_b && (m->n_layers == 0 || m->layers_host),
+              "b2t_clm: null weight pointer");
+  for (int l = 0; l < m->n_layers; ++l) {
+    const b2t_clm_layer_t& w = m->layers_host[l];
+    B2T_REQUIRE(w.ln1_w && w.ln1_b && w.qkv_w && w.qkv_b && w.out_w && w.out_b && w.ln2_w && w.ln2_b && w.fc1_w && w.fc1_b &&
+                w.fc2_w && w.fc2_b, "b2t_clm: null weight pointer in layer %d", l);
+  }
+  return 0;
+}
+
+}  // namespace
+}  // namespace b2t
+
+using namespace b2t;
+
+extern "C" size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, int n_seq) {
+  if (!model || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
+  return clm_layout(model, n_tokens, n_seq).total;
+}
+
+extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                 float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_model(model)) return rc;
+  const b2t_clm_t& m = *model;
+  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "b2t_clm_score_f16: null argument");
+  B2T_REQUIRE(n_seq >= 1, "b2t_clm_score_f16: n_seq %d < 1", n_seq);
+  B2T_REQUIRE(seq_off_host[0] == 0, "b2t_clm_score_f16: seq_off[0] = %d, expected 0", seq_off_host[0]);
+  for (int s = 0; s < n_seq; ++s) {
+    const long long n = (long long)seq_off_host[s + 1] - seq_off_host[s];
+    B2T_REQUIRE(n >= 1, "b2t_clm_score_f16: sequence %d is empty", s);
+    B2T_REQUIRE(n <= m.max_pos, "b2t_clm_score_f16: sequence %d has %lld tokens, more than max_pos %d", s, n, m.max_pos);
+  }
+  const long long M = seq_off_host[n_seq];
+  for (long long t = 0; t < M; ++t)
+    B2T_REQUIRE(ids_host[t] >= 0 && ids_host[t] < m.vocab, "b2t_clm_score_f16: token %lld has id %d outside [0, %d)", t,
+                ids_host[t], m.vocab);
+  const ClmLayout L = clm_layout(model, M, n_seq);
+  B2T_REQUIRE(ws_bytes >= L.total, "b2t_clm_score_f16: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+  const hipStream_t s = as_stream(stream);
+  const int d = m.d_model, H = m.n_heads, hd = d / H, F = m.ffn_dim;
+  const long long Mh = L.Mh;
+
+  // index arrays, built on the host and uploaded once: ids[M] pos[M] head_src[Mh] head_tgt[Mh] seq_off[n+1] head_off[n+1]
+  static thread_local std::vector<int> host;
+  host.assign((size_t)(2 * M + 2 * Mh + 2 * (n_seq + 1)), 0);
+  int* h_ids = host.data(); int* h_pos = h_ids + M; int* h_src = h_pos + M; int* h_tgt = h_src + Mh;
+  int* h_soff = h_tgt + Mh; int* h_hoff = h_soff + n_seq + 1;
+  long long r = 0;
+  for (int q = 0; q < n_seq; ++q) {
+    const int a = seq_off_host[q], b = seq_off_host[q + 1];
+    h_soff[q] = a; h_hoff[q] = (int)r;
+    for (int t = a; t < b; ++t) {
+      h_ids[t] = ids_host[t]; h_pos[t] = t - a;
+      if (t + 1 < b) { h_src[r] = t; h_tgt[r] = ids_host[t + 1]; ++r; }
+    }
+  }
+  h_soff[n_seq] = (int)M; h_hoff[n_seq] = (int)r;
+  char* base = static_cast<char*>(ws);
+  int* d_ids = reinterpret_cast<int*>(base + L.ints);
+  int* d_pos = d_ids + M; int* d_src = d_pos + M; int* d_tgt = d_src + Mh; int* d_soff = d_tgt + Mh; int* d_hoff = d_soff + n_seq + 1;
+  if (int rc = check_hip(hipMemcpyAsync(d_ids, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s), "b2t_clm_score_f16 upload"))
+    return rc;
+  // the staging vector is reused by the next call on this thread: wait for the copy out of it
+  if (int rc = check_hip(hipStreamSynchronize(s), "b2t_clm_score_f16 upload")) return rc;
+
+  float* resid = reinterpret_cast<float*>(base + L.resid);
+  _Float16* x16 = reinterpret_cast<_Float16*>(base + L.x16);
+  _Float16* qkv = reinterpret_cast<_Float16*>(base + L.qkv);
+  _Float16* hb = reinterpret_cast<_Float16*>(base + L.hbuf);
+  const _Float16* et = static_cast<const _Float16*>(m.embed_tokens);
+
+  hipLaunchKernelGGL(clm_embed_kernel, dim3((unsigned)M), dim3(256), 0, s, d_ids, d_pos, et,
+                     static_cast<const _Float16*>(m.embed_positions), resid, d);
+  B2T_CHECK_LAUNCH("clm_embed_kernel");
+  auto H16 = [](const void* p) { return static_cast<const _Float16*>(p); };
+  for (int l = 0; l < m.n_layers; ++l) {
+    const b2t_clm_layer_t& w = m.layers_host[l];
+    hipLaunchKernelGGL(clm_layernorm_kernel, dim3((unsigned)L.Mp), dim3(256), 0, s, resid, (const int*)nullptr, (int)M,
+                       H16(w.ln1_w), H16(w.ln1_b), x16, d);
+    B2T_CHECK_LAUNCH("clm_layernorm_kernel");
+    ClmGemm g{};
+    g.A = x16; g.B = H16(w.qkv_w); g.M = (int)M; g.N = 3 * d; g.K = d; g.bias = H16(w.qkv_b); g.out16 = qkv; g.ldo = 3 * d;
+    g.qscale = 1.0f / sqrtf((float)hd); g.qcols = d;
+    if (int rc = launch_gemm<EP_F16>(g, s)) return rc;
+    if (hd == 64) hipLaunchKernelGGL(clm_attn_kernel<64>, dim3(n_seq, H), dim3(256), 0, s, qkv, x16, d_soff, d);
+    else if (hd == 80) hipLaunchKernelGGL(clm_attn_kernel<80>, dim3(n_seq, H), dim3(256), 0, s, qkv, x16, d_soff, d);
+    else hipLaunchKernelGGL(clm_attn_kernel<128>, dim3(n_seq, H), dim3(256), 0, s, qkv, x16, d_soff, d);
+    B2T_CHECK_LAUNCH("clm_attn_kernel");
+    g = ClmGemm{};
+    g.A = x16; g.B = H16(w.out_w); g.M = (int)M; g.N = d; g.K = d; g.bias = H16(w.out_b); g.resid = resid; g.ldo = d;
+    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
+    hipLaunchKernelGGL(clm_layernorm_kernel, dim3((unsigned)L.Mp), dim3(256), 0, s, resid, (const int*)nullptr, (int)M,
+                       H16(w.ln2_w), H16(w.ln2_b), x16, d);
+    B2T_CHECK_LAUNCH("clm_layernorm_kernel");
+    g = ClmGemm{};
+    g.A = x16; g.B = H16(w.fc1_w); g.M = (int)M; g.N = F; g.K = d; g.bias = H16(w.fc1_b); g.out16 = hb; g.ldo = F;
+    if (int rc = launch_gemm<EP_RELU>(g, s)) return rc;
+    g = ClmGemm{};
+    g.A = hb; g.B = H16(w.fc2_w); g.M = (int)M; g.N = d; g.K = F; g.bias = H16(w.fc2_b); g.resid = resid; g.ldo = d;
+    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
+  }
+  float* logp = reinterpret_cast<float*>(base + L.logp);
+  if (Mh > 0) {
+    hipLaunchKernelGGL(clm_layernorm_kernel, dim3((unsigned)rup(Mh, ROWPAD)), dim3(256), 0, s, resid, (const int*)d_src, (int)Mh,
+                       H16(m.final_ln_w), H16(m.final_ln_b), x16, d);
+    B2T_CHECK_LAUNCH("clm_layernorm_kernel");
+    ClmGemm g{};
+    g.A = x16; g.B = et; g.M = (int)Mh; g.N = m.vocab; g.K = d;
+    g.pmax = reinterpret_cast<float*>(base + L.pmax); g.psum = reinterpret_cast<float*>(base + L.psum);
+    g.tlogit = reinterpret_cast<float*>(base + L.tlogit); g.tgt = d_tgt; g.ncg = (int)L.ncg;
+    if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
+    hipLaunchKernelGGL(clm_head_combine_kernel, dim3((unsigned)Mh), dim3(256), 0, s, g.pmax, g.psum, g.tlogit, g.ncg, logp);
+    B2T_CHECK_LAUNCH("clm_head_combine_kernel");
+  }
+  hipLaunchKernelGGL(clm_seq_sum_kernel, dim3(n_seq), dim3(64), 0, s, logp, d_soff, d_hoff, scores_out, tok_logp_out);
+  B2T_CHECK_LAUNCH("clm_seq_sum_kernel");
+  return 0;
+}

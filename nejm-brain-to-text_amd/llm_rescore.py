@@ -1,0 +1,425 @@
+"""OPT n-best rescoring: the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
+:127-162, gpt2_lm_decode :165-251, get_string_differences :273-311, augment_nbest :327-411) with the causal-LM forward on the
+HIP path (b2t_clm_score_f16, csrc/causal_lm.hip).
+
+Call surfaces are the reference's: `build_opt(model_name, cache_dir, device)` returns `(model, tokenizer)`, and the three
+functions take them as the reference's do.  `model` here is an `OptScorer`: the checkpoint's fp16 weights converted once into
+the device layout of include/b2t.h, scored on packed variable-length token ids (no padding).  Tokenisation stays on the host.
+`build_opt` never reaches the network: it reads a local directory (the model name itself, or the hub-cache layout under
+`cache_dir`) and refuses what the kernels do not run (post-LN OPT, opt-350m's projection layers, non-ReLU activations).
+"""
+from __future__ import annotations
+
+import glob
+import json
+import logging
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+ROWPAD = 256   # weight rows are padded to this multiple (b2t_clm_t layout)
+HEAD_DIMS = (64, 80, 128)
+
+_LAYER_FIELDS = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
+
+
+# ---- n-best arithmetic of the reference (pure host code) ---------------------------------------------------------------
+def get_string_differences(cue: str, decoder_output: str):
+    """Word-level edit distance from decoder_output to cue with its backtrace: (cost, path, spans).  path holds, per word of
+    decoder_output in order, its index when it matches or 'R' / 'D', with 'I' for words of cue that are inserted; 'I' entries
+    are then dropped.  spans are the (start, end) character ranges of decoder_output's replaced or deleted words.  Ties are
+    broken insertion first, then deletion, then substitution, as in the reference."""
+    out_w, cue_w = decoder_output.split(), cue.split()
+    n, m = len(out_w), len(cue_w)
+    # cost[i][j]: distance between the first i words of decoder_output and the first j words of cue
+    cost = [[0] * (m + 1) for _ in range(n + 1)]
+    for i in range(n + 1):
+        for j in range(m + 1):
+            if i == 0:
+                cost[i][j] = j
+            elif j == 0:
+                cost[i][j] = i
+            elif out_w[i - 1] == cue_w[j - 1]:
+                cost[i][j] = cost[i - 1][j - 1]
+            else:
+                cost[i][j] = 1 + min(cost[i][j - 1], cost[i - 1][j], cost[i - 1][j - 1])
+    rev = []
+    i, j = n, m
+    while i > 0 and j > 0:
+        if out_w[i - 1] == cue_w[j - 1]:
+            rev.append(i - 1); i -= 1; j -= 1
+            continue
+        ins, dele, sub = cost[i][j - 1], cost[i - 1][j], cost[i - 1][j - 1]
+        if ins <= dele and ins <= sub:
+            rev.append("I"); j -= 1
+        elif dele <= ins and dele <= sub:
+            rev.append("D"); i -= 1
+        else:
+            rev.append("R"); i -= 1; j -= 1
+    rev.extend(["D"] * i)
+    rev.extend(["I"] * j)
+    path = [p for p in reversed(rev) if p != "I"]
+    spans, pos = [], 0
+    for label, word in zip(path, out_w):
+        if label in ("R", "D"):
+            spans.append((pos, pos + len(word)))
+        pos += len(word) + 1
+    return cost[n][m], path, spans
+
+
+def _sorted_desc(total: Sequence[float]) -> np.ndarray:
+    return np.argsort(total)[::-1]
+
+
+def augment_nbest(nbest, top_candidates_to_augment=20, acoustic_scale=0.3, score_penalty_percent=0.01):
+    """Grow an n-best list of [sentence, ac, lm] by exchanging substituted words between pairs of the top candidates of equal
+    word count.  A new sentence gets the pair's mean scores, each lowered by score_penalty_percent of its magnitude; the result
+    is sorted by acoustic_scale * ac + lm, best first."""
+    sent = [e[0].strip() for e in nbest]
+    ac = [e[1] for e in nbest]
+    lm = [e[2] for e in nbest]
+    tot = [acoustic_scale * a + b for a, b in zip(ac, lm)]
+    order = _sorted_desc(tot)
+    sent, ac, lm, tot = ([x[i] for i in order] for x in (sent, ac, lm, tot))
+
+    new_s, new_ac, new_lm, new_tot = [], [], [], []
+    top = top_candidates_to_augment
+    for a in range(min(len(sent) - 1, top)):
+        wa = sent[a].split()
+        for b in range(a + 1, min(len(sent), top)):
+            wb = sent[b].split()
+            if len(wa) != len(wb):
+                continue
+            _, path_ab, _ = get_string_differences(sent[a], sent[b])
+            _, path_ba, _ = get_string_differences(sent[b], sent[a])
+            ra = [k for k, p in enumerate(path_ba) if p == "R"]
+            rb = [k for k, p in enumerate(path_ab) if p == "R"]
+            mac, mlm = np.mean([ac[a], ac[b]]), np.mean([lm[a], lm[b]])
+            for ia, ib in zip(ra, rb):
+                xa, xb = list(wa), list(wb)
+                xa[ia], xb[ib] = wb[ib], wa[ia]
+                for cand in (" ".join(xa), " ".join(xb)):
+                    if cand in sent or cand in new_s:
+                        continue
+                    new_s.append(cand)
+                    new_ac.append(mac - score_penalty_percent * np.abs(mac))
+                    new_lm.append(mlm - score_penalty_percent * np.abs(mlm))
+                    new_tot.append(acoustic_scale * new_ac[-1] + new_lm[-1])
+    sent += new_s; ac += new_ac; lm += new_lm; tot += new_tot
+    order = _sorted_desc(tot)
+    return [[sent[i], ac[i], lm[i]] for i in order]
+
+
+# ---- scoring ------------------------------------------------------------------------------------------------------------
+def rescore_with_gpt2(model, tokenizer, device, hypotheses, length_penalty):
+    """LLM score of every hypothesis: sum over t >= 1 of log p(token t | tokens < t) - n_tokens * length_penalty, n_tokens
+    counting the tokenizer's BOS.  `model` is an OptScorer (or any object with its `score`); `device` is kept for the
+    reference's signature (the scorer's weights say where it runs)."""
+    enc = tokenizer(list(hypotheses))
+    ids = []
+    for row, mask in zip(enc["input_ids"], enc["attention_mask"]):
+        row, mask = np.asarray(row), np.asarray(mask)
+        ids.append(row[mask != 0].astype(np.int32))
+    return list(model.score(ids, length_penalty))
+
+
+def _normalise(hyp: str) -> str:
+    for a, b in ((">", ""), ("  ", " "), (" ,", ","), (" .", "."), (" ?", "?")):
+        hyp = hyp.replace(a, b)
+    return hyp
+
+
+def gpt2_lm_decode(model, tokenizer, device, nbest, acoustic_scale, length_penalty, alpha, returnConfidence=False,
+                   current_context_str=None):
+    """Pick the best of an n-best list [sentence, ac, lm, ...] by acoustic_scale * ac + (1 - alpha) * lm + alpha * llm.
+    Returns (best, nbest_out) or (best, nbest_out, confidence); nbest_out entries are 'sentence;ac;lm;llm;total'.  Empty
+    hypotheses are skipped, and -- as in the reference -- nbest_out still pairs nbest[i] with the i-th kept hypothesis' scores."""
+    ctx = current_context_str if current_context_str is not None and len(current_context_str.split()) > 0 else None
+    hyps, ac, old_lm = [], [], []
+    for e in nbest:
+        h = e[0].strip()
+        if not h:
+            continue
+        if ctx is not None:
+            h = ctx + " " + h
+        hyps.append(_normalise(h))
+        ac.append(e[1])
+        old_lm.append(e[2])
+    if not hyps:
+        logging.error("gpt2_lm_decode: no hypotheses")
+        return ("", [], 0.0) if returnConfidence else ("", [])
+    ac, old_lm = np.array(ac), np.array(old_lm)
+    try:
+        new_lm = np.array(rescore_with_gpt2(model, tokenizer, device, hyps, length_penalty))
+    except Exception as e:   # the reference retries in five slices, then gives up with zeros
+        logging.error(f"OPT rescore failed: {e}")
+        try:
+            step = int(np.ceil(len(hyps) / 5))
+            parts = []
+            for i in range(0, len(hyps), step):
+                parts.extend(rescore_with_gpt2(model, tokenizer, device, hyps[i:i + step], length_penalty))
+            new_lm = np.array(parts)
+        except Exception as e2:
+            logging.error(f"OPT rescore failed: {e2}")
+            new_lm = np.zeros(len(hyps))
+    if ctx is not None:
+        hyps = [h[len(ctx) + 1:] for h in hyps]
+    total = acoustic_scale * ac + (1 - alpha) * old_lm + alpha * new_lm
+    best = int(np.argmax(total))
+    n_out = min(len(nbest), len(new_lm), len(total))
+    out = [";".join(map(str, [nbest[i][0], nbest[i][1], nbest[i][2], new_lm[i], total[i]])) for i in range(n_out)]
+    if not returnConfidence:
+        return hyps[best], out
+    p = np.exp(total - np.max(total))
+    return hyps[best], out, p[best] / np.sum(p)
+
+
+# ---- checkpoint loading -------------------------------------------------------------------------------------------------
+def resolve_model_dir(model_name: str, cache_dir: Optional[str] = None) -> str:
+    """The local directory of a checkpoint: model_name itself, or its snapshot in the hub-cache layout
+    (<cache>/models--org--name/snapshots/<revision>/) under cache_dir (default: $HF_HUB_CACHE, $HF_HOME/hub,
+    ~/.cache/huggingface/hub).  Never downloads."""
+    if os.path.isdir(model_name):
+        return model_name
+    caches = [cache_dir] if cache_dir else [os.environ.get("HF_HUB_CACHE"),
+                                             os.path.join(os.environ.get("HF_HOME", os.path.expanduser("~/.cache/huggingface")), "hub")]
+    tried = []
+    for c in caches:
+        if not c:
+            continue
+        repo = os.path.join(c, "models--" + model_name.replace("/", "--"))
+        tried.append(repo)
+        snaps = os.path.join(repo, "snapshots")
+        if not os.path.isdir(snaps):
+            continue
+        ref = os.path.join(repo, "refs", "main")
+        if os.path.exists(ref):
+            with open(ref) as f:
+                cand = os.path.join(snaps, f.read().strip())
+            if os.path.isdir(cand):
+                return cand
+        revs = sorted(os.listdir(snaps))
+        if revs:
+            return os.path.join(snaps, revs[-1])
+    raise FileNotFoundError(f"build_opt: no local copy of {model_name!r} (looked for a directory of that name and in {tried}); "
+                            "model files are read from disk only, never downloaded")
+
+
+def _load_state_dict(model_dir: str) -> Dict[str, "object"]:
+    import torch
+    def st(path):
+        from safetensors.torch import load_file
+        return load_file(path)
+
+    def pt(path):
+        return torch.load(path, map_location="cpu", weights_only=True)
+    for index, loader in (("model.safetensors.index.json", st), ("pytorch_model.bin.index.json", pt)):
+        p = os.path.join(model_dir, index)
+        if os.path.exists(p):
+            with open(p) as f:
+                files = sorted(set(json.load(f)["weight_map"].values()))
+            sd = {}
+            for fn in files:
+                sd.update(loader(os.path.join(model_dir, fn)))
+            return sd
+    for single, loader in (("model.safetensors", st), ("pytorch_model.bin", pt)):
+        p = os.path.join(model_dir, single)
+        if os.path.exists(p):
+            return loader(p)
+    found = sorted(glob.glob(os.path.join(model_dir, "*.safetensors")) + glob.glob(os.path.join(model_dir, "pytorch_model*.bin")))
+    if len(found) == 1:
+        return (st if found[0].endswith(".safetensors") else pt)(found[0])
+    raise FileNotFoundError(f"build_opt: no weights (*.safetensors or pytorch_model*.bin) in {model_dir}")
+
+
+def opt_dims(cfg: dict) -> dict:
+    """The dimensions b2t_clm_t needs, after refusing what the kernels do not run."""
+    d = int(cfg["hidden_size"])
+    if not cfg.get("do_layer_norm_before", True):
+        raise ValueError("OPT with do_layer_norm_before=False (post-LN, opt-350m) is not supported")
+    if int(cfg.get("word_embed_proj_dim", d)) != d:
+        raise ValueError(f"OPT with word_embed_proj_dim {cfg['word_embed_proj_dim']} != hidden_size {d} (opt-350m's "
+                         "projection layers) is not supported")
+    act = cfg.get("activation_function", "relu")
+    if act != "relu":
+        raise ValueError(f"OPT activation {act!r} is not supported (ReLU only)")
+    heads = int(cfg["num_attention_heads"])
+    if d % heads or d // heads not in HEAD_DIMS:
+        raise ValueError(f"head dim {d}/{heads} is not supported (one of {HEAD_DIMS})")
+    ffn = int(cfg["ffn_dim"])
+    if d % 64 or ffn % 64:
+        raise ValueError(f"hidden_size {d} and ffn_dim {ffn} must be multiples of 64")
+    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=heads, ffn_dim=ffn, vocab=int(cfg["vocab_size"]),
+                max_pos=int(cfg["max_position_embeddings"]))
+
+
+def _pad_rows(w, rows):
+    import torch
+    if w.shape[0] == rows:
+        return w
+    return torch.cat([w, w.new_zeros((rows - w.shape[0],) + tuple(w.shape[1:]))], 0)
+
+
+def _rup(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
+
+
+def device_layout(state: dict, dims: dict) -> Dict[str, "object"]:
+    """Host (CPU) fp16 tensors in the layout of b2t_clm_t from an OPT state dict (keys with or without the 'model.' prefix,
+    lm_head tied to embed_tokens).  Names: embed_tokens, embed_positions, final_ln_w, final_ln_b, layers.<i>.<field>."""
+    import torch
+    sd = {}
+    for k, v in state.items():
+        sd[k[len("model."):] if k.startswith("model.") else k] = v
+    d, ffn, V = dims["d_model"], dims["ffn_dim"], dims["vocab"]
+
+    def get(name, shape=None, default=None):
+        if name not in sd:
+            if default is None:
+                raise KeyError(f"OPT checkpoint lacks {name}")
+            return default
+        t = sd[name].detach().to("cpu", torch.float16).contiguous()
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    ones, zeros = torch.ones(d, dtype=torch.float16), torch.zeros(d, dtype=torch.float16)
+    emb = get("decoder.embed_tokens.weight", (V, d))
+    if "lm_head.weight" in sd and not torch.equal(get("lm_head.weight", (V, d)), emb):
+        raise ValueError("OPT checkpoint with an lm_head not tied to embed_tokens is not supported")
+    out = {"embed_tokens": _pad_rows(emb, _rup(V, ROWPAD)),
+           "embed_positions": get("decoder.embed_positions.weight", (dims["max_pos"] + 2, d)),
+           "final_ln_w": get("decoder.final_layer_norm.weight", (d,), ones),
+           "final_ln_b": get("decoder.final_layer_norm.bias", (d,), zeros)}
+    for i in range(dims["n_layers"]):
+        p = f"decoder.layers.{i}."
+        lin = lambda n, shp: get(p + n + ".weight", shp)
+        bias = lambda n, sz: get(p + n + ".bias", (sz,), torch.zeros(sz, dtype=torch.float16))
+        L = {"ln1_w": get(p + "self_attn_layer_norm.weight", (d,), ones), "ln1_b": get(p + "self_attn_layer_norm.bias", (d,), zeros),
+             "qkv_w": _pad_rows(torch.cat([lin("self_attn.q_proj", (d, d)), lin("self_attn.k_proj", (d, d)),
+                                           lin("self_attn.v_proj", (d, d))], 0), _rup(3 * d, ROWPAD)),
+             "qkv_b": torch.cat([bias("self_attn.q_proj", d), bias("self_attn.k_proj", d), bias("self_attn.v_proj", d)]),
+             "out_w": _pad_rows(lin("self_attn.out_proj", (d, d)), _rup(d, ROWPAD)), "out_b": bias("self_attn.out_proj", d),
+             "ln2_w": get(p + "final_layer_norm.weight", (d,), ones), "ln2_b": get(p + "final_layer_norm.bias", (d,), zeros),
+             "fc1_w": _pad_rows(lin("fc1", (ffn, d)), _rup(ffn, ROWPAD)), "fc1_b": bias("fc1", ffn),
+             "fc2_w": _pad_rows(lin("fc2", (d, ffn)), _rup(d, ROWPAD)), "fc2_b": bias("fc2", d)}
+        for f in _LAYER_FIELDS:
+            out[f"layers.{i}.{f}"] = L[f]
+    return out
+
+
+def load_opt_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host fp16 tensors in the device layout) of the checkpoint in model_dir."""
+    with open(os.path.join(model_dir, "config.json")) as f:
+        cfg = json.load(f)
+    dims = opt_dims(cfg)
+    return dims, device_layout(_load_state_dict(model_dir), dims)
+
+
+class OptScorer:
+    """An OPT decoder on the GPU in the b2t_clm_t layout; `score` runs b2t_clm_score_f16 on packed ids."""
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda"):
+        import torch
+        import b2t_native as N
+        self.dims = dict(dims)
+        self.device = torch.device(device)
+        self.w = {k: v.to(self.device, torch.float16).contiguous() for k, v in arrays.items()}
+        self._layers = (N.ClmLayer * max(1, dims["n_layers"]))()
+        for i in range(dims["n_layers"]):
+            for f in _LAYER_FIELDS:
+                setattr(self._layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
+        self.desc = N.ClmDesc(dims["n_layers"], dims["d_model"], dims["n_heads"], dims["ffn_dim"], dims["vocab"], dims["max_pos"],
+                              self.w["embed_tokens"].data_ptr(), self.w["embed_positions"].data_ptr(),
+                              self.w["final_ln_w"].data_ptr(), self.w["final_ln_b"].data_ptr(), self._layers)
+        self._ws = None
+
+    def eval(self):   # the reference calls model.eval(); scoring has no training mode
+        return self
+
+    def _run(self, ids_list, want_tokens: bool):
+        import ctypes as C
+        import torch
+        import b2t_native as N
+        lib = N.load()
+        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in ids_list]
+        if not seqs:
+            return np.zeros(0, np.float32), np.zeros(0, np.int64), None
+        lens = np.array([len(s) for s in seqs], dtype=np.int64)
+        ids = np.ascontiguousarray(np.concatenate(seqs).astype(np.int32))
+        off = np.zeros(len(seqs) + 1, dtype=np.int32)
+        off[1:] = np.cumsum(lens)
+        if int(lens.min()) < 1:
+            raise ValueError("OptScorer: empty token sequence")
+        if int(off[-1]) != int(lens.sum()) or lens.sum() > np.iinfo(np.int32).max:
+            raise ValueError("OptScorer: too many tokens")
+        need = lib.b2t_clm_ws_bytes(C.byref(self.desc), int(off[-1]), len(seqs))
+        if need == 0:
+            raise RuntimeError(f"b2t_clm_ws_bytes: invalid sizes: {N.last_error()}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        scores = torch.empty(len(seqs), dtype=torch.float32, device=self.device)
+        tok = torch.empty(int(off[-1]), dtype=torch.float32, device=self.device) if want_tokens else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            N.check(lib.b2t_clm_score_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs), scores.data_ptr(),
+                                          tok.data_ptr() if tok is not None else None, self._ws.data_ptr(), self._ws.numel(),
+                                          stream), "b2t_clm_score_f16")
+            s = scores.cpu().numpy()
+            t = tok.cpu().numpy() if tok is not None else None
+        return s, lens, t
+
+    def score(self, ids_list, length_penalty: float = 0.0) -> np.ndarray:
+        """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores."""
+        s, lens, _ = self._run(ids_list, False)
+        return s.astype(np.float32) - (lens * float(length_penalty)).astype(np.float32)
+
+    def token_logprobs(self, ids_list) -> List[np.ndarray]:
+        """Per sequence the fp32 log-prob of each token given its prefix (0 for the first token)."""
+        _, lens, t = self._run(ids_list, True)
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return [t[off[i]:off[i + 1]] for i in range(len(lens))]
+
+
+def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda"):
+    """(OptScorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16)."""
+    model_dir = resolve_model_dir(model_name, cache_dir)
+    dims, arrays = load_opt_arrays(model_dir)
+    from transformers import AutoTokenizer
+    tok = AutoTokenizer.from_pretrained(model_dir, local_files_only=True)
+    tok.padding_side = "right"
+    if tok.pad_token is None:
+        tok.pad_token = tok.eos_token
+    return OptScorer(dims, arrays, device), tok
+
+
+class WordTokenizer:
+    """A whitespace word-level tokenizer with the call shape of a HF tokenizer (input_ids / attention_mask, BOS first): id =
+    a fixed table entry, else a CRC32 bucket.  For synthetic models (tests, benchmarks) that have no BPE files."""
+
+    def __init__(self, vocab_size: int, bos_id: int = 2, pad_id: int = 1, first_id: int = 4, words: Sequence[str] = ()):
+        self.vocab_size, self.bos_id, self.pad_id, self.first_id = vocab_size, bos_id, pad_id, first_id
+        self.table = {w: first_id + i for i, w in enumerate(words)}
+
+    def word_id(self, w: str) -> int:
+        import zlib
+        if w in self.table:
+            return self.table[w]
+        return self.first_id + zlib.crc32(w.encode()) % (self.vocab_size - self.first_id)
+
+    def __call__(self, texts, return_tensors=None, padding=False):
+        if isinstance(texts, str):
+            texts = [texts]
+        rows = [[self.bos_id] + [self.word_id(w) for w in t.split()] for t in texts]
+        if padding or return_tensors is not None:
+            n = max(len(r) for r in rows)
+            mask = [[1] * len(r) + [0] * (n - len(r)) for r in rows]
+            rows = [r + [self.pad_id] * (n - len(r)) for r in rows]
+        else:
+            mask = [[1] * len(r) for r in rows]
+        if return_tensors == "pt":
+            import torch
+            return {"input_ids": torch.tensor(rows), "attention_mask": torch.tensor(mask)}
+        if return_tensors == "np":
+            return {"input_ids": np.array(rows), "attention_mask": np.array(mask)}
+        return {"input_ids": rows, "attention_mask": mask}
