@@ -6,7 +6,9 @@
 //   - weights are stored fp16 (as the checkpoint and the reference's torch_dtype=float16 hold them);
 //   - GEMM operands are fp16, accumulation fp32 (v_mfma_f32_32x32x16_f16);
 //   - the residual stream, LayerNorm statistics, softmax / log-softmax and the per-sequence sums are fp32;
-//   - the LayerNorm, attention and fc1 outputs (the next GEMM's operands) and q / k / v are rounded to fp16.
+//   - the LayerNorm, attention and fc1 outputs (the next GEMM's operands) and q / k / v are rounded to fp16, and so are the
+//     attention's probabilities exp(s - m) per 32-key block, m the running maximum, as the P.V operand (its normaliser sums
+//     them unrounded).
 //   Every output element is computed by one thread in a fixed order that depends only on its own row: a sequence's score is
 //   bit-identical alone or anywhere in any batch.
 //
@@ -187,10 +189,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
 
 constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * sizeof(_Float16); }
 
+// B2T_CLM_GEMM_256 (read on every call): 0 = 128 x 128 tiles always, 1 or unset = 256 x 256 tiles where they fill the chip,
+// 2 = 256 x 256 tiles always.  Both kernels give bit-identical results (same k order per output element); every A operand and
+// weight is padded to ROWPAD = 256 rows, so either tile reads inside its buffers at any M and N.
 template <int EP>
 int launch_gemm(const ClmGemm& g, hipStream_t s) {
+  const char* e = getenv("B2T_CLM_GEMM_256");
+  const int mode = e ? atoi(e) : 1;
   const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
-  if ((long long)m256 * n256 >= 256) {   // the 256-tiles fill the chip's 256 CUs: one 8-wave workgroup per CU
+  if (mode == 2 || (mode != 0 && (long long)m256 * n256 >= 256)) {   // the 256-tiles fill the chip's 256 CUs: one 8-wave workgroup per CU
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<256, 256, 2, 4, EP>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));

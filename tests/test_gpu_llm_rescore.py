@@ -63,21 +63,23 @@ def test_batch_invariance():
     assert a.tobytes() == b.tobytes()
 
 
-def _random_opt(d, heads, ffn, vocab, max_pos, seed):
+def _random_opt(d, heads, ffn, vocab, max_pos, seed, n_layers=1):
+    """A random pre-LN OPT state dict (fp16, on the GPU) and its dims.  The scales give log-prob spreads of about 2."""
     import torch
     g = torch.Generator(device="cuda").manual_seed(seed)
     rn = lambda *s, std: (torch.randn(*s, generator=g, device="cuda") * std).half()
     st = {"decoder.embed_tokens.weight": rn(vocab, d, std=2.0 / d ** 0.5), "decoder.embed_positions.weight": rn(max_pos + 2, d, std=0.5),
           "decoder.final_layer_norm.weight": (1 + rn(d, std=0.2).float()).half(), "decoder.final_layer_norm.bias": rn(d, std=0.1)}
-    p = "decoder.layers.0."
-    for n, (o, i) in {"self_attn.q_proj": (d, d), "self_attn.k_proj": (d, d), "self_attn.v_proj": (d, d),
-                      "self_attn.out_proj": (d, d), "fc1": (ffn, d), "fc2": (d, ffn)}.items():
-        st[p + n + ".weight"] = rn(o, i, std=1.0 / i ** 0.5)
-        st[p + n + ".bias"] = rn(o, std=0.1)
-    for n in ("self_attn_layer_norm", "final_layer_norm"):
-        st[p + n + ".weight"] = (1 + rn(d, std=0.2).float()).half()
-        st[p + n + ".bias"] = rn(d, std=0.1)
-    return st, dict(n_layers=1, d_model=d, n_heads=heads, ffn_dim=ffn, vocab=vocab, max_pos=max_pos)
+    for l in range(n_layers):
+        p = f"decoder.layers.{l}."
+        for n, (o, i) in {"self_attn.q_proj": (d, d), "self_attn.k_proj": (d, d), "self_attn.v_proj": (d, d),
+                          "self_attn.out_proj": (d, d), "fc1": (ffn, d), "fc2": (d, ffn)}.items():
+            st[p + n + ".weight"] = rn(o, i, std=1.0 / i ** 0.5)
+            st[p + n + ".bias"] = rn(o, std=0.1)
+        for n in ("self_attn_layer_norm", "final_layer_norm"):
+            st[p + n + ".weight"] = (1 + rn(d, std=0.2).float()).half()
+            st[p + n + ".bias"] = rn(d, std=0.1)
+    return st, dict(n_layers=n_layers, d_model=d, n_heads=heads, ffn_dim=ffn, vocab=vocab, max_pos=max_pos)
 
 
 def _torch_fp32_logp(st, dims, seq):
