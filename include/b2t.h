@@ -633,6 +633,34 @@ size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, int n_seq);
 int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                       float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same scoring over a shared-prefix token tree (csrc/causal_lm_tree.hip) --------------------------------------
+ * The candidates of an n-best list repeat each other's prefixes (and with contextual decoding all start with the same
+ * context).  A NODE is a distinct token prefix: token t of sequence a and token u of sequence b are the same node iff they
+ * sit at the same position p and the two sequences have identical ids at positions 0..p.  In a causal LM a node's hidden
+ * state, K and V are the same in every sequence that passes through it, so the tree path computes n_nodes rows instead of
+ * n_tokens; its results are bit-identical to b2t_clm_score_f16's.  Opt-in: the flat call is unchanged.
+ *
+ * HOST function (no GPU): the plan.  Nodes are numbered in order of first appearance in the packed ids (no sharing:
+ * node_of_token[t] == t); sequences with different first tokens give several roots; duplicates share all their nodes.
+ * node_of_token[n_tokens]; parent_of_node[cap], -1 for roots; *n_nodes = the number of nodes.  Returns 0; -2 when cap is
+ * too small (node_of_token and *n_nodes are still complete, parent_of_node holds its first cap entries and nothing is
+ * written past cap); 2 on a null argument, seq_off[0] != 0 or an empty sequence. */
+int b2t_clm_tree_plan_host(const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                           int32_t* node_of_token, int32_t* parent_of_node, long long cap, long long* n_nodes);
+/* Workspace bytes of b2t_clm_score_tree_f16 for n_nodes nodes of n_tokens tokens in n_seq sequences (0 if the sizes are
+ * invalid: n_nodes < 1, n_nodes > n_tokens, n_seq < 1, n_seq > n_tokens); non-decreasing in each argument.  n_nodes =
+ * n_tokens is always enough for a list of n_tokens tokens. */
+size_t b2t_clm_tree_ws_bytes(const b2t_clm_t* model, long long n_nodes, long long n_tokens, int n_seq);
+/* b2t_clm_score_f16 over the tree: same inputs, same outputs in the same layout (tok_logp_out [n_tokens] in the caller's
+ * packed order, 0 at each first token), same refusals before any launch; the workspace needed is b2t_clm_tree_ws_bytes of
+ * the plan's n_nodes, which *n_nodes_out (optional, host) receives.  The call plans the tree itself.  Embedding, LayerNorm,
+ * the GEMMs (B2T_CLM_GEMM_256 applies) and the LM head are the flat path's kernels over n_nodes rows -- the head has one row
+ * per non-root node, source = its parent's row; the attention walks each sequence's path and writes only the rows that
+ * sequence is the first to reach; the per-sequence sums follow the path in token order. */
+int b2t_clm_score_tree_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                           float* scores_out, float* tok_logp_out, long long* n_nodes_out,
+                           void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,9 @@ _SIGNATURES = {
                                                 C.c_float, C.c_float, C.c_float, VP, VP]),
     "b2t_clm_ws_bytes": (C.c_size_t, [C.POINTER(ClmDesc), LL, C.c_int]),
     "b2t_clm_score_f16": (C.c_int, [C.POINTER(ClmDesc), VP, VP, C.c_int, VP, VP, VP, C.c_size_t, VP]),
+    "b2t_clm_tree_plan_host": (C.c_int, [VP, VP, C.c_int, VP, VP, LL, C.POINTER(LL)]),
+    "b2t_clm_tree_ws_bytes": (C.c_size_t, [C.POINTER(ClmDesc), LL, LL, C.c_int]),
+    "b2t_clm_score_tree_f16": (C.c_int, [C.POINTER(ClmDesc), VP, VP, C.c_int, VP, VP, C.POINTER(LL), VP, C.c_size_t, VP]),
 }
 
 

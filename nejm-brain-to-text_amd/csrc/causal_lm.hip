@@ -22,10 +22,13 @@
 // LDS with 144-byte rows, one barrier per 64-k tile) as a sibling fp16 kernel, 128 x 128 (4 waves) and 256 x 256 (8 waves)
 // tiles.  Operands are never packed at run time: the LayerNorm / attention / fc1 kernels write the k-contiguous, row-padded
 // fp16 A operand directly, and nn.Linear weights ([N][K], k-contiguous) are padded once at load time to 256 rows.
+//
+// The host-side pieces the shared-prefix tree path (causal_lm_tree.hip) reuses -- launch_gemm, the embed / LayerNorm / head
+// launchers, clm_check_model -- have external linkage and are declared in clm_internal.h; the kernels stay private to this file.
 #include <math.h>
 #include <vector>
 
-#include "common.h"
+#include "clm_internal.h"
 
 namespace b2t {
 namespace {
@@ -34,22 +37,9 @@ using f32x16 = float __attribute__((ext_vector_type(16)));
 using half8 = _Float16 __attribute__((ext_vector_type(8)));
 
 constexpr int CK = 64, CPITCH = CK + 8;      // k tile; LDS row pitch in fp16 elements (144 B)
-constexpr int ROWPAD = 256;                   // A operands and weights are padded to this many rows
+constexpr int ROWPAD = CLM_ROWPAD;                  // A operands and weights are padded to this many rows
 
-enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3 };
-
-struct ClmGemm {
-  const _Float16* A;      // [round_up(M, 256)][K]
-  const _Float16* B;      // [round_up(N, 256)][K]
-  int M, N, K;            // K % 64 == 0
-  const _Float16* bias;   // [N] or null
-  _Float16* out16;        // EP_F16 / EP_RELU: [M][ldo]
-  float* resid;           // EP_RESID: [M][ldo] += C
-  int ldo;
-  float qscale; int qcols;   // EP_F16: columns < qcols are multiplied by qscale after the bias (OPT's q scaling)
-  float* pmax; float* psum;  // EP_HEAD: [M][ncg] per 64-column group max / sum exp(v - max)
-  float* tlogit; const int* tgt; int ncg;   // EP_HEAD: tlogit[r] = C[r][tgt[r]]
-};
+// ClmGemm (the GEMM's arguments) and the EP_* epilogue ids: clm_internal.h
 
 __device__ __forceinline__ float warp32_max(float v) {
 #pragma unroll
@@ -189,6 +179,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
 
 constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * sizeof(_Float16); }
 
+}  // namespace
+
 // B2T_CLM_GEMM_256 (read on every call): 0 = 128 x 128 tiles always, 1 or unset = 256 x 256 tiles where they fill the chip,
 // 2 = 256 x 256 tiles always.  Both kernels give bit-identical results (same k order per output element); every A operand and
 // weight is padded to ROWPAD = 256 rows, so either tile reads inside its buffers at any M and N.
@@ -212,6 +204,12 @@ int launch_gemm(const ClmGemm& g, hipStream_t s) {
   B2T_CHECK_LAUNCH("clm_gemm_kernel");
   return 0;
 }
+template int launch_gemm<EP_F16>(const ClmGemm&, hipStream_t);
+template int launch_gemm<EP_RELU>(const ClmGemm&, hipStream_t);
+template int launch_gemm<EP_RESID>(const ClmGemm&, hipStream_t);
+template int launch_gemm<EP_HEAD>(const ClmGemm&, hipStream_t);
+
+namespace {
 
 __device__ __forceinline__ float block_sum256(float v, float* red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -404,7 +402,9 @@ ClmLayout clm_layout(const b2t_clm_t* m, long long M, int n_seq) {
   return L;
 }
 
-int check_model(const b2t_clm_t* m) {
+}  // namespace
+
+int clm_check_model(const b2t_clm_t* m) {
   B2T_REQUIRE(m, "b2t_clm: null model");
   B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 && m->max_pos > 0,
               "b2t_clm: bad dimensions (layers %d, d %d, heads %d, ffn %d, vocab %d, max_pos %d)", m->n_layers, m->d_model,
@@ -424,7 +424,28 @@ int check_model(const b2t_clm_t* m) {
   return 0;
 }
 
-}  // namespace
+// the launchers clm_internal.h declares, used below and by the tree path (causal_lm_tree.hip)
+int clm_launch_embed(const int* ids, const int* pos, const _Float16* et, const _Float16* ep, float* resid, int d, long long rows,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(clm_embed_kernel, dim3((unsigned)rows), dim3(256), 0, s, ids, pos, et, ep, resid, d);
+  B2T_CHECK_LAUNCH("clm_embed_kernel");
+  return 0;
+}
+
+int clm_launch_layernorm(const float* x, const int* rowmap, long long rows, const _Float16* w, const _Float16* b, _Float16* out,
+                         int d, hipStream_t s) {
+  hipLaunchKernelGGL(clm_layernorm_kernel, dim3((unsigned)rup(rows, ROWPAD)), dim3(256), 0, s, x, rowmap, (int)rows, w, b, out, d);
+  B2T_CHECK_LAUNCH("clm_layernorm_kernel");
+  return 0;
+}
+
+int clm_launch_head_combine(const float* pmax, const float* psum, const float* tlogit, int ncg, float* logp, long long rows,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(clm_head_combine_kernel, dim3((unsigned)rows), dim3(256), 0, s, pmax, psum, tlogit, ncg, logp);
+  B2T_CHECK_LAUNCH("clm_head_combine_kernel");
+  return 0;
+}
+
 }  // namespace b2t
 
 using namespace b2t;
@@ -436,7 +457,7 @@ extern "C" size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, i
 
 extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                  float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = check_model(model)) return rc;
+  if (int rc = clm_check_model(model)) return rc;
   const b2t_clm_t& m = *model;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "b2t_clm_score_f16: null argument");
   B2T_REQUIRE(n_seq >= 1, "b2t_clm_score_f16: n_seq %d < 1", n_seq);
@@ -485,15 +506,11 @@ extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host
   _Float16* hb = reinterpret_cast<_Float16*>(base + L.hbuf);
   const _Float16* et = static_cast<const _Float16*>(m.embed_tokens);
 
-  hipLaunchKernelGGL(clm_embed_kernel, dim3((unsigned)M), dim3(256), 0, s, d_ids, d_pos, et,
-                     static_cast<const _Float16*>(m.embed_positions), resid, d);
-  B2T_CHECK_LAUNCH("clm_embed_kernel");
+  if (int rc = clm_launch_embed(d_ids, d_pos, et, static_cast<const _Float16*>(m.embed_positions), resid, d, M, s)) return rc;
   auto H16 = [](const void* p) { return static_cast<const _Float16*>(p); };
   for (int l = 0; l < m.n_layers; ++l) {
     const b2t_clm_layer_t& w = m.layers_host[l];
-    hipLaunchKernelGGL(clm_layernorm_kernel, dim3((unsigned)L.Mp), dim3(256), 0, s, resid, (const int*)nullptr, (int)M,
-                       H16(w.ln1_w), H16(w.ln1_b), x16, d);
-    B2T_CHECK_LAUNCH("clm_layernorm_kernel");
+    if (int rc = clm_launch_layernorm(resid, nullptr, M, H16(w.ln1_w), H16(w.ln1_b), x16, d, s)) return rc;
     ClmGemm g{};
     g.A = x16; g.B = H16(w.qkv_w); g.M = (int)M; g.N = 3 * d; g.K = d; g.bias = H16(w.qkv_b); g.out16 = qkv; g.ldo = 3 * d;
     g.qscale = 1.0f / sqrtf((float)hd); g.qcols = d;
@@ -505,9 +522,7 @@ extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host
     g = ClmGemm{};
     g.A = x16; g.B = H16(w.out_w); g.M = (int)M; g.N = d; g.K = d; g.bias = H16(w.out_b); g.resid = resid; g.ldo = d;
     if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
-    hipLaunchKernelGGL(clm_layernorm_kernel, dim3((unsigned)L.Mp), dim3(256), 0, s, resid, (const int*)nullptr, (int)M,
-                       H16(w.ln2_w), H16(w.ln2_b), x16, d);
-    B2T_CHECK_LAUNCH("clm_layernorm_kernel");
+    if (int rc = clm_launch_layernorm(resid, nullptr, M, H16(w.ln2_w), H16(w.ln2_b), x16, d, s)) return rc;
     g = ClmGemm{};
     g.A = x16; g.B = H16(w.fc1_w); g.M = (int)M; g.N = F; g.K = d; g.bias = H16(w.fc1_b); g.out16 = hb; g.ldo = F;
     if (int rc = launch_gemm<EP_RELU>(g, s)) return rc;
@@ -517,16 +532,13 @@ extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host
   }
   float* logp = reinterpret_cast<float*>(base + L.logp);
   if (Mh > 0) {
-    hipLaunchKernelGGL(clm_layernorm_kernel, dim3((unsigned)rup(Mh, ROWPAD)), dim3(256), 0, s, resid, (const int*)d_src, (int)Mh,
-                       H16(m.final_ln_w), H16(m.final_ln_b), x16, d);
-    B2T_CHECK_LAUNCH("clm_layernorm_kernel");
+    if (int rc = clm_launch_layernorm(resid, d_src, Mh, H16(m.final_ln_w), H16(m.final_ln_b), x16, d, s)) return rc;
     ClmGemm g{};
     g.A = x16; g.B = et; g.M = (int)Mh; g.N = m.vocab; g.K = d;
     g.pmax = reinterpret_cast<float*>(base + L.pmax); g.psum = reinterpret_cast<float*>(base + L.psum);
     g.tlogit = reinterpret_cast<float*>(base + L.tlogit); g.tgt = d_tgt; g.ncg = (int)L.ncg;
     if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
-    hipLaunchKernelGGL(clm_head_combine_kernel, dim3((unsigned)Mh), dim3(256), 0, s, g.pmax, g.psum, g.tlogit, g.ncg, logp);
-    B2T_CHECK_LAUNCH("clm_head_combine_kernel");
+    if (int rc = clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, logp, Mh, s)) return rc;
   }
   hipLaunchKernelGGL(clm_seq_sum_kernel, dim3(n_seq), dim3(64), 0, s, logp, d_soff, d_hoff, scores_out, tok_logp_out);
   B2T_CHECK_LAUNCH("clm_seq_sum_kernel");

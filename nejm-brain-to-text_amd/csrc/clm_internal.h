@@ -1,0 +1,46 @@
+// clm_internal.h — host-side pieces of the causal-LM forward shared by causal_lm.hip (the flat scoring path, which defines
+// them) and causal_lm_tree.hip (the shared-prefix tree path).  The kernels themselves stay private to causal_lm.hip; these
+// are their launchers, so the GEMM is instantiated once.
+#pragma once
+#include "common.h"
+
+namespace b2t {
+
+constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this many rows
+
+enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3 };
+
+struct ClmGemm {
+  const _Float16* A;      // [round_up(M, 256)][K]
+  const _Float16* B;      // [round_up(N, 256)][K]
+  int M, N, K;            // K % 64 == 0
+  const _Float16* bias;   // [N] or null
+  _Float16* out16;        // EP_F16 / EP_RELU: [M][ldo]
+  float* resid;           // EP_RESID: [M][ldo] += C
+  int ldo;
+  float qscale; int qcols;   // EP_F16: columns < qcols are multiplied by qscale after the bias (OPT's q scaling)
+  float* pmax; float* psum;  // EP_HEAD: [M][ncg] per 64-column group max / sum exp(v - max)
+  float* tlogit; const int* tgt; int ncg;   // EP_HEAD: tlogit[r] = C[r][tgt[r]]
+};
+
+// The tile rule (B2T_CLM_GEMM_256) lives in the definition, causal_lm.hip; instantiated there for the four epilogues.
+template <int EP>
+int launch_gemm(const ClmGemm& g, hipStream_t s);
+extern template int launch_gemm<EP_F16>(const ClmGemm&, hipStream_t);
+extern template int launch_gemm<EP_RELU>(const ClmGemm&, hipStream_t);
+extern template int launch_gemm<EP_RESID>(const ClmGemm&, hipStream_t);
+extern template int launch_gemm<EP_HEAD>(const ClmGemm&, hipStream_t);
+
+// resid[r] = embed_tokens[ids[r]] + embed_positions[pos[r] + 2] for r < rows
+int clm_launch_embed(const int* ids, const int* pos, const _Float16* et, const _Float16* ep, float* resid, int d, long long rows,
+                     hipStream_t s);
+// out[r] = fp16(LayerNorm(x[rowmap ? rowmap[r] : r])) for r < rows, zeros for rows <= r < round_up(rows, 256)
+int clm_launch_layernorm(const float* x, const int* rowmap, long long rows, const _Float16* w, const _Float16* b, _Float16* out,
+                         int d, hipStream_t s);
+// logp[r] = tlogit[r] - logsumexp over the row's 64-column groups, r < rows
+int clm_launch_head_combine(const float* pmax, const float* psum, const float* tlogit, int ncg, float* logp, long long rows,
+                            hipStream_t s);
+// dimensions, head dim and weight pointers of a model descriptor (0, or an error with the message set)
+int clm_check_model(const b2t_clm_t* m);
+
+}  // namespace b2t

@@ -1,6 +1,7 @@
 """OPT n-best rescoring: the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
 :127-162, gpt2_lm_decode :165-251, get_string_differences :273-311, augment_nbest :327-411) with the causal-LM forward on the
-HIP path (b2t_clm_score_f16, csrc/causal_lm.hip).
+HIP path (b2t_clm_score_f16, csrc/causal_lm.hip; opt-in b2t_clm_score_tree_f16, csrc/causal_lm_tree.hip, which computes the
+prefixes the candidates share once).
 
 Call surfaces are the reference's: `build_opt(model_name, cache_dir, device)` returns `(model, tokenizer)`, and the three
 functions take them as the reference's do.  `model` here is an `OptScorer`: the checkpoint's fp16 weights converted once into
@@ -317,13 +318,18 @@ def load_opt_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
 
 
 class OptScorer:
-    """An OPT decoder on the GPU in the b2t_clm_t layout; `score` runs b2t_clm_score_f16 on packed ids."""
+    """An OPT decoder on the GPU in the b2t_clm_t layout; `score` runs b2t_clm_score_f16 on packed ids, or, with
+    share_prefixes, b2t_clm_score_tree_f16: the same forward over the list's shared-prefix token tree (each distinct prefix
+    computed once; results bit-identical to the flat call).  `share_prefixes` here is the default of `score` and
+    `token_logprobs`; after a call `last_stats` = {"tokens": packed tokens, "nodes": rows computed}."""
 
-    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda"):
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False):
         import torch
         import b2t_native as N
         self.dims = dict(dims)
         self.device = torch.device(device)
+        self.share_prefixes = bool(share_prefixes)
+        self.last_stats = None
         self.w = {k: v.to(self.device, torch.float16).contiguous() for k, v in arrays.items()}
         self._layers = (N.ClmLayer * max(1, dims["n_layers"]))()
         for i in range(dims["n_layers"]):
@@ -337,13 +343,15 @@ class OptScorer:
     def eval(self):   # the reference calls model.eval(); scoring has no training mode
         return self
 
-    def _run(self, ids_list, want_tokens: bool):
+    def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None):
         import ctypes as C
         import torch
         import b2t_native as N
         lib = N.load()
+        tree = self.share_prefixes if share_prefixes is None else bool(share_prefixes)
         seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in ids_list]
         if not seqs:
+            self.last_stats = {"tokens": 0, "nodes": 0}
             return np.zeros(0, np.float32), np.zeros(0, np.int64), None
         lens = np.array([len(s) for s in seqs], dtype=np.int64)
         ids = np.ascontiguousarray(np.concatenate(seqs).astype(np.int32))
@@ -353,36 +361,66 @@ class OptScorer:
             raise ValueError("OptScorer: empty token sequence")
         if int(off[-1]) != int(lens.sum()) or lens.sum() > np.iinfo(np.int32).max:
             raise ValueError("OptScorer: too many tokens")
-        need = lib.b2t_clm_ws_bytes(C.byref(self.desc), int(off[-1]), len(seqs))
+        M = int(off[-1])
+        nodes = M
+        if tree:
+            nodes = tree_plan(ids, off)[2]
+            need = lib.b2t_clm_tree_ws_bytes(C.byref(self.desc), nodes, M, len(seqs))
+        else:
+            need = lib.b2t_clm_ws_bytes(C.byref(self.desc), M, len(seqs))
         if need == 0:
             raise RuntimeError(f"b2t_clm_ws_bytes: invalid sizes: {N.last_error()}")
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         scores = torch.empty(len(seqs), dtype=torch.float32, device=self.device)
-        tok = torch.empty(int(off[-1]), dtype=torch.float32, device=self.device) if want_tokens else None
+        tok = torch.empty(M, dtype=torch.float32, device=self.device) if want_tokens else None
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            N.check(lib.b2t_clm_score_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs), scores.data_ptr(),
-                                          tok.data_ptr() if tok is not None else None, self._ws.data_ptr(), self._ws.numel(),
-                                          stream), "b2t_clm_score_f16")
+            if tree:
+                N.check(lib.b2t_clm_score_tree_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs),
+                                                   scores.data_ptr(), tok.data_ptr() if tok is not None else None, None,
+                                                   self._ws.data_ptr(), self._ws.numel(), stream), "b2t_clm_score_tree_f16")
+            else:
+                N.check(lib.b2t_clm_score_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs), scores.data_ptr(),
+                                              tok.data_ptr() if tok is not None else None, self._ws.data_ptr(), self._ws.numel(),
+                                              stream), "b2t_clm_score_f16")
             s = scores.cpu().numpy()
             t = tok.cpu().numpy() if tok is not None else None
+        self.last_stats = {"tokens": M, "nodes": int(nodes)}
         return s, lens, t
 
-    def score(self, ids_list, length_penalty: float = 0.0) -> np.ndarray:
-        """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores."""
-        s, lens, _ = self._run(ids_list, False)
+    def score(self, ids_list, length_penalty: float = 0.0, share_prefixes: Optional[bool] = None) -> np.ndarray:
+        """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores.
+        share_prefixes: None = the scorer's own setting."""
+        s, lens, _ = self._run(ids_list, False, share_prefixes)
         return s.astype(np.float32) - (lens * float(length_penalty)).astype(np.float32)
 
-    def token_logprobs(self, ids_list) -> List[np.ndarray]:
+    def token_logprobs(self, ids_list, share_prefixes: Optional[bool] = None) -> List[np.ndarray]:
         """Per sequence the fp32 log-prob of each token given its prefix (0 for the first token)."""
-        _, lens, t = self._run(ids_list, True)
+        _, lens, t = self._run(ids_list, True, share_prefixes)
         off = np.concatenate([[0], np.cumsum(lens)])
         return [t[off[i]:off[i + 1]] for i in range(len(lens))]
 
 
-def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda"):
-    """(OptScorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16)."""
+def tree_plan(ids, seq_off, cap: Optional[int] = None):
+    """b2t_clm_tree_plan_host on packed int32 ids / offsets (host only, no GPU): (node_of_token, parent_of_node, n_nodes).
+    A node is a distinct token prefix, numbered by first appearance; parent_of_node is -1 at roots."""
+    import ctypes as C
+    import b2t_native as N
+    ids = np.ascontiguousarray(ids, np.int32)
+    off = np.ascontiguousarray(seq_off, np.int32)
+    cap = len(ids) if cap is None else int(cap)
+    node = np.empty(len(ids), np.int32)
+    parent = np.empty(max(cap, 1), np.int32)
+    n = C.c_longlong(0)
+    N.check(N.load().b2t_clm_tree_plan_host(ids.ctypes.data, off.ctypes.data, len(off) - 1, node.ctypes.data, parent.ctypes.data,
+                                            cap, C.byref(n)), "b2t_clm_tree_plan_host")
+    return node, parent[:n.value], int(n.value)
+
+
+def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False):
+    """(OptScorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16).
+    share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once."""
     model_dir = resolve_model_dir(model_name, cache_dir)
     dims, arrays = load_opt_arrays(model_dir)
     from transformers import AutoTokenizer
@@ -390,7 +428,7 @@ def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda"):
     tok.padding_side = "right"
     if tok.pad_token is None:
         tok.pad_token = tok.eos_token
-    return OptScorer(dims, arrays, device), tok
+    return OptScorer(dims, arrays, device, share_prefixes), tok
 
 
 class WordTokenizer:

@@ -36,7 +36,10 @@ def _b(v) -> bytes:
 class LocalLMService:
     """decoder: object with Reset() / FinishDecoding() / result() (entries with .sentence, .ac_score, .lm_score).
     decode_fn(decoder, logits[T, C], log_priors, log_blank_penalty): defaults to lm_decoder.DecodeNumpy (HIP path).
-    llm: (model, tokenizer) of llm_rescore.build_opt, used when do_opt is set (then required)."""
+    llm: (model, tokenizer) of llm_rescore.build_opt, used when do_opt is set (then required).  Whether the candidates'
+    shared prefixes -- the context string in front of every one of them above all -- are computed once is the scorer's own
+    setting (build_opt(..., share_prefixes=True) / model.share_prefixes); the service has no parameter for it and its replies
+    are the same either way."""
 
     def __init__(self, decoder, n_classes: int = 41, acoustic_scale: float = 0.35, blank_penalty: float = 90.0,
                  alpha: float = 0.55, nbest: int = 100, input_stream: str = INPUT_STREAM,

@@ -4,6 +4,16 @@ hipBLASLt, SDPA) on the same weights.  OPT-6.7b shape (32 layers, d 4096, 32 x 1
 fp16 weights (~13.3 GB); one "list" = 100 candidates of 10-40 tokens.  Prints one JSON line.
 
   python tools/bench_llm_rescore.py [--layers 32] [--lists 5] [--warmup 2]
+
+The default list is 100 candidates of independent random ids: no two share a prefix beyond BOS, the one shape the service
+never sees.  `--list nbest` draws what augment_nbest produces (a base sentence with single words exchanged), `--context N`
+puts N shared tokens in front of every candidate (contextual decoding), and either of them, or `--tree`, switches to an A/B of
+the flat call against the shared-prefix tree call (b2t_clm_score_tree_f16) in one process: the two alternate list by list
+after a warm-up of both, --reps passes over the lists, and the line reports tokens, nodes and the median / min / max ms per
+list of each, with the largest spread between the repeats of one list
+(hip_ms_per_list = flat, hip_tree_ms_per_list = tree); the torch baseline is not run in that mode.
+
+  python tools/bench_llm_rescore.py --list nbest --context 64 [--lists 7]
 """
 import argparse
 import json
@@ -17,6 +27,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "nejm-brain-to-text_amd"))
 
 
+def random_list(rng, V, cands=100, context=()):
+    """cands candidates of 10-40 independent random tokens, BOS first, behind the shared context tokens."""
+    return [[2] + list(context) + list(rng.integers(4, V, int(n) - 1)) for n in rng.integers(10, 41, cands)]
+
+
+def nbest_list(rng, V, cands=100, context=()):
+    """An n-best list as augment_nbest leaves it: a base sentence of 10-40 random tokens (BOS first, the first candidate), and
+    cands - 1 more made from it by replacing 1-3 positions with another id of that position's confusion set (2-4 ids, the
+    base's among them).  Duplicates may occur, as they may not in the service; the scorer accepts them."""
+    n = int(rng.integers(10, 41)) - 1
+    conf = [rng.choice(np.arange(4, V), size=int(rng.integers(2, 5)), replace=False) for _ in range(n)]
+    base = [int(c[0]) for c in conf]
+    out = [[2] + list(context) + base]
+    for _ in range(cands - 1):
+        cand = list(base)
+        for p in rng.choice(n, size=int(rng.integers(1, 4)), replace=False):
+            cand[p] = int(rng.choice(conf[p][1:]))
+        out.append([2] + list(context) + cand)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=32)
@@ -27,6 +58,10 @@ def main():
     ap.add_argument("--cands", type=int, default=100)
     ap.add_argument("--lists", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--list", choices=("random", "nbest"), default="random", help="candidate generator (nbest: A/B with the tree path)")
+    ap.add_argument("--context", type=int, default=0, help="shared tokens in front of every candidate (A/B with the tree path)")
+    ap.add_argument("--tree", action="store_true", help="A/B flat against tree on the chosen list")
+    ap.add_argument("--reps", type=int, default=3, help="A/B: timed passes over the lists")
     a = ap.parse_args()
     import torch
     import torch.nn.functional as F
@@ -52,8 +87,15 @@ def main():
     sc = R.OptScorer(dims, lay, dev)
     del lay
     rng = np.random.default_rng(0)
-    lists = [[[2] + list(rng.integers(4, V, int(n) - 1)) for n in rng.integers(10, 41, a.cands)] for _ in range(a.lists)]
+    ab = a.tree or a.list != "random" or a.context > 0
+    if not ab:
+        lists = [random_list(rng, V, a.cands) for _ in range(a.lists)]
+    else:   # the context differs from list to list, as the sentences decoded so far do
+        gen = nbest_list if a.list == "nbest" else random_list
+        lists = [gen(rng, V, a.cands, [int(x) for x in rng.integers(4, V, a.context)]) for _ in range(a.lists)]
     ntok = [sum(len(s) for s in l) for l in lists]
+    if ab:
+        return ab_flat_tree(a, sc, lists, ntok)
 
     def torch_score(seqs):   # padded batch, fp16 weights, causal + key-padding mask through SDPA
         B, T = len(seqs), max(len(s) for s in seqs)
@@ -98,6 +140,40 @@ def main():
                       "tokens_per_list": float(np.mean(ntok)), "hip_ms_per_list": round(ms_hip, 2),
                       "torch_fp16_ms_per_list": round(ms_torch, 2), "hip_tflops": round(tf, 1),
                       "speedup_vs_torch": round(ms_torch / ms_hip, 3), "max_abs_score_diff_vs_torch": round(diff, 4)}))
+
+
+def ab_flat_tree(a, sc, lists, ntok):
+    """Flat and tree path on the same lists in this process, alternating list by list, --reps passes over the lists; both
+    warmed up first.  Lists differ in size, so the run-to-run spread is taken per list: the largest max - min over the
+    repeats of one list."""
+    import torch
+    ms = {False: [[] for _ in lists], True: [[] for _ in lists]}
+    nodes, same = [0] * len(lists), True
+    with torch.inference_mode():
+        for i in range(max(1, a.warmup)):
+            for tree in (False, True):
+                sc.score(lists[i % len(lists)], share_prefixes=tree)
+        torch.cuda.synchronize()
+        for _ in range(max(1, a.reps)):
+            for i, l in enumerate(lists):
+                out = {}
+                for tree in (False, True):
+                    t0 = time.perf_counter()
+                    out[tree] = sc.score(l, share_prefixes=tree)   # returns host scores: the call is complete
+                    ms[tree][i].append((time.perf_counter() - t0) * 1e3)
+                nodes[i] = sc.last_stats["nodes"]
+                same = same and out[False].tobytes() == out[True].tobytes()
+    r2 = lambda x: round(float(x), 2)
+    per = {t: [float(np.median(v)) for v in ms[t]] for t in ms}   # per list, median over its repeats
+    st = lambda t: {"median": r2(np.median(per[t])), "min": r2(np.min(per[t])), "max": r2(np.max(per[t])),
+                    "repeat_spread": r2(max(max(v) - min(v) for v in ms[t]))}
+    print(json.dumps({"bench": "llm_rescore_tree", "layers": a.layers, "d": a.d, "heads": a.heads, "ffn": a.ffn, "vocab": a.vocab,
+                      "cands": a.cands, "list": a.list, "context": a.context, "lists": len(lists), "reps": max(1, a.reps),
+                      "tokens": float(np.mean(ntok)), "nodes": float(np.mean(nodes)),
+                      "hip_ms_per_list": st(False)["median"], "hip_tree_ms_per_list": st(True)["median"],
+                      "flat_ms": st(False), "tree_ms": st(True), "per_list_tokens": ntok, "per_list_nodes": nodes,
+                      "per_list_flat_ms": [r2(x) for x in per[False]], "per_list_tree_ms": [r2(x) for x in per[True]],
+                      "scores_bit_identical": bool(same)}))
 
 
 if __name__ == "__main__":
