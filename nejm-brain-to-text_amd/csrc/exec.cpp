@@ -84,27 +84,8 @@ int splitk_for(int M, int N, long long K, int target_blocks) {
   if (v >= 8) v = v / 8 * 8;   // (rounding 7 up to 8 was measured at H = 768: 19.03 -> 19.31 ms, more than one wave of blocks)
   return (int)std::max<long long>(1, v);
 }
-// bf16 mode, round 5: a weight gradient with few output tiles and a long K on the 256 x 256 tile kernel (gemm_bf16p.hip) -- slices
-// so that tiles x slices fill ONE round of 256 workgroups (a multiple of 8 slices where that still fills 200: a slice per XCD), each
-// slice at least 512 deep.  0: stay on 128-tiles (splitk_for).  dW of the shipped shape's layers (2304 x 768 x 7808): 27 tiles x 8
-// instead of 108 x 4; configs[1] (1536 x 512 x 32000): 12 x 21 instead of 48 x 8.  OPT-IN (B2T_SPLITK256=1, under the kernel's
-// automatic choice only): measured neutral inside the step -- c3_amp 5.75 / 5.83 off, 5.87 / 5.83 on; c2_amp 9.87 / 9.91 off, 9.97 / 9.86 on:
-// these GEMMs run next to the backward sweeps, and a 144-KB-LDS workgroup per CU is no better a neighbour than two 74-KB ones.
-int splitk_for256(int M, int N, long long K) {
-  const char* e = getenv("B2T_GEMM_256");
-  const char* o = getenv("B2T_SPLITK256");
-  if ((e && atoi(e) != 1) || !(o && atoi(o) == 1)) return 0;
-  const int t = ((M + 255) / 256) * ((N + 255) / 256);
-  if (t > 128 || M < 256 || N < 256) return 0;
-  const long long v = std::min<long long>(256 / t, K / 512);
-  const long long v8 = v / 8 * 8;
-  if (v8 >= 8 && t * v8 >= 200) return (int)v8;
-  return t * v >= 200 ? (int)v : 0;
-}
 int splitk_cap(int M, int N, long long K) {   // workspace sizing
-  const int t = ((M + 255) / 256) * ((N + 255) / 256);
-  const int s256 = (t <= 128 && M >= 256 && N >= 256) ? (int)std::min<long long>(256 / t, K / 512) : 0;
-  return std::max(std::max(splitk_for(M, N, K, splitk_target(false)), splitk_for(M, N, K, splitk_target(true))), s256);
+  return std::max(splitk_for(M, N, K, splitk_target(false)), splitk_for(M, N, K, splitk_target(true)));
 }
 
 // Time chunks of the layer pipeline: `chunks` equal parts (at least 16 steps each).
@@ -215,7 +196,7 @@ void carve(const b2t_model_t* m, const b2t_pass_t* p, char* base, Layout& w) {
     }
   for (size_t l = 0; l < L; ++l) w.res[l] = take(Tp * B * 4 * H);
   if (wave_pass(m, p, p->bwd_mode)) {
-    const int Tc = (int)Tp;      // one launch for the whole sequence (its time chunks are the gated consumers' chunks)
+    const int Tc = (int)Tp;      // rings and counters hold the whole sequence (one chunk = one launch over all of it)
     w.wv_cnt_b = reinterpret_cast<unsigned*>(base + off); off += align_up(gru_wave_cnt_words_bwd((int)L, Tc, (int)B) * sizeof(unsigned), 256);
     const size_t rb = align_up(gru_wave_ring_bytes_bwd(Tc, (int)B, (int)H), 256);
     for (size_t l = 0; l < L; ++l) { w.wv_ring_b[l] = base + off; off += rb; w.wv_ringx_b[l] = w.wv_ring_b[l]; }
@@ -439,7 +420,7 @@ constexpr unsigned Q_ANY = 0xffffffffu, Q_MAIN = 1u;
 struct Task {
   const char* name; float est; unsigned qmask; std::vector<int> deps; std::function<void(hipStream_t)> run;
   int q = -1; float start = 0.f, end = 0.f, rank = 0.f; bool cross = false; hipEvent_t ev = nullptr;
-  int cls = -1;   // admission class (XCD set of a sweep under the XCD-local hand-off): classes 0 / 1 (layer parity) hold two tasks in flight, classes 2..5 (the paired backward sweeps' XCD sets, one workgroup per CU) one
+  int cls = -1;   // admission class (XCD set of a sweep under the XCD-local hand-off): classes 0 / 1 (layer parity) hold two tasks in flight, classes 2..5 (not used by the plans here: sweeps with one workgroup per CU) one
 };
 
 struct Plan {
@@ -527,8 +508,8 @@ std::vector<int> schedule_plan(Plan& P, int nq) {
 // the hand-off timeout (seen under rocprofv3 in the trainer loop, about once in 150 steps).  So the k-th task of a class, in
 // planned start order, waits for the (k-2)-th to finish: never more than two in flight.  The extra edges point forward in a
 // topological order, so the graph stays acyclic; they rarely bind (the third sweep of a parity normally starts later anyway).
-// (Round 5: the paired backward sweeps -- one 512-thread workgroup per CU on the two XCDs of their set -- are classes 2..5 with
-// room for ONE task in flight: the k-th waits for the (k-1)-th.)
+// (Classes 2..5 have room for ONE task in flight -- the k-th waits for the (k-1)-th: sweeps that fill their XCD set with one
+// workgroup per CU.  The plans here use classes 0 / 1 only.)
 constexpr int N_CLS = 6;
 inline int cls_capacity(int k) { return k < 2 ? 2 : 1; }
 void add_admission_edges(Plan& P, const std::vector<int>& order) {
@@ -563,7 +544,7 @@ uint64_t pass_key(int which, const b2t_model_t* prm, const b2t_model_t* grd, con
   h = key_of(h, p->in_drop); h = key_of(h, p->rnn_drop);
   for (const void* q : ptrs) h = key_of(h, q);
   for (long long v : ints) h = key_of(h, v);
-  for (const char* name : {"B2T_FUSED_PROJ", "B2T_HANDOFF16", "B2T_PREPACK", "B2T_WGRAD_SPLIT", "B2T_ZPACK", "B2T_GEMM_256", "B2T_GI0_CHAIN", "B2T_SPLITK256"}) {   // read per pass by the code below / the sweeps
+  for (const char* name : {"B2T_FUSED_PROJ", "B2T_HANDOFF16", "B2T_PREPACK", "B2T_WGRAD_SPLIT", "B2T_ZPACK", "B2T_GEMM_256", "B2T_WAVE_KS", "B2T_WAVE_LOCAL", "B2T_WAVE_SC1_LOADS"}) {   // read per pass by the code below / the sweeps
     const char* e = getenv(name);
     h = key_bytes(h, e ? e : "", e ? strlen(e) + 1 : 1);   // the whole value ("1" and "10" are different plans)
   }
@@ -1060,8 +1041,6 @@ extern "C" int b2t_model_forward(b2t_exec* ex, const b2t_model_t* prm, const b2t
       c.call(gemm_bf16p_pack(&d, 1, w.wpk_f[l], s));
     });
   }
-  const bool gi0_chain = c.bf16_gemm && In0 >= 2048 && nc > 1 && getenv("B2T_GI0_CHAIN") && atoi(getenv("B2T_GI0_CHAIN")) == 1;   // opt-in: measured slower
-  int t_gi0_prev = -1;
   int t_hfin = -1;      // wavefront: the task that copies the final states out
   int t_gi_l0c[MAXC];   // wavefront: layer 0's projection task of every chunk (the only projections left)
   for (int i = 0; i < MAXC; ++i) t_gi_l0c[i] = -1;
@@ -1131,9 +1110,8 @@ extern "C" int b2t_model_forward(b2t_exec* ex, const b2t_model_t* prm, const b2t
       });
       // Layer 0 of a patch model in the bf16 mode: the chunks' projections (2624 x 2304 x 7168 each at the shipped shape: 150 us alone) are
       // all ready behind the day layer; launched together on three queues they share the chip and the FIRST one -- the only one the
-      // first sweep waits for -- finishes after 290 us.  B2T_GI0_CHAIN=1 runs them one after the other: the first sweep then starts 150 us
-      // earlier, and the step is SLOWER (5.85 against 5.81 ms: the later chunks' GEMMs now run next to the sweeps instead of in front of them).
-      if (l == 0 && gi0_chain && !fused_from(l - 1)) { if (ci > 0 && t_gi0_prev >= 0) P.dep(t_gi, t_gi0_prev); t_gi0_prev = t_gi; }
+      // first sweep waits for -- finishes after 290 us.  Chained one after the other the first sweep starts 150 us earlier and the step is
+      // SLOWER (5.85 against 5.81 ms: the later chunks' GEMMs then run next to the sweeps instead of in front of them; NOTES.md R5.7).
       if (wave) {
         // 3w. the layer wavefront: ONE task per time chunk for the whole stack, created with the top layer (it needs every layer's
         // initial state).  Chunks are launches one behind the other on a sweep queue: the only thing pipelined over them is what runs
@@ -1261,8 +1239,7 @@ void layer_weight_grads(Ctx& c, hipStream_t s, const b2t_model_t* prm, const b2t
   if (part != 2) {
     b2t_gemm_desc d = gd(w.dG[l] + a0, w.out[l] + (long long)t0 * B * H, grd->w_hh[l], 3 * H, H, (int)K);
     d.a_kcontig = 0; d.a_s0 = 4 * H; d.b_kcontig = 0; d.b_s0 = H; d.c_s0 = H;
-    int sk = splitk_for(3 * H, H, K, splitk_target(c.bf16_gemm));
-    if (c.bf16_gemm && which != 1 && c.would_pack(d, s)) { const int s256 = splitk_for256(3 * H, H, K); if (s256 > 0) sk = s256; }
+    const int sk = splitk_for(3 * H, H, K, splitk_target(c.bf16_gemm));
     if (which == 1) { c.call(gemm_bf16p_pack(&d, 1, w.xpk_hh[l], s)); }
     else {
       if (fused_bias) { d.a_sum = asum_x; d.a_sum_ks = 3 * H; }
@@ -1286,8 +1263,7 @@ void layer_weight_grads(Ctx& c, hipStream_t s, const b2t_model_t* prm, const b2t
     b2t_gemm_desc d = gd(w.dG[l] + a0 + a_off, inp, grd->w_ih[l] + c_off, M, In, (int)K);
     d.a_kcontig = 0; d.a_s0 = 4 * H; d.b_kcontig = 0; d.b_s0 = b_s0; d.b_s1 = b_s1; d.b_div = b_div; d.c_s0 = In;
     d.a_brk = brk; d.a_gap = gap;
-    int sk = splitk_for(M, In, K, splitk_target(c.bf16_gemm));
-    if (c.bf16_gemm && which != 1 && c.would_pack(d, s)) { const int s256 = splitk_for256(M, In, K); if (s256 > 0) sk = s256; }
+    const int sk = splitk_for(M, In, K, splitk_target(c.bf16_gemm));
     if (which == 1) { c.call(gemm_bf16p_pack(&d, 1, w.xpk_ih[l], s)); return; }
     if (fused_bias) { d.a_sum = w.asum[l]; d.a_sum_ks = 3 * H; }
     c.gemm(s, d, sk, w.slab[l], accumulate, l, (pre && c.would_pack(d, s)) ? w.xpk_ih[l] : nullptr);
@@ -1325,9 +1301,6 @@ extern "C" int b2t_model_backward(b2t_exec* ex, const b2t_model_t* prm, const b2
   const long long M = (long long)Tp * B;
   const int mode = p->bwd_mode;
   B2T_REQUIRE((mode & 0xff) == 0 || sync_ws, "model_backward: sync_ws is required for the persistent sweeps");
-  // the backward sweeps with W_hh^T in LDS (B2T_GRU_PAIRED): where the shape allows them, each layer's sweeps go to the XCD set
-  // l & 3 and are admitted one at a time per set (class 2 + set)
-  const bool paired = (mode & B2T_GRU_PAIRED) != 0 && (mode & 0xff) == 1 && !(mode & (B2T_GRU_BF16 | B2T_GRU_WIDE)) && gru_persistent_bwd_pair_ok(B, H);
   Layout w;
   carve(prm, p, reinterpret_cast<char*>(ws), w);
   Ctx c{ex, as_stream(stream), p->bf16_gemm != 0};
@@ -1462,23 +1435,14 @@ extern "C" int b2t_model_backward(b2t_exec* ex, const b2t_model_t* prm, const b2
   // Weight gradients: per chunk (bit l of wgrad_chunk_mask: the first chunk swept overwrites, the others accumulate in sweep
   // order -- a dependency chain, so the sums do not depend on the schedule) or once per layer after its last chunk.
   int t_bs[MAXL][MAXC], t_dx[MAXL][MAXC], t_wg_last[MAXL];
-  int t_wb = -1, t_wclear = -1;   // wavefront, gated form: the one backward sweep task and the task that clears its counters
-  int t_wbc[MAXC];                // wavefront, launch-per-chunk form: the sweep task of each time chunk
+  int t_wbc[MAXC];                // wavefront: the sweep task of each time chunk
   for (int ci = 0; ci < MAXC; ++ci) t_wbc[ci] = -1;
-  // Wavefront with more than one time chunk, two forms.  DEFAULT: one sweep launch per chunk, last chunk first, each behind the one
-  // before (the state gradient crosses in w.carry); a chunk's consumers -- layer 0's input gradient, every layer's weight gradients --
-  // are ordinary successors of that launch and run BESIDE the next chunk's sweep on the CUs it leaves free.  B2T_WAVE_GATED=1: ONE
-  // launch for the whole sequence and consumers that wait on the DEVICE for the sweep's progress words (gru_wave_gate; dG written
-  // through): they must never sit in front of the sweep on its own queue (the caller's stream) -- queues 1..3 only.  Measured at C2
-  // with the K-split sweep (NOTES.md R6.2b): gated 8.46 / 8.63 / 9.53, launch per chunk 8.06 / 8.37 / 9.27 ms with 2 / 4 / 8 chunks against 7.6 with
-  // one -- a kernel launched beside the sweep cannot finish before it (workgroup i is dealt to XCD i % 8 and waits there; the sweep fills XCDs 0-4).
-  static const bool gated_env = [] { const char* e = getenv("B2T_WAVE_GATED"); return e && atoi(e) != 0; }();
-  const bool gated = wave && nc > 1 && c.nq > 1 && gated_env;
-  const bool wave_chunked = wave && !gated;      // (nc == 1 included: one launch)
-  const unsigned q_gated = gated ? (((1u << c.nq) - 1u) & ~1u) : Q_ANY;
-  auto gate = [&](hipStream_t s, int l, int t0) { if (gated && t0 > 0 && !c.rc) c.call(gru_wave_gate(w.wv_cnt_b, l, t0, Tp, B, H, reinterpret_cast<unsigned*>(sync_of(0)), s)); };
+  // Wavefront with more than one time chunk: one sweep launch per chunk, last chunk first, each behind the one before (the state
+  // gradient crosses in w.carry); a chunk's consumers -- layer 0's input gradient, every layer's weight gradients -- are ordinary
+  // successors of that launch and run BESIDE the next chunk's sweep on the CUs it leaves free.  (One launch for the whole sequence
+  // with consumers gated on the device measured slower at every chunk count: NOTES.md R6.2b.)
   // one sweep launch of the whole stack over the steps [t0, t0 + n)
-  auto wave_sweep = [&, dhidden](hipStream_t ss, int ci, int t0, int n, bool whole) {
+  auto wave_sweep = [&, dhidden](hipStream_t ss, int ci, int t0, int n) {
     if (c.rc) return;
     Ctx::Scope sc(c, ss, 9, 2.0 * n * B * 3.0 * H * H * (2 * L - 1));
     WaveBwdArgs a;
@@ -1490,12 +1454,11 @@ extern "C" int b2t_model_backward(b2t_exec* ex, const b2t_model_t* prm, const b2
       a.h_init[k] = w.out[k] + (long long)t0 * B * H; a.out[k] = w.out[k] + (long long)(1 + t0) * B * H;
       a.reserve[k] = w.res[k] + (long long)t0 * B * 4 * H; a.dG[k] = w.dG[k] + (long long)t0 * B * 4 * H;
       a.ring[k] = w.wv_ring_b[k]; a.ringx[k] = w.wv_ringx_b[k]; a.seed[k] = mix_seed(p->seed, 101 + k);
-      a.dh_last[k] = (whole || ci == nc - 1) ? (dhidden ? dhidden + (size_t)k * B * H : nullptr) : w.carry[k] + (size_t)((ci + 1) % 2) * B * H;
-      a.dh_init[k] = (whole || ci == 0) ? w.dh_init + (size_t)k * B * H : w.carry[k] + (size_t)(ci % 2) * B * H;
+      a.dh_last[k] = ci == nc - 1 ? (dhidden ? dhidden + (size_t)k * B * H : nullptr) : w.carry[k] + (size_t)((ci + 1) % 2) * B * H;
+      a.dh_init[k] = ci == 0 ? w.dh_init + (size_t)k * B * H : w.carry[k] + (size_t)(ci % 2) * B * H;
     }
     a.cnt = w.wv_cnt_b; a.err = reinterpret_cast<unsigned*>(sync_of(0));
-    // gated: counters cleared by wbclear (the gates are already polling), dG written through + progress words
-    a.flags = (whole && gated ? (2 | 4) : 0) | (ks_direct ? 8 : 0); a.prog = whole && gated ? w.wv_cnt_b : nullptr;
+    a.ks = ks_direct; a.flags = ks_direct ? 8 : 0;
     a.drop_p = drop ? p->rnn_drop : 0.f; a.drop_scale = drop ? 1.0f / (1.0f - p->rnn_drop) : 1.f; a.elem0 = (long long)t0 * B * H;
     c.call(gru_wave_bwd(a, ss));
   };
@@ -1508,21 +1471,12 @@ extern "C" int b2t_model_backward(b2t_exec* ex, const b2t_model_t* prm, const b2
       const int t0 = chunks[ci][0], t1 = chunks[ci][1], n = t1 - t0;
       if (wave) {
         // created with the top layer (the first iteration of the layer loop)
-        if (wave_chunked) {
-          if (l == L - 1) {
-            t_wbc[ci] = P.add("wbsweep", 60.f + (n + 2 * L) * est_step_us(1) * hs, Q_MAIN, {ci == nc - 1 ? t_top : t_wbc[ci + 1]},
-                              [&, ci, t0, n](hipStream_t ss) { wave_sweep(ss, ci, t0, n, false); });
-            if (ci == nc - 1 && !ks_direct) for (int k = 0; k < L; ++k) { P.dep(t_wbc[ci], t_wt[k]); P.dep(t_wbc[ci], t_wit[k]); }
-          }
-          t_bs[l][ci] = t_wbc[ci];
-        } else {
-        if (l == L - 1 && ci == nc - 1) {
-          t_wclear = P.add("wbclear", 5.f, Q_MAIN, {t_start}, [&](hipStream_t ss) { c.call(gru_wave_bwd_clear(w.wv_cnt_b, L, Tp, B, ss)); });
-          t_wb = P.add("wbsweep", 60.f + (Tp + 2 * L) * est_step_us(1) * hs, Q_MAIN, {t_top, t_wclear}, [&](hipStream_t ss) { wave_sweep(ss, 0, 0, Tp, true); });
-          if (!ks_direct) for (int k = 0; k < L; ++k) { P.dep(t_wb, t_wt[k]); P.dep(t_wb, t_wit[k]); }
+        if (l == L - 1) {
+          t_wbc[ci] = P.add("wbsweep", 60.f + (n + 2 * L) * est_step_us(1) * hs, Q_MAIN, {ci == nc - 1 ? t_top : t_wbc[ci + 1]},
+                            [&, ci, t0, n](hipStream_t ss) { wave_sweep(ss, ci, t0, n); });
+          if (ci == nc - 1 && !ks_direct) for (int k = 0; k < L; ++k) { P.dep(t_wbc[ci], t_wt[k]); P.dep(t_wbc[ci], t_wit[k]); }
         }
-        t_bs[l][ci] = t_wb;
-        }
+        t_bs[l][ci] = t_wbc[ci];
       } else
       t_bs[l][ci] = P.add("bsweep", 40.f + n * est_step_us(1) * hs, q_sweep,
                           {l < L - 1 ? t_dx[l + 1][ci] : t_top, ci == nc - 1 ? t_wt[l] : t_bs[l][ci + 1]}, [&, l, ci, t0, n](hipStream_t ss) {
@@ -1537,17 +1491,16 @@ extern "C" int b2t_model_backward(b2t_exec* ex, const b2t_model_t* prm, const b2
         c.call(b2t_gru_layer_bwd_f32(w.dY[l] + (long long)t0 * B * H, dh_last, w.res[l] + (long long)t0 * B * 4 * H,
                                      w.out[l] + (long long)(1 + t0) * B * H, w.out[l] + (long long)t0 * B * H, w.whh_t[l],
                                      w.dG[l] + (long long)t0 * B * 4 * H, dh_out, w.scratch[l], n, B, H,
-                                     paired ? (mode | ((l & 3) << B2T_GRU_SET_SHIFT)) : (mode & B2T_GRU_LOCAL) ? (mode | ((l & 1) ? B2T_GRU_PARITY : 0)) : mode,
+                                     (mode & B2T_GRU_LOCAL) ? (mode | ((l & 1) ? B2T_GRU_PARITY : 0)) : mode,
                                      sync_of(l), ssp));
       });
-      if (paired) P.t[t_bs[l][ci]].cls = 2 + (l & 3);     // XCD set {l & 3, (l & 3) + 4}: one paired sweep in flight per set
-      else if (mode & B2T_GRU_LOCAL) P.t[t_bs[l][ci]].cls = l & 1;
+      if (mode & B2T_GRU_LOCAL) P.t[t_bs[l][ci]].cls = l & 1;
       float e_dx = est_gemm((double)n * B, l > 0 ? H : In0, 3 * H);
       if (l == 0 && fast_day) e_dx += est_gemm(F, F, n, B) + 30.f;
       if (wave && l > 0) t_dx[l][ci] = t_bs[l][ci];   // made inside the sweep
       else
-      t_dx[l][ci] = P.add("dx", e_dx, (gated && t0 > 0) ? q_gated : Q_ANY, {(gated && t0 > 0) ? t_wclear : t_bs[l][ci], (l == 0 && fast_day && ci < nc - 1) ? t_dx[l][ci + 1] : -1, t_wpk[l]},
-                          [&, l, t0, n](hipStream_t s) { gate(s, l, t0); dx_gemm(s, l, t0, n); });
+      t_dx[l][ci] = P.add("dx", e_dx, Q_ANY, {t_bs[l][ci], (l == 0 && fast_day && ci < nc - 1) ? t_dx[l][ci + 1] : -1, t_wpk[l]},
+                          [&, l, t0, n](hipStream_t s) { dx_gemm(s, l, t0, n); });
       if (per_chunk || ci == 0) {
         const int w0 = per_chunk ? t0 : 0, w1 = per_chunk ? t1 : Tp;
         const int acc = per_chunk && ci != nc - 1 ? 1 : 0;
@@ -1577,22 +1530,14 @@ extern "C" int b2t_model_backward(b2t_exec* ex, const b2t_model_t* prm, const b2
           t_wg_hh = t_hh; t_wg_ih = t_ih;
           t_wg = P.add("wgrad_join", 0.f, Q_ANY, {t_hh, t_ih}, nullptr);
         } else
-        t_wg = P.add("wgrad", est_gemm(3 * H, H, K) + est_gemm(3 * H, In, K) + 60.f, (gated && w0 > 0) ? q_gated : Q_ANY, {(gated && w0 > 0) ? t_wclear : t_bs[l][ci], t_wg, t_xp},
-                     [&, l, w0, w1, acc, fin, xpre](hipStream_t s) { gate(s, l, w0); layer_weight_grads(c, s, prm, grd, p, w, l, w0, w1, acc, fin, 3, xpre); });
+        t_wg = P.add("wgrad", est_gemm(3 * H, H, K) + est_gemm(3 * H, In, K) + 60.f, Q_ANY, {t_bs[l][ci], t_wg, t_xp},
+                     [&, l, w0, w1, acc, fin, xpre](hipStream_t s) { layer_weight_grads(c, s, prm, grd, p, w, l, w0, w1, acc, fin, 3, xpre); });
       }
     }
     t_wg_last[l] = t_wg;
     bucket(1 + l, t_wg);
   }
 
-  // probe (B2T_WGRAD_AFTER=k): the weight-gradient GEMMs of layers >= k wait for the LAST backward sweep (they block the
-  // placement of sweep workgroups and are slowed by them in turn: tools/r4_sweep_probe.py)
-  if (const char* wa = getenv("B2T_WGRAD_AFTER")) {
-    const int k0 = atoi(wa);
-    for (int l = std::max(0, k0); l < L; ++l)
-      for (size_t i = 0; i < P.t.size(); ++i)
-        if (P.t[i].name && !strcmp(P.t[i].name, "wgrad") && (int)i == t_wg_last[l]) P.dep((int)i, t_bs[0][0]);
-  }
   // layer-0 input gradient -> day layer
   auto day_wgrad_desc = [&]() {      // per-sentence x[b]^T dpre[b] -> day_slab[b] (whole sequence)
     b2t_gemm_desc d = gd(x, w.dU, w.day_slab, F, F, T);
@@ -1647,21 +1592,6 @@ extern "C" int b2t_model_backward(b2t_exec* ex, const b2t_model_t* prm, const b2
     t_end = P.add("end", 0.f, Q_MAIN, {t_h0, t_dayfin, t_head_w, t_bucket}, nullptr);
     for (int l = 0; l < L; ++l) { P.dep(t_end, t_wg_last[l]); P.dep(t_end, t_dx[l][0]); }
     P.dep(t_end, t_top);
-  }
-  if (gated && t_wb >= 0) {
-    // Gated consumers wait on the DEVICE for the sweep.  The sweep runs on the caller's stream; anything issued IN FRONT of it there
-    // that (transitively) waited for a gated task would wait for a sweep queued behind itself.  So the caller's stream carries the
-    // sweep, what the sweep itself needs, and the final join -- everything else goes to the worker queues.
-    std::vector<char> need(P.t.size(), 0);
-    std::vector<int> stack{t_wb};
-    while (!stack.empty()) {
-      const int i = stack.back(); stack.pop_back();
-      if (need[(size_t)i]) continue;
-      need[(size_t)i] = 1;
-      for (int d : P.t[(size_t)i].deps) stack.push_back(d);
-    }
-    for (size_t i = 0; i < P.t.size(); ++i)
-      if (!need[i] && (int)i != t_end) P.t[i].qmask &= q_gated;
   }
   run_plan(c, P, c.nq, c.qs);
   return c.rc;

@@ -173,57 +173,22 @@ __device__ __forceinline__ u32x4 load_frag(const char* ring, unsigned base, int 
     }                                                                                                                  \
   }
 
-// The same stream in the row-group form (RGF): the workgroup's four waves all need the SAME row group's fragments, so each wave
-// fetches a quarter of the pairs, the stream goes through LDS (SBUF: NP KB) and every wave reads every pair from there -- a
-// quarter of the L2 -> L1 traffic of four waves fetching four different row groups.  One workgroup barrier per stream.
-#define B2T_WAVE_STREAM_LDS(SBUF, RING, BASE, BODY)                                                                    \
-  {                                                                                                                    \
-    static_assert(NP % 4 == 0, "row-group form: pairs split over four waves");                                         \
-    u32x4 v_[NP / 4];                                                                                                  \
-    _Pragma("unroll") for (int i = 0; i < NP / 4; ++i) v_[i] = load_frag(RING, BASE, wave + 4 * i, P, H, lane, q, plain_); \
-    _Pragma("unroll") for (int i = 0; i < NP / 4; ++i)                                                                 \
-      *reinterpret_cast<u32x4*>((SBUF) + (unsigned)(wave + 4 * i) * 1024u + (unsigned)lane * 16u) = v_[i];             \
-    __syncthreads();                                                                                                   \
-    u32x4 f_[4];                                                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) f_[i] = lds_read_async((SBUF) + (unsigned)i * 1024u + (unsigned)lane * 16u); \
-    _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                                                   \
-      if (p + 4 <= NP) lds_wait<3>(); else if (p + 3 == NP) lds_wait<2>(); else if (p + 2 == NP) lds_wait<1>(); else lds_wait<0>(); \
-      const bf16x8 av = __builtin_bit_cast(bf16x8, lds_use(f_[p % 4]));                                                \
-      if (p + 4 < NP) f_[p % 4] = lds_read_async((SBUF) + (unsigned)(p + 4) * 1024u + (unsigned)lane * 16u);           \
-      BODY                                                                                                             \
-    }                                                                                                                  \
-  }
-
 // ---------------------------------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------------------------------
-// RGF (row-group form, H % 64 == 0, H <= 512): a workgroup = (layer, ROW GROUP, 64 units) -- wave w owns units 64 ub + 16 w .. + 15 of
-// that one row group -- instead of (layer, 16 units) for all row groups.  Same hand-off protocol, same tiles, same counters; but the
-// four waves now consume the SAME operand streams (B2T_WAVE_STREAM_LDS) and each holds BOTH of its weight slices in registers
-// (W_hh and W_ih: 384 at H = 512, pinned to register classes), since four different W_ih slices do not fit LDS.
-template <int NP, bool DROP, bool LOC, bool RGF = false>   // NP: pairs of 16-unit chunks per row (H <= 32 NP); LOC: a layer = one XCD (wave_role)
+template <int NP, bool DROP, bool LOC>   // NP: pairs of 16-unit chunks per row (H <= 32 NP); LOC: a layer = one XCD (wave_role)
 __global__ __launch_bounds__(256, 1) void gru_wave_fwd_kernel(const WaveFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char wave_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
   const int H = a.H, B = a.B, T = a.T, G = H / 16, P = (G + 1) / 2, ngrp = (B + 15) / 16, L = a.L;
   const bool plain_ = LOC || (a.flags & 1) == 0;
-  int layer, slice, rg_of_wg = 0;
-  if constexpr (RGF) {
-    int k;
-    if (!wave_role<LOC>(a.tickets, L, ngrp * (H / 64), false, layer, k)) return;
-    rg_of_wg = k / (H / 64);
-    slice = 4 * (k % (H / 64)) + wave;
-  } else {
-    if (!wave_role<LOC>(a.tickets, L, G, false, layer, slice)) return;
-  }
+  int layer, slice;
+  if (!wave_role<LOC>(a.tickets, L, G, false, layer, slice)) return;
   const int u0 = slice * 16, unit = u0 + j;
-  const int frot_ = (!RGF && P == NP && H == 32 * NP) ? slice % NP : 0;
-  // LDS: fat form [3][NP][64] W_ih slice as B fragments; row-group form two stream buffers of NP KB; then the waves' tiles
+  const int frot_ = (P == NP && H == 32 * NP) ? slice % NP : 0;
+  // LDS: [3][NP][64] W_ih slice as B fragments; then the waves' tiles
   u32x4* wl = reinterpret_cast<u32x4*>(wave_lds);
-  char* sbuf_c = wave_lds;
-  char* sbuf_p = wave_lds + (size_t)NP * 1024;
-  float* tiles = reinterpret_cast<float*>(wave_lds + (size_t)(RGF ? 2 : 3) * NP * 1024) + wave * (WAVE_TILES * WTILE_F);
-  (void)wl; (void)sbuf_c; (void)sbuf_p;
+  float* tiles = reinterpret_cast<float*>(wave_lds + (size_t)3 * NP * 1024) + wave * (WAVE_TILES * WTILE_F);
 
   bf16x8 w[3][NP];
   {
@@ -240,28 +205,12 @@ __global__ __launch_bounds__(256, 1) void gru_wave_fwd_kernel(const WaveFwdArgs 
         // in front of every MFMA; pinned -- two gates in accumulation registers (192 of the 256), the third in architectural ones --
         // nothing spills (R6.2)
         if constexpr (NP > 16) { if (g < 2) asm volatile("" : "+a"(w[g][p])); else asm volatile("" : "+v"(w[g][p])); }
-        else if constexpr (NP == 16 && !RGF) asm volatile("" : "+a"(w[g][p]));
-        if constexpr (RGF) asm volatile("" : "+a"(w[g][p]));      // row-group form: W_hh in accumulation registers, W_ih (below) mostly in architectural ones
+        else if constexpr (NP == 16) asm volatile("" : "+a"(w[g][p]));
       }
       __builtin_amdgcn_sched_barrier(0);   // (a pair's six loads are converted before the next pair's go out: hoisted, all 6 NP loads would be live)
     }
   }
-  bf16x8 w2[RGF ? 3 : 1][RGF ? NP : 1];      // row-group form: the W_ih slice
-  if constexpr (RGF) {
-    const float* wih = a.w_ih[layer > 0 ? layer : 1 < L ? 1 : 0];     // (layer 0 projects nothing: any valid matrix, never used)
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int k0 = 32 * p + 8 * q;
-      const bool ok = k0 < H && layer > 0;
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        const float* src = (layer > 0 ? wih : a.w_hh[layer]) + ((long long)g * H + unit) * H + (k0 < H ? k0 : 0);
-        w2[g][p] = __builtin_bit_cast(bf16x8, masked8(ld4(src), ld4(src + 4), ok));
-        if (g == 0 && p < (NP * 3) / 4) asm volatile("" : "+a"(w2[g][p])); else asm volatile("" : "+v"(w2[g][p]));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else if (layer > 0) {
+  if (layer > 0) {
     const float* wih = a.w_ih[layer];
     for (int idx = wave; idx < 3 * NP; idx += 4) {
       const int g = idx / NP, p = idx % NP, k0 = 32 * B2T_ROTP(p) + 8 * q;
@@ -271,7 +220,7 @@ __global__ __launch_bounds__(256, 1) void gru_wave_fwd_kernel(const WaveFwdArgs 
     }
   }
   __syncthreads();
-  if (!RGF && wave >= ngrp) return;
+  if (wave >= ngrp) return;
   __builtin_amdgcn_s_setprio(3);
 
   // Two rings per layer when the layer above must not read the own-recurrence ring: with dropout (it reads the DROPPED states) and
@@ -279,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void gru_wave_fwd_kernel(const WaveFwdArgs 
   // is written through to memory).  The cross ring's counter of slot s moves one step late -- when the NEXT own publish has drained
   // this wave's stores anyway -- so that no step waits for a memory acknowledgement of its own.
   constexpr bool XRING = DROP || LOC;
-  const int rg = RGF ? rg_of_wg : wave, m0 = rg * 16;
+  const int rg = wave, m0 = rg * 16;
   unsigned* err = a.err;
   const size_t cstride = (size_t)(T + 1);
   unsigned* cnt_own = a.cnt + ((size_t)(layer * 2 + 0) * ngrp + rg) * cstride;
@@ -328,21 +277,15 @@ __global__ __launch_bounds__(256, 1) void gru_wave_fwd_kernel(const WaveFwdArgs 
 #pragma unroll
     for (int g = 0; g < 3; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
     const unsigned pbase = (unsigned)(t + 1) * slot_bytes + rg_off;
-    if constexpr (RGF) {
-      B2T_WAVE_STREAM_LDS(sbuf_p, ring_in, pbase, {
-        _Pragma("unroll") for (int g = 0; g < 3; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w2[g][p], acc[g], 0, 0, 0);
-      })
-    } else {
-      // the B fragments come from LDS: the NEXT pair's three are requested before this pair's MFMAs (asynchronous reads, above)
-      u32x4 b_[2][3];
-      _Pragma("unroll") for (int g = 0; g < 3; ++g) b_[0][g] = lds_read_async(&wl[(g * NP + 0) * 64 + lane]);
-      B2T_WAVE_STREAM(ring_in, pbase, {
-        if (p + 1 < NP) { _Pragma("unroll") for (int g = 0; g < 3; ++g) b_[(p + 1) & 1][g] = lds_read_async(&wl[(g * NP + p + 1) * 64 + lane]); }
-        if (p + 1 < NP) lds_wait<3>(); else lds_wait<0>();
-        _Pragma("unroll") for (int g = 0; g < 3; ++g)
-          acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf16x8, lds_use(b_[p & 1][g])), acc[g], 0, 0, 0);
-      })
-    }
+    // the B fragments come from LDS: the NEXT pair's three are requested before this pair's MFMAs (asynchronous reads, above)
+    u32x4 b_[2][3];
+    _Pragma("unroll") for (int g = 0; g < 3; ++g) b_[0][g] = lds_read_async(&wl[(g * NP + 0) * 64 + lane]);
+    B2T_WAVE_STREAM(ring_in, pbase, {
+      if (p + 1 < NP) { _Pragma("unroll") for (int g = 0; g < 3; ++g) b_[(p + 1) & 1][g] = lds_read_async(&wl[(g * NP + p + 1) * 64 + lane]); }
+      if (p + 1 < NP) lds_wait<3>(); else lds_wait<0>();
+      _Pragma("unroll") for (int g = 0; g < 3; ++g)
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf16x8, lds_use(b_[p & 1][g])), acc[g], 0, 0, 0);
+    })
 #pragma unroll
     for (int g = 0; g < 3; ++g)
 #pragma unroll
@@ -371,15 +314,9 @@ __global__ __launch_bounds__(256, 1) void gru_wave_fwd_kernel(const WaveFwdArgs 
 #pragma unroll
       for (int g = 0; g < 3; ++g) gh[g] = f32x4{0.f, 0.f, 0.f, 0.f};
       const unsigned cbase = (unsigned)t * slot_bytes + rg_off;
-      if constexpr (RGF) {
-        B2T_WAVE_STREAM_LDS(sbuf_c, ring, cbase, {
-          _Pragma("unroll") for (int g = 0; g < 3; ++g) gh[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w[g][p], gh[g], 0, 0, 0);
-        })
-      } else {
-        B2T_WAVE_STREAM2(ring, cbase, {}, {
-          _Pragma("unroll") for (int g = 0; g < 3; ++g) gh[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w[g][p], gh[g], 0, 0, 0);
-        })
-      }
+      B2T_WAVE_STREAM2(ring, cbase, {}, {
+        _Pragma("unroll") for (int g = 0; g < 3; ++g) gh[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w[g][p], gh[g], 0, 0, 0);
+      })
     }
     asm volatile("s_nop 0" :: "v"(gh[0][0]), "v"(gh[1][0]), "v"(gh[2][0]));
     WSTAMP(1)   // operand loads + recurrent product
@@ -451,30 +388,20 @@ __global__ __launch_bounds__(256, 1) void gru_wave_fwd_kernel(const WaveFwdArgs 
 // ---------------------------------------------------------------------------------------------------------------------
 // backward.  Ring of layer l, slot t: the gate gradients of step t as fragments, 4 arrays (dr, dz, dn r, dn) x P pairs.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NP, bool DROP, bool LOC, bool RGF = false>      // RGF: the row-group form (see the forward kernel)
+template <int NP, bool DROP, bool LOC>
 __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char wave_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
   const int H = a.H, B = a.B, T = a.T, G = H / 16, P = (G + 1) / 2, ngrp = (B + 15) / 16, L = a.L;
   const bool plain_ = LOC || (a.flags & 1) == 0;
   // (placement-independent form: the TOP layer starts the wavefront and gets the first workgroups)
-  int layer, slice, rg_of_wg = 0;
-  if constexpr (RGF) {
-    int k;
-    if (!wave_role<LOC>(a.tickets, L, ngrp * (H / 64), true, layer, k)) return;
-    rg_of_wg = k / (H / 64);
-    slice = 4 * (k % (H / 64)) + wave;
-  } else {
-    if (!wave_role<LOC>(a.tickets, L, G, true, layer, slice)) return;
-  }
+  int layer, slice;
+  if (!wave_role<LOC>(a.tickets, L, G, true, layer, slice)) return;
   const int u0 = slice * 16, unit = u0 + j;
-  const int frot_ = (!RGF && P == NP && H == 32 * NP) ? slice % NP : 0;
-  // LDS: fat form [3][NP][64] W_ih[layer + 1]^T slice; row-group form two stream buffers of 3 NP KB (three arrays each); then the tiles
+  const int frot_ = (P == NP && H == 32 * NP) ? slice % NP : 0;
+  // LDS: [3][NP][64] W_ih[layer + 1]^T slice; then the tiles
   u32x4* wl = reinterpret_cast<u32x4*>(wave_lds);
-  char* sbuf_c = wave_lds;
-  char* sbuf_p = wave_lds + (size_t)3 * NP * 1024;
-  float* tiles = reinterpret_cast<float*>(wave_lds + (size_t)(RGF ? 6 : 3) * NP * 1024) + wave * (WAVE_TILES * WTILE_F);
-  (void)wl; (void)sbuf_c; (void)sbuf_p;
+  float* tiles = reinterpret_cast<float*>(wave_lds + (size_t)3 * NP * 1024) + wave * (WAVE_TILES * WTILE_F);
   const bool has_up = layer + 1 < L;
 
   bf16x8 w[3][NP];     // W_hh^T slice: column `unit`, k = array * H + 32 p + 8 q .. + 7
@@ -492,28 +419,12 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
         // in front of every MFMA; pinned -- two gates in accumulation registers (192 of the 256), the third in architectural ones --
         // nothing spills (R6.2)
         if constexpr (NP > 16) { if (g < 2) asm volatile("" : "+a"(w[g][p])); else asm volatile("" : "+v"(w[g][p])); }
-        else if constexpr (NP == 16 && !RGF) asm volatile("" : "+a"(w[g][p]));
-        if constexpr (RGF) asm volatile("" : "+a"(w[g][p]));
+        else if constexpr (NP == 16) asm volatile("" : "+a"(w[g][p]));
       }
       __builtin_amdgcn_sched_barrier(0);   // (a pair's six loads are converted before the next pair's go out: hoisted, all 6 NP loads would be live)
     }
   }
-  bf16x8 w2[RGF ? 3 : 1][RGF ? NP : 1];      // row-group form: the W_ih[layer + 1]^T slice
-  if constexpr (RGF) {
-    const float* wt = (has_up ? a.w_ih_t[layer + 1] : a.w_hh_t[layer]) + (long long)unit * 3 * H;     // (top layer: any valid matrix, masked to zero)
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int k0 = 32 * p + 8 * q;
-      const bool ok = k0 < H && has_up;
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        const float* src = wt + (long long)g * H + (k0 < H ? k0 : 0);
-        w2[g][p] = __builtin_bit_cast(bf16x8, masked8(ld4(src), ld4(src + 4), ok));
-        if (g == 0 && p < (NP * 3) / 4) asm volatile("" : "+a"(w2[g][p])); else asm volatile("" : "+v"(w2[g][p]));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else if (has_up) {
+  if (has_up) {
     const float* wt = a.w_ih_t[layer + 1] + (long long)unit * 3 * H;
     for (int idx = wave; idx < 3 * NP; idx += 4) {
       const int g = idx / NP, p = idx % NP, k0 = 32 * B2T_ROTP(p) + 8 * q;
@@ -523,13 +434,13 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
     }
   }
   __syncthreads();
-  if (!RGF && wave >= ngrp) return;
+  if (wave >= ngrp) return;
   __builtin_amdgcn_s_setprio(3);
 
   // LOC: the own-recurrence ring stays in this XCD's L2 (ordinary stores, L2 counters); the layer BELOW (another XCD) reads a
   // second, written-through copy whose counter moves one step late (see the forward kernel)
   constexpr bool XRING = LOC;
-  const int rg = RGF ? rg_of_wg : wave, m0 = rg * 16;
+  const int rg = wave, m0 = rg * 16;
   unsigned* err = a.err;
   const size_t cstride = (size_t)T;
   unsigned* cnt_own = a.cnt + ((size_t)(layer * 2 + 0) * ngrp + rg) * cstride;
@@ -556,39 +467,6 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
     wave_wait<false>(cnt_up + t, (unsigned)G, err, lane);
     WSTAMP(5)
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (RGF) {
-      // the three arrays (dr, dz, dn) of the layer above, a quarter of the pairs per wave, through LDS: ONE barrier
-      static_assert(!RGF || NP % 4 == 0, "row-group form: pairs split over four waves");
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {      // (array by array: NP / 4 loads in flight per wave, not 3 NP / 4 -- registers)
-        u32x4 v_[NP / 4];
-#pragma unroll
-        for (int i = 0; i < NP / 4; ++i)
-          v_[i] = load_frag(ring_up, (unsigned)t * slot_bytes + rg_off + (unsigned)(g == 2 ? 3 : g) * arr_bytes, wave + 4 * i, P, H, lane, q, plain_);
-#pragma unroll
-        for (int i = 0; i < NP / 4; ++i)
-          *reinterpret_cast<u32x4*>(sbuf_p + (unsigned)(g * NP + wave + 4 * i) * 1024u + (unsigned)lane * 16u) = v_[i];
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __syncthreads();
-      {
-        // LDS reads four fragments ahead, two accumulators (a read's ~128 cycles and a dependent MFMA's ~40 were the loop: 150 per pair)
-        f32x4 acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-        u32x4 f_[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f_[i] = lds_read_async(sbuf_p + (unsigned)i * 1024u + (unsigned)lane * 16u);
-#pragma unroll
-        for (int k = 0; k < 3 * NP; ++k) {
-          if (k + 4 <= 3 * NP) lds_wait<3>(); else if (k + 3 == 3 * NP) lds_wait<2>(); else if (k + 2 == 3 * NP) lds_wait<1>(); else lds_wait<0>();
-          const bf16x8 av = __builtin_bit_cast(bf16x8, lds_use(f_[k % 4]));
-          if (k + 4 < 3 * NP) f_[k % 4] = lds_read_async(sbuf_p + (unsigned)(k + 4) * 1024u + (unsigned)lane * 16u);
-          if (k & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w2[k / NP][k % NP], acc1, 0, 0, 0);
-          else acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w2[k / NP][k % NP], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] += acc1[i];
-      }
-    } else {
     // (two accumulators, pairs alternating: one accumulator is a chain of dependent MFMAs at ~40 cycles each instead of 17)
     f32x4 acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -601,7 +479,6 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] += acc1[i];
-    }
     if (DROP) {
       // the mask of the forward's dropout on out[layer]: row-major through the wave's tile (one Philox block per lane)
       float* td = tiles;
@@ -645,36 +522,6 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
       wave_wait<LOC>(cnt_own + (t + 1), (unsigned)G, err, lane);
       WSTAMP(0)
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-      if constexpr (RGF) {
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-          u32x4 v_[NP / 4];
-#pragma unroll
-          for (int i = 0; i < NP / 4; ++i)
-            v_[i] = load_frag(ring, (unsigned)(t + 1) * slot_bytes + rg_off + (unsigned)g * arr_bytes, wave + 4 * i, P, H, lane, q, plain_);
-#pragma unroll
-          for (int i = 0; i < NP / 4; ++i)
-            *reinterpret_cast<u32x4*>(sbuf_c + (unsigned)(g * NP + wave + 4 * i) * 1024u + (unsigned)lane * 16u) = v_[i];
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-        {
-          f32x4 acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-          u32x4 f_[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) f_[i] = lds_read_async(sbuf_c + (unsigned)i * 1024u + (unsigned)lane * 16u);
-#pragma unroll
-          for (int k = 0; k < 3 * NP; ++k) {
-            if (k + 4 <= 3 * NP) lds_wait<3>(); else if (k + 3 == 3 * NP) lds_wait<2>(); else if (k + 2 == 3 * NP) lds_wait<1>(); else lds_wait<0>();
-          const bf16x8 av = __builtin_bit_cast(bf16x8, lds_use(f_[k % 4]));
-            if (k + 4 < 3 * NP) f_[k % 4] = lds_read_async(sbuf_c + (unsigned)(k + 4) * 1024u + (unsigned)lane * 16u);
-            if (k & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w[k / NP][k % NP], acc1, 0, 0, 0);
-            else acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, w[k / NP][k % NP], acc, 0, 0, 0);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc[i] += acc1[i];
-        }
-      } else {
       f32x4 acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
@@ -686,7 +533,6 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[i] += acc1[i];
-      }
       asm volatile("s_nop 0" :: "v"(acc[0]));
       WSTAMP(1)
 #pragma unroll
@@ -724,9 +570,6 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
     wave_drain();
     wave_bump<LOC>(cnt_own + t, lane);
     if (XRING && pending_x >= 0) wave_bump<false>(cnt_x + pending_x, lane);
-    // progress for consumers OUTSIDE the launch (the gated weight-gradient GEMMs, wave_gate_kernel): the drain above acknowledged
-    // every store of the steps > t, so G x (T - t) bumps of this word certify dG[t + 1 .. T) in memory (written through below)
-    if (a.prog) wave_bump<false>(a.prog + layer * ngrp + rg, lane);
     WSTAMP(3)
     if (XRING && feeds) {
       store_u4<16>(ringx, base + (unsigned)a0 * arr_bytes, f0);
@@ -736,39 +579,17 @@ __global__ __launch_bounds__(256, 1) void gru_wave_bwd_kernel(const WaveBwdArgs 
     if (rrow < B) {
       float* dgl = a.dG[layer] + (long long)t * B * 4 * H;
       const unsigned off = (unsigned)(((long long)rrow * 4 * H + u0 + 4 * kg) * 4);
-      if (a.flags & 4) {      // (written through only for readers inside the sweep's lifetime: see gru_wave_ks.h)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) store_f4<16>(dgl, off + (unsigned)g * (unsigned)H * 4u, ld4(tiles + g * WTILE_F + (lane & 15) * WTP + 4 * kg));
-      } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) store_f4<0>(dgl, off + (unsigned)g * (unsigned)H * 4u, ld4(tiles + g * WTILE_F + (lane & 15) * WTP + 4 * kg));
-      }
+      for (int g = 0; g < 4; ++g) store_f4<0>(dgl, off + (unsigned)g * (unsigned)H * 4u, ld4(tiles + g * WTILE_F + (lane & 15) * WTP + 4 * kg));
     }
     WSTAMP(4)
     if (has_up && t > 0) project(t - 1);
   }
   if (XRING && pending_x >= 0) { wave_drain(); wave_bump<false>(cnt_x + pending_x, lane); }
-  if (a.prog) { wave_drain(); wave_bump<false>(a.prog + layer * ngrp + rg, lane); }     // G x (T + 1): everything is in memory
 #ifdef B2T_WAVE_TIMING
   if (slice == 0 && wave == 0 && lane == 0 && a.timing)
     for (int i = 0; i < 8; ++i) a.timing[layer * 8 + i] = (unsigned)(tacc[i] / (unsigned long long)T);
 #endif
-}
-
-// A consumer outside the launch waits for the sweep's progress: one wave, lane r polls word r (row group r of the layer) until
-// it reaches `target` = G x (T - t0 + 1) -- dG[t0 .. T) of that layer is then in memory.  Enqueued in front of a gated GEMM on the
-// GEMM's queue; it runs on a CU the sweeps leave free.  Bounded like every spin here (sets the sticky error word).
-__global__ void wave_gate_kernel(const unsigned* prog, int n, unsigned target, unsigned* err) {
-  const int lane = threadIdx.x;
-  if (lane >= n) return;
-  unsigned spins = 0;
-  while (__hip_atomic_load(prog + lane, RLX_AGENT) < target) {
-    if ((++spins & 255u) == 0u) {
-      if (__hip_atomic_load(err, RLX_AGENT) != 0u) break;
-      if (spins > SPIN_LIMIT) { __hip_atomic_store(err, 1u, RLX_AGENT); break; }
-    }
-    __builtin_amdgcn_s_sleep(8);
-  }
 }
 
 #include "gru_wave_ks.h"
@@ -787,14 +608,12 @@ static int wave_cus() {
   return n;
 }
 
-size_t gru_wave_lds_bytes_rgf_bwd(int H);
 static int wave_np(int H) { return H <= 128 ? 4 : H <= 256 ? 8 : H <= 512 ? 16 : 24; }   // the kernel template's pair count
 size_t gru_wave_lds_bytes(int H) { return (size_t)3 * wave_np(H) * 1024 + (size_t)4 * WAVE_TILES * WTILE_F * sizeof(float); }
-size_t gru_wave_lds_bytes_rgf_bwd(int H) { return (size_t)6 * wave_np(H) * 1024 + (size_t)4 * WAVE_TILES * WTILE_F * sizeof(float); }   // two stream buffers of three arrays
 size_t gru_wave_ring_bytes_fwd(int T, int B, int H) { return (size_t)(T + 1 > KS_D ? T + 1 : KS_D) * ((B + 15) / 16) * ((H / 16 + 1) / 2) * 1024; }   // (>= KS_D slots: the K-split form's own ring)
 size_t gru_wave_ring_bytes_bwd(int T, int B, int H) { return (size_t)(T > KS_D ? T : KS_D) * ((B + 15) / 16) * 4 * ((H / 16 + 1) / 2) * 1024; }
 size_t gru_wave_cnt_words_fwd(int L, int T, int B) { return 16 + (size_t)L * 2 * ((B + 15) / 16) * (T + 1); }   // 16: the XCD tickets of the local form
-size_t gru_wave_cnt_words_bwd(int L, int T, int B) { return 16 + 64 + (size_t)L * 2 * ((B + 15) / 16) * T; }   // tickets, progress words [L][row groups] (<= 32), counters
+size_t gru_wave_cnt_words_bwd(int L, int T, int B) { return 16 + (size_t)L * 2 * ((B + 15) / 16) * T; }   // tickets, counters
 
 // Shapes the wavefront serves; `why` (optional) receives the reason when it does not.
 bool gru_wave_ok(int L, int T, int B, int H, const char** why) {
@@ -824,18 +643,11 @@ bool gru_wave_local(int L, int H) {
   return L <= 8 && H / 16 <= 32 && wave_cus() >= 256 && gru_xcd_dispatch_ok();
 }
 
-template <int NPV, bool DR, bool LC, bool RG = false> static int wave_launch_fwd(const WaveFwdArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+template <int NPV, bool DR, bool LC> static int wave_launch_fwd(const WaveFwdArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   static bool at = false;
-  if (!at) { const int rc = wave_lds_attr(gru_wave_fwd_kernel<NPV, DR, LC, RG>, gru_wave_lds_bytes(32 * NPV)); if (rc) return rc; at = true; }
-  hipLaunchKernelGGL((gru_wave_fwd_kernel<NPV, DR, LC, RG>), grid, dim3(256), lds, s, a);
+  if (!at) { const int rc = wave_lds_attr(gru_wave_fwd_kernel<NPV, DR, LC>, gru_wave_lds_bytes(32 * NPV)); if (rc) return rc; at = true; }
+  hipLaunchKernelGGL((gru_wave_fwd_kernel<NPV, DR, LC>), grid, dim3(256), lds, s, a);
   return 0;
-}
-// the row-group form serves H % 64 == 0, H <= 256 (both weight slices of a wave in registers); B2T_WAVE_RGF=1 (read per call) selects it
-// (round 6, late: superseded by the K-split form and OFF unless B2T_WAVE_RGF=1; H <= 256 only -- at H = 512 both weight slices of a
-// wave plus the stream buffers do not fit 512 registers and the allocator spilled MFMA operand tuples: see gru_wave_ks.h)
-bool gru_wave_rgf(int H) {
-  const char* e = getenv("B2T_WAVE_RGF");
-  return e && atoi(e) != 0 && H % 64 == 0 && H <= 256;
 }
 // the K-split form (gru_wave_ks.h): local placement, H % 128 == 0, H <= 512, a layer's workgroups fit one XCD; B2T_WAVE_KS=0 (read per call): off
 bool gru_wave_ks(int L, int T, int B, int H) {
@@ -865,10 +677,10 @@ template <int NPQ, bool DR> static int ks_launch_bwd(const WaveBwdArgs& a, hipSt
   hipLaunchKernelGGL((gru_ks_bwd_kernel<NPQ, DR>), dim3(256), dim3(256), ks_lds_bytes(true), s, a);
   return 0;
 }
-template <int NPV, bool DR, bool LC, bool RG = false> static int wave_launch_bwd(const WaveBwdArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+template <int NPV, bool DR, bool LC> static int wave_launch_bwd(const WaveBwdArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   static bool at = false;
-  if (!at) { const int rc = wave_lds_attr(gru_wave_bwd_kernel<NPV, DR, LC, RG>, RG ? gru_wave_lds_bytes_rgf_bwd(32 * NPV) : gru_wave_lds_bytes(32 * NPV)); if (rc) return rc; at = true; }
-  hipLaunchKernelGGL((gru_wave_bwd_kernel<NPV, DR, LC, RG>), grid, dim3(256), lds, s, a);
+  if (!at) { const int rc = wave_lds_attr(gru_wave_bwd_kernel<NPV, DR, LC>, gru_wave_lds_bytes(32 * NPV)); if (rc) return rc; at = true; }
+  hipLaunchKernelGGL((gru_wave_bwd_kernel<NPV, DR, LC>), grid, dim3(256), lds, s, a);
   return 0;
 }
 
@@ -894,52 +706,37 @@ int gru_wave_fwd(const WaveFwdArgs& a_in, hipStream_t s) {
     if (rc) return rc;
     return check_hip(hipGetLastError(), "gru_wave_fwd");
   }
-  const bool rgf = gru_wave_rgf(a.H);
-  const int ngrp_ = (a.B + 15) / 16;
-  const dim3 grid(loc ? 256 : (rgf ? a.L * ngrp_ * (a.H / 64) : a.L * (a.H / 16)));
+  const dim3 grid(loc ? 256 : a.L * (a.H / 16));
 #define B2T_WAVE_FWD(NPV)                                                                                              \
   do {                                                                                                                 \
-    if (rgf && loc) rc = drop ? wave_launch_fwd<NPV, true, true, true>(a, grid, lds, s) : wave_launch_fwd<NPV, false, true, true>(a, grid, lds, s); \
-    else if (rgf) rc = drop ? wave_launch_fwd<NPV, true, false, true>(a, grid, lds, s) : wave_launch_fwd<NPV, false, false, true>(a, grid, lds, s); \
-    else if (loc) rc = drop ? wave_launch_fwd<NPV, true, true>(a, grid, lds, s) : wave_launch_fwd<NPV, false, true>(a, grid, lds, s);   \
+    if (loc) rc = drop ? wave_launch_fwd<NPV, true, true>(a, grid, lds, s) : wave_launch_fwd<NPV, false, true>(a, grid, lds, s);   \
     else rc = drop ? wave_launch_fwd<NPV, true, false>(a, grid, lds, s) : wave_launch_fwd<NPV, false, false>(a, grid, lds, s);     \
   } while (0)
   if (a.H <= 128) B2T_WAVE_FWD(4);
   else if (a.H <= 256) B2T_WAVE_FWD(8);
-  else if (a.H <= 512) {
-    if (loc) rc = drop ? wave_launch_fwd<16, true, true>(a, grid, lds, s) : wave_launch_fwd<16, false, true>(a, grid, lds, s);
-    else rc = drop ? wave_launch_fwd<16, true, false>(a, grid, lds, s) : wave_launch_fwd<16, false, false>(a, grid, lds, s);
-  } else rc = drop ? wave_launch_fwd<24, true, false>(a, grid, lds, s) : wave_launch_fwd<24, false, false>(a, grid, lds, s);
+  else if (a.H <= 512) B2T_WAVE_FWD(16);
+  else rc = drop ? wave_launch_fwd<24, true, false>(a, grid, lds, s) : wave_launch_fwd<24, false, false>(a, grid, lds, s);
 #undef B2T_WAVE_FWD
   if (rc) return rc;
   return check_hip(hipGetLastError(), "gru_wave_fwd");
 }
 
-int gru_wave_bwd_clear(unsigned* cnt, int L, int T, int B, hipStream_t s) {
-  return check_hip(hipMemsetAsync(cnt, 0, gru_wave_cnt_words_bwd(L, T, B) * sizeof(unsigned), s), "gru_wave_bwd: counters");
-}
-// gate of a consumer of layer `layer`'s dG[t0 .. T) (see wave_gate_kernel); cnt = the block gru_wave_bwd counts in
-int gru_wave_gate(unsigned* cnt, int layer, int t0, int T, int B, int H, unsigned* err, hipStream_t s) {
-  const int ngrp = (B + 15) / 16, G = H / 16;
-  hipLaunchKernelGGL(wave_gate_kernel, dim3(1), dim3(64), 0, s, cnt + 16 + layer * ngrp, ngrp, (unsigned)G * (unsigned)(T - t0 + 1), err);
-  return check_hip(hipGetLastError(), "gru_wave_gate");
-}
-
 int gru_wave_bwd(const WaveBwdArgs& a_in, hipStream_t s) {
   WaveBwdArgs a = a_in;
-  a.flags = wave_flags() | (a_in.flags & 4);     // bit 2: write dG through (consumers inside the sweep's lifetime: gated GEMMs)
+  a.flags = wave_flags();
+  if (a.ks && !gru_wave_ks(a.L, a.T, a.B, a.H)) { set_error("gru_wave_bwd: the K-split form does not serve L=%d T=%d B=%d H=%d", a.L, a.T, a.B, a.H); return 2; }
   if (a_in.flags & 8) {      // bit 3 (K-split form only): w_hh_t / w_ih_t point at the UNtransposed matrices
-    if (!gru_wave_ks(a.L, a.T, a.B, a.H)) { set_error("gru_wave_bwd: untransposed weights need the K-split form"); return 2; }
+    if (!a.ks) { set_error("gru_wave_bwd: untransposed weights need the K-split form"); return 2; }
     a.flags |= 8;
   }
   const char* why = nullptr;
   if (!gru_wave_ok(a.L, a.T, a.B, a.H, &why)) { set_error("gru_wave_bwd: unsupported shape L=%d T=%d B=%d H=%d (%s)", a.L, a.T, a.B, a.H, why); return 2; }
   const bool drop = a.drop_p > 0.f && a.L > 1, loc = gru_wave_local(a.L, a.H);
   const size_t lds = gru_wave_lds_bytes(a.H);
-  int rc = 0;
-  if (!(a_in.flags & 2)) { rc = gru_wave_bwd_clear(a.cnt, a.L, a.T, a.B, s); if (rc) return rc; }   // (bit 1: the caller cleared them, gated consumers are already waiting)
-  a.tickets = a.cnt; a.prog = a_in.prog ? a.cnt + 16 : nullptr; a.cnt = a.cnt + 16 + 64;
-  if (gru_wave_ks(a.L, a.T, a.B, a.H)) {
+  a.tickets = a.cnt; a.cnt = a.cnt + 16;
+  int rc = check_hip(hipMemsetAsync(a.tickets, 0, gru_wave_cnt_words_bwd(a.L, a.T, a.B) * sizeof(unsigned), s), "gru_wave_bwd: counters");
+  if (rc) return rc;
+  if (a.ks) {
     rc = ks_arm(a.ring, a.L, (size_t)((a.B + 15) / 16) * 4 * (a.H / 32) * 1024, s);
     if (rc) return rc;
     switch (a.H / 128) {
@@ -951,23 +748,16 @@ int gru_wave_bwd(const WaveBwdArgs& a_in, hipStream_t s) {
     if (rc) return rc;
     return check_hip(hipGetLastError(), "gru_wave_bwd");
   }
-  const bool rgf = gru_wave_rgf(a.H);
-  const int ngrp_ = (a.B + 15) / 16;
-  const dim3 grid(loc ? 256 : (rgf ? a.L * ngrp_ * (a.H / 64) : a.L * (a.H / 16)));
-  const size_t lds_r = gru_wave_lds_bytes_rgf_bwd(a.H);
+  const dim3 grid(loc ? 256 : a.L * (a.H / 16));
 #define B2T_WAVE_BWD(NPV)                                                                                              \
   do {                                                                                                                 \
-    if (rgf && loc) rc = drop ? wave_launch_bwd<NPV, true, true, true>(a, grid, lds_r, s) : wave_launch_bwd<NPV, false, true, true>(a, grid, lds_r, s); \
-    else if (rgf) rc = drop ? wave_launch_bwd<NPV, true, false, true>(a, grid, lds_r, s) : wave_launch_bwd<NPV, false, false, true>(a, grid, lds_r, s); \
-    else if (loc) rc = drop ? wave_launch_bwd<NPV, true, true>(a, grid, lds, s) : wave_launch_bwd<NPV, false, true>(a, grid, lds, s);   \
+    if (loc) rc = drop ? wave_launch_bwd<NPV, true, true>(a, grid, lds, s) : wave_launch_bwd<NPV, false, true>(a, grid, lds, s);   \
     else rc = drop ? wave_launch_bwd<NPV, true, false>(a, grid, lds, s) : wave_launch_bwd<NPV, false, false>(a, grid, lds, s);     \
   } while (0)
   if (a.H <= 128) B2T_WAVE_BWD(4);
   else if (a.H <= 256) B2T_WAVE_BWD(8);
-  else if (a.H <= 512) {
-    if (loc) rc = drop ? wave_launch_bwd<16, true, true>(a, grid, lds, s) : wave_launch_bwd<16, false, true>(a, grid, lds, s);
-    else rc = drop ? wave_launch_bwd<16, true, false>(a, grid, lds, s) : wave_launch_bwd<16, false, false>(a, grid, lds, s);
-  } else rc = drop ? wave_launch_bwd<24, true, false>(a, grid, lds, s) : wave_launch_bwd<24, false, false>(a, grid, lds, s);
+  else if (a.H <= 512) B2T_WAVE_BWD(16);
+  else rc = drop ? wave_launch_bwd<24, true, false>(a, grid, lds, s) : wave_launch_bwd<24, false, false>(a, grid, lds, s);
 #undef B2T_WAVE_BWD
   if (rc) return rc;
   return check_hip(hipGetLastError(), "gru_wave_bwd");
@@ -1034,7 +824,7 @@ extern "C" int b2t_gru_wave_bwd_f32(const b2t_wave_t* d, void* ws, unsigned* err
   B2T_REQUIRE(d->dY_top && d->dh_init && d->drop_p >= 0.f && d->drop_p < 1.f, "gru_wave_bwd: dY_top / dh_init / dropout");
   WaveBwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.L = L; a.T = T; a.B = B; a.H = H; a.dY_top = d->dY_top;
+  a.L = L; a.T = T; a.B = B; a.H = H; a.dY_top = d->dY_top; a.ks = gru_wave_ks(L, T, B, H);
   for (int l = 0; l < L; ++l) { a.dh_last[l] = d->dh_last ? d->dh_last + (size_t)l * B * H : nullptr; a.dh_init[l] = d->dh_init + (size_t)l * B * H; }
   const bool drop = d->drop_p > 0.f && L > 1;
   wave_carve(reinterpret_cast<char*>(ws), L, T, B, H, true, a.cnt, a.ring, a.ringx);

@@ -495,7 +495,6 @@ __global__ __launch_bounds__(256, 1) void gru_ks_bwd_kernel(const WaveBwdArgs a)
   for (int i = 0; i < 4; ++i) live[i] = rg_live && m0 + 4 * q + i < B;
   const int rrow = m0 + (lane & 15), kg = lane >> 4;
   int pending_x = -1;
-  unsigned* prog = (a.prog && rg_live) ? a.prog + layer * ngrp + rg : nullptr;
 
 #ifdef B2T_WAVE_TIMING
   unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
@@ -576,8 +575,6 @@ __global__ __launch_bounds__(256, 1) void gru_ks_bwd_kernel(const WaveBwdArgs a)
       // (nothing of this wave is in flight here -- the look above was waited for in full: the drain is free)
       wave_drain();
       if (pending_x >= 0) { wave_bump<false>(cnt_x + pending_x, lane); pending_x = -1; }
-      // progress for consumers OUTSIDE the launch (the gated weight-gradient GEMMs): every store of the steps > t is acknowledged
-      if (prog) wave_bump<false>(prog, lane);
       // Order of the rest (vector memory returns in order: nothing slow may sit in front of a look at the own ring):
       //   request dr, dz -> recurrent MFMAs of dn r (its registers are then free) -> request dn into them (layers that project) ->
       //   check dr, dz (re-request while something is missing) -> their MFMAs (recurrent + projection) -> check dn -> its MFMAs ->
@@ -711,7 +708,6 @@ __global__ __launch_bounds__(256, 1) void gru_ks_bwd_kernel(const WaveBwdArgs a)
       for (int i = 0; i < 4; ++i) carry[i] = rec[i] + dzterm[i];
     } else {
       wave_drain();
-      if (prog) wave_bump<false>(prog, lane);
       if (DB) fetch(t - 1, nxt, false);
       if (a.dh_last[layer]) {
 #pragma unroll
@@ -758,15 +754,9 @@ __global__ __launch_bounds__(256, 1) void gru_ks_bwd_kernel(const WaveBwdArgs a)
       if (rrow < B) {
         float* dgl = a.dG[layer] + (long long)t * B * 4 * H;
         const unsigned off = (unsigned)(((long long)rrow * 4 * H + u0 + 4 * kg) * 4);
-        // written THROUGH only for readers inside the sweep's lifetime (gated GEMMs, flags bit 2); otherwise ordinary stores (the kernel's
-        // end makes them visible)
-        if (a.flags & 4) {
+        // (ordinary stores: nothing reads dG before the kernel's end makes them visible)
 #pragma unroll
-          for (int g = 0; g < 4; ++g) store_f4<16>(dgl, off + (unsigned)g * (unsigned)H * 4u, ld4(tiles + g * WTILE_F + (lane & 15) * WTP + 4 * kg));
-        } else {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) store_f4<0>(dgl, off + (unsigned)g * (unsigned)H * 4u, ld4(tiles + g * WTILE_F + (lane & 15) * WTP + 4 * kg));
-        }
+        for (int g = 0; g < 4; ++g) store_f4<0>(dgl, off + (unsigned)g * (unsigned)H * 4u, ld4(tiles + g * WTILE_F + (lane & 15) * WTP + 4 * kg));
       }
       WSTAMP(4)
     }

@@ -258,10 +258,10 @@ def test_bf16_mode_step_on_the_wavefront_tracks_the_chunk_pipeline(monkeypatch, 
             assert diff <= 5e-3 * scale, f"{name} differ by {diff} (scale {scale})"
         for a, b in zip(got, again):       # the wavefront itself is deterministic
             assert torch.equal(a, b)
-        # forward: a launch per time chunk (states carried in fp32 exactly as inside one launch); backward: the consumers of the sweep's
-        # dG -- layer 0's input gradient, every weight gradient -- chunk by chunk BESIDE the one sweep launch, each behind a gate on the
-        # sweep's progress word: logits and losses bit-identical, the weight gradients accumulated chunk by chunk (another fp32
-        # summation order)
+        # forward: a launch per time chunk (states carried in fp32 exactly as inside one launch); backward: a sweep launch per time
+        # chunk too, last chunk first (the state gradient carried in fp32), the consumers of a chunk's dG -- layer 0's input gradient,
+        # every weight gradient -- behind that launch and beside the next one: logits and losses bit-identical, the weight gradients
+        # accumulated chunk by chunk (another fp32 summation order)
         cut = grads(True, "3,2")
         assert torch.equal(cut[2], got[2]) and torch.equal(cut[1], got[1])
         assert float((cut[0] - got[0]).abs().max()) <= 2e-4 * float(got[0].abs().max())
