@@ -659,6 +659,58 @@ int b2t_clm_score_tree_f16(const b2t_clm_t* model, const int32_t* ids_host, cons
                            float* scores_out, float* tok_logp_out, long long* n_nodes_out,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the tree scoring behind a context cache (csrc/causal_lm_cache.hip) ----------------------------------------------
+ * With contextual decoding the server glues the decoding context in front of every candidate and scores the whole string
+ * again at every sentence end (language-model-standalone.py:188-190), and the context only grows: it is the previous
+ * context plus the sentence just chosen (:577-583).  The kernels compute a row in an order that depends only on that row, so
+ * the K / V rows and the log-prob of a context token computed by an earlier call are the values this call would compute: the
+ * cache keeps them, and the scores stay bit-identical to b2t_clm_score_f16's and b2t_clm_score_tree_f16's.
+ *
+ * The cache holds ONE token chain c[0..n).  The rule of a call:
+ *   trunk Tn  = the longest token prefix common to ALL sequences of the call (0 when first tokens differ, the whole sequence
+ *               when the list is one sequence or all are equal) = nodes 0..Tn-1 of the tree plan;
+ *   common P  = the longest common prefix of the trunk and the cached chain;
+ *   reused R  = max(P - 1, 0): positions 0..R-1 are not computed, their K / V come from the cache in every layer and the
+ *               log-probs of positions 1..R come from the cache; position P-1 is recomputed (its hidden row feeds the head
+ *               of its children; hidden states are not cached).  Rows computed = tree nodes - R;
+ *   afterwards (update != 0) the cache holds the trunk: positions R..min(Tn, cap)-1 are written from this call, n =
+ *               min(Tn, cap), ids_host follows.  A context that diverges from the chain at P overwrites from there; an empty
+ *               or different context shrinks the cache.  update == 0 uses the cache and leaves it exactly as it was.
+ * The buffers are the caller's, like every other buffer of this library, which keeps no pointer after returning.  Calls that
+ * share a cache are ordered by the caller (one stream, or an event between streams). */
+typedef struct {
+  void* kv;           /* DEVICE fp16 [n_layers][cap][2 * d_model]: K row then V row per position */
+  float* logp;        /* DEVICE fp32 [cap]: log p(c[t] | c[<t]), [0] unused */
+  int32_t* ids_host;  /* HOST [cap]: the cached chain */
+  int cap, n;         /* capacity; positions held -- n is updated by the call */
+} b2t_clm_cache_t;
+/* Bytes of b2t_clm_cache_t.kv for `cap` positions: n_layers * cap * 2 * d_model * 2 (0 if invalid: null model, cap < 1,
+ * cap > max_pos, n_layers < 1). */
+size_t b2t_clm_cache_kv_bytes(const b2t_clm_t* model, int cap);
+/* HOST function (no GPU): the rule above for a cached chain cache_ids_host[0..cache_n) of capacity cap and a packed list.
+ * Every output is optional: *trunk = Tn, *common = P, *reused = R, *n_nodes = the tree plan's nodes, *n_rows = n_nodes - R
+ * (rows computed), *n_after = min(Tn, cap) (the cache's n after an updating call).  Returns 0; 2 on a null argument, cap < 1,
+ * cache_n outside [0, cap], n_seq < 1, seq_off[0] != 0 or an empty sequence. */
+int b2t_clm_cache_plan_host(const int32_t* cache_ids_host, int cache_n, int cap, const int32_t* ids_host,
+                            const int32_t* seq_off_host, int n_seq, int* trunk, int* common, int* reused,
+                            long long* n_nodes, long long* n_rows, int* n_after);
+/* Workspace bytes of b2t_clm_score_tree_cached_f16 for n_rows computed rows of n_tokens tokens in n_seq sequences (0 if the
+ * sizes are invalid, as b2t_clm_tree_ws_bytes); non-decreasing in each argument; the tree plan's node count is always enough
+ * for n_rows.  What the tree call needs for n_rows rows plus the per-row attention state of B2T_CLM_TRUNK_ATTN. */
+size_t b2t_clm_tree_cached_ws_bytes(const b2t_clm_t* model, long long n_rows, long long n_tokens, int n_seq);
+/* b2t_clm_score_tree_f16 behind the cache: same lists, same outputs in the same layout, same refusals before any launch,
+ * plus: a null cache or member, cap < 1, cap > max_pos, n outside [0, cap], a cached id outside the vocabulary.  (Without a
+ * cache callers use b2t_clm_score_tree_f16.)  *n_rows_out (optional, host) = rows computed, *n_reused_out (optional, host) =
+ * R.  cache->n and ids_host are updated only after every launch of the call was enqueued without error; on an error return
+ * after the first launch of an updating call the cache is left at min(n, R), never pointing at rows that were not written.
+ * B2T_CLM_GEMM_256 applies as in the tree call.  B2T_CLM_TRUNK_ATTN (read per call; 0 / 1) moves the attention over the
+ * whole 32-key blocks that lie in the cache to a kernel that runs them once per 32 computed rows instead of once per
+ * sequence; the bits do not depend on it. */
+int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache, int update,
+                                  const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                  float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
+                                  void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,11 @@ class ClmDesc(C.Structure):
                [("layers_host", C.POINTER(ClmLayer))]
 
 
+class ClmCache(C.Structure):
+    """Mirror of b2t_clm_cache_t (include/b2t.h): the caller-owned context cache of b2t_clm_score_tree_cached_f16."""
+    _fields_ = [("kv", VP), ("logp", VP), ("ids_host", VP), ("cap", C.c_int), ("n", C.c_int)]
+
+
 _SIGNATURES = {
     "b2t_version": (C.c_int, []),
     "b2t_last_error": (C.c_char_p, []),
@@ -216,6 +221,12 @@ _SIGNATURES = {
     "b2t_clm_tree_plan_host": (C.c_int, [VP, VP, C.c_int, VP, VP, LL, C.POINTER(LL)]),
     "b2t_clm_tree_ws_bytes": (C.c_size_t, [C.POINTER(ClmDesc), LL, LL, C.c_int]),
     "b2t_clm_score_tree_f16": (C.c_int, [C.POINTER(ClmDesc), VP, VP, C.c_int, VP, VP, C.POINTER(LL), VP, C.c_size_t, VP]),
+    "b2t_clm_cache_kv_bytes": (C.c_size_t, [C.POINTER(ClmDesc), C.c_int]),
+    "b2t_clm_cache_plan_host": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.POINTER(LL), C.POINTER(LL), C.POINTER(C.c_int)]),
+    "b2t_clm_tree_cached_ws_bytes": (C.c_size_t, [C.POINTER(ClmDesc), LL, LL, C.c_int]),
+    "b2t_clm_score_tree_cached_f16": (C.c_int, [C.POINTER(ClmDesc), C.POINTER(ClmCache), C.c_int, VP, VP, C.c_int, VP, VP,
+                                                C.POINTER(LL), C.POINTER(C.c_int), VP, C.c_size_t, VP]),
 }
 
 

@@ -170,12 +170,9 @@ __global__ __launch_bounds__(64) void clm_seq_sum_tree_kernel(const float* logp,
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline long long rup(long long x, long long m) { return (x + m - 1) / m * m; }
 
-// Sized by n_nodes alone where the flat path has n_tokens - n_seq head rows: the head has n_nodes - roots rows.
-struct TreeLayout {
-  size_t ints, resid, x16, qkv, hbuf, pmax, psum, tlogit, logp, total;
-  long long Mp, ncg;
-};
+}  // namespace
 
+// The layout and the plan have external linkage (clm_internal.h): causal_lm_cache.hip sizes and plans its call with them.
 size_t tree_ints(long long Mn, long long M, int n_seq) { return (size_t)(4 * Mn + 2 * M + 2 * (long long)n_seq + 1); }
 
 TreeLayout tree_layout(const b2t_clm_t* m, long long Mn, long long M, int n_seq) {
@@ -222,7 +219,6 @@ long long tree_plan(const int32_t* ids, const int32_t* seq_off, int n_seq, int32
   return n;
 }
 
-}  // namespace
 }  // namespace b2t
 
 using namespace b2t;

@@ -1,5 +1,6 @@
 // clm_internal.h — host-side pieces of the causal-LM forward shared by causal_lm.hip (the flat scoring path, which defines
-// them) and causal_lm_tree.hip (the shared-prefix tree path).  The kernels themselves stay private to causal_lm.hip; these
+// them), causal_lm_tree.hip (the shared-prefix tree path, which defines the plan and the workspace layout) and
+// causal_lm_cache.hip (the tree path behind a context cache).  The kernels themselves stay private to causal_lm.hip; these
 // are their launchers, so the GEMM is instantiated once.
 #pragma once
 #include "common.h"
@@ -42,5 +43,20 @@ int clm_launch_head_combine(const float* pmax, const float* psum, const float* t
                             hipStream_t s);
 // dimensions, head dim and weight pointers of a model descriptor (0, or an error with the message set)
 int clm_check_model(const b2t_clm_t* m);
+
+// ---- causal_lm_tree.hip ----
+// Workspace of a forward over Mn rows for M packed tokens in n_seq sequences: sized by Mn alone where the flat path has
+// n_tokens - n_seq head rows (the head has at most a row per computed row).
+struct TreeLayout {
+  size_t ints, resid, x16, qkv, hbuf, pmax, psum, tlogit, logp, total;
+  long long Mp, ncg;
+};
+// ints of the index arrays: node_id[Mn] node_pos[Mn] head_src[Mn] head_tgt[Mn] tok_node[M] tok_hrow[M] seq_off[n+1] own_start[n]
+size_t tree_ints(long long Mn, long long M, int n_seq);
+TreeLayout tree_layout(const b2t_clm_t* m, long long Mn, long long M, int n_seq);
+// The shared-prefix plan (b2t_clm_tree_plan_host): node_of_token gets all n_tokens entries; parent_of_node (and own_start,
+// optional, per sequence) only below cap.  Returns the number of nodes.
+long long tree_plan(const int32_t* ids, const int32_t* seq_off, int n_seq, int32_t* node_of_token, int32_t* parent_of_node,
+                    long long cap, int32_t* own_start);
 
 }  // namespace b2t

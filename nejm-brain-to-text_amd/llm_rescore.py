@@ -1,7 +1,8 @@
 """OPT n-best rescoring: the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
 :127-162, gpt2_lm_decode :165-251, get_string_differences :273-311, augment_nbest :327-411) with the causal-LM forward on the
 HIP path (b2t_clm_score_f16, csrc/causal_lm.hip; opt-in b2t_clm_score_tree_f16, csrc/causal_lm_tree.hip, which computes the
-prefixes the candidates share once).
+prefixes the candidates share once; opt-in b2t_clm_score_tree_cached_f16, csrc/causal_lm_cache.hip, which also keeps the
+decoding context's keys, values and log-probs from one call to the next).
 
 Call surfaces are the reference's: `build_opt(model_name, cache_dir, device)` returns `(model, tokenizer)`, and the three
 functions take them as the reference's do.  `model` here is an `OptScorer`: the checkpoint's fp16 weights converted once into
@@ -321,9 +322,18 @@ class OptScorer:
     """An OPT decoder on the GPU in the b2t_clm_t layout; `score` runs b2t_clm_score_f16 on packed ids, or, with
     share_prefixes, b2t_clm_score_tree_f16: the same forward over the list's shared-prefix token tree (each distinct prefix
     computed once; results bit-identical to the flat call).  `share_prefixes` here is the default of `score` and
-    `token_logprobs`; after a call `last_stats` = {"tokens": packed tokens, "nodes": rows computed}."""
+    `token_logprobs`; after a call `last_stats` = {"tokens": packed tokens, "nodes": rows computed}.
 
-    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False):
+    context_cache_tokens > 0 allocates a context cache of that many positions (n_layers * 4 * d_model bytes each: 512 KiB at
+    the OPT-6.7b shape, 1 GiB for 2048) and makes `score` / `token_logprobs` take b2t_clm_score_tree_cached_f16: the tree
+    forward (prefixes shared by construction) in which the positions of the list's common prefix that an earlier call already
+    computed are read from the cache instead.  The cache is matched by token ids, so it is never wrong, only more or less
+    useful; results stay bit-identical.  Per call `use_cache` = None (the scorer's setting) | True | False; after a cached
+    call `last_stats` = {"tokens", "nodes": rows computed, "reused": positions taken from the cache}."""
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0):
+        import ctypes as C
         import torch
         import b2t_native as N
         self.dims = dict(dims)
@@ -339,16 +349,49 @@ class OptScorer:
                               self.w["embed_tokens"].data_ptr(), self.w["embed_positions"].data_ptr(),
                               self.w["final_ln_w"].data_ptr(), self.w["final_ln_b"].data_ptr(), self._layers)
         self._ws = None
+        self.context_cache_tokens = int(context_cache_tokens)
+        self._cache = None
+        if self.context_cache_tokens < 0:
+            raise ValueError("OptScorer: context_cache_tokens < 0")
+        if self.context_cache_tokens > 0:
+            cap = self.context_cache_tokens
+            nbytes = N.load().b2t_clm_cache_kv_bytes(C.byref(self.desc), cap)
+            if nbytes == 0:
+                raise ValueError(f"OptScorer: context_cache_tokens {cap} outside [1, max_pos {dims['max_pos']}]")
+            self._cache_kv = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._cache_logp = torch.empty(cap, dtype=torch.float32, device=self.device)
+            self._cache_ids = np.zeros(cap, np.int32)
+            self._cache = N.ClmCache(self._cache_kv.data_ptr(), self._cache_logp.data_ptr(), self._cache_ids.ctypes.data, cap, 0)
+
+    @property
+    def cache_len(self) -> int:
+        """Positions the context cache holds (0 without a cache)."""
+        return int(self._cache.n) if self._cache is not None else 0
+
+    @property
+    def cache_ids(self) -> np.ndarray:
+        """The cached token chain (a copy)."""
+        return self._cache_ids[:self.cache_len].copy() if self._cache is not None else np.zeros(0, np.int32)
+
+    def cache_reset(self, keep: int = 0) -> None:
+        """Forget the cached context beyond its first `keep` positions (default: all of it).  Never needed for correctness
+        (the cache is matched by token ids)."""
+        if self._cache is not None:
+            self._cache.n = max(0, min(int(keep), int(self._cache.n)))
 
     def eval(self):   # the reference calls model.eval(); scoring has no training mode
         return self
 
-    def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None):
+    def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
+             update_cache: bool = True):
         import ctypes as C
         import torch
         import b2t_native as N
         lib = N.load()
         tree = self.share_prefixes if share_prefixes is None else bool(share_prefixes)
+        cached = self._cache is not None if use_cache is None else bool(use_cache)
+        if cached and self._cache is None:
+            raise ValueError("OptScorer: use_cache=True on a scorer built without context_cache_tokens")
         seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in ids_list]
         if not seqs:
             self.last_stats = {"tokens": 0, "nodes": 0}
@@ -363,7 +406,12 @@ class OptScorer:
             raise ValueError("OptScorer: too many tokens")
         M = int(off[-1])
         nodes = M
-        if tree:
+        reused = 0
+        if cached:
+            plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
+            nodes, reused = plan["rows"], plan["reused"]
+            need = lib.b2t_clm_tree_cached_ws_bytes(C.byref(self.desc), nodes, M, len(seqs))
+        elif tree:
             nodes = tree_plan(ids, off)[2]
             need = lib.b2t_clm_tree_ws_bytes(C.byref(self.desc), nodes, M, len(seqs))
         else:
@@ -376,7 +424,13 @@ class OptScorer:
         tok = torch.empty(M, dtype=torch.float32, device=self.device) if want_tokens else None
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            if tree:
+            if cached:
+                N.check(lib.b2t_clm_score_tree_cached_f16(C.byref(self.desc), C.byref(self._cache), 1 if update_cache else 0,
+                                                          ids.ctypes.data, off.ctypes.data, len(seqs), scores.data_ptr(),
+                                                          tok.data_ptr() if tok is not None else None, None, None,
+                                                          self._ws.data_ptr(), self._ws.numel(), stream),
+                        "b2t_clm_score_tree_cached_f16")
+            elif tree:
                 N.check(lib.b2t_clm_score_tree_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs),
                                                    scores.data_ptr(), tok.data_ptr() if tok is not None else None, None,
                                                    self._ws.data_ptr(), self._ws.numel(), stream), "b2t_clm_score_tree_f16")
@@ -387,17 +441,22 @@ class OptScorer:
             s = scores.cpu().numpy()
             t = tok.cpu().numpy() if tok is not None else None
         self.last_stats = {"tokens": M, "nodes": int(nodes)}
+        if cached:
+            self.last_stats["reused"] = int(reused)
         return s, lens, t
 
-    def score(self, ids_list, length_penalty: float = 0.0, share_prefixes: Optional[bool] = None) -> np.ndarray:
+    def score(self, ids_list, length_penalty: float = 0.0, share_prefixes: Optional[bool] = None,
+              use_cache: Optional[bool] = None, update_cache: bool = True) -> np.ndarray:
         """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores.
-        share_prefixes: None = the scorer's own setting."""
-        s, lens, _ = self._run(ids_list, False, share_prefixes)
+        share_prefixes: None = the scorer's own setting.  use_cache: None = cached iff the scorer has a context cache; a
+        cached call shares prefixes whatever share_prefixes says.  update_cache=False reads the cache and leaves it as it was."""
+        s, lens, _ = self._run(ids_list, False, share_prefixes, use_cache, update_cache)
         return s.astype(np.float32) - (lens * float(length_penalty)).astype(np.float32)
 
-    def token_logprobs(self, ids_list, share_prefixes: Optional[bool] = None) -> List[np.ndarray]:
+    def token_logprobs(self, ids_list, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
+                       update_cache: bool = True) -> List[np.ndarray]:
         """Per sequence the fp32 log-prob of each token given its prefix (0 for the first token)."""
-        _, lens, t = self._run(ids_list, True, share_prefixes)
+        _, lens, t = self._run(ids_list, True, share_prefixes, use_cache, update_cache)
         off = np.concatenate([[0], np.cumsum(lens)])
         return [t[off[i]:off[i + 1]] for i in range(len(lens))]
 
@@ -418,9 +477,27 @@ def tree_plan(ids, seq_off, cap: Optional[int] = None):
     return node, parent[:n.value], int(n.value)
 
 
-def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False):
+def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
+    """b2t_clm_cache_plan_host (host only, no GPU): what a cached call on the packed list does against the cached chain
+    cache_ids of capacity cap: {"trunk": Tn, "common": P, "reused": R, "nodes", "rows": nodes - R, "n_after": min(Tn, cap)}."""
+    import ctypes as C
+    import b2t_native as N
+    cid = np.ascontiguousarray(cache_ids, np.int32)
+    ids = np.ascontiguousarray(ids, np.int32)
+    off = np.ascontiguousarray(seq_off, np.int32)
+    tn, p, r, na = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    nn, nr = C.c_longlong(0), C.c_longlong(0)
+    N.check(N.load().b2t_clm_cache_plan_host(cid.ctypes.data if len(cid) else None, len(cid), int(cap), ids.ctypes.data,
+                                             off.ctypes.data, len(off) - 1, C.byref(tn), C.byref(p), C.byref(r), C.byref(nn),
+                                             C.byref(nr), C.byref(na)), "b2t_clm_cache_plan_host")
+    return {"trunk": tn.value, "common": p.value, "reused": r.value, "nodes": int(nn.value), "rows": int(nr.value),
+            "n_after": na.value}
+
+
+def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0):
     """(OptScorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16).
-    share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once."""
+    share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
+    context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (OptScorer)."""
     model_dir = resolve_model_dir(model_name, cache_dir)
     dims, arrays = load_opt_arrays(model_dir)
     from transformers import AutoTokenizer
@@ -428,7 +505,7 @@ def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", sha
     tok.padding_side = "right"
     if tok.pad_token is None:
         tok.pad_token = tok.eos_token
-    return OptScorer(dims, arrays, device, share_prefixes), tok
+    return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens), tok
 
 
 class WordTokenizer:

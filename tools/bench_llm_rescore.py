@@ -14,6 +14,16 @@ list of each, with the largest spread between the repeats of one list
 (hip_ms_per_list = flat, hip_tree_ms_per_list = tree); the torch baseline is not run in that mode.
 
   python tools/bench_llm_rescore.py --list nbest --context 64 [--lists 7]
+
+`--session` measures the context cache (b2t_clm_score_tree_cached_f16) in the closed loop it is for: a conversation of
+--sentences calls, call k scoring a 100-candidate nbest list behind the context = the base sentences of the calls before it.
+Per call the tree path, the cached path with B2T_CLM_TRUNK_ATTN=0 (stage A) and with 1 (stage A + B) run one after the other
+in this process on the same cache state (the cache is cut back to what it held before the call in between); --reps passes
+over the conversation after one untimed pass.  The line reports per call the context tokens, tree nodes, rows computed,
+positions reused, the median ms of each path with the spread (max - min) over the repeats of that call, and whether all
+scores were byte-identical.
+
+  python tools/bench_llm_rescore.py --session [--sentences 12] [--reps 5]
 """
 import argparse
 import json
@@ -62,6 +72,8 @@ def main():
     ap.add_argument("--context", type=int, default=0, help="shared tokens in front of every candidate (A/B with the tree path)")
     ap.add_argument("--tree", action="store_true", help="A/B flat against tree on the chosen list")
     ap.add_argument("--reps", type=int, default=3, help="A/B: timed passes over the lists")
+    ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
+    ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
     import torch
     import torch.nn.functional as F
@@ -84,9 +96,11 @@ def main():
             st[p + n + ".weight"] = torch.ones(d, device=dev).half()
             st[p + n + ".bias"] = rn(d, std=0.1)
     lay = R.device_layout({k: v for k, v in st.items()}, dims)   # (host copies; the device copies below are the scorer's)
-    sc = R.OptScorer(dims, lay, dev)
+    sc = R.OptScorer(dims, lay, dev, context_cache_tokens=dims["max_pos"] if a.session else 0)
     del lay
     rng = np.random.default_rng(0)
+    if a.session:
+        return session(a, sc, rng)
     ab = a.tree or a.list != "random" or a.context > 0
     if not ab:
         lists = [random_list(rng, V, a.cands) for _ in range(a.lists)]
@@ -173,6 +187,55 @@ def ab_flat_tree(a, sc, lists, ntok):
                       "hip_ms_per_list": st(False)["median"], "hip_tree_ms_per_list": st(True)["median"],
                       "flat_ms": st(False), "tree_ms": st(True), "per_list_tokens": ntok, "per_list_nodes": nodes,
                       "per_list_flat_ms": [r2(x) for x in per[False]], "per_list_tree_ms": [r2(x) for x in per[True]],
+                      "scores_bit_identical": bool(same)}))
+
+
+def session(a, sc, rng):
+    """Tree path against the cached path (stage A, stage A + B) call by call over one conversation; see the module docstring."""
+    import torch
+    ENV = "B2T_CLM_TRUNK_ATTN"
+    calls, ctx_len, ctx = [], [], []
+    for _ in range(a.sentences):
+        calls.append(nbest_list(rng, a.vocab, a.cands, ctx))
+        ctx_len.append(len(ctx))
+        ctx = [int(x) for x in calls[-1][0][1:]]   # the context so far + the base sentence of this call
+    if len(ctx) + 1 > sc.dims["max_pos"]:
+        raise SystemExit(f"--sentences {a.sentences}: the conversation outgrows max_pos {sc.dims['max_pos']}")
+    paths = ("tree", "cached_a", "cached_ab")
+    ms = {p: [[] for _ in calls] for p in paths}
+    info, same = [None] * len(calls), True
+    old = os.environ.get(ENV)
+    try:
+        with torch.inference_mode():
+            for rep in range(max(1, a.reps) + 1):   # pass 0 warms every path and is not timed
+                sc.cache_reset()
+                for k, l in enumerate(calls):
+                    held, out = sc.cache_len, {}
+                    for p in paths:
+                        if p != "tree":
+                            os.environ[ENV] = "0" if p == "cached_a" else "1"
+                            sc.cache_reset(keep=held)
+                        t0 = time.perf_counter()
+                        out[p] = sc.score(l, share_prefixes=True, use_cache=p != "tree")   # host scores: the call is complete
+                        if rep:
+                            ms[p][k].append((time.perf_counter() - t0) * 1e3)
+                        if p == "tree":
+                            nodes = sc.last_stats["nodes"]
+                    same = same and out["tree"].tobytes() == out["cached_a"].tobytes() == out["cached_ab"].tobytes()
+                    info[k] = {"context": ctx_len[k], "tokens": sum(map(len, l)), "nodes": nodes, "rows": sc.last_stats["nodes"],
+                               "reused": sc.last_stats["reused"]}
+    finally:
+        if old is None:
+            os.environ.pop(ENV, None)
+        else:
+            os.environ[ENV] = old
+    r2 = lambda x: round(float(x), 2)
+    for k in range(len(calls)):
+        for p in paths:
+            info[k][p + "_ms"] = r2(np.median(ms[p][k]))
+            info[k][p + "_spread"] = r2(max(ms[p][k]) - min(ms[p][k]))
+    print(json.dumps({"bench": "llm_rescore_session", "layers": a.layers, "d": a.d, "heads": a.heads, "ffn": a.ffn, "vocab": a.vocab,
+                      "cands": a.cands, "sentences": len(calls), "reps": max(1, a.reps), "per_call": info,
                       "scores_bit_identical": bool(same)}))
 
 
