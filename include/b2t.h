@@ -711,6 +711,58 @@ int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache
                                   float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
                                   void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same scoring for the Llama family (csrc/causal_lm_llama.hip) --------------------------------------------------
+ * HF LlamaForCausalLM, MistralForCausalLM and Qwen2ForCausalLM: RMSNorm, rotary positions (rotate-half convention),
+ * grouped-query attention, a SwiGLU MLP, no biases but optionally q / k / v's, an LM head that may be untied.  The reference
+ * loads its rescoring LLM through AutoModelForCausalLM (language-model-standalone.py:92-123), so these are models its users can
+ * name.  Weights are fp16 DEVICE arrays in this layout (nejm-brain-to-text_amd/llm_rescore.py builds it once at load time),
+ * with hd = d_model / n_heads, Hq = n_heads, Hkv = n_kv_heads, F = ffn_dim:
+ *   rows of every nn.Linear weight [N][K] zero-padded to a multiple of 256;
+ *   qkv_w rows = q_proj | k_proj | v_proj; for hd == 128 the rows of each q and k head (and their entries of qkv_b) are
+ *     stored in the order [0..31, 64..95, 32..63, 96..127], which puts the two halves of a rotary pair 32 rows apart as they
+ *     are for hd == 64 (q . k does not change when both are permuted alike; v_proj and o_proj are stored as they are);
+ *   gate_up_w rows = gate_proj and up_proj interleaved in blocks of 32: row 64b + i = gate[32b + i], row 64b + 32 + i =
+ *     up[32b + i], i < 32;
+ *   rope_cos / rope_sin: fp32 [max_pos][hd / 2], cos and sin of p * inv_freq[i] -- the host computes them in double, so the
+ *     frequency scaling ("default", "llama3") is data to the kernels.
+ * Required: Hq * hd == d_model, hd 64 or 128, Hq % Hkv == 0, d_model % 64 == 0, ffn_dim % 64 == 0; anything else is refused
+ * before any launch.
+ * Numerics: fp16 operands, fp32 accumulation; the residual stream (the fp16 embedding row widened), RMSNorm statistics, the
+ * rotation, softmax / log-softmax and the sums are fp32.  Rounded to fp16, once each: the RMSNorm output
+ * x * rsqrt(mean(x^2) + rms_eps) * w; q, k, v -- q and k after bias, rotation and (q) the factor hd^-0.5, all applied to the
+ * fp32 accumulator; the attention's probabilities exp(s - m) per 32-key block as the P.V operand (the normaliser sums them
+ * unrounded) and its output; silu(gate) * up, from the two fp32 accumulators.  A sequence's result does not depend on the
+ * other sequences of the batch, and the tree call is bit-identical to the flat call. */
+typedef struct {
+  const void *norm1_w, *norm2_w;  /* fp16 [d] input_layernorm, post_attention_layernorm */
+  const void *qkv_w, *qkv_b;      /* fp16 [round_up((Hq + 2 Hkv) hd, 256)][d]; [(Hq + 2 Hkv) hd] or NULL (no biases) */
+  const void* o_w;                /* fp16 [round_up(d, 256)][d] */
+  const void* gate_up_w;          /* fp16 [round_up(2 F, 256)][d], interleaved as above */
+  const void* down_w;             /* fp16 [round_up(d, 256)][F] */
+} b2t_clm_llama_layer_t;
+
+typedef struct {
+  int n_layers, d_model, n_heads, n_kv_heads, ffn_dim, vocab, max_pos;
+  float rms_eps;
+  const void* embed_tokens;            /* fp16 [>= vocab][d] */
+  const void* lm_head;                 /* fp16 [round_up(vocab, 256)][d]; may be embed_tokens (tied) if that is padded so */
+  const void* final_norm_w;            /* fp16 [d] */
+  const float *rope_cos, *rope_sin;    /* fp32 [max_pos][hd / 2] */
+  const b2t_clm_llama_layer_t* layers_host;  /* HOST array of n_layers entries (device pointers inside) */
+} b2t_clm_llama_t;
+
+/* As b2t_clm_ws_bytes / b2t_clm_score_f16: same arguments, output layout, refusals before any launch (plus the model
+ * requirements above) and the one synchronisation of `stream` for the index upload.  Sequences are at most max_pos tokens. */
+size_t b2t_clm_llama_ws_bytes(const b2t_clm_llama_t* model, long long n_tokens, int n_seq);
+int b2t_clm_llama_score_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                            float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+/* As b2t_clm_tree_ws_bytes / b2t_clm_score_tree_f16, on the plan of b2t_clm_tree_plan_host; a node's rotary position is its
+ * depth.  Bit-identical to b2t_clm_llama_score_f16.  (The context cache is OPT's only so far.) */
+size_t b2t_clm_llama_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq);
+int b2t_clm_llama_score_tree_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                 float* scores_out, float* tok_logp_out, long long* n_nodes_out,
+                                 void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,19 @@ class ClmCache(C.Structure):
     _fields_ = [("kv", VP), ("logp", VP), ("ids_host", VP), ("cap", C.c_int), ("n", C.c_int)]
 
 
+class ClmLlamaLayer(C.Structure):
+    """Mirror of b2t_clm_llama_layer_t (include/b2t.h): fp16 device weights of one Llama-family decoder layer."""
+    _fields_ = [(n, VP) for n in ("norm1_w", "norm2_w", "qkv_w", "qkv_b", "o_w", "gate_up_w", "down_w")]
+
+
+class ClmLlamaDesc(C.Structure):
+    """Mirror of b2t_clm_llama_t (include/b2t.h)."""
+    _fields_ = [(n, C.c_int) for n in ("n_layers", "d_model", "n_heads", "n_kv_heads", "ffn_dim", "vocab", "max_pos")] + \
+               [("rms_eps", C.c_float)] + \
+               [(n, VP) for n in ("embed_tokens", "lm_head", "final_norm_w", "rope_cos", "rope_sin")] + \
+               [("layers_host", C.POINTER(ClmLlamaLayer))]
+
+
 _SIGNATURES = {
     "b2t_version": (C.c_int, []),
     "b2t_last_error": (C.c_char_p, []),
@@ -227,6 +240,11 @@ _SIGNATURES = {
     "b2t_clm_tree_cached_ws_bytes": (C.c_size_t, [C.POINTER(ClmDesc), LL, LL, C.c_int]),
     "b2t_clm_score_tree_cached_f16": (C.c_int, [C.POINTER(ClmDesc), C.POINTER(ClmCache), C.c_int, VP, VP, C.c_int, VP, VP,
                                                 C.POINTER(LL), C.POINTER(C.c_int), VP, C.c_size_t, VP]),
+    "b2t_clm_llama_ws_bytes": (C.c_size_t, [C.POINTER(ClmLlamaDesc), LL, C.c_int]),
+    "b2t_clm_llama_score_f16": (C.c_int, [C.POINTER(ClmLlamaDesc), VP, VP, C.c_int, VP, VP, VP, C.c_size_t, VP]),
+    "b2t_clm_llama_tree_ws_bytes": (C.c_size_t, [C.POINTER(ClmLlamaDesc), LL, LL, C.c_int]),
+    "b2t_clm_llama_score_tree_f16": (C.c_int, [C.POINTER(ClmLlamaDesc), VP, VP, C.c_int, VP, VP, C.POINTER(LL), VP, C.c_size_t,
+                                               VP]),
 }
 
 

@@ -24,185 +24,29 @@
 // fp16 A operand directly, and nn.Linear weights ([N][K], k-contiguous) are padded once at load time to 256 rows.
 //
 // The host-side pieces the shared-prefix tree path (causal_lm_tree.hip) reuses -- launch_gemm, the embed / LayerNorm / head
-// launchers, clm_check_model -- have external linkage and are declared in clm_internal.h; the kernels stay private to this file.
+// launchers, clm_check_model -- have external linkage and are declared in clm_internal.h; the kernels stay private to this file
+// (the GEMM's template is clm_gemm.h, instantiated here for the four epilogues of this forward).
 #include <math.h>
 #include <vector>
 
-#include "clm_internal.h"
+#include "clm_gemm.h"
 
 namespace b2t {
-namespace {
-
-using f32x16 = float __attribute__((ext_vector_type(16)));
-using half8 = _Float16 __attribute__((ext_vector_type(8)));
-
-constexpr int CK = 64, CPITCH = CK + 8;      // k tile; LDS row pitch in fp16 elements (144 B)
-constexpr int ROWPAD = CLM_ROWPAD;                  // A operands and weights are padded to this many rows
-
-// ClmGemm (the GEMM's arguments) and the EP_* epilogue ids: clm_internal.h
-
-__device__ __forceinline__ float warp32_max(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float warp32_sum(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.
-template <int BM, int BN, int WGM, int WGN, int EP>
-__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
-  constexpr int T = 64 * WGM * WGN, WTM = BM / WGM, WTN = BN / WGN, FM = WTM / 32, FN = WTN / 32, RS = T / 8;
-  static_assert(WTN == 64, "the head epilogue reduces over 64-column wave slices");
-  static_assert(BM * 8 == 4 * T && BN * 8 == 4 * T, "four 16-byte loads per operand and thread per k tile");
-  extern __shared__ __attribute__((aligned(16))) _Float16 clm_lds[];
-  _Float16* As = clm_lds;
-  _Float16* Bs = clm_lds + 2 * BM * CPITCH;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WGN, wn = wave % WGN;
-  const int li = lane & 31, hh = lane >> 5;
-  int m0, n0;
-  {   // tiles column-major (consecutive tiles share the weight panel), a contiguous range of tiles per XCD
-    const int mt = (g.M + BM - 1) / BM, nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-    m0 = (tile % mt) * BM; n0 = (tile / mt) * BN;
-  }
-  const int K = g.K, nk = K / CK;
-  const _Float16* ag = g.A + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
-  const _Float16* bg = g.B + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
-  const long long rstep = (long long)RS * K;
-  uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-#define CLM_FETCH(k0)                                                                                                   \
-  ra0 = *reinterpret_cast<const uint4*>(ag + (k0)); ra1 = *reinterpret_cast<const uint4*>(ag + rstep + (k0));             \
-  ra2 = *reinterpret_cast<const uint4*>(ag + 2 * rstep + (k0)); ra3 = *reinterpret_cast<const uint4*>(ag + 3 * rstep + (k0)); \
-  rb0 = *reinterpret_cast<const uint4*>(bg + (k0)); rb1 = *reinterpret_cast<const uint4*>(bg + rstep + (k0));             \
-  rb2 = *reinterpret_cast<const uint4*>(bg + 2 * rstep + (k0)); rb3 = *reinterpret_cast<const uint4*>(bg + 3 * rstep + (k0));
-#define CLM_STASH(buf)                                                                                                  \
-  { _Float16* ad = As + (buf) * BM * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
-    _Float16* bd = Bs + (buf) * BN * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
-    *reinterpret_cast<uint4*>(ad) = ra0; *reinterpret_cast<uint4*>(ad + RS * CPITCH) = ra1;                             \
-    *reinterpret_cast<uint4*>(ad + 2 * RS * CPITCH) = ra2; *reinterpret_cast<uint4*>(ad + 3 * RS * CPITCH) = ra3;       \
-    *reinterpret_cast<uint4*>(bd) = rb0; *reinterpret_cast<uint4*>(bd + RS * CPITCH) = rb1;                             \
-    *reinterpret_cast<uint4*>(bd + 2 * RS * CPITCH) = rb2; *reinterpret_cast<uint4*>(bd + 3 * RS * CPITCH) = rb3; }
-  f32x16 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  CLM_FETCH(0)
-  CLM_STASH(0)
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) { CLM_FETCH((kt + 1) * CK) }
-    const _Float16* ap = As + cur * BM * CPITCH + (wm * WTM + li) * CPITCH + 8 * hh;
-    const _Float16* bp = Bs + cur * BN * CPITCH + (wn * WTN + li) * CPITCH + 8 * hh;
-#pragma unroll
-    for (int kk = 0; kk < CK; kk += 16) {
-      half8 a[FM], b[FN];
-#pragma unroll
-      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const half8*>(ap + i * 32 * CPITCH + kk);
-#pragma unroll
-      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const half8*>(bp + j * 32 * CPITCH + kk);
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) { CLM_STASH(cur ^ 1) }
-    __syncthreads();
-  }
-#undef CLM_FETCH
-#undef CLM_STASH
-  // epilogue: C/D layout of the 32x32 MFMAs: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
-  const int colw = n0 + wn * WTN;
-  if (EP == EP_HEAD) {
-    if (colw >= g.N) return;   // a 64-column group entirely beyond the vocabulary (wave-uniform)
-    const int cg = colw / 64;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        float v[FN];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-          v[j] = colw + j * 32 + li < g.N ? acc[i][j][e] : -INFINITY;
-          mx = fmaxf(mx, v[j]);
-        }
-        mx = warp32_max(mx);
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < FN; ++j) s += __expf(v[j] - mx);
-        s = warp32_sum(s);
-        if (row < g.M) {
-          if (li == 0) { g.pmax[(long long)row * g.ncg + cg] = mx; g.psum[(long long)row * g.ncg + cg] = s; }
-          const int t = g.tgt[row];
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            if (colw + j * 32 + li == t) g.tlogit[row] = v[j];
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < FN; ++j) {
-    const int col = colw + j * 32 + li;
-    if (col >= g.N) continue;
-    const float bv = g.bias ? (float)g.bias[col] : 0.f;
-    const float sc = col < g.qcols ? g.qscale : 1.f;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        if (row >= g.M) continue;
-        float v = acc[i][j][e] + bv;
-        const long long off = (long long)row * g.ldo + col;
-        if (EP == EP_RESID) {
-          g.resid[off] += v;
-        } else {
-          if (EP == EP_RELU) v = fmaxf(v, 0.f);
-          else v *= sc;
-          g.out16[off] = (_Float16)v;
-        }
-      }
-    }
-  }
-}
-
-constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * sizeof(_Float16); }
-
-}  // namespace
 
 // B2T_CLM_GEMM_256 (read on every call): 0 = 128 x 128 tiles always, 1 or unset = 256 x 256 tiles where they fill the chip,
 // 2 = 256 x 256 tiles always.  Both kernels give bit-identical results (same k order per output element); every A operand and
-// weight is padded to ROWPAD = 256 rows, so either tile reads inside its buffers at any M and N.
-template <int EP>
-int launch_gemm(const ClmGemm& g, hipStream_t s) {
+// weight is padded to ROWPAD = 256 rows, so either tile reads inside its buffers at any M and N.  The rule is here alone:
+// `tiles` is the caller's instantiation of clm_gemm_tiles (clm_gemm.h) for its epilogue.
+int launch_gemm(const ClmGemm& g, hipStream_t s, ClmGemmTiles tiles) {
   const char* e = getenv("B2T_CLM_GEMM_256");
   const int mode = e ? atoi(e) : 1;
   const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
-  if (mode == 2 || (mode != 0 && (long long)m256 * n256 >= 256)) {   // the 256-tiles fill the chip's 256 CUs: one 8-wave workgroup per CU
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<256, 256, 2, 4, EP>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
-    B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));
-    hipLaunchKernelGGL((clm_gemm_kernel<256, 256, 2, 4, EP>), dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
-  } else {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<128, 128, 2, 2, EP>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128));
-    B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(128, 128));
-    const int m128 = (g.M + 127) / 128, n128 = (g.N + 127) / 128;
-    hipLaunchKernelGGL((clm_gemm_kernel<128, 128, 2, 2, EP>), dim3(m128 * n128), dim3(256), lds_bytes(128, 128), s, g);
-  }
-  B2T_CHECK_LAUNCH("clm_gemm_kernel");
-  return 0;
+  // the 256-tiles fill the chip's 256 CUs: one 8-wave workgroup per CU
+  return tiles(g, s, mode == 2 || (mode != 0 && (long long)m256 * n256 >= 256));
+}
+template <int EP>
+int launch_gemm(const ClmGemm& g, hipStream_t s) {
+  return launch_gemm(g, s, &clm_gemm_tiles<EP>);
 }
 template int launch_gemm<EP_F16>(const ClmGemm&, hipStream_t);
 template int launch_gemm<EP_RELU>(const ClmGemm&, hipStream_t);
@@ -446,6 +290,13 @@ int clm_launch_head_combine(const float* pmax, const float* psum, const float* t
   return 0;
 }
 
+int clm_launch_seq_sum(const float* logp, const int* seq_off, const int* head_off, float* scores, float* tok_logp, int n_seq,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(clm_seq_sum_kernel, dim3(n_seq), dim3(64), 0, s, logp, seq_off, head_off, scores, tok_logp);
+  B2T_CHECK_LAUNCH("clm_seq_sum_kernel");
+  return 0;
+}
+
 }  // namespace b2t
 
 using namespace b2t;
@@ -540,7 +391,5 @@ extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host
     if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
     if (int rc = clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, logp, Mh, s)) return rc;
   }
-  hipLaunchKernelGGL(clm_seq_sum_kernel, dim3(n_seq), dim3(64), 0, s, logp, d_soff, d_hoff, scores_out, tok_logp_out);
-  B2T_CHECK_LAUNCH("clm_seq_sum_kernel");
-  return 0;
+  return clm_launch_seq_sum(logp, d_soff, d_hoff, scores_out, tok_logp_out, n_seq, s);
 }

@@ -219,6 +219,13 @@ long long tree_plan(const int32_t* ids, const int32_t* seq_off, int n_seq, int32
   return n;
 }
 
+int clm_launch_seq_sum_tree(const float* logp, const int* seq_off, const int* tok_hrow, float* scores, float* tok_logp,
+                            int n_seq, hipStream_t s) {
+  hipLaunchKernelGGL(clm_seq_sum_tree_kernel, dim3(n_seq), dim3(64), 0, s, logp, seq_off, tok_hrow, scores, tok_logp);
+  B2T_CHECK_LAUNCH("clm_seq_sum_tree_kernel");
+  return 0;
+}
+
 }  // namespace b2t
 
 using namespace b2t;
@@ -345,7 +352,5 @@ extern "C" int b2t_clm_score_tree_f16(const b2t_clm_t* model, const int32_t* ids
     if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
     if (int rc = clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, logp, Mh, s)) return rc;
   }
-  hipLaunchKernelGGL(clm_seq_sum_tree_kernel, dim3(n_seq), dim3(64), 0, s, logp, d_soff, d_hrow, scores_out, tok_logp_out);
-  B2T_CHECK_LAUNCH("clm_seq_sum_tree_kernel");
-  return 0;
+  return clm_launch_seq_sum_tree(logp, d_soff, d_hrow, scores_out, tok_logp_out, n_seq, s);
 }

@@ -1,0 +1,227 @@
+// clm_gemm.h — the fp16 tile GEMM of the causal-LM forward with its fused epilogues (the design notes are in the header of
+// causal_lm.hip).  A kernel template with internal linkage: a translation unit instantiates the epilogues it launches --
+// causal_lm.hip the four of the OPT forward (its launch_gemm serves the tree and cache paths too), causal_lm_llama.hip the
+// two of the Llama family (rotary embedding on q | k, SwiGLU).  Which tile a GEMM gets is decided in one place, launch_gemm
+// of causal_lm.hip; clm_gemm_tiles below only launches it.
+#pragma once
+#include <math.h>
+
+#include "clm_internal.h"
+
+namespace b2t {
+namespace {
+
+using f32x16 = float __attribute__((ext_vector_type(16)));
+using half8 = _Float16 __attribute__((ext_vector_type(8)));
+
+constexpr int CK = 64, CPITCH = CK + 8;      // k tile; LDS row pitch in fp16 elements (144 B)
+constexpr int ROWPAD = CLM_ROWPAD;                  // A operands and weights are padded to this many rows
+
+// ClmGemm (the GEMM's arguments) and the EP_* epilogue ids: clm_internal.h
+
+__device__ __forceinline__ float warp32_max(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float warp32_sum(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.
+template <int BM, int BN, int WGM, int WGN, int EP>
+__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
+  constexpr int T = 64 * WGM * WGN, WTM = BM / WGM, WTN = BN / WGN, FM = WTM / 32, FN = WTN / 32, RS = T / 8;
+  static_assert(WTN == 64, "the head epilogue reduces over 64-column wave slices");
+  static_assert(BM * 8 == 4 * T && BN * 8 == 4 * T, "four 16-byte loads per operand and thread per k tile");
+  extern __shared__ __attribute__((aligned(16))) _Float16 clm_lds[];
+  _Float16* As = clm_lds;
+  _Float16* Bs = clm_lds + 2 * BM * CPITCH;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WGN, wn = wave % WGN;
+  const int li = lane & 31, hh = lane >> 5;
+  int m0, n0;
+  {   // tiles column-major (consecutive tiles share the weight panel), a contiguous range of tiles per XCD
+    const int mt = (g.M + BM - 1) / BM, nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
+    const int tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
+    m0 = (tile % mt) * BM; n0 = (tile / mt) * BN;
+  }
+  const int K = g.K, nk = K / CK;
+  const _Float16* ag = g.A + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
+  const _Float16* bg = g.B + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
+  const long long rstep = (long long)RS * K;
+  uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
+#define CLM_FETCH(k0)                                                                                                   \
+  ra0 = *reinterpret_cast<const uint4*>(ag + (k0)); ra1 = *reinterpret_cast<const uint4*>(ag + rstep + (k0));             \
+  ra2 = *reinterpret_cast<const uint4*>(ag + 2 * rstep + (k0)); ra3 = *reinterpret_cast<const uint4*>(ag + 3 * rstep + (k0)); \
+  rb0 = *reinterpret_cast<const uint4*>(bg + (k0)); rb1 = *reinterpret_cast<const uint4*>(bg + rstep + (k0));             \
+  rb2 = *reinterpret_cast<const uint4*>(bg + 2 * rstep + (k0)); rb3 = *reinterpret_cast<const uint4*>(bg + 3 * rstep + (k0));
+#define CLM_STASH(buf)                                                                                                  \
+  { _Float16* ad = As + (buf) * BM * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
+    _Float16* bd = Bs + (buf) * BN * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
+    *reinterpret_cast<uint4*>(ad) = ra0; *reinterpret_cast<uint4*>(ad + RS * CPITCH) = ra1;                             \
+    *reinterpret_cast<uint4*>(ad + 2 * RS * CPITCH) = ra2; *reinterpret_cast<uint4*>(ad + 3 * RS * CPITCH) = ra3;       \
+    *reinterpret_cast<uint4*>(bd) = rb0; *reinterpret_cast<uint4*>(bd + RS * CPITCH) = rb1;                             \
+    *reinterpret_cast<uint4*>(bd + 2 * RS * CPITCH) = rb2; *reinterpret_cast<uint4*>(bd + 3 * RS * CPITCH) = rb3; }
+  f32x16 acc[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  CLM_FETCH(0)
+  CLM_STASH(0)
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) { CLM_FETCH((kt + 1) * CK) }
+    const _Float16* ap = As + cur * BM * CPITCH + (wm * WTM + li) * CPITCH + 8 * hh;
+    const _Float16* bp = Bs + cur * BN * CPITCH + (wn * WTN + li) * CPITCH + 8 * hh;
+#pragma unroll
+    for (int kk = 0; kk < CK; kk += 16) {
+      half8 a[FM], b[FN];
+#pragma unroll
+      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const half8*>(ap + i * 32 * CPITCH + kk);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const half8*>(bp + j * 32 * CPITCH + kk);
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    if (kt + 1 < nk) { CLM_STASH(cur ^ 1) }
+    __syncthreads();
+  }
+#undef CLM_FETCH
+#undef CLM_STASH
+  // epilogue: C/D layout of the 32x32 MFMAs: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+  const int colw = n0 + wn * WTN;
+  if (EP == EP_HEAD) {
+    if (colw >= g.N) return;   // a 64-column group entirely beyond the vocabulary (wave-uniform)
+    const int cg = colw / 64;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        float v[FN];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          v[j] = colw + j * 32 + li < g.N ? acc[i][j][e] : -INFINITY;
+          mx = fmaxf(mx, v[j]);
+        }
+        mx = warp32_max(mx);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < FN; ++j) s += __expf(v[j] - mx);
+        s = warp32_sum(s);
+        if (row < g.M) {
+          if (li == 0) { g.pmax[(long long)row * g.ncg + cg] = mx; g.psum[(long long)row * g.ncg + cg] = s; }
+          const int t = g.tgt[row];
+#pragma unroll
+          for (int j = 0; j < FN; ++j)
+            if (colw + j * 32 + li == t) g.tlogit[row] = v[j];
+        }
+      }
+    }
+    return;
+  }
+  if (EP == EP_ROPE || EP == EP_SWIGLU) {
+    // a lane holds columns colw + li (fragment 0) and colw + 32 + li (fragment 1) of every row it owns: the two halves of a
+    // rotary pair (head dims of 128 are stored [0..31, 64..95, 32..63, 96..127], so their pairs are 32 columns apart as
+    // well), and the gate and up values of one SwiGLU column (the weight's rows are interleaved in blocks of 32).  N is a
+    // multiple of 64 here, so a wave's slice is inside the matrix or outside it as a whole.
+    static_assert(FN == 2, "rotary pairs and gate / up pairs are the two fragments of a lane");
+    if (colw >= g.N) return;
+    const int c0 = colw + li, c1 = c0 + 32;
+    if (EP == EP_SWIGLU) {
+      const int oc = (colw >> 1) + li;
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+          if (row >= g.M) continue;
+          const float gt = acc[i][0][e], up = acc[i][1][e];
+          g.out16[(long long)row * g.ldo + oc] = (_Float16)(gt / (1.0f + __expf(-gt)) * up);
+        }
+      }
+      return;
+    }
+    const float b0 = g.bias ? (float)g.bias[c0] : 0.f, b1 = g.bias ? (float)g.bias[c1] : 0.f;
+    const float sc = colw < g.qcols ? g.qscale : 1.f;
+    const bool rot = colw < g.rope_cols;   // wave-uniform: q | k | v boundaries are multiples of the head dim
+    const int half = g.hd >> 1, fi = ((colw % g.hd) >> 1) + li;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        if (row >= g.M) continue;
+        float x0 = acc[i][0][e] + b0, x1 = acc[i][1][e] + b1;
+        if (rot) {
+          const long long a = (long long)g.pos[row] * half + fi;
+          const float cs = g.rope_cos[a], sn = g.rope_sin[a];
+          const float y0 = x0 * cs - x1 * sn, y1 = x1 * cs + x0 * sn;
+          x0 = y0; x1 = y1;
+        }
+        _Float16* o = g.out16 + (long long)row * g.ldo;
+        o[c0] = (_Float16)(x0 * sc);
+        o[c1] = (_Float16)(x1 * sc);
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < FN; ++j) {
+    const int col = colw + j * 32 + li;
+    if (col >= g.N) continue;
+    const float bv = g.bias ? (float)g.bias[col] : 0.f;
+    const float sc = col < g.qcols ? g.qscale : 1.f;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        if (row >= g.M) continue;
+        float v = acc[i][j][e] + bv;
+        const long long off = (long long)row * g.ldo + col;
+        if (EP == EP_RESID) {
+          g.resid[off] += v;
+        } else {
+          if (EP == EP_RELU) v = fmaxf(v, 0.f);
+          else v *= sc;
+          g.out16[off] = (_Float16)v;
+        }
+      }
+    }
+  }
+}
+
+constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * sizeof(_Float16); }
+
+// The launch of one GEMM on the tile the rule chose (ClmGemmTiles of clm_internal.h).
+template <int EP>
+int clm_gemm_tiles(const ClmGemm& g, hipStream_t s, bool use256) {
+  if (use256) {   // one 8-wave workgroup per CU
+    const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<256, 256, 2, 4, EP>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
+    B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));
+    hipLaunchKernelGGL((clm_gemm_kernel<256, 256, 2, 4, EP>), dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
+  } else {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<128, 128, 2, 2, EP>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128));
+    B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(128, 128));
+    const int m128 = (g.M + 127) / 128, n128 = (g.N + 127) / 128;
+    hipLaunchKernelGGL((clm_gemm_kernel<128, 128, 2, 2, EP>), dim3(m128 * n128), dim3(256), lds_bytes(128, 128), s, g);
+  }
+  B2T_CHECK_LAUNCH("clm_gemm_kernel");
+  return 0;
+}
+
+}  // namespace
+}  // namespace b2t

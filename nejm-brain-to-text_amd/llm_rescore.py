@@ -1,4 +1,4 @@
-"""OPT n-best rescoring: the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
+"""LLM n-best rescoring (OPT, and the Llama family: Llama, Mistral, Qwen2): the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
 :127-162, gpt2_lm_decode :165-251, get_string_differences :273-311, augment_nbest :327-411) with the causal-LM forward on the
 HIP path (b2t_clm_score_f16, csrc/causal_lm.hip; opt-in b2t_clm_score_tree_f16, csrc/causal_lm_tree.hip, which computes the
 prefixes the candidates share once; opt-in b2t_clm_score_tree_cached_f16, csrc/causal_lm_cache.hip, which also keeps the
@@ -9,6 +9,11 @@ functions take them as the reference's do.  `model` here is an `OptScorer`: the 
 the device layout of include/b2t.h, scored on packed variable-length token ids (no padding).  Tokenisation stays on the host.
 `build_opt` never reaches the network: it reads a local directory (the model name itself, or the hub-cache layout under
 `cache_dir`) and refuses what the kernels do not run (post-LN OPT, opt-350m's projection layers, non-ReLU activations).
+
+`build_opt` dispatches on config.json's model_type, as the reference's AutoModelForCausalLM does: "opt" gives an OptScorer;
+"llama", "mistral" and "qwen2" give a `LlamaScorer` (b2t_clm_llama_score_f16 / b2t_clm_llama_score_tree_f16,
+csrc/causal_lm_llama.hip: RMSNorm, rotary positions, grouped-query attention, SwiGLU) with the same `score` /
+`token_logprobs` surface, so the three functions and remote_lm.LocalLMService take either.  The context cache is OPT's only.
 """
 from __future__ import annotations
 
@@ -461,6 +466,277 @@ class OptScorer:
         return [t[off[i]:off[i + 1]] for i in range(len(lens))]
 
 
+# ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM) ---------------------------------------
+LLAMA_MODEL_TYPES = ("llama", "mistral", "qwen2")
+LLAMA_HEAD_DIMS = (64, 128)
+LLAMA_MAX_POSITIONS = 8192   # default cap of the rotary cos / sin table: max_pos * head_dim * 4 bytes (4 MiB at head dim 128)
+_LLAMA_LAYER_FIELDS = ("norm1_w", "norm2_w", "qkv_w", "qkv_b", "o_w", "gate_up_w", "down_w")
+
+
+def _rope_parameters(cfg: dict) -> dict:
+    """config.json's rotary description in one dict, from either spelling: rope_parameters (rope_theta inside), or rope_theta
+    beside an optional rope_scaling (whose type is under "rope_type" or the older "type")."""
+    rp = dict(cfg.get("rope_parameters") or cfg.get("rope_scaling") or {})
+    if "rope_type" not in rp:
+        rp["rope_type"] = rp.get("type", "default")
+    if "rope_theta" not in rp:
+        rp["rope_theta"] = cfg.get("rope_theta", 10000.0)
+    return rp
+
+
+def rope_inv_freq(cfg: dict) -> np.ndarray:
+    """fp32 inv_freq[head_dim / 2] of a Llama-family config, computed as HF's ROPE_INIT_FUNCTIONS compute it (fp32 torch
+    arithmetic, same operation order) for rope_type "default" and "llama3"; every other type is refused."""
+    import math
+    import torch
+    rp = _rope_parameters(cfg)
+    kind = rp["rope_type"]
+    if kind not in ("default", "llama3"):
+        raise ValueError(f"rope_type {kind!r} is not supported (default or llama3)")
+    if float(rp.get("partial_rotary_factor", cfg.get("partial_rotary_factor", 1.0)) or 1.0) != 1.0:
+        raise ValueError("partial rotary embeddings are not supported")
+    dim = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // int(cfg["num_attention_heads"]))
+    base = rp["rope_theta"]
+    if kind == "default":
+        inv = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.float) / dim))
+        return inv.numpy().astype(np.float32)
+    inv = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.int64).to(dtype=torch.float) / dim))
+    factor, low, high = rp["factor"], rp["low_freq_factor"], rp["high_freq_factor"]
+    old_len = rp["original_max_position_embeddings"]
+    low_wavelen, high_wavelen = old_len / low, old_len / high
+    wavelen = 2 * math.pi / inv
+    inv_l = torch.where(wavelen > low_wavelen, inv / factor, inv)
+    smooth = (old_len / wavelen - low) / (high - low)
+    smoothed = (1 - smooth) * inv_l / factor + smooth * inv_l
+    medium = ~(wavelen < high_wavelen) * ~(wavelen > low_wavelen)
+    return torch.where(medium, smoothed, inv_l).numpy().astype(np.float32)
+
+
+def rope_tables(inv_freq: np.ndarray, max_pos: int) -> Tuple[np.ndarray, np.ndarray]:
+    """fp32 cos / sin [max_pos][head_dim / 2] of position * inv_freq, the angle and the functions evaluated in double."""
+    ang = np.arange(max_pos, dtype=np.float64)[:, None] * np.asarray(inv_freq, np.float32).astype(np.float64)[None, :]
+    return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+
+
+def llama_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
+    """The dimensions b2t_clm_llama_t needs, after refusing what the kernels do not run.  max_pos is the model's
+    max_position_embeddings, lowered to the sliding window where one is configured and in use (within it full causal attention
+    is what the model computes) and to max_positions (default LLAMA_MAX_POSITIONS), which sizes the rotary table."""
+    mt = cfg.get("model_type")
+    if mt not in LLAMA_MODEL_TYPES:
+        raise ValueError(f"model_type {mt!r} is not one of {LLAMA_MODEL_TYPES}")
+    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    Hkv = int(cfg.get("num_key_value_heads") or Hq)
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise ValueError(f"{mt} activation {act!r} is not supported (silu only)")
+    if d % Hq or d // Hq not in LLAMA_HEAD_DIMS or int(cfg.get("head_dim") or d // Hq) != d // Hq:
+        raise ValueError(f"head dim {cfg.get('head_dim') or d}/{Hq} is not supported (hidden_size / heads, one of {LLAMA_HEAD_DIMS})")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    ffn = int(cfg["intermediate_size"])
+    if d % 64 or ffn % 64:
+        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    if cfg.get("mlp_bias"):
+        raise ValueError("mlp_bias=True is not supported")
+    rope_inv_freq(cfg)   # refuses the rotary variants the table does not describe
+    max_pos = int(cfg["max_position_embeddings"])
+    window = cfg.get("sliding_window")
+    in_use = window is not None and (mt == "mistral" or (bool(cfg.get("use_sliding_window")) and
+                                                         "sliding_attention" in (cfg.get("layer_types") or ["sliding_attention"])))
+    if in_use:
+        max_pos = min(max_pos, int(window))
+    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
+    if cap < 1:
+        raise ValueError(f"max_positions {cap} < 1")
+    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
+                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                tied=bool(cfg.get("tie_word_embeddings", False)))
+
+
+def head_dim_perm(hd: int) -> np.ndarray:
+    """stored row i of a q / k head = original row perm[i]: the identity for 64; for 128 [0..31, 64..95, 32..63, 96..127], so
+    that the rotary pair (c, c + hd / 2) is 32 rows apart."""
+    if hd == 64:
+        return np.arange(64)
+    return np.concatenate([np.arange(0, 32), np.arange(64, 96), np.arange(32, 64), np.arange(96, 128)])
+
+
+def qkv_row_perm(Hq: int, Hkv: int, hd: int) -> np.ndarray:
+    """stored row i of qkv_w = row perm[i] of cat(q_proj, k_proj, v_proj): head_dim_perm inside every q and k head."""
+    p = head_dim_perm(hd)
+    rows = [h * hd + p for h in range(Hq + Hkv)] + [np.arange((Hq + Hkv) * hd, (Hq + 2 * Hkv) * hd)]
+    return np.concatenate(rows)
+
+
+def gate_up_row_perm(ffn: int) -> np.ndarray:
+    """stored row i of gate_up_w = row perm[i] of cat(gate_proj, up_proj): row 64b + i = gate[32b + i], 64b + 32 + i = up[32b + i]."""
+    b = np.arange(ffn // 32)[:, None] * 32 + np.arange(32)[None, :]
+    return np.concatenate([b, ffn + b], axis=1).reshape(-1)
+
+
+def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray) -> Dict[str, "object"]:
+    """Tensors in the layout of b2t_clm_llama_t from a Llama / Mistral / Qwen2 state dict, on the device the state dict is on
+    (the CPU for a checkpoint read from disk): fp16 embed_tokens, lm_head (the same tensor when tied), final_norm_w,
+    layers.<i>.<field> (qkv_b absent when the model has no q / k / v biases), and the fp32 rope_cos / rope_sin tables (CPU)."""
+    import torch
+    sd = dict(state)
+    d, ffn, V, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"], dims["n_kv_heads"]
+    hd = d // Hq
+
+    def get(name, shape):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name}")
+        t = sd[name].detach().to(torch.float16).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
+    dev = emb.device
+    tied = dims.get("tied", False) or "lm_head.weight" not in sd
+    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
+           "final_norm_w": get("model.norm.weight", (d,))}
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    qperm = torch.from_numpy(qkv_row_perm(Hq, Hkv, hd)).to(dev)
+    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
+    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    for i in range(dims["n_layers"]):
+        p = f"model.layers.{i}."
+        for n in ("self_attn.o_proj.bias", "mlp.gate_proj.bias", "mlp.up_proj.bias", "mlp.down_proj.bias"):
+            if p + n in sd:
+                raise ValueError(f"{p + n}: biases other than q / k / v's are not supported")
+        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
+        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
+             "qkv_w": _pad_rows(qkv[qperm].contiguous(), _rup(qkv.shape[0], ROWPAD)),
+             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, d)), _rup(d, ROWPAD)),
+             "gate_up_w": _pad_rows(torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))],
+                                              0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
+             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
+        if any(p + f"self_attn.{n}.bias" in sd for n in widths):
+            zero = lambda w: torch.zeros(w, dtype=torch.float16, device=dev)
+            L["qkv_b"] = torch.cat([get(p + f"self_attn.{n}.bias", (w,)) if p + f"self_attn.{n}.bias" in sd else zero(w)
+                                    for n, w in widths.items()])[qperm].contiguous()
+        for f, t in L.items():
+            out[f"layers.{i}.{f}"] = t
+    return out
+
+
+def load_config(model_dir: str) -> dict:
+    with open(os.path.join(model_dir, "config.json")) as f:
+        return json.load(f)
+
+
+def load_llama_arrays(model_dir: str, max_positions: Optional[int] = None) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the Llama-family checkpoint in model_dir."""
+    cfg = load_config(model_dir)
+    dims = llama_dims(cfg, max_positions)
+    return dims, llama_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg))
+
+
+class LlamaScorer:
+    """A Llama-family decoder on the GPU in the b2t_clm_llama_t layout, with OptScorer's scoring surface: `score` runs
+    b2t_clm_llama_score_f16 on packed ids, or, with share_prefixes, b2t_clm_llama_score_tree_f16 over the list's shared-prefix
+    token tree (bit-identical to the flat call); after a call `last_stats` = {"tokens", "nodes": rows computed}.  There is no
+    context cache for this family yet: context_cache_tokens > 0 and use_cache=True raise ValueError."""
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0):
+        import torch
+        import b2t_native as N
+        if int(context_cache_tokens) != 0:
+            raise ValueError("LlamaScorer: the context cache (context_cache_tokens > 0) is not available for Llama-family "
+                             "models; use share_prefixes=True")
+        self.dims = dict(dims)
+        self.device = torch.device(device)
+        self.share_prefixes = bool(share_prefixes)
+        self.context_cache_tokens = 0
+        self.last_stats = None
+        self.w = {k: v.to(self.device).contiguous() for k, v in arrays.items()}
+        if dims.get("tied", False) or arrays["lm_head"] is arrays["embed_tokens"]:
+            self.w["lm_head"] = self.w["embed_tokens"]
+        for k, v in self.w.items():
+            want = torch.float32 if k.startswith("rope_") else torch.float16
+            if v.dtype != want:
+                raise ValueError(f"LlamaScorer: {k} is {v.dtype}, expected {want}")
+        self._layers = (N.ClmLlamaLayer * max(1, dims["n_layers"]))()
+        for i in range(dims["n_layers"]):
+            for f in _LLAMA_LAYER_FIELDS:
+                t = self.w.get(f"layers.{i}.{f}")
+                setattr(self._layers[i], f, t.data_ptr() if t is not None else None)
+        self.desc = N.ClmLlamaDesc(dims["n_layers"], dims["d_model"], dims["n_heads"], dims["n_kv_heads"], dims["ffn_dim"],
+                                   dims["vocab"], dims["max_pos"], dims["rms_eps"], self.w["embed_tokens"].data_ptr(),
+                                   self.w["lm_head"].data_ptr(), self.w["final_norm_w"].data_ptr(),
+                                   self.w["rope_cos"].data_ptr(), self.w["rope_sin"].data_ptr(), self._layers)
+        self._ws = None
+
+    def eval(self):   # the reference calls model.eval(); scoring has no training mode
+        return self
+
+    def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None):
+        import ctypes as C
+        import torch
+        import b2t_native as N
+        if use_cache:
+            raise ValueError("LlamaScorer: no context cache for Llama-family models")
+        lib = N.load()
+        tree = self.share_prefixes if share_prefixes is None else bool(share_prefixes)
+        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in ids_list]
+        if not seqs:
+            self.last_stats = {"tokens": 0, "nodes": 0}
+            return np.zeros(0, np.float32), np.zeros(0, np.int64), None
+        lens = np.array([len(s) for s in seqs], dtype=np.int64)
+        if int(lens.min()) < 1:
+            raise ValueError("LlamaScorer: empty token sequence")
+        if lens.sum() > np.iinfo(np.int32).max:
+            raise ValueError("LlamaScorer: too many tokens")
+        ids = np.ascontiguousarray(np.concatenate(seqs).astype(np.int32))
+        off = np.zeros(len(seqs) + 1, dtype=np.int32)
+        off[1:] = np.cumsum(lens)
+        M = int(off[-1])
+        nodes = M
+        if tree:
+            nodes = tree_plan(ids, off)[2]
+            need = lib.b2t_clm_llama_tree_ws_bytes(C.byref(self.desc), nodes, M, len(seqs))
+        else:
+            need = lib.b2t_clm_llama_ws_bytes(C.byref(self.desc), M, len(seqs))
+        if need == 0:
+            raise RuntimeError("b2t_clm_llama_ws_bytes: invalid sizes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        scores = torch.empty(len(seqs), dtype=torch.float32, device=self.device)
+        tok = torch.empty(M, dtype=torch.float32, device=self.device) if want_tokens else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if tree:
+                N.check(lib.b2t_clm_llama_score_tree_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs),
+                                                         scores.data_ptr(), tok.data_ptr() if tok is not None else None, None,
+                                                         self._ws.data_ptr(), self._ws.numel(), stream),
+                        "b2t_clm_llama_score_tree_f16")
+            else:
+                N.check(lib.b2t_clm_llama_score_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs),
+                                                    scores.data_ptr(), tok.data_ptr() if tok is not None else None,
+                                                    self._ws.data_ptr(), self._ws.numel(), stream), "b2t_clm_llama_score_f16")
+            s = scores.cpu().numpy()
+            t = tok.cpu().numpy() if tok is not None else None
+        self.last_stats = {"tokens": M, "nodes": int(nodes)}
+        return s, lens, t
+
+    def score(self, ids_list, length_penalty: float = 0.0, share_prefixes: Optional[bool] = None,
+              use_cache: Optional[bool] = None, update_cache: bool = True) -> np.ndarray:
+        """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores.
+        share_prefixes: None = the scorer's own setting.  use_cache / update_cache: OptScorer's arguments; use_cache=True raises."""
+        s, lens, _ = self._run(ids_list, False, share_prefixes, use_cache)
+        return s.astype(np.float32) - (lens * float(length_penalty)).astype(np.float32)
+
+    def token_logprobs(self, ids_list, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
+                       update_cache: bool = True) -> List[np.ndarray]:
+        """Per sequence the fp32 log-prob of each token given its prefix (0 for the first token)."""
+        _, lens, t = self._run(ids_list, True, share_prefixes, use_cache)
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return [t[off[i]:off[i + 1]] for i in range(len(lens))]
+
+
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
     """b2t_clm_tree_plan_host on packed int32 ids / offsets (host only, no GPU): (node_of_token, parent_of_node, n_nodes).
     A node is a distinct token prefix, numbered by first appearance; parent_of_node is -1 at roots."""
@@ -494,18 +770,36 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
             "n_after": na.value}
 
 
-def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0):
-    """(OptScorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16).
+def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None):
+    """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", LlamaScorer for "llama",
+    "mistral" and "qwen2"; anything else is refused.  max_positions caps a Llama-family model's rotary table."""
+    mt = load_config(model_dir).get("model_type", "opt")
+    if mt == "opt":
+        dims, arrays = load_opt_arrays(model_dir)
+        return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens)
+    if mt in LLAMA_MODEL_TYPES:
+        if int(context_cache_tokens) != 0:   # before the weights are read
+            raise ValueError(f"context_cache_tokens > 0 is not available for {mt} models (the context cache is OPT's); "
+                             "use share_prefixes=True")
+        dims, arrays = load_llama_arrays(model_dir, max_positions)
+        return LlamaScorer(dims, arrays, device, share_prefixes, 0)
+    raise ValueError(f"model_type {mt!r} is not supported (opt, {', '.join(LLAMA_MODEL_TYPES)})")
+
+
+def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
+              max_positions=None):
+    """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16).  The scorer is an
+    OptScorer, or a LlamaScorer for a Llama / Mistral / Qwen2 directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
-    context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (OptScorer)."""
+    context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (OptScorer only)."""
     model_dir = resolve_model_dir(model_name, cache_dir)
-    dims, arrays = load_opt_arrays(model_dir)
+    scorer = build_scorer(model_dir, device, share_prefixes, context_cache_tokens, max_positions)
     from transformers import AutoTokenizer
     tok = AutoTokenizer.from_pretrained(model_dir, local_files_only=True)
     tok.padding_side = "right"
     if tok.pad_token is None:
         tok.pad_token = tok.eos_token
-    return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens), tok
+    return scorer, tok
 
 
 class WordTokenizer:

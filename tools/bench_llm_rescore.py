@@ -24,6 +24,13 @@ positions reused, the median ms of each path with the spread (max - min) over th
 scores were byte-identical.
 
   python tools/bench_llm_rescore.py --session [--sentences 12] [--reps 5]
+
+`--arch llama` runs the Llama family's path (b2t_clm_llama_score_f16 / b2t_clm_llama_score_tree_f16) at the Llama-3-8B shape
+(32 layers, d 4096, 32 query / 8 kv heads, ffn 14336, vocab 128256, untied head; random fp16 weights, ~16 GB twice) on the
+same lists under the same protocol: without --tree the HIP path against HF's LlamaForCausalLM in fp16 on the same weights
+in this process (padded batch, SDPA), with --tree / --list nbest / --context the flat call against the tree call.
+
+  python tools/bench_llm_rescore.py --arch llama [--tree --context 64]
 """
 import argparse
 import json
@@ -60,11 +67,13 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", choices=("opt", "llama"), default="opt", help="opt: OPT-6.7b shape; llama: Llama-3-8B shape")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--d", type=int, default=4096)
     ap.add_argument("--heads", type=int, default=32)
-    ap.add_argument("--ffn", type=int, default=16384)
-    ap.add_argument("--vocab", type=int, default=50272)
+    ap.add_argument("--kv-heads", type=int, default=8, help="--arch llama: key / value heads")
+    ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama)")
+    ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama)")
     ap.add_argument("--cands", type=int, default=100)
     ap.add_argument("--lists", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -75,6 +84,10 @@ def main():
     ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
     ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
+    a.ffn = a.ffn or (14336 if a.arch == "llama" else 16384)
+    a.vocab = a.vocab or (128256 if a.arch == "llama" else 50272)
+    if a.arch == "llama":
+        return main_llama(a)
     import torch
     import torch.nn.functional as F
     import llm_rescore as R
@@ -156,7 +169,91 @@ def main():
                       "speedup_vs_torch": round(ms_torch / ms_hip, 3), "max_abs_score_diff_vs_torch": round(diff, 4)}))
 
 
-def ab_flat_tree(a, sc, lists, ntok):
+def main_llama(a):
+    """--arch llama: the lists and the protocol of main() with a LlamaScorer, and HF's fp16 model as the torch side."""
+    import torch
+    import transformers
+    import llm_rescore as R
+    if a.session:
+        raise SystemExit("--session needs the context cache, which the Llama family does not have yet")
+    torch.manual_seed(0)
+    d, H, Hkv, ffn, V, L = a.d, a.heads, a.kv_heads, a.ffn, a.vocab, a.layers
+    dev = "cuda"
+    cfg = transformers.LlamaConfig(hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, intermediate_size=ffn,
+                                   vocab_size=V, num_hidden_layers=L, max_position_embeddings=2048, rms_norm_eps=1e-5,
+                                   tie_word_embeddings=False, attn_implementation="sdpa",
+                                   rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                                     original_max_position_embeddings=8192, rope_theta=500000.0))
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float16)
+    try:
+        with torch.device(dev):
+            model = transformers.LlamaForCausalLM(cfg).eval()
+    finally:
+        torch.set_default_dtype(old)
+    with torch.no_grad():   # HF's init (std 0.02) gives a flat distribution; widths as in the OPT rows
+        for k, p in model.named_parameters():
+            if p.dim() == 2:
+                std = 2.0 / d ** 0.5 if ("embed_tokens" in k or "lm_head" in k) else 1.0 / p.shape[1] ** 0.5
+                p.copy_((torch.randn(p.shape, device=dev) * std).half())
+    cj = json.loads(cfg.to_json_string())
+    dims = R.llama_dims(cj)
+    sc = R.LlamaScorer(dims, R.llama_device_layout(model.state_dict(), dims, R.rope_inv_freq(cj)), dev)
+    rng = np.random.default_rng(0)
+    ab = a.tree or a.list != "random" or a.context > 0
+    if not ab:
+        lists = [random_list(rng, V, a.cands) for _ in range(a.lists)]
+    else:
+        gen = nbest_list if a.list == "nbest" else random_list
+        lists = [gen(rng, V, a.cands, [int(x) for x in rng.integers(4, V, a.context)]) for _ in range(a.lists)]
+    ntok = [sum(len(s) for s in l) for l in lists]
+    if ab:
+        del model
+        torch.cuda.empty_cache()
+        return ab_flat_tree(a, sc, lists, ntok, arch="llama")
+
+    def torch_score(seqs):   # padded batch through the HF model, fp16
+        B, T = len(seqs), max(len(s) for s in seqs)
+        ids = torch.zeros(B, T, dtype=torch.long, device=dev)
+        mask = torch.zeros(B, T, dtype=torch.long, device=dev)
+        for i, s in enumerate(seqs):
+            ids[i, :len(s)] = torch.as_tensor(s, device=dev); mask[i, :len(s)] = 1
+        lp = torch.log_softmax(model(input_ids=ids, attention_mask=mask).logits.float(), -1)
+        g = lp[:, :-1].gather(-1, ids[:, 1:, None])[..., 0] * mask[:, 1:]
+        return g.sum(1).cpu().numpy()
+
+    def timed(fn):   # per list, so that the medians and the spread can be reported
+        for i in range(a.warmup):
+            fn(lists[i % len(lists)])
+        torch.cuda.synchronize()
+        ms, outs = [], []
+        for l in lists:
+            t0 = time.perf_counter()
+            outs.append(fn(l))   # returns host scores: the call is complete
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return ms, outs
+
+    with torch.inference_mode():
+        ms_hip, s_hip = timed(lambda l: sc.score(l))
+        ms_torch, s_torch = timed(torch_score)
+        ms_hip2, _ = timed(lambda l: sc.score(l))      # once more after the torch pass: the order does not decide
+    diff = max(float(np.abs(np.asarray(x, np.float64) - np.asarray(y, np.float64)).max()) for x, y in zip(s_hip, s_torch))
+    hd = d // H
+    flop_tok = 2 * (L * (d * (H + 2 * Hkv) * hd + d * d + 3 * d * ffn) + d * V)
+    r2 = lambda x: round(float(x), 2)
+    mh, mt = float(np.mean(ms_hip)), float(np.mean(ms_torch))
+    print(json.dumps({"bench": "llm_rescore", "arch": "llama", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn,
+                      "vocab": V, "cands": a.cands, "tokens_per_list": float(np.mean(ntok)), "hip_ms_per_list": r2(mh),
+                      "torch_fp16_ms_per_list": r2(mt), "hip_tflops": round(np.mean(ntok) * flop_tok / (mh * 1e-3) / 1e12, 1),
+                      "speedup_vs_torch": round(mt / mh, 3), "max_abs_score_diff_vs_torch": round(diff, 4),
+                      "hip_ms": {"median": r2(np.median(ms_hip)), "min": r2(min(ms_hip)), "max": r2(max(ms_hip))},
+                      "hip_ms_second_pass": {"median": r2(np.median(ms_hip2)), "min": r2(min(ms_hip2)), "max": r2(max(ms_hip2))},
+                      "torch_ms": {"median": r2(np.median(ms_torch)), "min": r2(min(ms_torch)), "max": r2(max(ms_torch))},
+                      "per_list_tokens": ntok, "per_list_hip_ms": [r2(x) for x in ms_hip],
+                      "per_list_torch_ms": [r2(x) for x in ms_torch]}))
+
+
+def ab_flat_tree(a, sc, lists, ntok, arch="opt"):
     """Flat and tree path on the same lists in this process, alternating list by list, --reps passes over the lists; both
     warmed up first.  Lists differ in size, so the run-to-run spread is taken per list: the largest max - min over the
     repeats of one list."""
@@ -181,7 +278,7 @@ def ab_flat_tree(a, sc, lists, ntok):
     per = {t: [float(np.median(v)) for v in ms[t]] for t in ms}   # per list, median over its repeats
     st = lambda t: {"median": r2(np.median(per[t])), "min": r2(np.min(per[t])), "max": r2(np.max(per[t])),
                     "repeat_spread": r2(max(max(v) - min(v) for v in ms[t]))}
-    print(json.dumps({"bench": "llm_rescore_tree", "layers": a.layers, "d": a.d, "heads": a.heads, "ffn": a.ffn, "vocab": a.vocab,
+    print(json.dumps({"bench": "llm_rescore_tree", "arch": arch, "layers": a.layers, "d": a.d, "heads": a.heads, "ffn": a.ffn, "vocab": a.vocab,
                       "cands": a.cands, "list": a.list, "context": a.context, "lists": len(lists), "reps": max(1, a.reps),
                       "tokens": float(np.mean(ntok)), "nodes": float(np.mean(nodes)),
                       "hip_ms_per_list": st(False)["median"], "hip_tree_ms_per_list": st(True)["median"],
