@@ -596,7 +596,8 @@ int b2t_nbest_convert_to_inputs(const int32_t* ali, const int32_t* a_off, int n,
 
 
 /* ---- causal LM scoring (the n-best rescoring LLM, language-model-standalone.py:92-162) ------------------------------
- * Scoring-only forward of a pre-LayerNorm OPT decoder (OPTForCausalLM with ReLU, word_embed_proj_dim == hidden_size), csrc/causal_lm.hip.
+ * Scoring-only forward of a pre-LayerNorm OPT decoder (OPTForCausalLM with ReLU, word_embed_proj_dim == hidden_size), csrc/causal_lm.hip
+ * (the layer loop and the host pieces every path shares: csrc/clm_internal.h; the attention arithmetic: csrc/clm_attn.h).
  * Weights are fp16 DEVICE arrays in this layout (nejm-brain-to-text_amd/llm_rescore.py builds it once at load time):
  *   rows of every nn.Linear weight [N][K] zero-padded to a multiple of 256; K (= d_model or ffn_dim) a multiple of 64;
  *   qkv_w = [q_proj; k_proj; v_proj] rows, qkv_b the three biases; embed_tokens [round_up(vocab, 256)][d] (zero rows beyond
@@ -711,7 +712,8 @@ int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache
                                   float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
                                   void* ws, size_t ws_bytes, void* stream);
 
-/* ---- the same scoring for the Llama family (csrc/causal_lm_llama.hip) --------------------------------------------------
+/* ---- the same scoring for the Llama family (csrc/causal_lm_llama.hip; its attention kernels are the OPT paths', ------
+ * csrc/causal_lm.hip and csrc/causal_lm_tree.hip, on the row q[Hq hd] | k[Hkv hd] | v[Hkv hd]) ---------------------------
  * HF LlamaForCausalLM, MistralForCausalLM and Qwen2ForCausalLM: RMSNorm, rotary positions (rotate-half convention),
  * grouped-query attention, a SwiGLU MLP, no biases but optionally q / k / v's, an LM head that may be untied.  The reference
  * loads its rescoring LLM through AutoModelForCausalLM (language-model-standalone.py:92-123), so these are models its users can

@@ -23,12 +23,15 @@
 // tiles.  Operands are never packed at run time: the LayerNorm / attention / fc1 kernels write the k-contiguous, row-padded
 // fp16 A operand directly, and nn.Linear weights ([N][K], k-contiguous) are padded once at load time to 256 rows.
 //
-// The host-side pieces the shared-prefix tree path (causal_lm_tree.hip) reuses -- launch_gemm, the embed / LayerNorm / head
-// launchers, clm_check_model -- have external linkage and are declared in clm_internal.h; the kernels stay private to this file
-// (the GEMM's template is clm_gemm.h, instantiated here for the four epilogues of this forward).
+// The host-side pieces the other paths (causal_lm_tree.hip, causal_lm_cache.hip, causal_lm_llama.hip) reuse -- launch_gemm,
+// the embed / LayerNorm / attention / head launchers, clm_check_model, the list check, the workspace layout and the flat
+// index builder -- have external linkage and are declared in clm_internal.h, which also holds the layer loop (clm_forward).
+// The kernels stay private to this file: the GEMM's template is clm_gemm.h, instantiated here for the four epilogues of this
+// forward; the attention's arithmetic is clm_attn.h's, and clm_attn_kernel serves the Llama family's row layout too.
 #include <math.h>
 #include <vector>
 
+#include "clm_attn.h"
 #include "clm_gemm.h"
 
 namespace b2t {
@@ -55,13 +58,6 @@ template int launch_gemm<EP_HEAD>(const ClmGemm&, hipStream_t);
 
 namespace {
 
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 __device__ __forceinline__ float block_max256(float v, float* red) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   __syncthreads();
@@ -100,92 +96,32 @@ __global__ __launch_bounds__(256) void clm_layernorm_kernel(const float* x, cons
   for (int c = threadIdx.x; c < d; c += 256) o[c] = (_Float16)((xr[c] - mean) * rstd * (float)w[c] + (float)b[c]);
 }
 
-// Causal attention, one workgroup per (sequence, head), 4 waves; a wave takes 32 query rows at a time.  The score tile is
-// computed transposed, S^T = K . Q^T (v_mfma_f32_32x32x16_f16: A = 32 keys, B = 32 queries), so a lane owns one query column:
-// its online-softmax state (m, l) is per lane and the row reductions are in-lane plus one swap of the lane halves.  P^T is
-// then the B operand of O^T = V^T . P^T with no data movement (registers 8s..8s+7 of the accumulator are k-step s, keys in
-// the order 16s + 8(j >> 2) + 4h + (j & 3)), and O^T's rescale by exp(m_old - m_new) is per lane too.
+// Causal attention, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query rows at a time and runs the key
+// blocks up to the diagonal through attn_block (clm_attn.h), V gathered from global memory.  The row is q[Hq * D] |
+// k[Hkv * D] | v[Hkv * D]; query head h reads K / V head h / (Hq / Hkv) (OPT: Hkv = Hq).
 template <int D>
-__global__ __launch_bounds__(256) void clm_attn_kernel(const _Float16* qkv, _Float16* out, const int* seq_off, int d) {
-  constexpr int KS = D / 16, NF = (D + 31) / 32;
-  const int sq = blockIdx.x, h = blockIdx.y;
+__global__ __launch_bounds__(256) void clm_attn_kernel(const _Float16* qkv, _Float16* out, const int* seq_off, int Hq, int Hkv) {
+  const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
   const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
-  const long long RS = 3LL * d;
+  const long long RS = (long long)(Hq + 2 * Hkv) * D;
   const _Float16* Qb = qkv + (long long)t0 * RS + h * D;
-  const _Float16* Kb = Qb + d;
-  const _Float16* Vb = Qb + 2 * d;
+  const _Float16* Kb = qkv + (long long)t0 * RS + (Hq + hk) * D;
+  const _Float16* Vb = Kb + Hkv * D;
   const int nqb = (L + 31) / 32;
   for (int qb = wave; qb < nqb; qb += 4) {
-    const int q0 = qb * 32, q = q0 + li;
-    const _Float16* qp = Qb + (long long)min(q, L - 1) * RS + 8 * hh;
-    half8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const half8*>(qp + 16 * ks);
-    float m = -INFINITY, l = 0.f;
-    f32x16 o[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[f][e] = 0.f;
+    const int q = qb * 32 + li;
+    half8 qf[AttnDims<D>::KS];
+    load_q<D>(Qb + (long long)min(q, L - 1) * RS + 8 * hh, qf);
+    float m, l;
+    f32x16 o[AttnDims<D>::NF];
+    attn_zero<D>(m, l, o);
     for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
       const int k0 = kb * 32;
       const _Float16* kp = Kb + (long long)min(k0 + li, L - 1) * RS + 8 * hh;
-      f32x16 sacc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(kp + 16 * ks), qf[ks], sacc, 0, 0, 0);
-      float mx = -INFINITY;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int key = k0 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        if (key > q || key >= L) sacc[e] = -INFINITY;
-        mx = fmaxf(mx, sacc[e]);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mnew = fmaxf(m, mx);
-      const float alpha = __expf(m - mnew);
-      float ps = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { const float p = __expf(sacc[e] - mnew); sacc[e] = p; ps += p; }
-      ps += __shfl_xor(ps, 32);
-      l = l * alpha + ps;
-      m = mnew;
-      half8 pb[2];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pb[s2][j] = (_Float16)sacc[8 * s2 + j];
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[f][e] *= alpha;
-        const int dim = 32 * f + li;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          half8 va;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int key = k0 + 16 * s2 + 8 * (j >> 2) + 4 * hh + (j & 3);
-            va[j] = (dim < D && key < L) ? Vb[(long long)key * RS + dim] : (_Float16)0.f;
-          }
-          o[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb[s2], o[f], 0, 0, 0);
-        }
-      }
+      attn_block<D, true>(kp, qf, VGather{Vb, RS, k0, L}, k0, q, L, li, hh, m, l, o);
     }
-    if (q < L) {
-      const float inv = 1.0f / l;
-      _Float16* op = out + (long long)(t0 + q) * d + h * D;
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int dim = 32 * f + (e & 3) + 8 * (e >> 2) + 4 * hh;
-          if (dim < D) op[dim] = (_Float16)(o[f][e] * inv);
-        }
-    }
+    if (q < L) attn_store<D>(out + ((long long)(t0 + q) * Hq + h) * D, o, l, hh);
   }
 }
 
@@ -218,32 +154,6 @@ __global__ __launch_bounds__(64) void clm_seq_sum_kernel(const float* logp, cons
     for (int i = 0; i < n; ++i) acc += logp[h0 + i];
     scores[s] = acc;
   }
-}
-
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline long long rup(long long x, long long m) { return (x + m - 1) / m * m; }
-
-struct ClmLayout {
-  size_t ints, resid, x16, qkv, hbuf, pmax, psum, tlogit, logp, total;
-  long long M, Mh, Mp, ncg;
-};
-
-ClmLayout clm_layout(const b2t_clm_t* m, long long M, int n_seq) {
-  ClmLayout L{};
-  const long long d = m->d_model, Mh = M - n_seq;
-  L.M = M; L.Mh = Mh; L.Mp = rup(M > 0 ? M : 1, ROWPAD); L.ncg = (m->vocab + 63) / 64;
-  size_t off = 0;
-  L.ints = off;   off += al256(sizeof(int) * (size_t)(2 * M + 2 * (Mh > 0 ? Mh : 0) + 2 * (n_seq + 1)));
-  L.resid = off;  off += al256(sizeof(float) * (size_t)(M * d));
-  L.x16 = off;    off += al256(sizeof(_Float16) * (size_t)(L.Mp * d));
-  L.qkv = off;    off += al256(sizeof(_Float16) * (size_t)(M * 3 * d));
-  L.hbuf = off;   off += al256(sizeof(_Float16) * (size_t)(L.Mp * m->ffn_dim));
-  L.pmax = off;   off += al256(sizeof(float) * (size_t)(Mh * L.ncg));
-  L.psum = off;   off += al256(sizeof(float) * (size_t)(Mh * L.ncg));
-  L.tlogit = off; off += al256(sizeof(float) * (size_t)Mh);
-  L.logp = off;   off += al256(sizeof(float) * (size_t)Mh);
-  L.total = off;
-  return L;
 }
 
 }  // namespace
@@ -297,99 +207,107 @@ int clm_launch_seq_sum(const float* logp, const int* seq_off, const int* head_of
   return 0;
 }
 
+int clm_launch_attn(const _Float16* qkv, _Float16* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
+  const dim3 grid(n_seq, Hq);
+  if (hd == 64) hipLaunchKernelGGL(clm_attn_kernel<64>, grid, dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv);
+  else if (hd == 80) hipLaunchKernelGGL(clm_attn_kernel<80>, grid, dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv);
+  else hipLaunchKernelGGL(clm_attn_kernel<128>, grid, dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv);
+  B2T_CHECK_LAUNCH("clm_attn_kernel");
+  return 0;
+}
+
+ClmLayout clm_layout(int d_model, long long qkv_width, int ffn, int vocab, long long rows, long long head_rows, size_t ints) {
+  ClmLayout L{};
+  const long long d = d_model, Mh = head_rows > 0 ? head_rows : 0;
+  L.Mp = rup(rows > 0 ? rows : 1, ROWPAD); L.ncg = (vocab + 63) / 64;
+  size_t off = 0;
+  L.ints = off;   off += al256(sizeof(int) * ints);
+  L.resid = off;  off += al256(sizeof(float) * (size_t)(rows * d));
+  L.x16 = off;    off += al256(sizeof(_Float16) * (size_t)(L.Mp * d));
+  L.qkv = off;    off += al256(sizeof(_Float16) * (size_t)(rows * qkv_width));
+  L.hbuf = off;   off += al256(sizeof(_Float16) * (size_t)(L.Mp * ffn));
+  L.pmax = off;   off += al256(sizeof(float) * (size_t)(Mh * L.ncg));
+  L.psum = off;   off += al256(sizeof(float) * (size_t)(Mh * L.ncg));
+  L.tlogit = off; off += al256(sizeof(float) * (size_t)Mh);
+  L.logp = off;   off += al256(sizeof(float) * (size_t)Mh);
+  L.total = off;
+  return L;
+}
+
+size_t flat_ints(long long M, int n_seq) {
+  const long long Mh = M - n_seq;
+  return (size_t)(2 * M + 2 * (Mh > 0 ? Mh : 0) + 2 * ((long long)n_seq + 1));
+}
+
+int clm_check_lists(const char* who, const int32_t* ids, const int32_t* seq_off, int n_seq, int vocab, int max_pos) {
+  B2T_REQUIRE(n_seq >= 1, "%s: n_seq %d < 1", who, n_seq);
+  B2T_REQUIRE(seq_off[0] == 0, "%s: seq_off[0] = %d, expected 0", who, seq_off[0]);
+  for (int s = 0; s < n_seq; ++s) {
+    const long long n = (long long)seq_off[s + 1] - seq_off[s];
+    B2T_REQUIRE(n >= 1, "%s: sequence %d is empty", who, s);
+    B2T_REQUIRE(max_pos <= 0 || n <= max_pos, "%s: sequence %d has %lld tokens, more than max_pos %d", who, s, n, max_pos);
+  }
+  if (vocab > 0) {
+    const long long M = seq_off[n_seq];
+    for (long long t = 0; t < M; ++t)
+      B2T_REQUIRE(ids[t] >= 0 && ids[t] < vocab, "%s: token %lld has id %d outside [0, %d)", who, t, ids[t], vocab);
+  }
+  return 0;
+}
+
+int clm_build_flat_index(const char* what, const int32_t* ids, const int32_t* seq_off, int n_seq, int* d_ints, hipStream_t s,
+                         ClmFlatIndex* ix) {
+  const long long M = seq_off[n_seq], Mh = M - n_seq;
+  static thread_local std::vector<int> host;
+  host.assign(flat_ints(M, n_seq), 0);
+  int* h_ids = host.data(); int* h_pos = h_ids + M; int* h_src = h_pos + M; int* h_tgt = h_src + Mh;
+  int* h_soff = h_tgt + Mh; int* h_hoff = h_soff + n_seq + 1;
+  long long r = 0;
+  for (int q = 0; q < n_seq; ++q) {
+    const int a = seq_off[q], b = seq_off[q + 1];
+    h_soff[q] = a; h_hoff[q] = (int)r;
+    for (int t = a; t < b; ++t) {
+      h_ids[t] = ids[t]; h_pos[t] = t - a;
+      if (t + 1 < b) { h_src[r] = t; h_tgt[r] = ids[t + 1]; ++r; }
+    }
+  }
+  h_soff[n_seq] = (int)M; h_hoff[n_seq] = (int)r;
+  if (int rc = check_hip(hipMemcpyAsync(d_ints, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s), what)) return rc;
+  // the staging vector is reused by the next call on this thread: wait for the copy out of it
+  if (int rc = check_hip(hipStreamSynchronize(s), what)) return rc;
+  const int* d_src = d_ints + 2 * M;
+  *ix = ClmFlatIndex{{M, Mh, d_ints, d_ints + M, d_src, d_src + Mh}, d_src + 2 * Mh, d_src + 2 * Mh + n_seq + 1};
+  return 0;
+}
+
 }  // namespace b2t
 
 using namespace b2t;
 
 extern "C" size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, int n_seq) {
   if (!model || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return clm_layout(model, n_tokens, n_seq).total;
+  return clm_opt_layout(model, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
 }
 
 extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                  float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "b2t_clm_score_f16";
   if (int rc = clm_check_model(model)) return rc;
   const b2t_clm_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "b2t_clm_score_f16: null argument");
-  B2T_REQUIRE(n_seq >= 1, "b2t_clm_score_f16: n_seq %d < 1", n_seq);
-  B2T_REQUIRE(seq_off_host[0] == 0, "b2t_clm_score_f16: seq_off[0] = %d, expected 0", seq_off_host[0]);
-  for (int s = 0; s < n_seq; ++s) {
-    const long long n = (long long)seq_off_host[s + 1] - seq_off_host[s];
-    B2T_REQUIRE(n >= 1, "b2t_clm_score_f16: sequence %d is empty", s);
-    B2T_REQUIRE(n <= m.max_pos, "b2t_clm_score_f16: sequence %d has %lld tokens, more than max_pos %d", s, n, m.max_pos);
-  }
+  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
-  for (long long t = 0; t < M; ++t)
-    B2T_REQUIRE(ids_host[t] >= 0 && ids_host[t] < m.vocab, "b2t_clm_score_f16: token %lld has id %d outside [0, %d)", t,
-                ids_host[t], m.vocab);
-  const ClmLayout L = clm_layout(model, M, n_seq);
-  B2T_REQUIRE(ws_bytes >= L.total, "b2t_clm_score_f16: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+  const ClmLayout L = clm_opt_layout(model, M, M - n_seq, flat_ints(M, n_seq));
+  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
   const hipStream_t s = as_stream(stream);
-  const int d = m.d_model, H = m.n_heads, hd = d / H, F = m.ffn_dim;
-  const long long Mh = L.Mh;
-
-  // index arrays, built on the host and uploaded once: ids[M] pos[M] head_src[Mh] head_tgt[Mh] seq_off[n+1] head_off[n+1]
-  static thread_local std::vector<int> host;
-  host.assign((size_t)(2 * M + 2 * Mh + 2 * (n_seq + 1)), 0);
-  int* h_ids = host.data(); int* h_pos = h_ids + M; int* h_src = h_pos + M; int* h_tgt = h_src + Mh;
-  int* h_soff = h_tgt + Mh; int* h_hoff = h_soff + n_seq + 1;
-  long long r = 0;
-  for (int q = 0; q < n_seq; ++q) {
-    const int a = seq_off_host[q], b = seq_off_host[q + 1];
-    h_soff[q] = a; h_hoff[q] = (int)r;
-    for (int t = a; t < b; ++t) {
-      h_ids[t] = ids_host[t]; h_pos[t] = t - a;
-      if (t + 1 < b) { h_src[r] = t; h_tgt[r] = ids_host[t + 1]; ++r; }
-    }
-  }
-  h_soff[n_seq] = (int)M; h_hoff[n_seq] = (int)r;
   char* base = static_cast<char*>(ws);
-  int* d_ids = reinterpret_cast<int*>(base + L.ints);
-  int* d_pos = d_ids + M; int* d_src = d_pos + M; int* d_tgt = d_src + Mh; int* d_soff = d_tgt + Mh; int* d_hoff = d_soff + n_seq + 1;
-  if (int rc = check_hip(hipMemcpyAsync(d_ids, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s), "b2t_clm_score_f16 upload"))
+  ClmFlatIndex ix;
+  if (int rc = clm_build_flat_index("b2t_clm_score_f16 upload", ids_host, seq_off_host, n_seq, reinterpret_cast<int*>(base + L.ints),
+                                    s, &ix))
     return rc;
-  // the staging vector is reused by the next call on this thread: wait for the copy out of it
-  if (int rc = check_hip(hipStreamSynchronize(s), "b2t_clm_score_f16 upload")) return rc;
-
-  float* resid = reinterpret_cast<float*>(base + L.resid);
-  _Float16* x16 = reinterpret_cast<_Float16*>(base + L.x16);
-  _Float16* qkv = reinterpret_cast<_Float16*>(base + L.qkv);
-  _Float16* hb = reinterpret_cast<_Float16*>(base + L.hbuf);
-  const _Float16* et = static_cast<const _Float16*>(m.embed_tokens);
-
-  if (int rc = clm_launch_embed(d_ids, d_pos, et, static_cast<const _Float16*>(m.embed_positions), resid, d, M, s)) return rc;
-  auto H16 = [](const void* p) { return static_cast<const _Float16*>(p); };
-  for (int l = 0; l < m.n_layers; ++l) {
-    const b2t_clm_layer_t& w = m.layers_host[l];
-    if (int rc = clm_launch_layernorm(resid, nullptr, M, H16(w.ln1_w), H16(w.ln1_b), x16, d, s)) return rc;
-    ClmGemm g{};
-    g.A = x16; g.B = H16(w.qkv_w); g.M = (int)M; g.N = 3 * d; g.K = d; g.bias = H16(w.qkv_b); g.out16 = qkv; g.ldo = 3 * d;
-    g.qscale = 1.0f / sqrtf((float)hd); g.qcols = d;
-    if (int rc = launch_gemm<EP_F16>(g, s)) return rc;
-    if (hd == 64) hipLaunchKernelGGL(clm_attn_kernel<64>, dim3(n_seq, H), dim3(256), 0, s, qkv, x16, d_soff, d);
-    else if (hd == 80) hipLaunchKernelGGL(clm_attn_kernel<80>, dim3(n_seq, H), dim3(256), 0, s, qkv, x16, d_soff, d);
-    else hipLaunchKernelGGL(clm_attn_kernel<128>, dim3(n_seq, H), dim3(256), 0, s, qkv, x16, d_soff, d);
-    B2T_CHECK_LAUNCH("clm_attn_kernel");
-    g = ClmGemm{};
-    g.A = x16; g.B = H16(w.out_w); g.M = (int)M; g.N = d; g.K = d; g.bias = H16(w.out_b); g.resid = resid; g.ldo = d;
-    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
-    if (int rc = clm_launch_layernorm(resid, nullptr, M, H16(w.ln2_w), H16(w.ln2_b), x16, d, s)) return rc;
-    g = ClmGemm{};
-    g.A = x16; g.B = H16(w.fc1_w); g.M = (int)M; g.N = F; g.K = d; g.bias = H16(w.fc1_b); g.out16 = hb; g.ldo = F;
-    if (int rc = launch_gemm<EP_RELU>(g, s)) return rc;
-    g = ClmGemm{};
-    g.A = hb; g.B = H16(w.fc2_w); g.M = (int)M; g.N = d; g.K = F; g.bias = H16(w.fc2_b); g.resid = resid; g.ldo = d;
-    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
-  }
-  float* logp = reinterpret_cast<float*>(base + L.logp);
-  if (Mh > 0) {
-    if (int rc = clm_launch_layernorm(resid, d_src, Mh, H16(m.final_ln_w), H16(m.final_ln_b), x16, d, s)) return rc;
-    ClmGemm g{};
-    g.A = x16; g.B = et; g.M = (int)Mh; g.N = m.vocab; g.K = d;
-    g.pmax = reinterpret_cast<float*>(base + L.pmax); g.psum = reinterpret_cast<float*>(base + L.psum);
-    g.tlogit = reinterpret_cast<float*>(base + L.tlogit); g.tgt = d_tgt; g.ncg = (int)L.ncg;
-    if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
-    if (int rc = clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, logp, Mh, s)) return rc;
-  }
-  return clm_launch_seq_sum(logp, d_soff, d_hoff, scores_out, tok_logp_out, n_seq, s);
+  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
+    return clm_launch_attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
+  };
+  if (int rc = clm_forward(m, ix.run, L, base, attn, s)) return rc;
+  return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
 }

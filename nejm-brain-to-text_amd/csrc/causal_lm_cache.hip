@@ -29,83 +29,22 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "clm_internal.h"
+#include "clm_attn.h"
 
 namespace b2t {
 namespace {
 
-using f32x16 = float __attribute__((ext_vector_type(16)));
-using f32x4 = float __attribute__((ext_vector_type(4)));
-using half8 = _Float16 __attribute__((ext_vector_type(8)));
-
-// One key block of clm_attn_tree_kernel's online softmax, operand for operand: S^T = K . Q^T from the lane's key row kp,
-// the mask (keys beyond the query or the path; `masked` false = no key of the block can be either), the per-lane state
-// update, P rounded to fp16, O^T += V^T . P^T from the wave's LDS slab vs (written by the caller before the second barrier).
-template <int D, bool MASK>
-__device__ __forceinline__ void attn_block(const _Float16* kp, const half8* qf, const _Float16* vs, int k0, int q, int L, int li,
-                                           int hh, float& m, float& l, f32x16* o) {
-  constexpr int KS = D / 16, NF = (D + 31) / 32, VP = D + 8;
-  f32x16 sacc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-    sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(kp + 16 * ks), qf[ks], sacc, 0, 0, 0);
-  float mx = -INFINITY;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    if (MASK) {
-      const int key = k0 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      if (key > q || key >= L) sacc[e] = -INFINITY;
-    }
-    mx = fmaxf(mx, sacc[e]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  const float mnew = fmaxf(m, mx);
-  const float alpha = __expf(m - mnew);
-  float ps = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) { const float p = __expf(sacc[e] - mnew); sacc[e] = p; ps += p; }
-  ps += __shfl_xor(ps, 32);
-  l = l * alpha + ps;
-  m = mnew;
-  half8 pb[2];
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pb[s2][j] = (_Float16)sacc[8 * s2 + j];
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();   // the slab is written
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[f][e] *= alpha;
-    const int dim = 32 * f + li;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      half8 va;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int key = 16 * s2 + 8 * (j >> 2) + 4 * hh + (j & 3);
-        va[j] = dim < D ? vs[key * VP + dim] : (_Float16)0.f;
-      }
-      o[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb[s2], o[f], 0, 0, 0);
-    }
-  }
-}
-
 // clm_attn_tree_kernel with a two-source gather: path node < R is row `node` of the cache's layer slab ([cap][2d], K then V),
 // else row node - R of this call's qkv ([rows][3d], Q K V).  In both a row's V sits d elements behind its K, so one address
-// per key row serves both; the select is on the address (base and pitch), the loads behind it are unconditional 16-byte
-// pieces.  Queries start at max(own_start, R); out has the computed rows.  With st_o set (stage B) the key loop starts at
+// per key row serves both; the select is on the address (base and pitch), not around the loads, which are 16-byte pieces
+// (stage_v and attn_block, clm_attn.h).  Queries start at max(own_start, R); out has the computed rows.  With st_o set (stage B) the key loop starts at
 // block kb0 = Rb / 32 from the state clm_attn_trunk_kernel left for the query's row: st_ml [rows][H][2], st_o [rows][d].
 template <int D>
 __global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float16* qkv, const _Float16* slab, _Float16* out,
                                                                    const int* seq_off, const int* tok_node, const int* own_start,
                                                                    int d, int R, const float* st_ml, const float* st_o, int kb0) {
-  constexpr int KS = D / 16, NF = (D + 31) / 32, VP = D + 8, PCS = D / 8, NIT = PCS / 2;
-  static_assert(32 * PCS == 64 * NIT, "a V block is a whole number of 16-byte pieces per lane");
-  __shared__ __attribute__((aligned(16))) _Float16 vslab[4][32 * VP];
+  constexpr int NF = AttnDims<D>::NF;
+  __shared__ __attribute__((aligned(16))) _Float16 vslab[4][32 * AttnDims<D>::VP];
   const int sq = blockIdx.x, h = blockIdx.y, H = gridDim.y;
   const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, start = max(own_start[sq], R);
   if (start >= L) return;   // every node of this path is owned by an earlier sequence or held by the cache
@@ -115,22 +54,21 @@ __global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float1
   const _Float16* Qb = qkv + h * D;
   const _Float16* Kq = Qb + d;           // K of a computed row; its V is d further
   const _Float16* Kc = slab + h * D;     // K of a cached row; its V is d further
+  auto krow_of = [&](int node) {
+    const bool c = node < R;
+    return (c ? Kc : Kq) + (long long)(c ? node : node - R) * (c ? CS : RS);
+  };
   _Float16* vs = vslab[wave];
   const int nqb = (L + 31) / 32;
   for (int qb = start / 32 + wave; qb < nqb; qb += 4) {
-    const int q0 = qb * 32, q = q0 + li;
+    const int q = qb * 32 + li;
     const bool live = q >= start && q < L;
     const int qrow = max(path[min(q, L - 1)] - R, 0);   // lanes below R read row 0 and write nothing
-    const _Float16* qp = Qb + (long long)qrow * RS + 8 * hh;
-    half8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const half8*>(qp + 16 * ks);
-    float m = -INFINITY, l = 0.f;
+    half8 qf[AttnDims<D>::KS];
+    load_q<D>(Qb + (long long)qrow * RS + 8 * hh, qf);
+    float m, l;
     f32x16 o[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[f][e] = 0.f;
+    attn_zero<D>(m, l, o);
     if (st_o) {   // wave-uniform
       const float* mp = st_ml + ((long long)qrow * H + h) * 2;
       const float m_in = mp[0], l_in = mp[1];
@@ -150,36 +88,10 @@ __global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float1
     for (int kb = kb0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
       const int k0 = kb * 32;
       const int knode = path[min(k0 + li, L - 1)];
-      const bool kc = knode < R;
-      const _Float16* krow = (kc ? Kc : Kq) + (long long)(kc ? knode : knode - R) * (kc ? CS : RS);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();   // the previous block's reads of the slab are done
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int p = 64 * it + lane, key = p / PCS, c = p % PCS;
-        const int vnode = __shfl(knode, key);
-        const bool vc = vnode < R;
-        const _Float16* vrow = (vc ? Kc : Kq) + (long long)(vc ? vnode : vnode - R) * (vc ? CS : RS) + d;
-        half8 v = *reinterpret_cast<const half8*>(vrow + 8 * c);   // the row is clamped to the path: always readable
-        if (k0 + key >= L) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = (_Float16)0.f;
-        }
-        *reinterpret_cast<half8*>(vs + key * VP + 8 * c) = v;
-      }
-      attn_block<D, true>(krow + 8 * hh, qf, vs, k0, q, L, li, hh, m, l, o);
+      stage_v<D>(vs, lane, L - k0, [&](int key) { return krow_of(__shfl(knode, key)) + d; });
+      attn_block<D, true>(krow_of(knode) + 8 * hh, qf, VSlab<D>{vs}, k0, q, L, li, hh, m, l, o);
     }
-    if (live) {
-      const float inv = 1.0f / l;
-      _Float16* op = out + (long long)qrow * d + h * D;
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int dim = 32 * f + (e & 3) + 8 * (e >> 2) + 4 * hh;
-          if (dim < D) op[dim] = (_Float16)(o[f][e] * inv);
-        }
-    }
+    if (live) attn_store<D>(out + (long long)qrow * d + h * D, o, l, hh);
   }
 }
 
@@ -188,35 +100,22 @@ __global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float1
 template <int D>
 __global__ __launch_bounds__(64) void clm_attn_trunk_kernel(const _Float16* qkv, const _Float16* slab, int d, int rows, int nkb,
                                                             float* st_ml, float* st_o) {
-  constexpr int KS = D / 16, NF = (D + 31) / 32, VP = D + 8, PCS = D / 8, NIT = PCS / 2;
-  __shared__ __attribute__((aligned(16))) _Float16 vs[32 * VP];
+  constexpr int NF = AttnDims<D>::NF;
+  __shared__ __attribute__((aligned(16))) _Float16 vs[32 * AttnDims<D>::VP];
   const int h = blockIdx.y, H = gridDim.y;
   const int lane = threadIdx.x, li = lane & 31, hh = lane >> 5;
   const long long RS = 3LL * d, CS = 2LL * d;
   const int r = blockIdx.x * 32 + li, row = min(r, rows - 1);
-  const _Float16* qp = qkv + h * D + (long long)row * RS + 8 * hh;
   const _Float16* Kc = slab + h * D;
-  half8 qf[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const half8*>(qp + 16 * ks);
-  float m = -INFINITY, l = 0.f;
+  half8 qf[AttnDims<D>::KS];
+  load_q<D>(qkv + h * D + (long long)row * RS + 8 * hh, qf);
+  float m, l;
   f32x16 o[NF];
-#pragma unroll
-  for (int f = 0; f < NF; ++f)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[f][e] = 0.f;
+  attn_zero<D>(m, l, o);
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * 32;
-    const _Float16* krow = Kc + (long long)(k0 + li) * CS;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();   // the previous block's reads of the slab are done
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int p = 64 * it + lane, key = p / PCS, c = p % PCS;
-      *reinterpret_cast<half8*>(vs + key * VP + 8 * c) =
-          *reinterpret_cast<const half8*>(Kc + (long long)(k0 + key) * CS + d + 8 * c);
-    }
-    attn_block<D, false>(krow + 8 * hh, qf, vs, k0, 0, 0, li, hh, m, l, o);
+    stage_v<D>(vs, lane, 32, [&](int key) { return Kc + (long long)(k0 + key) * CS + d; });
+    attn_block<D, false>(Kc + (long long)(k0 + li) * CS + 8 * hh, qf, VSlab<D>{vs}, k0, 0, 0, li, hh, m, l, o);
   }
   if (r < rows) {
     if (hh == 0) {
@@ -279,8 +178,6 @@ __global__ __launch_bounds__(64) void clm_seq_sum_tree_cached_kernel(const float
   }
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct CachePlan { int Tn, P, R, n_after; };
 
 // The rule of the file header.  Sequences are non-empty, seq_off[0] == 0, 0 <= cache_n <= cap.
@@ -302,11 +199,11 @@ CachePlan cache_plan(const int32_t* cache_ids, int cache_n, int cap, const int32
 }
 
 // the state of stage B behind the tree layout: m, l per (row, head) and the unnormalised o per row
-struct CachedLayout { TreeLayout T; size_t st_ml, st_o, total; };
+struct CachedLayout { ClmLayout T; size_t st_ml, st_o, total; };
 
 CachedLayout cached_layout(const b2t_clm_t* m, long long rows, long long M, int n_seq) {
   CachedLayout L{};
-  L.T = tree_layout(m, rows, M, n_seq);
+  L.T = clm_opt_layout(m, rows, rows, tree_ints(rows, M, n_seq));
   size_t off = L.T.total;
   L.st_ml = off; off += al256(sizeof(float) * (size_t)(rows * m->n_heads * 2));
   L.st_o = off;  off += al256(sizeof(float) * (size_t)(rows * m->d_model));
@@ -323,34 +220,26 @@ bool trunk_attn_on() {
   return e && *e ? atoi(e) != 0 : CLM_TRUNK_ATTN_DEFAULT;
 }
 
+// one layer's attention of the cached call: stage B over the whole cached blocks (trunk on and R >= 32), then the tree walk
+struct CachedAttn {
+  const int *soff, *node, *own;
+  int d, H, n_seq, R;
+  long long rows;
+  bool trunk;
+  float *st_ml, *st_o;
+};
+
 template <int D>
-int launch_attn(const _Float16* qkv, const _Float16* slab, _Float16* out, const int* soff, const int* node, const int* own, int d,
-                int H, int n_seq, int R, long long rows, bool trunk, float* st_ml, float* st_o, hipStream_t s) {
-  const int Rb = trunk ? R - R % 32 : 0;
+int launch_attn(const CachedAttn& a, const _Float16* qkv, const _Float16* slab, _Float16* out, hipStream_t s) {
+  const int Rb = a.trunk ? a.R - a.R % 32 : 0;
   if (Rb > 0) {
-    hipLaunchKernelGGL(clm_attn_trunk_kernel<D>, dim3((unsigned)((rows + 31) / 32), H), dim3(64), 0, s, qkv, slab, d, (int)rows,
-                       Rb / 32, st_ml, st_o);
+    hipLaunchKernelGGL(clm_attn_trunk_kernel<D>, dim3((unsigned)((a.rows + 31) / 32), a.H), dim3(64), 0, s, qkv, slab, a.d,
+                       (int)a.rows, Rb / 32, a.st_ml, a.st_o);
     B2T_CHECK_LAUNCH("clm_attn_trunk_kernel");
   }
-  hipLaunchKernelGGL(clm_attn_tree_cached_kernel<D>, dim3(n_seq, H), dim3(256), 0, s, qkv, slab, out, soff, node, own, d, R,
-                     Rb > 0 ? st_ml : nullptr, Rb > 0 ? st_o : nullptr, Rb / 32);
+  hipLaunchKernelGGL(clm_attn_tree_cached_kernel<D>, dim3(a.n_seq, a.H), dim3(256), 0, s, qkv, slab, out, a.soff, a.node, a.own,
+                     a.d, a.R, Rb > 0 ? a.st_ml : nullptr, Rb > 0 ? a.st_o : nullptr, Rb / 32);
   B2T_CHECK_LAUNCH("clm_attn_tree_cached_kernel");
-  return 0;
-}
-
-int check_lists(const char* who, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, int vocab, int max_pos) {
-  B2T_REQUIRE(n_seq >= 1, "%s: n_seq %d < 1", who, n_seq);
-  B2T_REQUIRE(seq_off_host[0] == 0, "%s: seq_off[0] = %d, expected 0", who, seq_off_host[0]);
-  for (int s = 0; s < n_seq; ++s) {
-    const long long n = (long long)seq_off_host[s + 1] - seq_off_host[s];
-    B2T_REQUIRE(n >= 1, "%s: sequence %d is empty", who, s);
-    B2T_REQUIRE(max_pos <= 0 || n <= max_pos, "%s: sequence %d has %lld tokens, more than max_pos %d", who, s, n, max_pos);
-  }
-  if (vocab > 0) {
-    const long long M = seq_off_host[n_seq];
-    for (long long t = 0; t < M; ++t)
-      B2T_REQUIRE(ids_host[t] >= 0 && ids_host[t] < vocab, "%s: token %lld has id %d outside [0, %d)", who, t, ids_host[t], vocab);
-  }
   return 0;
 }
 
@@ -371,7 +260,7 @@ extern "C" int b2t_clm_cache_plan_host(const int32_t* cache_ids_host, int cache_
   B2T_REQUIRE(ids_host && seq_off_host && (cache_ids_host || cache_n == 0), "%s: null argument", who);
   B2T_REQUIRE(cap >= 1, "%s: cap %d < 1", who, cap);
   B2T_REQUIRE(cache_n >= 0 && cache_n <= cap, "%s: n %d outside [0, cap %d]", who, cache_n, cap);
-  if (int rc = check_lists(who, ids_host, seq_off_host, n_seq, 0, 0)) return rc;
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, 0, 0)) return rc;
   const CachePlan p = cache_plan(cache_ids_host, cache_n, cap, ids_host, seq_off_host, n_seq);
   if (trunk) *trunk = p.Tn;
   if (common) *common = p.P;
@@ -406,121 +295,56 @@ extern "C" int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cac
   for (int t = 0; t < cache->n; ++t)
     B2T_REQUIRE(cache->ids_host[t] >= 0 && cache->ids_host[t] < m.vocab, "%s: cached token %d has id %d outside [0, %d)", who, t,
                 cache->ids_host[t], m.vocab);
-  if (int rc = check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
 
-  // the tree plan and the rule; the index arrays in upload order, over the computed rows (node n is row n - R):
-  // row_id[rows] row_pos[rows] head_src[rows] head_tgt[rows] (Mh used) tok_node[M] tok_hrow[M] seq_off[n+1] own_start[n]
-  static thread_local std::vector<int32_t> tok_node, parent, own, host;
-  tok_node.resize((size_t)M); parent.resize((size_t)M); own.resize((size_t)n_seq);
-  const long long Mn = tree_plan(ids_host, seq_off_host, n_seq, tok_node.data(), parent.data(), M, own.data());
+  // the tree plan and the rule; the index arrays are over the computed rows (node n is row n - R)
+  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);
   const CachePlan P = cache_plan(cache->ids_host, cache->n, cache->cap, ids_host, seq_off_host, n_seq);
   const int R = P.R;
-  const long long rows = Mn - R;
+  const long long rows = plan.Mn - R;
   if (n_rows_out) *n_rows_out = rows;
   if (n_reused_out) *n_reused_out = R;
   const CachedLayout CL = cached_layout(model, rows, M, n_seq);
-  const TreeLayout& L = CL.T;
+  const ClmLayout& L = CL.T;
   B2T_REQUIRE(ws_bytes >= CL.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, CL.total);
   const hipStream_t s = as_stream(stream);
-  const int d = m.d_model, H = m.n_heads, hd = d / H, F = m.ffn_dim;
-  const bool trunk = trunk_attn_on();
-
-  host.assign(tree_ints(rows, M, n_seq), 0);
-  int* h_id = host.data(); int* h_pos = h_id + rows; int* h_src = h_pos + rows; int* h_tgt = h_src + rows;
-  int* h_node = h_tgt + rows; int* h_hrow = h_node + M; int* h_soff = h_hrow + M; int* h_own = h_soff + n_seq + 1;
-  for (int q = 0; q < n_seq; ++q) {
-    const int a = seq_off_host[q], b = seq_off_host[q + 1];
-    h_soff[q] = a; h_own[q] = own[q];
-    for (int t = a; t < b; ++t) {
-      const int n = tok_node[t];
-      h_node[t] = n;
-      if (n >= R) { h_id[n - R] = ids_host[t]; h_pos[n - R] = t - a; }   // the true position: R + the row's depth below R
-    }
-  }
-  h_soff[n_seq] = (int)M;
-  long long Mh = 0;   // head rows: the non-root nodes > R in node order, source = the parent's row, target = the node's id
-  {
-    std::vector<int32_t>& hrow = parent;   // parent[n] is read before hrow[n] is written
-    for (long long n = 0; n < Mn; ++n) {
-      const int p = parent[n];
-      if (n > R && p >= 0) { h_src[Mh] = p - R; h_tgt[Mh] = h_id[n - R]; hrow[n] = (int32_t)Mh++; }
-      else hrow[n] = 0;
-    }
-    for (long long t = 0; t < M; ++t) h_hrow[t] = hrow[tok_node[t]];
-  }
+  const int d = m.d_model, H = m.n_heads, hd = d / H;
   // what the cache gains: positions R .. n_after - 1 (K | V rows 0.. of qkv, head rows 0.. of logp)
   const int app_rows = update && P.n_after > R ? P.n_after - R : 0;
   const int app_logp = update && P.n_after > R + 1 ? P.n_after - R - 1 : 0;
 
   char* base = static_cast<char*>(ws);
-  int* d_id = reinterpret_cast<int*>(base + L.ints);
-  int* d_pos = d_id + rows; int* d_src = d_pos + rows; int* d_tgt = d_src + rows; int* d_node = d_tgt + rows;
-  int* d_hrow = d_node + M; int* d_soff = d_hrow + M; int* d_own = d_soff + n_seq + 1;
-  if (int rc = check_hip(hipMemcpyAsync(d_id, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s), who)) return rc;
-  // the staging vector is reused by the next call on this thread: wait for the copy out of it
-  if (int rc = check_hip(hipStreamSynchronize(s), who)) return rc;
-
-  float* resid = reinterpret_cast<float*>(base + L.resid);
-  _Float16* x16 = reinterpret_cast<_Float16*>(base + L.x16);
-  _Float16* qkv = reinterpret_cast<_Float16*>(base + L.qkv);
-  _Float16* hb = reinterpret_cast<_Float16*>(base + L.hbuf);
+  ClmTreeIndex ix;
+  if (int rc = clm_build_tree_index(who, ids_host, seq_off_host, n_seq, plan, R, reinterpret_cast<int*>(base + L.ints), s, &ix))
+    return rc;
   float* logp = reinterpret_cast<float*>(base + L.logp);
-  float* st_ml = reinterpret_cast<float*>(base + CL.st_ml);
-  float* st_o = reinterpret_cast<float*>(base + CL.st_o);
-  auto H16 = [](const void* p) { return static_cast<const _Float16*>(p); };
-  const _Float16* et = H16(m.embed_tokens);
+  const CachedAttn ca{ix.d_soff, ix.d_node, ix.d_own, d, H, n_seq, R, rows, trunk_attn_on(),
+                      reinterpret_cast<float*>(base + CL.st_ml), reinterpret_cast<float*>(base + CL.st_o)};
   _Float16* kv = static_cast<_Float16*>(cache->kv);
   const size_t slab_elems = (size_t)cache->cap * 2 * d;
-
+  // a layer's K | V append, then its attention against the layer's slab
+  auto attn = [&](int l, const _Float16* qkv, _Float16* out) -> int {
+    _Float16* slab = kv + (size_t)l * slab_elems;
+    if (app_rows > 0) {
+      const long long pieces = (long long)app_rows * (d / 4);
+      hipLaunchKernelGGL(clm_cache_append_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, qkv,
+                         slab + (size_t)R * 2 * d, d, (long long)app_rows);
+      B2T_CHECK_LAUNCH("clm_cache_append_kernel");
+    }
+    if (hd == 64) return launch_attn<64>(ca, qkv, slab, out, s);
+    if (hd == 80) return launch_attn<80>(ca, qkv, slab, out, s);
+    return launch_attn<128>(ca, qkv, slab, out, s);
+  };
   // from here on rows >= R of the cache may be overwritten: an error return leaves it at min(n, R)
   auto forward = [&]() -> int {
-    if (int rc = clm_launch_embed(d_id, d_pos, et, H16(m.embed_positions), resid, d, rows, s)) return rc;
-    for (int l = 0; l < m.n_layers; ++l) {
-      const b2t_clm_layer_t& w = m.layers_host[l];
-      _Float16* slab = kv + (size_t)l * slab_elems;
-      if (int rc = clm_launch_layernorm(resid, nullptr, rows, H16(w.ln1_w), H16(w.ln1_b), x16, d, s)) return rc;
-      ClmGemm g{};
-      g.A = x16; g.B = H16(w.qkv_w); g.M = (int)rows; g.N = 3 * d; g.K = d; g.bias = H16(w.qkv_b); g.out16 = qkv; g.ldo = 3 * d;
-      g.qscale = 1.0f / sqrtf((float)hd); g.qcols = d;
-      if (int rc = launch_gemm<EP_F16>(g, s)) return rc;
-      if (app_rows > 0) {
-        const long long pieces = (long long)app_rows * (d / 4);
-        hipLaunchKernelGGL(clm_cache_append_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, qkv,
-                           slab + (size_t)R * 2 * d, d, (long long)app_rows);
-        B2T_CHECK_LAUNCH("clm_cache_append_kernel");
-      }
-      int rc;
-      if (hd == 64) rc = launch_attn<64>(qkv, slab, x16, d_soff, d_node, d_own, d, H, n_seq, R, rows, trunk, st_ml, st_o, s);
-      else if (hd == 80) rc = launch_attn<80>(qkv, slab, x16, d_soff, d_node, d_own, d, H, n_seq, R, rows, trunk, st_ml, st_o, s);
-      else rc = launch_attn<128>(qkv, slab, x16, d_soff, d_node, d_own, d, H, n_seq, R, rows, trunk, st_ml, st_o, s);
-      if (rc) return rc;
-      g = ClmGemm{};
-      g.A = x16; g.B = H16(w.out_w); g.M = (int)rows; g.N = d; g.K = d; g.bias = H16(w.out_b); g.resid = resid; g.ldo = d;
-      if (int rc2 = launch_gemm<EP_RESID>(g, s)) return rc2;
-      if (int rc2 = clm_launch_layernorm(resid, nullptr, rows, H16(w.ln2_w), H16(w.ln2_b), x16, d, s)) return rc2;
-      g = ClmGemm{};
-      g.A = x16; g.B = H16(w.fc1_w); g.M = (int)rows; g.N = F; g.K = d; g.bias = H16(w.fc1_b); g.out16 = hb; g.ldo = F;
-      if (int rc2 = launch_gemm<EP_RELU>(g, s)) return rc2;
-      g = ClmGemm{};
-      g.A = hb; g.B = H16(w.fc2_w); g.M = (int)rows; g.N = d; g.K = F; g.bias = H16(w.fc2_b); g.resid = resid; g.ldo = d;
-      if (int rc2 = launch_gemm<EP_RESID>(g, s)) return rc2;
-    }
-    if (Mh > 0) {
-      if (int rc = clm_launch_layernorm(resid, d_src, Mh, H16(m.final_ln_w), H16(m.final_ln_b), x16, d, s)) return rc;
-      ClmGemm g{};
-      g.A = x16; g.B = et; g.M = (int)Mh; g.N = m.vocab; g.K = d;
-      g.pmax = reinterpret_cast<float*>(base + L.pmax); g.psum = reinterpret_cast<float*>(base + L.psum);
-      g.tlogit = reinterpret_cast<float*>(base + L.tlogit); g.tgt = d_tgt; g.ncg = (int)L.ncg;
-      if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
-      if (int rc = clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, logp, Mh, s)) return rc;
-    }
+    if (int rc = clm_forward(m, ix.run, L, base, attn, s)) return rc;
     if (app_logp > 0) {
       hipLaunchKernelGGL(clm_cache_logp_kernel, dim3((app_logp + 255) / 256), dim3(256), 0, s, logp, cache->logp + R + 1, app_logp);
       B2T_CHECK_LAUNCH("clm_cache_logp_kernel");
     }
-    hipLaunchKernelGGL(clm_seq_sum_tree_cached_kernel, dim3(n_seq), dim3(64), 0, s, logp, cache->logp, R, d_soff, d_hrow, scores_out,
-                       tok_logp_out);
+    hipLaunchKernelGGL(clm_seq_sum_tree_cached_kernel, dim3(n_seq), dim3(64), 0, s, logp, cache->logp, R, ix.d_soff, ix.d_hrow,
+                       scores_out, tok_logp_out);
     B2T_CHECK_LAUNCH("clm_seq_sum_tree_cached_kernel");
     return 0;
   };

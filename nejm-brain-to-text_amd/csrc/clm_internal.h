@@ -1,8 +1,15 @@
-// clm_internal.h — host-side pieces of the causal-LM forward shared by causal_lm.hip (the flat scoring path, which defines
-// them), causal_lm_tree.hip (the shared-prefix tree path, which defines the plan and the workspace layout),
-// causal_lm_cache.hip (the tree path behind a context cache) and causal_lm_llama.hip (the Llama family, flat and tree).  The
-// kernels themselves stay private to their files; these are their launchers, so each GEMM epilogue is instantiated once.
+// clm_internal.h — what the four units of the causal-LM forward share.  causal_lm.hip (the flat OPT path) defines the tile rule,
+// the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
+// list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
+// and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
+// causal_lm_llama.hip (the Llama family, flat and tree) use them.  Both attention launchers serve both families: OPT's row
+// q[d] | k[d] | v[d] is the Llama row q[Hq * D] | k[Hkv * D] | v[Hkv * D] with Hkv = Hq.  The kernels stay private to their
+// files (their arithmetic is clm_attn.h's, the GEMM's template clm_gemm.h's); these are their launchers, so each is
+// instantiated once.  clm_forward, the OPT layer loop of the flat, tree and cached entry points, is at the end.
 #pragma once
+#include <math.h>
+#include <vector>
+
 #include "common.h"
 
 namespace b2t {
@@ -58,22 +65,123 @@ int clm_launch_seq_sum(const float* logp, const int* seq_off, const int* head_of
 // dimensions, head dim and weight pointers of a model descriptor (0, or an error with the message set)
 int clm_check_model(const b2t_clm_t* m);
 
-// ---- causal_lm_tree.hip ----
-// Workspace of a forward over Mn rows for M packed tokens in n_seq sequences: sized by Mn alone where the flat path has
-// n_tokens - n_seq head rows (the head has at most a row per computed row).
-struct TreeLayout {
+// ---- sizes ----
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline long long rup(long long x, long long m) { return (x + m - 1) / m * m; }
+
+// sum of v over a 256-thread block (red: 4 floats of LDS); every thread gets the same value
+static __device__ __forceinline__ float block_sum256(float v, float* red) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Workspace of a forward over `rows` rows (qkv_width fp16 per row of the QKV GEMM's output) with `head_rows` head rows and
+// `ints` index entries.  The tree paths size the head by their rows (it has at most a row per computed row).
+struct ClmLayout {
   size_t ints, resid, x16, qkv, hbuf, pmax, psum, tlogit, logp, total;
   long long Mp, ncg;
 };
-// ints of the index arrays: node_id[Mn] node_pos[Mn] head_src[Mn] head_tgt[Mn] tok_node[M] tok_hrow[M] seq_off[n+1] own_start[n]
-size_t tree_ints(long long Mn, long long M, int n_seq);
-TreeLayout tree_layout(const b2t_clm_t* m, long long Mn, long long M, int n_seq);
-// The shared-prefix plan (b2t_clm_tree_plan_host): node_of_token gets all n_tokens entries; parent_of_node (and own_start,
-// optional, per sequence) only below cap.  Returns the number of nodes.
+ClmLayout clm_layout(int d_model, long long qkv_width, int ffn, int vocab, long long rows, long long head_rows, size_t ints);
+// ints of the flat index arrays: ids[M] pos[M] head_src[Mh] head_tgt[Mh] seq_off[n+1] head_off[n+1], Mh = M - n_seq
+size_t flat_ints(long long M, int n_seq);
+// ints of the tree index arrays: row_id[rows] row_pos[rows] head_src[rows] head_tgt[rows] (Mh used) tok_node[M] tok_hrow[M]
+// seq_off[n+1] own_start[n]
+size_t tree_ints(long long rows, long long M, int n_seq);
+
+// ---- the lists ----
+// Refusals of a packed list: n_seq < 1, seq_off[0] != 0, an empty sequence, one longer than max_pos (max_pos > 0), an id
+// outside [0, vocab) (vocab > 0).  `who` is the entry point's name.
+int clm_check_lists(const char* who, const int32_t* ids, const int32_t* seq_off, int n_seq, int vocab, int max_pos);
+
+// the rows of a forward and their index arrays on the device
+struct ClmRun {
+  long long rows, Mh;          // rows of the forward; head rows
+  const int *d_ids, *d_pos;    // [rows] token id and position
+  const int *d_src, *d_tgt;    // [Mh] head source row and target id
+};
+struct ClmFlatIndex { ClmRun run; const int *d_soff, *d_hoff; };
+struct ClmTreeIndex { ClmRun run; const int *d_node, *d_hrow, *d_soff, *d_own; };
+// Builds the flat index arrays on the host, uploads them to d_ints (flat_ints entries) and waits for the copy; `what` names
+// the upload in an error.
+int clm_build_flat_index(const char* what, const int32_t* ids, const int32_t* seq_off, int n_seq, int* d_ints, hipStream_t s,
+                         ClmFlatIndex* ix);
+
+// The shared-prefix plan: tok_node gets all n_tokens entries; parent_of_node (and own_start, optional, per sequence) only
+// below cap.  Returns the number of nodes.
+long long tree_plan(const int32_t* ids, const int32_t* seq_off, int n_seq, int32_t* node_of_token, int32_t* parent_of_node,
+                    long long cap, int32_t* own_start);
+struct ClmTreePlan { std::vector<int32_t> tok_node, parent, own; long long Mn; };
+// the plan of a checked list in this thread's buffers, valid until the thread's next call
+ClmTreePlan& clm_plan_tree(const int32_t* ids, const int32_t* seq_off, int n_seq);
+// The tree index arrays over the computed rows, node n >= R being row n - R (R = 0: every node; R > 0: the first R nodes are
+// a context cache's, causal_lm_cache.hip).  Head rows are the non-root nodes > R in node order, source = the parent's row,
+// target = the node's id.  Uploads to d_ints (tree_ints(Mn - R, ..) entries) and waits for the copy.  Uses up plan.parent.
+int clm_build_tree_index(const char* what, const int32_t* ids, const int32_t* seq_off, int n_seq, ClmTreePlan& plan, int R,
+                         int* d_ints, hipStream_t s, ClmTreeIndex* ix);
+
+// ---- attention and sums ----
+// Causal attention of every sequence over the rows [seq_off[s], seq_off[s + 1]) of qkv (row q[Hq * D] | k[Hkv * D] |
+// v[Hkv * D], query head h reads K / V head h / (Hq / Hkv)) into out ([rows][Hq * D]); D = hd is 64, 80 or 128.
+int clm_launch_attn(const _Float16* qkv, _Float16* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s);
+// The same over tree paths: position i of sequence s is row tok_node[seq_off[s] + i]; written are the rows a sequence owns.
+int clm_launch_attn_tree(const _Float16* qkv, _Float16* out, const int* seq_off, const int* tok_node, const int* own_start,
+                         int n_seq, int Hq, int Hkv, int hd, hipStream_t s);
 // scores[q] = sum of logp[tok_hrow[t]] along sequence q's tokens 1.. in order; tok_logp as above
 int clm_launch_seq_sum_tree(const float* logp, const int* seq_off, const int* tok_hrow, float* scores, float* tok_logp,
                             int n_seq, hipStream_t s);
-long long tree_plan(const int32_t* ids, const int32_t* seq_off, int n_seq, int32_t* node_of_token, int32_t* parent_of_node,
-                    long long cap, int32_t* own_start);
+
+// ---- the OPT forward ----
+inline ClmLayout clm_opt_layout(const b2t_clm_t* m, long long rows, long long head_rows, size_t ints) {
+  return clm_layout(m->d_model, 3LL * m->d_model, m->ffn_dim, m->vocab, rows, head_rows, ints);
+}
+
+// Fused LM head over r.Mh rows of x16 (already normalised): logp[i] = log p(r.d_tgt[i]) under the logits x16[i] . W^T
+inline int clm_head(const _Float16* x16, const _Float16* W, int vocab, int d, const ClmRun& r, const ClmLayout& L, char* base,
+                    hipStream_t s) {
+  ClmGemm g{};
+  g.A = x16; g.B = W; g.M = (int)r.Mh; g.N = vocab; g.K = d;
+  g.pmax = reinterpret_cast<float*>(base + L.pmax); g.psum = reinterpret_cast<float*>(base + L.psum);
+  g.tlogit = reinterpret_cast<float*>(base + L.tlogit); g.tgt = r.d_tgt; g.ncg = (int)L.ncg;
+  if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
+  return clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, reinterpret_cast<float*>(base + L.logp), r.Mh, s);
+}
+
+// The pre-LN OPT forward over r.rows rows up to the per-row log-probs logp[r.Mh] (base + L.logp); attn(layer, qkv, out)
+// enqueues one layer's attention from qkv ([rows][3d]) into out ([rows][d]).
+template <class Attn>
+int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s) {
+  const int d = m.d_model, hd = d / m.n_heads, F = m.ffn_dim, M = (int)r.rows;
+  float* resid = reinterpret_cast<float*>(base + L.resid);
+  _Float16* x16 = reinterpret_cast<_Float16*>(base + L.x16);
+  _Float16* qkv = reinterpret_cast<_Float16*>(base + L.qkv);
+  _Float16* hb = reinterpret_cast<_Float16*>(base + L.hbuf);
+  auto H16 = [](const void* p) { return static_cast<const _Float16*>(p); };
+  if (int rc = clm_launch_embed(r.d_ids, r.d_pos, H16(m.embed_tokens), H16(m.embed_positions), resid, d, r.rows, s)) return rc;
+  for (int l = 0; l < m.n_layers; ++l) {
+    const b2t_clm_layer_t& w = m.layers_host[l];
+    if (int rc = clm_launch_layernorm(resid, nullptr, r.rows, H16(w.ln1_w), H16(w.ln1_b), x16, d, s)) return rc;
+    ClmGemm g{};
+    g.A = x16; g.B = H16(w.qkv_w); g.M = M; g.N = 3 * d; g.K = d; g.bias = H16(w.qkv_b); g.out16 = qkv; g.ldo = 3 * d;
+    g.qscale = 1.0f / sqrtf((float)hd); g.qcols = d;
+    if (int rc = launch_gemm<EP_F16>(g, s)) return rc;
+    if (int rc = attn(l, qkv, x16)) return rc;
+    g = ClmGemm{};
+    g.A = x16; g.B = H16(w.out_w); g.M = M; g.N = d; g.K = d; g.bias = H16(w.out_b); g.resid = resid; g.ldo = d;
+    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
+    if (int rc = clm_launch_layernorm(resid, nullptr, r.rows, H16(w.ln2_w), H16(w.ln2_b), x16, d, s)) return rc;
+    g = ClmGemm{};
+    g.A = x16; g.B = H16(w.fc1_w); g.M = M; g.N = F; g.K = d; g.bias = H16(w.fc1_b); g.out16 = hb; g.ldo = F;
+    if (int rc = launch_gemm<EP_RELU>(g, s)) return rc;
+    g = ClmGemm{};
+    g.A = hb; g.B = H16(w.fc2_w); g.M = M; g.N = d; g.K = F; g.bias = H16(w.fc2_b); g.resid = resid; g.ldo = d;
+    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
+  }
+  if (r.Mh <= 0) return 0;
+  if (int rc = clm_launch_layernorm(resid, r.d_src, r.Mh, H16(m.final_ln_w), H16(m.final_ln_b), x16, d, s)) return rc;
+  return clm_head(x16, H16(m.embed_tokens), m.vocab, d, r, L, base, s);   // the head is tied to embed_tokens
+}
 
 }  // namespace b2t

@@ -323,7 +323,86 @@ def load_opt_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
     return dims, device_layout(_load_state_dict(model_dir), dims)
 
 
-class OptScorer:
+class _Scorer:
+    """What OptScorer and LlamaScorer share: packing and validating the ids, growing the workspace, the outputs, and the
+    `score` / `token_logprobs` / `eval` surface.  A subclass builds its descriptor (`desc`, with `device`, `share_prefixes`,
+    `last_stats`, `_ws` = None and, where it has one, `_cache`) and supplies `_sizes` and `_score`: its library calls on
+    the path "flat", "tree" or "cached"."""
+    _cache = None
+    _WS_BYTES = ""    # the family's flat sizing call, for the message of a refused size
+    _NO_CACHE = ""    # the ValueError of use_cache=True on a scorer without a context cache
+
+    def eval(self):   # the reference calls model.eval(); scoring has no training mode
+        return self
+
+    def _sizes(self, lib, path, ids, off):
+        """(rows computed, positions reused, workspace bytes) of a call on `path` for the packed ids / offsets."""
+        raise NotImplementedError
+
+    def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
+        """The library call of `path`; every array argument is an address (tok may be None)."""
+        raise NotImplementedError
+
+    def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
+             update_cache: bool = True):
+        import torch
+        import b2t_native as N
+        name = type(self).__name__
+        tree = self.share_prefixes if share_prefixes is None else bool(share_prefixes)
+        cached = self._cache is not None if use_cache is None else bool(use_cache)
+        if cached and self._cache is None:
+            raise ValueError(f"{name}: {self._NO_CACHE}")
+        lib = N.load()
+        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in ids_list]
+        if not seqs:
+            self.last_stats = {"tokens": 0, "nodes": 0}
+            return np.zeros(0, np.float32), np.zeros(0, np.int64), None
+        lens = np.array([len(s) for s in seqs], dtype=np.int64)
+        if int(lens.min()) < 1:
+            raise ValueError(f"{name}: empty token sequence")
+        if lens.sum() > np.iinfo(np.int32).max:
+            raise ValueError(f"{name}: too many tokens")
+        ids = np.ascontiguousarray(np.concatenate(seqs).astype(np.int32))
+        off = np.zeros(len(seqs) + 1, dtype=np.int32)
+        off[1:] = np.cumsum(lens)
+        M = int(off[-1])
+        path = "cached" if cached else "tree" if tree else "flat"
+        nodes, reused, need = self._sizes(lib, path, ids, off)
+        if need == 0:
+            raise RuntimeError(f"{self._WS_BYTES}: invalid sizes: {N.last_error()}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        scores = torch.empty(len(seqs), dtype=torch.float32, device=self.device)
+        tok = torch.empty(M, dtype=torch.float32, device=self.device) if want_tokens else None
+        with torch.cuda.device(self.device):
+            self._score(lib, path, update_cache, ids.ctypes.data, off.ctypes.data, len(seqs), scores.data_ptr(),
+                        tok.data_ptr() if tok is not None else None, self._ws.data_ptr(), self._ws.numel(),
+                        torch.cuda.current_stream(self.device).cuda_stream)
+            s = scores.cpu().numpy()
+            t = tok.cpu().numpy() if tok is not None else None
+        self.last_stats = {"tokens": M, "nodes": int(nodes)}
+        if cached:
+            self.last_stats["reused"] = int(reused)
+        return s, lens, t
+
+    def score(self, ids_list, length_penalty: float = 0.0, share_prefixes: Optional[bool] = None,
+              use_cache: Optional[bool] = None, update_cache: bool = True) -> np.ndarray:
+        """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores.
+        share_prefixes: None = the scorer's own setting.  use_cache: None = cached iff the scorer has a context cache (True
+        on a scorer without one raises); a cached call shares prefixes whatever share_prefixes says.  update_cache=False
+        reads the cache and leaves it as it was."""
+        s, lens, _ = self._run(ids_list, False, share_prefixes, use_cache, update_cache)
+        return s.astype(np.float32) - (lens * float(length_penalty)).astype(np.float32)
+
+    def token_logprobs(self, ids_list, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
+                       update_cache: bool = True) -> List[np.ndarray]:
+        """Per sequence the fp32 log-prob of each token given its prefix (0 for the first token)."""
+        _, lens, t = self._run(ids_list, True, share_prefixes, use_cache, update_cache)
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return [t[off[i]:off[i + 1]] for i in range(len(lens))]
+
+
+class OptScorer(_Scorer):
     """An OPT decoder on the GPU in the b2t_clm_t layout; `score` runs b2t_clm_score_f16 on packed ids, or, with
     share_prefixes, b2t_clm_score_tree_f16: the same forward over the list's shared-prefix token tree (each distinct prefix
     computed once; results bit-identical to the flat call).  `share_prefixes` here is the default of `score` and
@@ -335,6 +414,9 @@ class OptScorer:
     computed are read from the cache instead.  The cache is matched by token ids, so it is never wrong, only more or less
     useful; results stay bit-identical.  Per call `use_cache` = None (the scorer's setting) | True | False; after a cached
     call `last_stats` = {"tokens", "nodes": rows computed, "reused": positions taken from the cache}."""
+
+    _WS_BYTES = "b2t_clm_ws_bytes"
+    _NO_CACHE = "use_cache=True on a scorer built without context_cache_tokens"
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0):
@@ -384,86 +466,30 @@ class OptScorer:
         if self._cache is not None:
             self._cache.n = max(0, min(int(keep), int(self._cache.n)))
 
-    def eval(self):   # the reference calls model.eval(); scoring has no training mode
-        return self
-
-    def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
-             update_cache: bool = True):
+    def _sizes(self, lib, path, ids, off):
         import ctypes as C
-        import torch
-        import b2t_native as N
-        lib = N.load()
-        tree = self.share_prefixes if share_prefixes is None else bool(share_prefixes)
-        cached = self._cache is not None if use_cache is None else bool(use_cache)
-        if cached and self._cache is None:
-            raise ValueError("OptScorer: use_cache=True on a scorer built without context_cache_tokens")
-        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in ids_list]
-        if not seqs:
-            self.last_stats = {"tokens": 0, "nodes": 0}
-            return np.zeros(0, np.float32), np.zeros(0, np.int64), None
-        lens = np.array([len(s) for s in seqs], dtype=np.int64)
-        ids = np.ascontiguousarray(np.concatenate(seqs).astype(np.int32))
-        off = np.zeros(len(seqs) + 1, dtype=np.int32)
-        off[1:] = np.cumsum(lens)
-        if int(lens.min()) < 1:
-            raise ValueError("OptScorer: empty token sequence")
-        if int(off[-1]) != int(lens.sum()) or lens.sum() > np.iinfo(np.int32).max:
-            raise ValueError("OptScorer: too many tokens")
-        M = int(off[-1])
-        nodes = M
-        reused = 0
-        if cached:
+        desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
+        if path == "cached":
             plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
-            nodes, reused = plan["rows"], plan["reused"]
-            need = lib.b2t_clm_tree_cached_ws_bytes(C.byref(self.desc), nodes, M, len(seqs))
-        elif tree:
+            return plan["rows"], plan["reused"], lib.b2t_clm_tree_cached_ws_bytes(desc, plan["rows"], M, n_seq)
+        if path == "tree":
             nodes = tree_plan(ids, off)[2]
-            need = lib.b2t_clm_tree_ws_bytes(C.byref(self.desc), nodes, M, len(seqs))
+            return nodes, 0, lib.b2t_clm_tree_ws_bytes(desc, nodes, M, n_seq)
+        return M, 0, lib.b2t_clm_ws_bytes(desc, M, n_seq)
+
+    def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
+        import ctypes as C
+        import b2t_native as N
+        desc = C.byref(self.desc)
+        if path == "cached":
+            N.check(lib.b2t_clm_score_tree_cached_f16(desc, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq,
+                                                      scores, tok, None, None, ws, ws_bytes, stream),
+                    "b2t_clm_score_tree_cached_f16")
+        elif path == "tree":
+            N.check(lib.b2t_clm_score_tree_f16(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream),
+                    "b2t_clm_score_tree_f16")
         else:
-            need = lib.b2t_clm_ws_bytes(C.byref(self.desc), M, len(seqs))
-        if need == 0:
-            raise RuntimeError(f"b2t_clm_ws_bytes: invalid sizes: {N.last_error()}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        scores = torch.empty(len(seqs), dtype=torch.float32, device=self.device)
-        tok = torch.empty(M, dtype=torch.float32, device=self.device) if want_tokens else None
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if cached:
-                N.check(lib.b2t_clm_score_tree_cached_f16(C.byref(self.desc), C.byref(self._cache), 1 if update_cache else 0,
-                                                          ids.ctypes.data, off.ctypes.data, len(seqs), scores.data_ptr(),
-                                                          tok.data_ptr() if tok is not None else None, None, None,
-                                                          self._ws.data_ptr(), self._ws.numel(), stream),
-                        "b2t_clm_score_tree_cached_f16")
-            elif tree:
-                N.check(lib.b2t_clm_score_tree_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs),
-                                                   scores.data_ptr(), tok.data_ptr() if tok is not None else None, None,
-                                                   self._ws.data_ptr(), self._ws.numel(), stream), "b2t_clm_score_tree_f16")
-            else:
-                N.check(lib.b2t_clm_score_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs), scores.data_ptr(),
-                                              tok.data_ptr() if tok is not None else None, self._ws.data_ptr(), self._ws.numel(),
-                                              stream), "b2t_clm_score_f16")
-            s = scores.cpu().numpy()
-            t = tok.cpu().numpy() if tok is not None else None
-        self.last_stats = {"tokens": M, "nodes": int(nodes)}
-        if cached:
-            self.last_stats["reused"] = int(reused)
-        return s, lens, t
-
-    def score(self, ids_list, length_penalty: float = 0.0, share_prefixes: Optional[bool] = None,
-              use_cache: Optional[bool] = None, update_cache: bool = True) -> np.ndarray:
-        """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores.
-        share_prefixes: None = the scorer's own setting.  use_cache: None = cached iff the scorer has a context cache; a
-        cached call shares prefixes whatever share_prefixes says.  update_cache=False reads the cache and leaves it as it was."""
-        s, lens, _ = self._run(ids_list, False, share_prefixes, use_cache, update_cache)
-        return s.astype(np.float32) - (lens * float(length_penalty)).astype(np.float32)
-
-    def token_logprobs(self, ids_list, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
-                       update_cache: bool = True) -> List[np.ndarray]:
-        """Per sequence the fp32 log-prob of each token given its prefix (0 for the first token)."""
-        _, lens, t = self._run(ids_list, True, share_prefixes, use_cache, update_cache)
-        off = np.concatenate([[0], np.cumsum(lens)])
-        return [t[off[i]:off[i + 1]] for i in range(len(lens))]
+            N.check(lib.b2t_clm_score_f16(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), "b2t_clm_score_f16")
 
 
 # ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM) ---------------------------------------
@@ -634,11 +660,14 @@ def load_llama_arrays(model_dir: str, max_positions: Optional[int] = None) -> Tu
     return dims, llama_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg))
 
 
-class LlamaScorer:
+class LlamaScorer(_Scorer):
     """A Llama-family decoder on the GPU in the b2t_clm_llama_t layout, with OptScorer's scoring surface: `score` runs
     b2t_clm_llama_score_f16 on packed ids, or, with share_prefixes, b2t_clm_llama_score_tree_f16 over the list's shared-prefix
     token tree (bit-identical to the flat call); after a call `last_stats` = {"tokens", "nodes": rows computed}.  There is no
     context cache for this family yet: context_cache_tokens > 0 and use_cache=True raise ValueError."""
+
+    _WS_BYTES = "b2t_clm_llama_ws_bytes"
+    _NO_CACHE = "no context cache for Llama-family models"
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0):
@@ -670,71 +699,23 @@ class LlamaScorer:
                                    self.w["rope_cos"].data_ptr(), self.w["rope_sin"].data_ptr(), self._layers)
         self._ws = None
 
-    def eval(self):   # the reference calls model.eval(); scoring has no training mode
-        return self
-
-    def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None):
+    def _sizes(self, lib, path, ids, off):
         import ctypes as C
-        import torch
-        import b2t_native as N
-        if use_cache:
-            raise ValueError("LlamaScorer: no context cache for Llama-family models")
-        lib = N.load()
-        tree = self.share_prefixes if share_prefixes is None else bool(share_prefixes)
-        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in ids_list]
-        if not seqs:
-            self.last_stats = {"tokens": 0, "nodes": 0}
-            return np.zeros(0, np.float32), np.zeros(0, np.int64), None
-        lens = np.array([len(s) for s in seqs], dtype=np.int64)
-        if int(lens.min()) < 1:
-            raise ValueError("LlamaScorer: empty token sequence")
-        if lens.sum() > np.iinfo(np.int32).max:
-            raise ValueError("LlamaScorer: too many tokens")
-        ids = np.ascontiguousarray(np.concatenate(seqs).astype(np.int32))
-        off = np.zeros(len(seqs) + 1, dtype=np.int32)
-        off[1:] = np.cumsum(lens)
-        M = int(off[-1])
-        nodes = M
-        if tree:
+        desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
+        if path == "tree":
             nodes = tree_plan(ids, off)[2]
-            need = lib.b2t_clm_llama_tree_ws_bytes(C.byref(self.desc), nodes, M, len(seqs))
+            return nodes, 0, lib.b2t_clm_llama_tree_ws_bytes(desc, nodes, M, n_seq)
+        return M, 0, lib.b2t_clm_llama_ws_bytes(desc, M, n_seq)
+
+    def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
+        import ctypes as C
+        import b2t_native as N
+        desc = C.byref(self.desc)
+        if path == "tree":
+            N.check(lib.b2t_clm_llama_score_tree_f16(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream),
+                    "b2t_clm_llama_score_tree_f16")
         else:
-            need = lib.b2t_clm_llama_ws_bytes(C.byref(self.desc), M, len(seqs))
-        if need == 0:
-            raise RuntimeError("b2t_clm_llama_ws_bytes: invalid sizes")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        scores = torch.empty(len(seqs), dtype=torch.float32, device=self.device)
-        tok = torch.empty(M, dtype=torch.float32, device=self.device) if want_tokens else None
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if tree:
-                N.check(lib.b2t_clm_llama_score_tree_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs),
-                                                         scores.data_ptr(), tok.data_ptr() if tok is not None else None, None,
-                                                         self._ws.data_ptr(), self._ws.numel(), stream),
-                        "b2t_clm_llama_score_tree_f16")
-            else:
-                N.check(lib.b2t_clm_llama_score_f16(C.byref(self.desc), ids.ctypes.data, off.ctypes.data, len(seqs),
-                                                    scores.data_ptr(), tok.data_ptr() if tok is not None else None,
-                                                    self._ws.data_ptr(), self._ws.numel(), stream), "b2t_clm_llama_score_f16")
-            s = scores.cpu().numpy()
-            t = tok.cpu().numpy() if tok is not None else None
-        self.last_stats = {"tokens": M, "nodes": int(nodes)}
-        return s, lens, t
-
-    def score(self, ids_list, length_penalty: float = 0.0, share_prefixes: Optional[bool] = None,
-              use_cache: Optional[bool] = None, update_cache: bool = True) -> np.ndarray:
-        """Per sequence: sum_{t>=1} log p(id[t] | id[<t]) - len * length_penalty, in fp32 as the reference's numpy scores.
-        share_prefixes: None = the scorer's own setting.  use_cache / update_cache: OptScorer's arguments; use_cache=True raises."""
-        s, lens, _ = self._run(ids_list, False, share_prefixes, use_cache)
-        return s.astype(np.float32) - (lens * float(length_penalty)).astype(np.float32)
-
-    def token_logprobs(self, ids_list, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
-                       update_cache: bool = True) -> List[np.ndarray]:
-        """Per sequence the fp32 log-prob of each token given its prefix (0 for the first token)."""
-        _, lens, t = self._run(ids_list, True, share_prefixes, use_cache)
-        off = np.concatenate([[0], np.cumsum(lens)])
-        return [t[off[i]:off[i + 1]] for i in range(len(lens))]
+            N.check(lib.b2t_clm_llama_score_f16(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), "b2t_clm_llama_score_f16")
 
 
 def tree_plan(ids, seq_off, cap: Optional[int] = None):

@@ -16,7 +16,8 @@ FAKE = 0x10000   # a non-null "device" pointer that is never dereferenced
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_clm_kernels_do_not_spill():
     # spilled MFMA operand tuples came back wrong on ROCm 7.2 (NOTES.md R6.2); at the time of writing all 15 kernels have
-    # scratch 0 and at most 224 VGPRs (the 256-tile GEMM 222)
+    # scratch 0 and at most 224 VGPRs (the 256-tile GEMM 222; the attention 175 / 204 / 224 VGPRs and 62 / 68 / 124 AGPRs at
+    # head dim 64 / 80 / 128).  clm_attn_kernel is the Llama family's flat attention too
     import wave_kernel_resources as W
     res = {k: v for k, v in W.resources(src="causal_lm.hip").items() if "clm_" in k}
     gemm = [k for k in res if "clm_gemm_kernel" in k]

@@ -497,15 +497,15 @@ def test_score_refusals_before_device_work(tree):
 # ---- the kernels ------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_llama_kernels_do_not_spill():
-    # the bound of tests/test_clm_host.py; at the time of writing: attention 175 / 224 VGPRs (head dim 64 / 128), tree
-    # attention 110 / 193, the 256-tile GEMMs 222, scratch 0 everywhere
+    # the bound of tests/test_clm_host.py; at the time of writing: the 256-tile GEMMs 222 VGPRs, the 128-tile ones 86, embed
+    # and RMSNorm 16, scratch 0 everywhere.  The unit has no attention kernel of its own: it launches clm_attn_kernel
+    # (causal_lm.hip) and clm_attn_tree_kernel (causal_lm_tree.hip), the kernels OPT runs, so their scratch-0 and register
+    # assertions are the ones test_clm_kernels_do_not_spill and test_tree_kernels_do_not_spill make
     import wave_kernel_resources as W
     res = {k: v for k, v in W.resources(src="causal_lm_llama.hip").items() if "clm_" in k}
     gemm = [k for k in res if "clm_gemm_kernel" in k]
-    attn = [k for k in res if "clm_llama_attn_kernel" in k]
-    tattn = [k for k in res if "clm_llama_attn_tree_kernel" in k]
     # the two new epilogues on both tiles; the other four epilogues are instantiated in causal_lm.hip alone
-    assert len(gemm) == 4 and len(attn) == 2 and len(tattn) == 2 and len(res) == 10, sorted(res)
+    assert len(gemm) == 4 and not [k for k in res if "attn" in k] and len(res) == 6, sorted(res)
     assert any("clm_llama_embed_kernel" in k for k in res) and any("clm_llama_rmsnorm_kernel" in k for k in res)
     spilled = {k: v for k, v in res.items() if v.get("ScratchSize", -1) != 0}
     assert not spilled, spilled
