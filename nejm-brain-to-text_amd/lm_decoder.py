@@ -4,7 +4,7 @@
 Two searchers, chosen like the reference's BrainSpeechDecoder does (brain_speech_decoder.cc:23-28):
   * a decode graph is loaded (DecodeResource(fst_path, ..) -- an OpenFST vector/standard TLG.fst or an .npz written by
     wfst.save_graph -- or DecodeResource.set_graph(wfst.build_tlg(lexicon, arpa))): CtcWfstBeamSearch, i.e. Kaldi's
-    lattice-generating token passing over T o L o G, as batched GPU kernels (csrc/wfst.hip, wfst_decoder.WfstSearch):
+    lattice-generating token passing over T o L o G, as batched GPU kernels (csrc/wfst*.hip, wfst_decoder.WfstSearch):
     partial best path after every Decode(), n-best word sequences with separate graph / acoustic scores after
     FinishDecoding(), Rescore() with a second grammar;
   * no graph: the LM-free CtcPrefixBeamSearch (csrc/beam.hip), optionally fused with a token-level ARPA n-gram

@@ -1,4 +1,4 @@
-"""Host side of the WFST decoder: drives the batched token-passing kernels (csrc/wfst.hip) for U utterances and turns
+"""Host side of the WFST decoder: drives the batched token-passing kernels (csrc/wfst.hip, wfst_cluster.hip, wfst_prune.hip, wfst_lattice.hip) for U utterances and turns
 what they leave in HBM into the reference's outputs.
 
     WfstSearch.search(logp)      CtcWfstBeamSearch::Search        ctc_wfst_beam_search.cc:70-121  (partial best path)

@@ -42,7 +42,7 @@ class Config:
         self.acoustic_scale, self.nbest, self.blank_skip_thresh = acoustic_scale, nbest, blank_skip_thresh
         # "sequential": ProcessEmitting as the reference runs it -- next_cutoff tightens while the hash list is walked, so the
         # tokens created beyond the frame's final cutoff depend on the list's order (HashList below).  "final": the data-parallel
-        # rule of csrc/wfst.hip -- every candidate is compared with the frame's FINAL next_cutoff (best candidate +
+        # rule of csrc/wfst.hip and wfst_cluster.hip -- every candidate is compared with the frame's FINAL next_cutoff (best candidate +
         # adaptive_beam; the reference reaches the same value at the end of its walk), no token beyond it exists.  The two
         # differ only through GetCutoff's token COUNT / k-th cost in the next frame, i.e. while max_active (or min_active) binds.
         assert cutoff_rule in ("sequential", "final")
@@ -184,7 +184,7 @@ class LatticeFasterDecoder:
                     if nw + adaptive_beam < next_cutoff:
                         next_cutoff = nw + adaptive_beam
         self.cost_offsets.append(cost_offset)
-        if cfg.cutoff_rule == "final":      # the frame's final cutoff first (csrc/wfst.hip pass A), then every candidate against it
+        if cfg.cutoff_rule == "final":      # the frame's final cutoff first (pass A of csrc/wfst.hip and wfst_cluster.hip), then every candidate against it
             for tok in final_toks:
                 if tok.tot_cost <= cur_cutoff:
                     for a in range(self.row[tok.state], self.row[tok.state + 1]):

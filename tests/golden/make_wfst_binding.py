@@ -11,7 +11,7 @@ the oracle's 100-best list (words, graph / acoustic cost, alignment, times), and
   n_extra      how many of them are such tokens (cost >= the frame's final next_cutoff),
   bound        1 if max_active decided the cutoff,
   differs      1 if GetCutoff's (cutoff, adaptive_beam) would differ with those tokens left out -- exactly the frames in
-               which the data-parallel search (csrc/wfst.hip never creates them) can part from the sequential one.
+               which the data-parallel search (csrc/wfst.hip and wfst_cluster.hip never create them) can part from the sequential one.
 
 Run here (CPU); tests/test_gpu_wfst.py::test_wfst_binding_regime_bench_graph compares the HIP search with it.
 The oracle is parity-unpinned by the reference (no OpenFST in the image: the C++ cannot be built)."""

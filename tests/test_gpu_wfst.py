@@ -1,4 +1,4 @@
-"""GPU: the batched WFST token-passing search (csrc/wfst.hip + wfst_decoder.py, through the C ABI) against the oracle's
+"""GPU: the batched WFST token-passing search (csrc/wfst*.hip + wfst_decoder.py, through the C ABI) against the oracle's
 restatement of the reference decoder (oracle/wfst_oracle.py) on the same graph and log-probabilities, with the production
 options (language-model-standalone.py:486-496: beam 17, max_active 7000, min_active 200, lattice_beam 8, acoustic_scale
 0.325, no blank skipping) and with blank skipping / tight pruning.  Costs: abs 2e-3 (fp32 sums in a different order);
@@ -638,7 +638,7 @@ def test_wfst_search_matches_oracle_on_random_graphs_and_options(seed):
             S.search(dev_batch, lens)
         fin = S.finalize()
         for u in range(U):
-            # lists against the oracle's data-parallel cut-off rule (what csrc/wfst.hip computes: exact in every regime); the best
+            # lists against the oracle's data-parallel cut-off rule (what csrc/wfst.hip and wfst_cluster.hip compute: exact in every regime); the best
             # hypothesis also against the reference-order walk -- on these small graphs max_active = 400 can bind, and the two rules
             # then differ in the tail of a list (tools/r5_wfst_fuzz_more.py: 2 of 12 further seeds, ranks 14 and 18; NOTES.md R5.2)
             tag = f"seed {seed} case {case} utt {u}: words {n_words} order {order} opts {o.__dict__} interval {iv}"
@@ -669,7 +669,7 @@ def test_wfst_search_while_max_active_binds_in_every_frame(max_active):
     walks its hash list (lattice-faster-decoder.cc:786-810), so which tokens beyond the frame's FINAL cutoff get created depends on
     the list's order (kaldi/util/hash-list-inl.h), and the next frame's GetCutoff counts them (:650-720).  The oracle restates both
     readings: cutoff_rule="sequential" walks in HashList order (the reference), "final" compares every candidate with the frame's
-    final cutoff (the data-parallel rule of csrc/wfst.hip).  Contract on the nine fuzz graphs with max_active 60 / 150:
+    final cutoff (the data-parallel rule of csrc/wfst.hip and wfst_cluster.hip).  Contract on the nine fuzz graphs with max_active 60 / 150:
       * HIP == oracle("final"): identical n-best lists (compare_lists) -- the kernel is pinned to a precise rule in this regime too;
       * HIP vs oracle("sequential"): the best hypothesis (words, cost) is identical in every utterance; lists may differ in their
         tail: measured on these 21 utterances (tools/r5_cutoff_order.py, CPU): max_active 60 -> 1 list differs, from rank 4 on

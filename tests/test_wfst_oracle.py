@@ -346,7 +346,7 @@ def test_hash_list_hands_the_elements_out_in_the_reference_order():
 def test_order_dependent_cutoff_only_matters_while_max_active_binds():
     """lattice-faster-decoder.cc:786-810: ProcessEmitting tightens next_cutoff while it walks the hash list, so tokens beyond the
     frame's final cutoff exist or not depending on list order; the next frame's GetCutoff counts them (:650-720).  The oracle's
-    "sequential" rule restates that walk in HashList order; its "final" rule is the data-parallel form csrc/wfst.hip implements
+    "sequential" rule restates that walk in HashList order; its "final" rule is the data-parallel form csrc/wfst.hip and wfst_cluster.hip implement
     (every candidate against the frame's final cutoff).  With max_active far from binding the two give identical n-best lists;
     with max_active = 60 (binding in every frame of these graphs) they may differ in the tail of the list but not in the best
     hypothesis (tools/r5_cutoff_order.py over the 9 fuzz graphs x 21 utterances: max_active 60 -> 1 list differs, from rank 4 on;

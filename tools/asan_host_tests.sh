@@ -8,7 +8,7 @@ CL=/opt/rocm/lib/llvm/bin/clang++
 RT=$(find /opt/rocm/lib/llvm/lib/clang -name "libclang_rt.asan-x86_64.so" | head -1)
 C=nejm-brain-to-text_amd/csrc
 O=/tmp/b2t_asan_obj; rm -rf $O; mkdir -p $O
-for f in gemm.hip gemm_bf16.hip gemm_bf16p.hip elementwise.hip gru.hip gru_persistent.hip ctc.hip optimizer.hip decode.hip beam.hip wfst.hip stream.hip core.cpp exec.cpp lattice.cpp graphc.cpp; do
+for f in gemm.hip gemm_bf16.hip gemm_bf16p.hip elementwise.hip gru.hip gru_persistent.hip ctc.hip optimizer.hip decode.hip beam.hip wfst.hip wfst_cluster.hip wfst_prune.hip wfst_lattice.hip stream.hip core.cpp exec.cpp lattice.cpp graphc.cpp; do
   $CL -x hip --offload-host-only --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=address -shared-libsan -Iinclude -I$C -c $C/$f -o $O/${f%.*}.o &
 done
 wait

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Round-5 verdict 1d (CPU only): how much does the reference's ORDER-DEPENDENT next_cutoff tightening (lattice-faster-decoder.cc:786-810,
 walked in HashList order, kaldi/util/hash-list-inl.h) change results once max_active binds?  The oracle runs both rules on the fuzz
-graphs of tests/test_gpu_wfst.py -- "sequential" (the reference, hash-list order restated) and "final" (csrc/wfst.hip's data-parallel
-rule: every candidate against the frame's final cutoff) -- and reports, per utterance: list lengths, first differing rank, whether the
+graphs of tests/test_gpu_wfst.py -- "sequential" (the reference, hash-list order restated) and "final" (the data-parallel
+rule of csrc/wfst.hip and wfst_cluster.hip: every candidate against the frame's final cutoff) -- and reports, per utterance: list lengths, first differing rank, whether the
 best hypothesis and its cost agree.   usage: r5_cutoff_order.py [max_active ...]"""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase ticks of the cluster search (a -DB2T_WFST_TIMING build of csrc/wfst.hip selected by B2T_LIB): one offline search of the bench workload
+"""Phase ticks of the cluster search (a -DB2T_WFST_TIMING build of csrc/wfst.hip and csrc/wfst_cluster.hip selected by B2T_LIB): one offline search of the bench workload
 without prune passes (one launch per 25 frames); the kernel prints member 0 / utterance 0's accumulated 100 MHz ticks per phase."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
