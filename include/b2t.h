@@ -680,7 +680,7 @@ int b2t_clm_score_tree_f16(const b2t_clm_t* model, const int32_t* ids_host, cons
  * The buffers are the caller's, like every other buffer of this library, which keeps no pointer after returning.  Calls that
  * share a cache are ordered by the caller (one stream, or an event between streams). */
 typedef struct {
-  void* kv;           /* DEVICE fp16 [n_layers][cap][2 * d_model]: K row then V row per position */
+  void* kv;           /* DEVICE fp16 [n_layers][cap][2 * d_model] (Llama family: 2 * n_kv_heads * hd): K row then V row per position */
   float* logp;        /* DEVICE fp32 [cap]: log p(c[t] | c[<t]), [0] unused */
   int32_t* ids_host;  /* HOST [cap]: the cached chain */
   int cap, n;         /* capacity; positions held -- n is updated by the call */
@@ -759,11 +759,24 @@ size_t b2t_clm_llama_ws_bytes(const b2t_clm_llama_t* model, long long n_tokens, 
 int b2t_clm_llama_score_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                             float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
 /* As b2t_clm_tree_ws_bytes / b2t_clm_score_tree_f16, on the plan of b2t_clm_tree_plan_host; a node's rotary position is its
- * depth.  Bit-identical to b2t_clm_llama_score_f16.  (The context cache is OPT's only so far.) */
+ * depth.  Bit-identical to b2t_clm_llama_score_f16. */
 size_t b2t_clm_llama_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq);
 int b2t_clm_llama_score_tree_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                  float* scores_out, float* tok_logp_out, long long* n_nodes_out,
                                  void* ws, size_t ws_bytes, void* stream);
+/* As b2t_clm_cache_kv_bytes / b2t_clm_tree_cached_ws_bytes / b2t_clm_score_tree_cached_f16, with the same b2t_clm_cache_t, rule
+ * (b2t_clm_cache_plan_host), refusals, update semantics and B2T_CLM_TRUNK_ATTN.  Grouped-query K / V make a cached position
+ * n_layers * 2 * n_kv_heads * hd fp16 (128 KiB at the Llama-3-8B shape): kv is [n_layers][cap][2 * n_kv_heads * hd], a row
+ * k[n_kv_heads * hd] | v[n_kv_heads * hd], the K rows as the forward leaves them: rotated, at their absolute positions (a
+ * node's position is its depth, cached or not).  b2t_clm_llama_cache_kv_bytes = n_layers * cap * 2 * n_kv_heads * hd * 2 (0 if
+ * invalid: null model or bad dimensions, cap < 1, cap > max_pos, n_layers < 1).  Bit-identical to b2t_clm_llama_score_f16 and
+ * b2t_clm_llama_score_tree_f16. */
+size_t b2t_clm_llama_cache_kv_bytes(const b2t_clm_llama_t* model, int cap);
+size_t b2t_clm_llama_tree_cached_ws_bytes(const b2t_clm_llama_t* model, long long n_rows, long long n_tokens, int n_seq);
+int b2t_clm_llama_score_tree_cached_f16(const b2t_clm_llama_t* model, b2t_clm_cache_t* cache, int update,
+                                        const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                        float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
+                                        void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,7 @@
 // causal_lm_cache.hip — the shared-prefix tree forward of causal_lm_tree.hip behind a context cache
-// (b2t_clm_score_tree_cached_f16).  In closed-loop decoding every rescoring call scores its candidates behind the decoding
+// (b2t_clm_score_tree_cached_f16, and through the launchers of clm_internal.h b2t_clm_llama_score_tree_cached_f16 of
+// causal_lm_llama.hip: the kernels work on the row q[Hq * D] | k[Hkv * D] | v[Hkv * D], OPT being Hkv = Hq).  In closed-loop
+// decoding every rescoring call scores its candidates behind the decoding
 // context (language-model-standalone.py:188-190), and the context only grows: context k+1 = context k + the sentence just
 // chosen.  The kernels compute a row in an order that depends only on that row, so the K and V rows and the log-prob of a
 // context token computed by an earlier call ARE the values this call would compute.  The cache keeps them; scores stay
@@ -34,26 +36,29 @@
 namespace b2t {
 namespace {
 
-// clm_attn_tree_kernel with a two-source gather: path node < R is row `node` of the cache's layer slab ([cap][2d], K then V),
-// else row node - R of this call's qkv ([rows][3d], Q K V).  In both a row's V sits d elements behind its K, so one address
-// per key row serves both; the select is on the address (base and pitch), not around the loads, which are 16-byte pieces
-// (stage_v and attn_block, clm_attn.h).  Queries start at max(own_start, R); out has the computed rows.  With st_o set (stage B) the key loop starts at
-// block kb0 = Rb / 32 from the state clm_attn_trunk_kernel left for the query's row: st_ml [rows][H][2], st_o [rows][d].
+// clm_attn_tree_kernel with a two-source gather, on the row layout the flat and tree kernels share (query head h reads K / V
+// head hk = h / (Hq / Hkv); OPT is Hkv = Hq): path node < R is row `node` of the cache's layer slab ([cap][2 * Hkv * D],
+// k[Hkv * D] | v[Hkv * D]), else row node - R of this call's qkv ([rows][(Hq + 2 * Hkv) * D], q | k | v).  In both a row's V
+// sits Hkv * D elements behind its K, so one address per key row serves both; the select is on the address (base and pitch),
+// not around the loads, which are 16-byte pieces (stage_v and attn_block, clm_attn.h).  Queries start at max(own_start, R);
+// out has the computed rows.  With st_o set (stage B) the key loop starts at block kb0 = Rb / 32 from the state
+// clm_attn_trunk_kernel left for the query's row: st_ml [rows][Hq][2], st_o [rows][Hq * D].
 template <int D>
 __global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float16* qkv, const _Float16* slab, _Float16* out,
                                                                    const int* seq_off, const int* tok_node, const int* own_start,
-                                                                   int d, int R, const float* st_ml, const float* st_o, int kb0) {
+                                                                   int Hkv, int R, const float* st_ml, const float* st_o, int kb0) {
   constexpr int NF = AttnDims<D>::NF;
   __shared__ __attribute__((aligned(16))) _Float16 vslab[4][32 * AttnDims<D>::VP];
-  const int sq = blockIdx.x, h = blockIdx.y, H = gridDim.y;
+  const int sq = blockIdx.x, h = blockIdx.y, H = gridDim.y, hk = h / (H / Hkv);
   const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, start = max(own_start[sq], R);
   if (start >= L) return;   // every node of this path is owned by an earlier sequence or held by the cache
   const int* path = tok_node + t0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
-  const long long RS = 3LL * d, CS = 2LL * d;
+  const int d = H * D, vo = Hkv * D;     // the output row; V behind K in both sources
+  const long long RS = (long long)(H + 2 * Hkv) * D, CS = 2LL * vo;
   const _Float16* Qb = qkv + h * D;
-  const _Float16* Kq = Qb + d;           // K of a computed row; its V is d further
-  const _Float16* Kc = slab + h * D;     // K of a cached row; its V is d further
+  const _Float16* Kq = qkv + (H + hk) * D;   // K of a computed row
+  const _Float16* Kc = slab + hk * D;        // K of a cached row
   auto krow_of = [&](int node) {
     const bool c = node < R;
     return (c ? Kc : Kq) + (long long)(c ? node : node - R) * (c ? CS : RS);
@@ -88,7 +93,7 @@ __global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float1
     for (int kb = kb0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
       const int k0 = kb * 32;
       const int knode = path[min(k0 + li, L - 1)];
-      stage_v<D>(vs, lane, L - k0, [&](int key) { return krow_of(__shfl(knode, key)) + d; });
+      stage_v<D>(vs, lane, L - k0, [&](int key) { return krow_of(__shfl(knode, key)) + vo; });
       attn_block<D, true>(krow_of(knode) + 8 * hh, qf, VSlab<D>{vs}, k0, q, L, li, hh, m, l, o);
     }
     if (live) attn_store<D>(out + (long long)qrow * d + h * D, o, l, hh);
@@ -96,17 +101,19 @@ __global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float1
 }
 
 // Stage B: the cached key blocks 0 .. nkb-1 (keys [0, Rb), contiguous slab rows, no mask) for 32 computed rows at a time, a
-// wave per (row block, head).  Leaves m, l (st_ml [rows][H][2]) and the unnormalised o (st_o [rows][d]) of every row < rows.
+// wave per (row block, query head), reading slab head hk.  Leaves m, l (st_ml [rows][Hq][2]) and the unnormalised o (st_o
+// [rows][Hq * D]) of every row < rows.
 template <int D>
-__global__ __launch_bounds__(64) void clm_attn_trunk_kernel(const _Float16* qkv, const _Float16* slab, int d, int rows, int nkb,
+__global__ __launch_bounds__(64) void clm_attn_trunk_kernel(const _Float16* qkv, const _Float16* slab, int Hkv, int rows, int nkb,
                                                             float* st_ml, float* st_o) {
   constexpr int NF = AttnDims<D>::NF;
   __shared__ __attribute__((aligned(16))) _Float16 vs[32 * AttnDims<D>::VP];
-  const int h = blockIdx.y, H = gridDim.y;
+  const int h = blockIdx.y, H = gridDim.y, hk = h / (H / Hkv);
   const int lane = threadIdx.x, li = lane & 31, hh = lane >> 5;
-  const long long RS = 3LL * d, CS = 2LL * d;
+  const int d = H * D, vo = Hkv * D;
+  const long long RS = (long long)(H + 2 * Hkv) * D, CS = 2LL * vo;
   const int r = blockIdx.x * 32 + li, row = min(r, rows - 1);
-  const _Float16* Kc = slab + h * D;
+  const _Float16* Kc = slab + hk * D;
   half8 qf[AttnDims<D>::KS];
   load_q<D>(qkv + h * D + (long long)row * RS + 8 * hh, qf);
   float m, l;
@@ -114,7 +121,7 @@ __global__ __launch_bounds__(64) void clm_attn_trunk_kernel(const _Float16* qkv,
   attn_zero<D>(m, l, o);
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * 32;
-    stage_v<D>(vs, lane, 32, [&](int key) { return Kc + (long long)(k0 + key) * CS + d; });
+    stage_v<D>(vs, lane, 32, [&](int key) { return Kc + (long long)(k0 + key) * CS + vo; });
     attn_block<D, false>(Kc + (long long)(k0 + li) * CS + 8 * hh, qf, VSlab<D>{vs}, k0, 0, 0, li, hh, m, l, o);
   }
   if (r < rows) {
@@ -137,15 +144,15 @@ __global__ __launch_bounds__(64) void clm_attn_trunk_kernel(const _Float16* qkv,
   }
 }
 
-// cache append: K | V of the trunk's computed rows (qkv rows 0..rows-1, columns d..3d) -> dst rows 0.. ([.][2d], the layer slab
-// at row R), as 16-byte pieces
-__global__ __launch_bounds__(256) void clm_cache_append_kernel(const _Float16* qkv, _Float16* dst, int d, long long rows) {
-  const int pcs = d / 4;   // 2d / 8 pieces per row
-  const long long n = rows * pcs;
+// cache append: K | V of the trunk's computed rows (qkv rows 0..rows-1 of width rs, columns qc .. qc + cs) -> dst rows 0..
+// ([.][cs], the layer slab at row R), as 16-byte pieces; qc = Hq * D, cs = 2 * Hkv * D, rs = qc + cs
+__global__ __launch_bounds__(256) void clm_cache_append_kernel(const _Float16* qkv, _Float16* dst, int qc, int cs, long long rows) {
+  const int pcs = cs / 8;
+  const long long n = rows * pcs, rs = (long long)qc + cs;
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) {
     const long long r = i / pcs;
     const int c = (int)(i % pcs);
-    *reinterpret_cast<half8*>(dst + r * 2 * d + 8 * c) = *reinterpret_cast<const half8*>(qkv + r * 3 * d + d + 8 * c);
+    *reinterpret_cast<half8*>(dst + r * cs + 8 * c) = *reinterpret_cast<const half8*>(qkv + r * rs + qc + 8 * c);
   }
 }
 
@@ -178,10 +185,27 @@ __global__ __launch_bounds__(64) void clm_seq_sum_tree_cached_kernel(const float
   }
 }
 
-struct CachePlan { int Tn, P, R, n_after; };
+constexpr bool CLM_TRUNK_ATTN_DEFAULT = false;
+
+// one layer's attention of the cached call: stage B over the whole cached blocks (trunk on and R >= 32), then the tree walk
+template <int D>
+int launch_attn(const ClmCachedAttn& a, const _Float16* qkv, const _Float16* slab, _Float16* out, hipStream_t s) {
+  const int Rb = a.trunk ? a.R - a.R % 32 : 0;
+  if (Rb > 0) {
+    hipLaunchKernelGGL(clm_attn_trunk_kernel<D>, dim3((unsigned)((a.rows + 31) / 32), a.Hq), dim3(64), 0, s, qkv, slab, a.Hkv,
+                       (int)a.rows, Rb / 32, a.st_ml, a.st_o);
+    B2T_CHECK_LAUNCH("clm_attn_trunk_kernel");
+  }
+  hipLaunchKernelGGL(clm_attn_tree_cached_kernel<D>, dim3(a.n_seq, a.Hq), dim3(256), 0, s, qkv, slab, out, a.soff, a.node, a.own,
+                     a.Hkv, a.R, Rb > 0 ? a.st_ml : nullptr, Rb > 0 ? a.st_o : nullptr, Rb / 32);
+  B2T_CHECK_LAUNCH("clm_attn_tree_cached_kernel");
+  return 0;
+}
+
+}  // namespace
 
 // The rule of the file header.  Sequences are non-empty, seq_off[0] == 0, 0 <= cache_n <= cap.
-CachePlan cache_plan(const int32_t* cache_ids, int cache_n, int cap, const int32_t* ids, const int32_t* seq_off, int n_seq) {
+ClmCachePlan clm_cache_plan(const int32_t* cache_ids, int cache_n, int cap, const int32_t* ids, const int32_t* seq_off, int n_seq) {
   long long Tn = seq_off[1];
   for (int s = 1; s < n_seq && Tn > 0; ++s) {
     const int32_t* b = ids + seq_off[s];
@@ -192,58 +216,60 @@ CachePlan cache_plan(const int32_t* cache_ids, int cache_n, int cap, const int32
   }
   long long P = 0;
   while (P < Tn && P < cache_n && cache_ids[P] == ids[P]) ++P;
-  CachePlan p;
+  ClmCachePlan p;
   p.Tn = (int)Tn; p.P = (int)P; p.R = P > 0 ? (int)P - 1 : 0;
   p.n_after = (int)(Tn < cap ? Tn : cap);
   return p;
 }
 
-// the state of stage B behind the tree layout: m, l per (row, head) and the unnormalised o per row
-struct CachedLayout { ClmLayout T; size_t st_ml, st_o, total; };
-
-CachedLayout cached_layout(const b2t_clm_t* m, long long rows, long long M, int n_seq) {
-  CachedLayout L{};
-  L.T = clm_opt_layout(m, rows, rows, tree_ints(rows, M, n_seq));
-  size_t off = L.T.total;
-  L.st_ml = off; off += al256(sizeof(float) * (size_t)(rows * m->n_heads * 2));
-  L.st_o = off;  off += al256(sizeof(float) * (size_t)(rows * m->d_model));
-  L.total = off;
-  return L;
+ClmCachedState clm_cached_state(size_t tree_total, long long rows, int Hq, int d_model) {
+  ClmCachedState S{};
+  size_t off = tree_total;
+  S.st_ml = off; off += al256(sizeof(float) * (size_t)(rows * Hq * 2));
+  S.st_o = off;  off += al256(sizeof(float) * (size_t)(rows * d_model));
+  S.total = off;
+  return S;
 }
 
-constexpr bool CLM_TRUNK_ATTN_DEFAULT = false;
-
-// B2T_CLM_TRUNK_ATTN, read per call: 0 = every key block in clm_attn_tree_cached_kernel (stage A); 1 = the cached blocks in
-// clm_attn_trunk_kernel (stage B).
-bool trunk_attn_on() {
+// What clm_launch_attn_cached needs for every layer of one call: the index arrays, the shapes, the rows to append, where the
+// state of stage B lives in the workspace, and whether stage B runs.
+ClmCachedAttn clm_cached_attn(const ClmTreeIndex& ix, int n_seq, int Hq, int Hkv, int hd, int R, int app_rows, char* base,
+                              const ClmCachedState& S) {
+  // B2T_CLM_TRUNK_ATTN, read per call: 0 = every key block in clm_attn_tree_cached_kernel (stage A); 1 = the cached blocks
+  // in clm_attn_trunk_kernel (stage B)
   const char* e = getenv("B2T_CLM_TRUNK_ATTN");
-  return e && *e ? atoi(e) != 0 : CLM_TRUNK_ATTN_DEFAULT;
+  const bool trunk = e && *e ? atoi(e) != 0 : CLM_TRUNK_ATTN_DEFAULT;
+  return ClmCachedAttn{ix.d_soff, ix.d_node, ix.d_own, Hq, Hkv, hd, n_seq, R, app_rows, ix.run.rows, trunk,
+                       reinterpret_cast<float*>(base + S.st_ml), reinterpret_cast<float*>(base + S.st_o)};
 }
 
-// one layer's attention of the cached call: stage B over the whole cached blocks (trunk on and R >= 32), then the tree walk
-struct CachedAttn {
-  const int *soff, *node, *own;
-  int d, H, n_seq, R;
-  long long rows;
-  bool trunk;
-  float *st_ml, *st_o;
-};
-
-template <int D>
-int launch_attn(const CachedAttn& a, const _Float16* qkv, const _Float16* slab, _Float16* out, hipStream_t s) {
-  const int Rb = a.trunk ? a.R - a.R % 32 : 0;
-  if (Rb > 0) {
-    hipLaunchKernelGGL(clm_attn_trunk_kernel<D>, dim3((unsigned)((a.rows + 31) / 32), a.H), dim3(64), 0, s, qkv, slab, a.d,
-                       (int)a.rows, Rb / 32, a.st_ml, a.st_o);
-    B2T_CHECK_LAUNCH("clm_attn_trunk_kernel");
+int clm_launch_attn_cached(const ClmCachedAttn& a, const _Float16* qkv, _Float16* slab, _Float16* out, hipStream_t s) {
+  const int qc = a.Hq * a.hd, cs = 2 * a.Hkv * a.hd;
+  if (a.app_rows > 0) {
+    const long long pieces = (long long)a.app_rows * (cs / 8);
+    hipLaunchKernelGGL(clm_cache_append_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, qkv,
+                       slab + (size_t)a.R * cs, qc, cs, (long long)a.app_rows);
+    B2T_CHECK_LAUNCH("clm_cache_append_kernel");
   }
-  hipLaunchKernelGGL(clm_attn_tree_cached_kernel<D>, dim3(a.n_seq, a.H), dim3(256), 0, s, qkv, slab, out, a.soff, a.node, a.own,
-                     a.d, a.R, Rb > 0 ? a.st_ml : nullptr, Rb > 0 ? a.st_o : nullptr, Rb / 32);
-  B2T_CHECK_LAUNCH("clm_attn_tree_cached_kernel");
+  if (a.hd == 64) return launch_attn<64>(a, qkv, slab, out, s);
+  if (a.hd == 80) return launch_attn<80>(a, qkv, slab, out, s);
+  return launch_attn<128>(a, qkv, slab, out, s);
+}
+
+int clm_launch_cache_logp(const float* logp, float* dst, int n, hipStream_t s) {
+  hipLaunchKernelGGL(clm_cache_logp_kernel, dim3((n + 255) / 256), dim3(256), 0, s, logp, dst, n);
+  B2T_CHECK_LAUNCH("clm_cache_logp_kernel");
   return 0;
 }
 
-}  // namespace
+int clm_launch_seq_sum_tree_cached(const float* logp, const float* cache_logp, int R, const int* seq_off, const int* tok_hrow,
+                                   float* scores, float* tok_logp, int n_seq, hipStream_t s) {
+  hipLaunchKernelGGL(clm_seq_sum_tree_cached_kernel, dim3(n_seq), dim3(64), 0, s, logp, cache_logp, R, seq_off, tok_hrow, scores,
+                     tok_logp);
+  B2T_CHECK_LAUNCH("clm_seq_sum_tree_cached_kernel");
+  return 0;
+}
+
 }  // namespace b2t
 
 using namespace b2t;
@@ -261,7 +287,7 @@ extern "C" int b2t_clm_cache_plan_host(const int32_t* cache_ids_host, int cache_
   B2T_REQUIRE(cap >= 1, "%s: cap %d < 1", who, cap);
   B2T_REQUIRE(cache_n >= 0 && cache_n <= cap, "%s: n %d outside [0, cap %d]", who, cache_n, cap);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, 0, 0)) return rc;
-  const CachePlan p = cache_plan(cache_ids_host, cache_n, cap, ids_host, seq_off_host, n_seq);
+  const ClmCachePlan p = clm_cache_plan(cache_ids_host, cache_n, cap, ids_host, seq_off_host, n_seq);
   if (trunk) *trunk = p.Tn;
   if (common) *common = p.P;
   if (reused) *reused = p.R;
@@ -277,84 +303,19 @@ extern "C" int b2t_clm_cache_plan_host(const int32_t* cache_ids_host, int cache_
 
 extern "C" size_t b2t_clm_tree_cached_ws_bytes(const b2t_clm_t* model, long long n_rows, long long n_tokens, int n_seq) {
   if (!model || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return cached_layout(model, n_rows, n_tokens, n_seq).total;
+  const size_t tree = clm_opt_layout(model, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
+  return clm_cached_state(tree, n_rows, model->n_heads, model->d_model).total;
 }
 
 extern "C" int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache, int update, const int32_t* ids_host,
                                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                              long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "b2t_clm_score_tree_cached_f16";
   if (int rc = clm_check_model(model)) return rc;
   const b2t_clm_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  B2T_REQUIRE(cache, "%s: null cache (callers without one use b2t_clm_score_tree_f16)", who);
-  B2T_REQUIRE(cache->kv && cache->logp && cache->ids_host, "%s: null cache member", who);
-  B2T_REQUIRE(cache->cap >= 1, "%s: cache cap %d < 1", who, cache->cap);
-  B2T_REQUIRE(cache->cap <= m.max_pos, "%s: cache cap %d above max_pos %d", who, cache->cap, m.max_pos);
-  B2T_REQUIRE(cache->n >= 0 && cache->n <= cache->cap, "%s: cache n %d outside [0, cap %d]", who, cache->n, cache->cap);
-  for (int t = 0; t < cache->n; ++t)
-    B2T_REQUIRE(cache->ids_host[t] >= 0 && cache->ids_host[t] < m.vocab, "%s: cached token %d has id %d outside [0, %d)", who, t,
-                cache->ids_host[t], m.vocab);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-
-  // the tree plan and the rule; the index arrays are over the computed rows (node n is row n - R)
-  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);
-  const CachePlan P = cache_plan(cache->ids_host, cache->n, cache->cap, ids_host, seq_off_host, n_seq);
-  const int R = P.R;
-  const long long rows = plan.Mn - R;
-  if (n_rows_out) *n_rows_out = rows;
-  if (n_reused_out) *n_reused_out = R;
-  const CachedLayout CL = cached_layout(model, rows, M, n_seq);
-  const ClmLayout& L = CL.T;
-  B2T_REQUIRE(ws_bytes >= CL.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, CL.total);
-  const hipStream_t s = as_stream(stream);
-  const int d = m.d_model, H = m.n_heads, hd = d / H;
-  // what the cache gains: positions R .. n_after - 1 (K | V rows 0.. of qkv, head rows 0.. of logp)
-  const int app_rows = update && P.n_after > R ? P.n_after - R : 0;
-  const int app_logp = update && P.n_after > R + 1 ? P.n_after - R - 1 : 0;
-
-  char* base = static_cast<char*>(ws);
-  ClmTreeIndex ix;
-  if (int rc = clm_build_tree_index(who, ids_host, seq_off_host, n_seq, plan, R, reinterpret_cast<int*>(base + L.ints), s, &ix))
-    return rc;
-  float* logp = reinterpret_cast<float*>(base + L.logp);
-  const CachedAttn ca{ix.d_soff, ix.d_node, ix.d_own, d, H, n_seq, R, rows, trunk_attn_on(),
-                      reinterpret_cast<float*>(base + CL.st_ml), reinterpret_cast<float*>(base + CL.st_o)};
-  _Float16* kv = static_cast<_Float16*>(cache->kv);
-  const size_t slab_elems = (size_t)cache->cap * 2 * d;
-  // a layer's K | V append, then its attention against the layer's slab
-  auto attn = [&](int l, const _Float16* qkv, _Float16* out) -> int {
-    _Float16* slab = kv + (size_t)l * slab_elems;
-    if (app_rows > 0) {
-      const long long pieces = (long long)app_rows * (d / 4);
-      hipLaunchKernelGGL(clm_cache_append_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, qkv,
-                         slab + (size_t)R * 2 * d, d, (long long)app_rows);
-      B2T_CHECK_LAUNCH("clm_cache_append_kernel");
-    }
-    if (hd == 64) return launch_attn<64>(ca, qkv, slab, out, s);
-    if (hd == 80) return launch_attn<80>(ca, qkv, slab, out, s);
-    return launch_attn<128>(ca, qkv, slab, out, s);
-  };
-  // from here on rows >= R of the cache may be overwritten: an error return leaves it at min(n, R)
-  auto forward = [&]() -> int {
-    if (int rc = clm_forward(m, ix.run, L, base, attn, s)) return rc;
-    if (app_logp > 0) {
-      hipLaunchKernelGGL(clm_cache_logp_kernel, dim3((app_logp + 255) / 256), dim3(256), 0, s, logp, cache->logp + R + 1, app_logp);
-      B2T_CHECK_LAUNCH("clm_cache_logp_kernel");
-    }
-    hipLaunchKernelGGL(clm_seq_sum_tree_cached_kernel, dim3(n_seq), dim3(64), 0, s, logp, cache->logp, R, ix.d_soff, ix.d_hrow,
-                       scores_out, tok_logp_out);
-    B2T_CHECK_LAUNCH("clm_seq_sum_tree_cached_kernel");
-    return 0;
-  };
-  if (int rc = forward()) {
-    if (update && cache->n > R) cache->n = R;
-    return rc;
-  }
-  if (update) {
-    for (int t = R; t < P.n_after; ++t) cache->ids_host[t] = ids_host[t];
-    cache->n = P.n_after;
-  }
-  return 0;
+  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_heads, m.d_model / m.n_heads};
+  return clm_score_tree_cached(
+      "b2t_clm_score_tree_cached_f16", "b2t_clm_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq, scores_out,
+      tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
+      [&](long long rows, size_t ints) { return clm_opt_layout(model, rows, rows, ints); },
+      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) { return clm_forward(m, r, L, base, attn, s); });
 }

@@ -1,7 +1,9 @@
 // causal_lm_llama.hip — the scoring forward of causal_lm.hip for the Llama family (HF LlamaForCausalLM, MistralForCausalLM,
 // Qwen2ForCausalLM): RMSNorm, rotary positions, grouped-query attention, a SwiGLU MLP and an LM head of its own, over packed
-// sequences (b2t_clm_llama_score_f16) and over the shared-prefix token tree (b2t_clm_llama_score_tree_f16; the plan is
-// causal_lm_tree.hip's, and a node's rotary position is its depth).
+// sequences (b2t_clm_llama_score_f16), over the shared-prefix token tree (b2t_clm_llama_score_tree_f16; the plan is
+// causal_lm_tree.hip's, and a node's rotary position is its depth) and over that tree behind a context cache
+// (b2t_clm_llama_score_tree_cached_f16; the rule, the kernels and the entry point's body are causal_lm_cache.hip's and
+// clm_internal.h's: K rows are cached after the rotation, at their absolute positions).
 //
 // Numerics contract (what the fp64 restatement of tests/test_clm_llama_host.py rounds):
 //   - weights are fp16; GEMM operands are fp16, accumulation fp32 (v_mfma_f32_32x32x16_f16);
@@ -15,8 +17,9 @@
 //   is bit-identical alone or in any batch, and the tree call is bit-identical to the flat call.
 //
 // Kernels per layer: RMSNorm -> QKV GEMM with the rotation in its epilogue (EP_ROPE, clm_gemm.h) -> causal GQA attention
-// (causal_lm.hip's and causal_lm_tree.hip's kernels through clm_launch_attn / clm_launch_attn_tree: query head h reads K / V
-// head h / (Hq / Hkv); head dim 64 or 128) -> o_proj GEMM into the residual -> RMSNorm -> gate / up GEMM with SwiGLU in
+// (causal_lm.hip's, causal_lm_tree.hip's and causal_lm_cache.hip's kernels through clm_launch_attn / clm_launch_attn_tree /
+// clm_launch_attn_cached: query head h reads K / V head h / (Hq / Hkv); head dim 64 or 128) -> o_proj GEMM into the
+// residual -> RMSNorm -> gate / up GEMM with SwiGLU in
 // its epilogue (EP_SWIGLU; the [M][2F] intermediate never exists) -> down GEMM into the residual.  Then the final RMSNorm of
 // every position but the last of each sequence and causal_lm.hip's fused head (clm_head with W = lm_head) and sums.  The
 // list check, the plan, the index arrays and the workspace layout are the OPT paths' (clm_internal.h).
@@ -92,7 +95,7 @@ int clm_llama_check_model(const b2t_clm_llama_t* m) {
   return 0;
 }
 
-// The forward over r.rows rows up to the per-row log-probs logp[Mh]; attn(qkv, out) enqueues one layer's attention.
+// The forward over r.rows rows up to the per-row log-probs logp[Mh]; attn(layer, qkv, out) enqueues one layer's attention.
 template <class Attn>
 int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s) {
   const int d = m.d_model, Hq = m.n_heads, Hkv = m.n_kv_heads, hd = d / Hq, F = m.ffn_dim, qw = (Hq + 2 * Hkv) * hd;
@@ -118,7 +121,7 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
     g.qscale = 1.0f / sqrtf((float)hd); g.qcols = Hq * hd;
     g.pos = r.d_pos; g.rope_cos = m.rope_cos; g.rope_sin = m.rope_sin; g.rope_cols = (Hq + Hkv) * hd; g.hd = hd;
     if (int rc = launch_gemm(g, s, &clm_gemm_tiles<EP_ROPE>)) return rc;
-    if (int rc = attn(qkv, x16)) return rc;
+    if (int rc = attn(l, qkv, x16)) return rc;
     g = ClmGemm{};
     g.A = x16; g.B = H16(w.o_w); g.M = (int)rows; g.N = d; g.K = d; g.resid = resid; g.ldo = d;
     if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
@@ -162,7 +165,7 @@ extern "C" int b2t_clm_llama_score_f16(const b2t_clm_llama_t* model, const int32
   if (int rc = clm_build_flat_index("b2t_clm_llama_score_f16 upload", ids_host, seq_off_host, n_seq,
                                     reinterpret_cast<int*>(base + L.ints), s, &ix))
     return rc;
-  auto attn = [&](const _Float16* qkv, _Float16* out) {
+  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
     return clm_launch_attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
   if (int rc = llama_forward(m, ix.run, L, base, attn, s)) return rc;
@@ -194,9 +197,35 @@ extern "C" int b2t_clm_llama_score_tree_f16(const b2t_clm_llama_t* model, const 
   if (int rc = clm_build_tree_index("b2t_clm_llama_score_tree_f16 upload", ids_host, seq_off_host, n_seq, plan, 0,
                                     reinterpret_cast<int*>(base + L.ints), s, &ix))
     return rc;
-  auto attn = [&](const _Float16* qkv, _Float16* out) {
+  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
     return clm_launch_attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
   if (int rc = llama_forward(m, ix.run, L, base, attn, s)) return rc;
   return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
+}
+
+extern "C" size_t b2t_clm_llama_cache_kv_bytes(const b2t_clm_llama_t* model, int cap) {
+  if (!llama_dims_ok(model) || cap < 1 || cap > model->max_pos || model->n_layers < 1) return 0;
+  return (size_t)model->n_layers * (size_t)cap * 2 * (size_t)model->n_kv_heads * (size_t)(model->d_model / model->n_heads) *
+         sizeof(_Float16);
+}
+
+extern "C" size_t b2t_clm_llama_tree_cached_ws_bytes(const b2t_clm_llama_t* model, long long n_rows, long long n_tokens, int n_seq) {
+  if (!llama_dims_ok(model) || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
+  const size_t tree = llama_layout(model, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
+  return clm_cached_state(tree, n_rows, model->n_heads, model->d_model).total;
+}
+
+extern "C" int b2t_clm_llama_score_tree_cached_f16(const b2t_clm_llama_t* model, b2t_clm_cache_t* cache, int update,
+                                                   const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                                   float* scores_out, float* tok_logp_out, long long* n_rows_out,
+                                                   int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = clm_llama_check_model(model)) return rc;
+  const b2t_clm_llama_t& m = *model;
+  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads};
+  return clm_score_tree_cached(
+      "b2t_clm_llama_score_tree_cached_f16", "b2t_clm_llama_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq,
+      scores_out, tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
+      [&](long long rows, size_t ints) { return llama_layout(model, rows, rows, ints); },
+      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) { return llama_forward(m, r, L, base, attn, s); });
 }

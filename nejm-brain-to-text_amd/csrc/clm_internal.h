@@ -2,10 +2,11 @@
 // the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
 // list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
 // and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
-// causal_lm_llama.hip (the Llama family, flat and tree) use them.  Both attention launchers serve both families: OPT's row
-// q[d] | k[d] | v[d] is the Llama row q[Hq * D] | k[Hkv * D] | v[Hkv * D] with Hkv = Hq.  The kernels stay private to their
+// causal_lm_llama.hip (the Llama family, flat, tree and cached) use them.  All attention launchers serve both families: OPT's
+// row q[d] | k[d] | v[d] is the Llama row q[Hq * D] | k[Hkv * D] | v[Hkv * D] with Hkv = Hq.  The kernels stay private to their
 // files (their arithmetic is clm_attn.h's, the GEMM's template clm_gemm.h's); these are their launchers, so each is
-// instantiated once.  clm_forward, the OPT layer loop of the flat, tree and cached entry points, is at the end.
+// instantiated once.  clm_forward, the OPT layer loop of the flat, tree and cached entry points, and clm_score_tree_cached, the
+// cached entry point of both families behind their model checks, are at the end.
 #pragma once
 #include <math.h>
 #include <vector>
@@ -182,6 +183,100 @@ int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* b
   if (r.Mh <= 0) return 0;
   if (int rc = clm_launch_layernorm(resid, r.d_src, r.Mh, H16(m.final_ln_w), H16(m.final_ln_b), x16, d, s)) return rc;
   return clm_head(x16, H16(m.embed_tokens), m.vocab, d, r, L, base, s);   // the head is tied to embed_tokens
+}
+
+// ---- the context cache (causal_lm_cache.hip) ----
+// The rule of a cached call (causal_lm_cache.hip's header; b2t_clm_cache_plan_host exports it): trunk Tn, common prefix P with
+// the cached chain, reused R = max(P - 1, 0), n_after = min(Tn, cap).  Family-independent.
+struct ClmCachePlan { int Tn, P, R, n_after; };
+ClmCachePlan clm_cache_plan(const int32_t* cache_ids, int cache_n, int cap, const int32_t* ids, const int32_t* seq_off, int n_seq);
+// the state of stage B behind a tree layout of tree_total bytes: m, l per (row, query head) and the unnormalised o per row
+struct ClmCachedState { size_t st_ml, st_o, total; };
+ClmCachedState clm_cached_state(size_t tree_total, long long rows, int Hq, int d_model);
+// One layer's attention of a cached call on the row q[Hq * hd] | k[Hkv * hd] | v[Hkv * hd]: the append of the trunk's K | V
+// (columns [Hq * hd, (Hq + 2 * Hkv) * hd) of qkv rows 0..app_rows-1 -> slab rows R.., slab row = k[Hkv * hd] | v[Hkv * hd]),
+// stage B over the whole cached blocks (trunk on and R >= 32), then the tree walk.  clm_cached_attn reads B2T_CLM_TRUNK_ATTN.
+struct ClmCachedAttn {
+  const int *soff, *node, *own;
+  int Hq, Hkv, hd, n_seq, R, app_rows;
+  long long rows;
+  bool trunk;
+  float *st_ml, *st_o;
+};
+ClmCachedAttn clm_cached_attn(const ClmTreeIndex& ix, int n_seq, int Hq, int Hkv, int hd, int R, int app_rows, char* base,
+                              const ClmCachedState& S);
+int clm_launch_attn_cached(const ClmCachedAttn& a, const _Float16* qkv, _Float16* slab, _Float16* out, hipStream_t s);
+// dst[i] = logp[i], i < n: the trunk's head rows -> the cache's logp at R + 1
+int clm_launch_cache_logp(const float* logp, float* dst, int n, hipStream_t s);
+// clm_launch_seq_sum_tree with the log-probs of positions 1..R taken from cache_logp
+int clm_launch_seq_sum_tree_cached(const float* logp, const float* cache_logp, int R, const int* seq_off, const int* tok_hrow,
+                                   float* scores, float* tok_logp, int n_seq, hipStream_t s);
+
+// What a family's cached entry point does behind its model check (b2t_clm_score_tree_cached_f16 and
+// b2t_clm_llama_score_tree_cached_f16): the refusals, the plan and the rule, the forward over the computed rows with the
+// cached attention, the appends, the sums and the cache's bookkeeping; `uncached` names the call for callers without a cache.
+// layout(rows, ints) is the family's tree layout; forward(run, L, base, attn, s) its forward, attn(layer, qkv, out) being one
+// layer's attention.  The cache's kv is [n_layers][cap][2 * Hkv * hd].
+struct ClmCacheDims { int vocab, max_pos, Hq, Hkv, hd; };
+template <class Layout, class Forward>
+int clm_score_tree_cached(const char* who, const char* uncached, const ClmCacheDims& m, b2t_clm_cache_t* cache, int update,
+                          const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                          long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes, hipStream_t s, Layout&& layout,
+                          Forward&& forward) {
+  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
+  B2T_REQUIRE(cache, "%s: null cache (callers without one use %s)", who, uncached);
+  B2T_REQUIRE(cache->kv && cache->logp && cache->ids_host, "%s: null cache member", who);
+  B2T_REQUIRE(cache->cap >= 1, "%s: cache cap %d < 1", who, cache->cap);
+  B2T_REQUIRE(cache->cap <= m.max_pos, "%s: cache cap %d above max_pos %d", who, cache->cap, m.max_pos);
+  B2T_REQUIRE(cache->n >= 0 && cache->n <= cache->cap, "%s: cache n %d outside [0, cap %d]", who, cache->n, cache->cap);
+  for (int t = 0; t < cache->n; ++t)
+    B2T_REQUIRE(cache->ids_host[t] >= 0 && cache->ids_host[t] < m.vocab, "%s: cached token %d has id %d outside [0, %d)", who, t,
+                cache->ids_host[t], m.vocab);
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
+  const long long M = seq_off_host[n_seq];
+
+  // the tree plan and the rule; the index arrays are over the computed rows (node n is row n - R)
+  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);
+  const ClmCachePlan P = clm_cache_plan(cache->ids_host, cache->n, cache->cap, ids_host, seq_off_host, n_seq);
+  const int R = P.R;
+  const long long rows = plan.Mn - R;
+  if (n_rows_out) *n_rows_out = rows;
+  if (n_reused_out) *n_reused_out = R;
+  const ClmLayout L = layout(rows, tree_ints(rows, M, n_seq));
+  const ClmCachedState S = clm_cached_state(L.total, rows, m.Hq, m.Hq * m.hd);
+  B2T_REQUIRE(ws_bytes >= S.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, S.total);
+  // what the cache gains: positions R .. n_after - 1 (K | V rows 0.. of qkv, head rows 0.. of logp)
+  const int app_rows = update && P.n_after > R ? P.n_after - R : 0;
+  const int app_logp = update && P.n_after > R + 1 ? P.n_after - R - 1 : 0;
+
+  char* base = static_cast<char*>(ws);
+  ClmTreeIndex ix;
+  if (int rc = clm_build_tree_index(who, ids_host, seq_off_host, n_seq, plan, R, reinterpret_cast<int*>(base + L.ints), s, &ix))
+    return rc;
+  float* logp = reinterpret_cast<float*>(base + L.logp);
+  const ClmCachedAttn ca = clm_cached_attn(ix, n_seq, m.Hq, m.Hkv, m.hd, R, app_rows, base, S);
+  _Float16* kv = static_cast<_Float16*>(cache->kv);
+  const size_t slab_elems = (size_t)cache->cap * 2 * m.Hkv * m.hd;
+  // a layer's K | V append, then its attention against the layer's slab
+  auto attn = [&](int l, const _Float16* qkv, _Float16* out) -> int {
+    return clm_launch_attn_cached(ca, qkv, kv + (size_t)l * slab_elems, out, s);
+  };
+  // from here on rows >= R of the cache may be overwritten: an error return leaves it at min(n, R)
+  auto run = [&]() -> int {
+    if (int rc = forward(ix.run, L, base, attn, s)) return rc;
+    if (app_logp > 0)
+      if (int rc = clm_launch_cache_logp(logp, cache->logp + R + 1, app_logp, s)) return rc;
+    return clm_launch_seq_sum_tree_cached(logp, cache->logp, R, ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
+  };
+  if (int rc = run()) {
+    if (update && cache->n > R) cache->n = R;
+    return rc;
+  }
+  if (update) {
+    for (int t = R; t < P.n_after; ++t) cache->ids_host[t] = ids_host[t];
+    cache->n = P.n_after;
+  }
+  return 0;
 }
 
 }  // namespace b2t

@@ -2,7 +2,7 @@
 :127-162, gpt2_lm_decode :165-251, get_string_differences :273-311, augment_nbest :327-411) with the causal-LM forward on the
 HIP path (b2t_clm_score_f16, csrc/causal_lm.hip; opt-in b2t_clm_score_tree_f16, csrc/causal_lm_tree.hip, which computes the
 prefixes the candidates share once; opt-in b2t_clm_score_tree_cached_f16, csrc/causal_lm_cache.hip, which also keeps the
-decoding context's keys, values and log-probs from one call to the next).
+decoding context's keys, values and log-probs from one call to the next; the Llama family has the same three paths).
 
 Call surfaces are the reference's: `build_opt(model_name, cache_dir, device)` returns `(model, tokenizer)`, and the three
 functions take them as the reference's do.  `model` here is an `OptScorer`: the checkpoint's fp16 weights converted once into
@@ -11,9 +11,10 @@ the device layout of include/b2t.h, scored on packed variable-length token ids (
 `cache_dir`) and refuses what the kernels do not run (post-LN OPT, opt-350m's projection layers, non-ReLU activations).
 
 `build_opt` dispatches on config.json's model_type, as the reference's AutoModelForCausalLM does: "opt" gives an OptScorer;
-"llama", "mistral" and "qwen2" give a `LlamaScorer` (b2t_clm_llama_score_f16 / b2t_clm_llama_score_tree_f16,
-csrc/causal_lm_llama.hip: RMSNorm, rotary positions, grouped-query attention, SwiGLU) with the same `score` /
-`token_logprobs` surface, so the three functions and remote_lm.LocalLMService take either.  The context cache is OPT's only.
+"llama", "mistral" and "qwen2" give a `LlamaScorer` (b2t_clm_llama_score_f16 / b2t_clm_llama_score_tree_f16 /
+b2t_clm_llama_score_tree_cached_f16, csrc/causal_lm_llama.hip: RMSNorm, rotary positions, grouped-query attention, SwiGLU) with
+the same `score` / `token_logprobs` surface and the same opt-in context cache, so the three functions and
+remote_lm.LocalLMService take either.
 """
 from __future__ import annotations
 
@@ -324,16 +325,55 @@ def load_opt_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
 
 
 class _Scorer:
-    """What OptScorer and LlamaScorer share: packing and validating the ids, growing the workspace, the outputs, and the
-    `score` / `token_logprobs` / `eval` surface.  A subclass builds its descriptor (`desc`, with `device`, `share_prefixes`,
-    `last_stats`, `_ws` = None and, where it has one, `_cache`) and supplies `_sizes` and `_score`: its library calls on
-    the path "flat", "tree" or "cached"."""
+    """What OptScorer and LlamaScorer share: packing and validating the ids, growing the workspace, the outputs, the context
+    cache and the `score` / `token_logprobs` / `eval` surface.  A subclass builds its descriptor (`desc`, with `device`,
+    `share_prefixes`, `last_stats` and `_ws` = None), calls `_alloc_cache`, and supplies `_cache_kv_bytes`, `_sizes` and
+    `_score`: its library calls on the path "flat", "tree" or "cached"."""
     _cache = None
     _WS_BYTES = ""    # the family's flat sizing call, for the message of a refused size
     _NO_CACHE = ""    # the ValueError of use_cache=True on a scorer without a context cache
 
     def eval(self):   # the reference calls model.eval(); scoring has no training mode
         return self
+
+    def _cache_kv_bytes(self, lib, cap):
+        """Bytes of the cache's K / V for `cap` positions by the family's library call (0: cap outside [1, max_pos])."""
+        raise NotImplementedError
+
+    def _alloc_cache(self, context_cache_tokens):
+        """context_cache_tokens > 0: the caller-owned b2t_clm_cache_t of that many positions, on the scorer's device."""
+        import torch
+        import b2t_native as N
+        name = type(self).__name__
+        self.context_cache_tokens = int(context_cache_tokens)
+        self._cache = None
+        if self.context_cache_tokens < 0:
+            raise ValueError(f"{name}: context_cache_tokens < 0")
+        if self.context_cache_tokens > 0:
+            cap = self.context_cache_tokens
+            nbytes = self._cache_kv_bytes(N.load(), cap)
+            if nbytes == 0:
+                raise ValueError(f"{name}: context_cache_tokens {cap} outside [1, max_pos {self.dims['max_pos']}]")
+            self._cache_kv = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._cache_logp = torch.empty(cap, dtype=torch.float32, device=self.device)
+            self._cache_ids = np.zeros(cap, np.int32)
+            self._cache = N.ClmCache(self._cache_kv.data_ptr(), self._cache_logp.data_ptr(), self._cache_ids.ctypes.data, cap, 0)
+
+    @property
+    def cache_len(self) -> int:
+        """Positions the context cache holds (0 without a cache)."""
+        return int(self._cache.n) if self._cache is not None else 0
+
+    @property
+    def cache_ids(self) -> np.ndarray:
+        """The cached token chain (a copy)."""
+        return self._cache_ids[:self.cache_len].copy() if self._cache is not None else np.zeros(0, np.int32)
+
+    def cache_reset(self, keep: int = 0) -> None:
+        """Forget the cached context beyond its first `keep` positions (default: all of it).  Never needed for correctness
+        (the cache is matched by token ids)."""
+        if self._cache is not None:
+            self._cache.n = max(0, min(int(keep), int(self._cache.n)))
 
     def _sizes(self, lib, path, ids, off):
         """(rows computed, positions reused, workspace bytes) of a call on `path` for the packed ids / offsets."""
@@ -420,7 +460,6 @@ class OptScorer(_Scorer):
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0):
-        import ctypes as C
         import torch
         import b2t_native as N
         self.dims = dict(dims)
@@ -436,35 +475,11 @@ class OptScorer(_Scorer):
                               self.w["embed_tokens"].data_ptr(), self.w["embed_positions"].data_ptr(),
                               self.w["final_ln_w"].data_ptr(), self.w["final_ln_b"].data_ptr(), self._layers)
         self._ws = None
-        self.context_cache_tokens = int(context_cache_tokens)
-        self._cache = None
-        if self.context_cache_tokens < 0:
-            raise ValueError("OptScorer: context_cache_tokens < 0")
-        if self.context_cache_tokens > 0:
-            cap = self.context_cache_tokens
-            nbytes = N.load().b2t_clm_cache_kv_bytes(C.byref(self.desc), cap)
-            if nbytes == 0:
-                raise ValueError(f"OptScorer: context_cache_tokens {cap} outside [1, max_pos {dims['max_pos']}]")
-            self._cache_kv = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._cache_logp = torch.empty(cap, dtype=torch.float32, device=self.device)
-            self._cache_ids = np.zeros(cap, np.int32)
-            self._cache = N.ClmCache(self._cache_kv.data_ptr(), self._cache_logp.data_ptr(), self._cache_ids.ctypes.data, cap, 0)
+        self._alloc_cache(context_cache_tokens)
 
-    @property
-    def cache_len(self) -> int:
-        """Positions the context cache holds (0 without a cache)."""
-        return int(self._cache.n) if self._cache is not None else 0
-
-    @property
-    def cache_ids(self) -> np.ndarray:
-        """The cached token chain (a copy)."""
-        return self._cache_ids[:self.cache_len].copy() if self._cache is not None else np.zeros(0, np.int32)
-
-    def cache_reset(self, keep: int = 0) -> None:
-        """Forget the cached context beyond its first `keep` positions (default: all of it).  Never needed for correctness
-        (the cache is matched by token ids)."""
-        if self._cache is not None:
-            self._cache.n = max(0, min(int(keep), int(self._cache.n)))
+    def _cache_kv_bytes(self, lib, cap):
+        import ctypes as C
+        return lib.b2t_clm_cache_kv_bytes(C.byref(self.desc), cap)
 
     def _sizes(self, lib, path, ids, off):
         import ctypes as C
@@ -663,23 +678,25 @@ def load_llama_arrays(model_dir: str, max_positions: Optional[int] = None) -> Tu
 class LlamaScorer(_Scorer):
     """A Llama-family decoder on the GPU in the b2t_clm_llama_t layout, with OptScorer's scoring surface: `score` runs
     b2t_clm_llama_score_f16 on packed ids, or, with share_prefixes, b2t_clm_llama_score_tree_f16 over the list's shared-prefix
-    token tree (bit-identical to the flat call); after a call `last_stats` = {"tokens", "nodes": rows computed}.  There is no
-    context cache for this family yet: context_cache_tokens > 0 and use_cache=True raise ValueError."""
+    token tree (bit-identical to the flat call); after a call `last_stats` = {"tokens", "nodes": rows computed}.
+
+    context_cache_tokens > 0 allocates a context cache of that many positions and makes `score` / `token_logprobs` take
+    b2t_clm_llama_score_tree_cached_f16, with OptScorer's `use_cache` / `update_cache` / `cache_len` / `cache_ids` /
+    `cache_reset` and `last_stats` = {"tokens", "nodes", "reused"}.  With grouped-query K / V a position costs n_layers * 4 *
+    n_kv_heads * head_dim bytes: 128 KiB at the Llama-3-8B shape, 256 MiB for 2048.  The cache is GPU memory for kernels that
+    have no CPU path, so on another device context_cache_tokens > 0 raises ValueError."""
 
     _WS_BYTES = "b2t_clm_llama_ws_bytes"
-    _NO_CACHE = "no context cache for Llama-family models"
+    _NO_CACHE = "use_cache=True on a scorer built without a context cache (context_cache_tokens)"
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0):
         import torch
         import b2t_native as N
-        if int(context_cache_tokens) != 0:
-            raise ValueError("LlamaScorer: the context cache (context_cache_tokens > 0) is not available for Llama-family "
-                             "models; use share_prefixes=True")
         self.dims = dict(dims)
         self.device = torch.device(device)
+        self.check_cache_device(self.device, context_cache_tokens)   # before the weights are copied
         self.share_prefixes = bool(share_prefixes)
-        self.context_cache_tokens = 0
         self.last_stats = None
         self.w = {k: v.to(self.device).contiguous() for k, v in arrays.items()}
         if dims.get("tied", False) or arrays["lm_head"] is arrays["embed_tokens"]:
@@ -698,10 +715,26 @@ class LlamaScorer(_Scorer):
                                    self.w["lm_head"].data_ptr(), self.w["final_norm_w"].data_ptr(),
                                    self.w["rope_cos"].data_ptr(), self.w["rope_sin"].data_ptr(), self._layers)
         self._ws = None
+        self._alloc_cache(context_cache_tokens)
+
+    @staticmethod
+    def check_cache_device(device, context_cache_tokens) -> None:
+        """Refuses context_cache_tokens > 0 on a device without GPU memory (the cached kernels have no CPU path)."""
+        import torch
+        if int(context_cache_tokens) > 0 and torch.device(device).type != "cuda":
+            raise ValueError(f"LlamaScorer: the context cache (context_cache_tokens > 0) lives in GPU memory; device "
+                             f"{torch.device(device)} has none")
+
+    def _cache_kv_bytes(self, lib, cap):
+        import ctypes as C
+        return lib.b2t_clm_llama_cache_kv_bytes(C.byref(self.desc), cap)
 
     def _sizes(self, lib, path, ids, off):
         import ctypes as C
         desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
+        if path == "cached":
+            plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
+            return plan["rows"], plan["reused"], lib.b2t_clm_llama_tree_cached_ws_bytes(desc, plan["rows"], M, n_seq)
         if path == "tree":
             nodes = tree_plan(ids, off)[2]
             return nodes, 0, lib.b2t_clm_llama_tree_ws_bytes(desc, nodes, M, n_seq)
@@ -711,7 +744,11 @@ class LlamaScorer(_Scorer):
         import ctypes as C
         import b2t_native as N
         desc = C.byref(self.desc)
-        if path == "tree":
+        if path == "cached":
+            N.check(lib.b2t_clm_llama_score_tree_cached_f16(desc, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq,
+                                                            scores, tok, None, None, ws, ws_bytes, stream),
+                    "b2t_clm_llama_score_tree_cached_f16")
+        elif path == "tree":
             N.check(lib.b2t_clm_llama_score_tree_f16(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream),
                     "b2t_clm_llama_score_tree_f16")
         else:
@@ -759,11 +796,9 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         dims, arrays = load_opt_arrays(model_dir)
         return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens)
     if mt in LLAMA_MODEL_TYPES:
-        if int(context_cache_tokens) != 0:   # before the weights are read
-            raise ValueError(f"context_cache_tokens > 0 is not available for {mt} models (the context cache is OPT's); "
-                             "use share_prefixes=True")
+        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_llama_arrays(model_dir, max_positions)
-        return LlamaScorer(dims, arrays, device, share_prefixes, 0)
+        return LlamaScorer(dims, arrays, device, share_prefixes, context_cache_tokens)
     raise ValueError(f"model_type {mt!r} is not supported (opt, {', '.join(LLAMA_MODEL_TYPES)})")
 
 
@@ -772,7 +807,7 @@ def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", sha
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16).  The scorer is an
     OptScorer, or a LlamaScorer for a Llama / Mistral / Qwen2 directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
-    context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (OptScorer only)."""
+    context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)
     scorer = build_scorer(model_dir, device, share_prefixes, context_cache_tokens, max_positions)
     from transformers import AutoTokenizer

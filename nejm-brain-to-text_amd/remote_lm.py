@@ -39,8 +39,8 @@ class LocalLMService:
     llm: (model, tokenizer) of llm_rescore.build_opt, used when do_opt is set (then required).  Whether the candidates'
     shared prefixes -- the context string in front of every one of them above all -- are computed once is the scorer's own
     setting (build_opt(..., share_prefixes=True) / model.share_prefixes); the service has no parameter for it and its replies
-    are the same either way.  The same holds for the scorer's context cache (build_opt(..., context_cache_tokens=N)): it is
-    matched by token ids, so remote_lm_reset leaves it alone."""
+    are the same either way.  The same holds for the scorer's context cache (build_opt(..., context_cache_tokens=N), for an
+    OPT and for a Llama-family model): it is matched by token ids, so remote_lm_reset leaves it alone."""
 
     def __init__(self, decoder, n_classes: int = 41, acoustic_scale: float = 0.35, blank_penalty: float = 90.0,
                  alpha: float = 0.55, nbest: int = 100, input_stream: str = INPUT_STREAM,

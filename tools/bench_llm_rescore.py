@@ -25,12 +25,13 @@ scores were byte-identical.
 
   python tools/bench_llm_rescore.py --session [--sentences 12] [--reps 5]
 
-`--arch llama` runs the Llama family's path (b2t_clm_llama_score_f16 / b2t_clm_llama_score_tree_f16) at the Llama-3-8B shape
-(32 layers, d 4096, 32 query / 8 kv heads, ffn 14336, vocab 128256, untied head; random fp16 weights, ~16 GB twice) on the
-same lists under the same protocol: without --tree the HIP path against HF's LlamaForCausalLM in fp16 on the same weights
-in this process (padded batch, SDPA), with --tree / --list nbest / --context the flat call against the tree call.
+`--arch llama` runs the Llama family's path (b2t_clm_llama_score_f16 / b2t_clm_llama_score_tree_f16 /
+b2t_clm_llama_score_tree_cached_f16) at the Llama-3-8B shape (32 layers, d 4096, 32 query / 8 kv heads, ffn 14336, vocab
+128256, untied head; random fp16 weights, ~16 GB twice) on the same lists under the same protocol: without --tree the HIP
+path against HF's LlamaForCausalLM in fp16 on the same weights in this process (padded batch, SDPA), with --tree / --list
+nbest / --context the flat call against the tree call, with --session the session comparison above.
 
-  python tools/bench_llm_rescore.py --arch llama [--tree --context 64]
+  python tools/bench_llm_rescore.py --arch llama [--tree --context 64 | --session]
 """
 import argparse
 import json
@@ -95,6 +96,8 @@ def main():
     d, H, ffn, V, L = a.d, a.heads, a.ffn, a.vocab, a.layers
     hd = d // H
     dims = dict(n_layers=L, d_model=d, n_heads=H, ffn_dim=ffn, vocab=V, max_pos=2048)
+    rng = np.random.default_rng(0)
+    calls = session_calls(a, rng, dims["max_pos"]) if a.session else None   # before the model is built
     dev = "cuda"
     rn = lambda *s, std: (torch.randn(*s, device=dev) * std).half()
     st = {"decoder.embed_tokens.weight": rn(V, d, std=2.0 / d ** 0.5), "decoder.embed_positions.weight": rn(2050, d, std=0.5),
@@ -111,9 +114,8 @@ def main():
     lay = R.device_layout({k: v for k, v in st.items()}, dims)   # (host copies; the device copies below are the scorer's)
     sc = R.OptScorer(dims, lay, dev, context_cache_tokens=dims["max_pos"] if a.session else 0)
     del lay
-    rng = np.random.default_rng(0)
     if a.session:
-        return session(a, sc, rng)
+        return session(a, sc, *calls)
     ab = a.tree or a.list != "random" or a.context > 0
     if not ab:
         lists = [random_list(rng, V, a.cands) for _ in range(a.lists)]
@@ -174,13 +176,14 @@ def main_llama(a):
     import torch
     import transformers
     import llm_rescore as R
-    if a.session:
-        raise SystemExit("--session needs the context cache, which the Llama family does not have yet")
     torch.manual_seed(0)
     d, H, Hkv, ffn, V, L = a.d, a.heads, a.kv_heads, a.ffn, a.vocab, a.layers
     dev = "cuda"
+    rng = np.random.default_rng(0)
+    max_pos = 2048
+    calls = session_calls(a, rng, max_pos) if a.session else None   # before the model is built
     cfg = transformers.LlamaConfig(hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, intermediate_size=ffn,
-                                   vocab_size=V, num_hidden_layers=L, max_position_embeddings=2048, rms_norm_eps=1e-5,
+                                   vocab_size=V, num_hidden_layers=L, max_position_embeddings=max_pos, rms_norm_eps=1e-5,
                                    tie_word_embeddings=False, attn_implementation="sdpa",
                                    rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
                                                      original_max_position_embeddings=8192, rope_theta=500000.0))
@@ -198,8 +201,12 @@ def main_llama(a):
                 p.copy_((torch.randn(p.shape, device=dev) * std).half())
     cj = json.loads(cfg.to_json_string())
     dims = R.llama_dims(cj)
-    sc = R.LlamaScorer(dims, R.llama_device_layout(model.state_dict(), dims, R.rope_inv_freq(cj)), dev)
-    rng = np.random.default_rng(0)
+    sc = R.LlamaScorer(dims, R.llama_device_layout(model.state_dict(), dims, R.rope_inv_freq(cj)), dev,
+                       context_cache_tokens=dims["max_pos"] if a.session else 0)
+    if a.session:
+        del model
+        torch.cuda.empty_cache()
+        return session(a, sc, *calls, arch="llama")
     ab = a.tree or a.list != "random" or a.context > 0
     if not ab:
         lists = [random_list(rng, V, a.cands) for _ in range(a.lists)]
@@ -287,17 +294,22 @@ def ab_flat_tree(a, sc, lists, ntok, arch="opt"):
                       "scores_bit_identical": bool(same)}))
 
 
-def session(a, sc, rng):
-    """Tree path against the cached path (stage A, stage A + B) call by call over one conversation; see the module docstring."""
-    import torch
-    ENV = "B2T_CLM_TRUNK_ATTN"
+def session_calls(a, rng, max_pos):
+    """(the lists of the conversation, the context length of each); exits when the conversation outgrows max_pos."""
     calls, ctx_len, ctx = [], [], []
     for _ in range(a.sentences):
         calls.append(nbest_list(rng, a.vocab, a.cands, ctx))
         ctx_len.append(len(ctx))
         ctx = [int(x) for x in calls[-1][0][1:]]   # the context so far + the base sentence of this call
-    if len(ctx) + 1 > sc.dims["max_pos"]:
-        raise SystemExit(f"--sentences {a.sentences}: the conversation outgrows max_pos {sc.dims['max_pos']}")
+    if len(ctx) + 1 > max_pos:
+        raise SystemExit(f"--sentences {a.sentences}: the conversation outgrows max_pos {max_pos}")
+    return calls, ctx_len
+
+
+def session(a, sc, calls, ctx_len, arch="opt"):
+    """Tree path against the cached path (stage A, stage A + B) call by call over one conversation; see the module docstring."""
+    import torch
+    ENV = "B2T_CLM_TRUNK_ATTN"
     paths = ("tree", "cached_a", "cached_ab")
     ms = {p: [[] for _ in calls] for p in paths}
     info, same = [None] * len(calls), True
@@ -331,7 +343,7 @@ def session(a, sc, rng):
         for p in paths:
             info[k][p + "_ms"] = r2(np.median(ms[p][k]))
             info[k][p + "_spread"] = r2(max(ms[p][k]) - min(ms[p][k]))
-    print(json.dumps({"bench": "llm_rescore_session", "layers": a.layers, "d": a.d, "heads": a.heads, "ffn": a.ffn, "vocab": a.vocab,
+    print(json.dumps({"bench": "llm_rescore_session", "arch": arch, "layers": a.layers, "d": a.d, "heads": a.heads, "ffn": a.ffn, "vocab": a.vocab,
                       "cands": a.cands, "sentences": len(calls), "reps": max(1, a.reps), "per_call": info,
                       "scores_bit_identical": bool(same)}))
 
