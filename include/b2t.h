@@ -717,7 +717,7 @@ int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache
  * HF LlamaForCausalLM, MistralForCausalLM and Qwen2ForCausalLM: RMSNorm, rotary positions (rotate-half convention),
  * grouped-query attention, a SwiGLU MLP, no biases but optionally q / k / v's, an LM head that may be untied.  The reference
  * loads its rescoring LLM through AutoModelForCausalLM (language-model-standalone.py:92-123), so these are models its users can
- * name.  Weights are fp16 DEVICE arrays in this layout (nejm-brain-to-text_amd/llm_rescore.py builds it once at load time),
+ * name.  Weights are fp16 DEVICE arrays (bf16 for the two _bf16 calls at the end) in this layout (nejm-brain-to-text_amd/llm_rescore.py builds it once at load time),
  * with hd = d_model / n_heads, Hq = n_heads, Hkv = n_kv_heads, F = ffn_dim:
  *   rows of every nn.Linear weight [N][K] zero-padded to a multiple of 256;
  *   qkv_w rows = q_proj | k_proj | v_proj; for hd == 128 the rows of each q and k head (and their entries of qkv_b) are
@@ -777,6 +777,25 @@ int b2t_clm_llama_score_tree_cached_f16(const b2t_clm_llama_t* model, b2t_clm_ca
                                         const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                         float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
                                         void* ws, size_t ws_bytes, void* stream);
+
+/* The same forward in bfloat16 (csrc/causal_lm_llama_bf16.hip), the format Llama-3, Mistral and Qwen2 are published in.
+ * Argument lists, output layout, refusals before any launch (the error text carries the entry point's own name) and the
+ * bit-identity of tree and flat are those of b2t_clm_llama_score_f16 / b2t_clm_llama_score_tree_f16.  The model is the same
+ * b2t_clm_llama_t: every weight pointer then points at a bf16 DEVICE array in the same layout (rope_cos / rope_sin stay
+ * fp32).  Elements are 2 bytes either way, so the workspace sizes are b2t_clm_llama_ws_bytes / b2t_clm_llama_tree_ws_bytes;
+ * there is no bf16 size function.  B2T_CLM_GEMM_256 applies as to the fp16 calls.
+ * Numerics: the contract above with "fp16" read as "bf16".  bf16 operands (v_mfma_f32_32x32x16_bf16), fp32 accumulation; the
+ * residual stream (the bf16 embedding row widened), RMSNorm statistics, the rotation (the same fp32 table), softmax /
+ * log-softmax and the sums are fp32.  Rounded to bf16, once each, to nearest even: the RMSNorm output; q after bias, rotation
+ * and the factor hd^-0.5; k after bias and rotation; v; the attention's probabilities per 32-key block as the P.V operand; the
+ * attention output; silu(gate) * up from the two fp32 accumulators.  With 8 exponent bits no value of a bf16 checkpoint
+ * overflows or goes subnormal, as it can in the fp16 calls; the price is 3 bits of mantissa (log-prob errors about 10 x the
+ * fp16 calls').  There is no cached bf16 call yet. */
+int b2t_clm_llama_score_bf16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                             float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_llama_score_tree_bf16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                  float* scores_out, float* tok_logp_out, long long* n_nodes_out,
+                                  void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -245,6 +245,9 @@ _SIGNATURES = {
     "b2t_clm_llama_tree_ws_bytes": (C.c_size_t, [C.POINTER(ClmLlamaDesc), LL, LL, C.c_int]),
     "b2t_clm_llama_score_tree_f16": (C.c_int, [C.POINTER(ClmLlamaDesc), VP, VP, C.c_int, VP, VP, C.POINTER(LL), VP, C.c_size_t,
                                                VP]),
+    "b2t_clm_llama_score_bf16": (C.c_int, [C.POINTER(ClmLlamaDesc), VP, VP, C.c_int, VP, VP, VP, C.c_size_t, VP]),
+    "b2t_clm_llama_score_tree_bf16": (C.c_int, [C.POINTER(ClmLlamaDesc), VP, VP, C.c_int, VP, VP, C.POINTER(LL), VP, C.c_size_t,
+                                                VP]),
     "b2t_clm_llama_cache_kv_bytes": (C.c_size_t, [C.POINTER(ClmLlamaDesc), C.c_int]),
     "b2t_clm_llama_tree_cached_ws_bytes": (C.c_size_t, [C.POINTER(ClmLlamaDesc), LL, LL, C.c_int]),
     "b2t_clm_llama_score_tree_cached_f16": (C.c_int, [C.POINTER(ClmLlamaDesc), C.POINTER(ClmCache), C.c_int, VP, VP, C.c_int,

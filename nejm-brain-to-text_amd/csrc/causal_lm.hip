@@ -27,7 +27,8 @@
 // the embed / LayerNorm / attention / head launchers, clm_check_model, the list check, the workspace layout and the flat
 // index builder -- have external linkage and are declared in clm_internal.h, which also holds the layer loop (clm_forward).
 // The kernels stay private to this file: the GEMM's template is clm_gemm.h, instantiated here for the four epilogues of this
-// forward; the attention's arithmetic is clm_attn.h's, and clm_attn_kernel serves the Llama family's row layout too.
+// forward; the attention's arithmetic and clm_attn_kernel itself are clm_attn.h's templates (instantiated here in fp16 for
+// head dims 64, 80 and 128, behind clm_launch_attn), and the kernel serves the Llama family's row layout too.
 #include <math.h>
 #include <vector>
 
@@ -94,35 +95,6 @@ __global__ __launch_bounds__(256) void clm_layernorm_kernel(const float* x, cons
   for (int c = threadIdx.x; c < d; c += 256) { const float q = xr[c] - mean; v += q * q; }
   const float rstd = 1.0f / sqrtf(block_sum256(v, red) / d + 1e-5f);
   for (int c = threadIdx.x; c < d; c += 256) o[c] = (_Float16)((xr[c] - mean) * rstd * (float)w[c] + (float)b[c]);
-}
-
-// Causal attention, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query rows at a time and runs the key
-// blocks up to the diagonal through attn_block (clm_attn.h), V gathered from global memory.  The row is q[Hq * D] |
-// k[Hkv * D] | v[Hkv * D]; query head h reads K / V head h / (Hq / Hkv) (OPT: Hkv = Hq).
-template <int D>
-__global__ __launch_bounds__(256) void clm_attn_kernel(const _Float16* qkv, _Float16* out, const int* seq_off, int Hq, int Hkv) {
-  const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
-  const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
-  const long long RS = (long long)(Hq + 2 * Hkv) * D;
-  const _Float16* Qb = qkv + (long long)t0 * RS + h * D;
-  const _Float16* Kb = qkv + (long long)t0 * RS + (Hq + hk) * D;
-  const _Float16* Vb = Kb + Hkv * D;
-  const int nqb = (L + 31) / 32;
-  for (int qb = wave; qb < nqb; qb += 4) {
-    const int q = qb * 32 + li;
-    half8 qf[AttnDims<D>::KS];
-    load_q<D>(Qb + (long long)min(q, L - 1) * RS + 8 * hh, qf);
-    float m, l;
-    f32x16 o[AttnDims<D>::NF];
-    attn_zero<D>(m, l, o);
-    for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
-      const int k0 = kb * 32;
-      const _Float16* kp = Kb + (long long)min(k0 + li, L - 1) * RS + 8 * hh;
-      attn_block<D, true>(kp, qf, VGather{Vb, RS, k0, L}, k0, q, L, li, hh, m, l, o);
-    }
-    if (q < L) attn_store<D>(out + ((long long)(t0 + q) * Hq + h) * D, o, l, hh);
-  }
 }
 
 // logp[r] = tlogit[r] - logsumexp over the row's 64-column groups

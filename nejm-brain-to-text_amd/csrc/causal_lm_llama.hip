@@ -26,50 +26,38 @@
 // The two weight layouts the epilogues rely on are made at load time (llm_rescore.py): gate / up rows interleaved in blocks
 // of 32, and for head dim 128 the q / k rows of each head in the order [0..31, 64..95, 32..63, 96..127] (q . k is invariant
 // under one permutation of both; V and o_proj are untouched).
-#include <math.h>
-#include <vector>
-
-#include "clm_gemm.h"
+//
+// The forward (llama_forward), the bodies of the flat and the tree entry point and the embed / RMSNorm kernels are templates in
+// clm_llama.h, on a per-element-type policy; this unit holds the fp16 policy (LlamaF16: the two GEMM launches of this family
+// through the one tile rule, the OPT paths' residual / head GEMMs and attention launchers) and the model check.  The same
+// forward in bf16 is causal_lm_llama_bf16.hip.
+#include "clm_llama.h"
 
 namespace b2t {
 namespace {
 
-// resid[t] = embed_tokens[id[t]] (fp32)
-__global__ __launch_bounds__(256) void clm_llama_embed_kernel(const int* ids, const _Float16* et, float* resid, int d) {
-  const int t = blockIdx.x;
-  const _Float16* a = et + (long long)ids[t] * d;
-  float* o = resid + (long long)t * d;
-  for (int c = threadIdx.x; c < d; c += 256) o[c] = (float)a[c];
-}
-
-// out[r] = fp16(RMSNorm(x[rowmap ? rowmap[r] : r])) for r < rows; zeros for rows <= r < gridDim.x (the operand's padding)
-__global__ __launch_bounds__(256) void clm_llama_rmsnorm_kernel(const float* x, const int* rowmap, int rows, const _Float16* w,
-                                                                float eps, _Float16* out, int d) {
-  __shared__ float red[4];
-  const int r = blockIdx.x;
-  _Float16* o = out + (long long)r * d;
-  if (r >= rows) {
-    for (int c = threadIdx.x; c < d; c += 256) o[c] = (_Float16)0.f;
-    return;
+// The fp16 policy of the forward (clm_llama.h): the attention kernels are causal_lm.hip's and causal_lm_tree.hip's.
+struct LlamaF16 : LlamaOps<_Float16> {
+  static int gemm_rope(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_ROPE>); }
+  static int gemm_swiglu(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_SWIGLU>); }
+  static int gemm_resid(const ClmGemm& g, hipStream_t s) { return launch_gemm<EP_RESID>(g, s); }
+  static int gemm_head(const ClmGemm& g, hipStream_t s) { return launch_gemm<EP_HEAD>(g, s); }
+  static int attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
+    return clm_launch_attn(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
   }
-  const float* xr = x + (long long)(rowmap ? rowmap[r] : r) * d;
-  float v = 0.f;
-  for (int c = threadIdx.x; c < d; c += 256) v += xr[c] * xr[c];
-  const float rstd = 1.0f / sqrtf(block_sum256(v, red) / d + eps);
-  for (int c = threadIdx.x; c < d; c += 256) o[c] = (_Float16)(xr[c] * rstd * (float)w[c]);
-}
+  static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
+                       int Hkv, int hd, hipStream_t s) {
+    return clm_launch_attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
+  }
+};
 
-// Workspace of a forward over `rows` rows with `hrows` head rows and `ints` index entries
-ClmLayout llama_layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints) {
-  const long long qw = (long long)(m->n_heads + 2 * m->n_kv_heads) * (m->d_model / m->n_heads);
-  return clm_layout(m->d_model, qw, m->ffn_dim, m->vocab, rows, hrows, ints);
-}
-
-// dimensions a descriptor must have for the sizes above to mean anything (the full check is clm_llama_check_model)
+// dimensions a descriptor must have for the sizes of llama_layout (clm_llama.h) to mean anything (the full check is clm_llama_check_model)
 bool llama_dims_ok(const b2t_clm_llama_t* m) {
   return m && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
          m->d_model % m->n_heads == 0;
 }
+
+}  // namespace
 
 int clm_llama_check_model(const b2t_clm_llama_t* m) {
   B2T_REQUIRE(m, "b2t_clm_llama: null model");
@@ -95,50 +83,6 @@ int clm_llama_check_model(const b2t_clm_llama_t* m) {
   return 0;
 }
 
-// The forward over r.rows rows up to the per-row log-probs logp[Mh]; attn(layer, qkv, out) enqueues one layer's attention.
-template <class Attn>
-int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s) {
-  const int d = m.d_model, Hq = m.n_heads, Hkv = m.n_kv_heads, hd = d / Hq, F = m.ffn_dim, qw = (Hq + 2 * Hkv) * hd;
-  const long long rows = r.rows;
-  float* resid = reinterpret_cast<float*>(base + L.resid);
-  _Float16* x16 = reinterpret_cast<_Float16*>(base + L.x16);
-  _Float16* qkv = reinterpret_cast<_Float16*>(base + L.qkv);
-  _Float16* hb = reinterpret_cast<_Float16*>(base + L.hbuf);
-  auto H16 = [](const void* p) { return static_cast<const _Float16*>(p); };
-  auto rmsnorm = [&](const int* rowmap, long long n, const void* w) {
-    hipLaunchKernelGGL(clm_llama_rmsnorm_kernel, dim3((unsigned)rup(n, ROWPAD)), dim3(256), 0, s, resid, rowmap, (int)n, H16(w),
-                       m.rms_eps, x16, d);
-    B2T_CHECK_LAUNCH("clm_llama_rmsnorm_kernel");
-    return 0;
-  };
-  hipLaunchKernelGGL(clm_llama_embed_kernel, dim3((unsigned)rows), dim3(256), 0, s, r.d_ids, H16(m.embed_tokens), resid, d);
-  B2T_CHECK_LAUNCH("clm_llama_embed_kernel");
-  for (int l = 0; l < m.n_layers; ++l) {
-    const b2t_clm_llama_layer_t& w = m.layers_host[l];
-    if (int rc = rmsnorm(nullptr, rows, w.norm1_w)) return rc;
-    ClmGemm g{};
-    g.A = x16; g.B = H16(w.qkv_w); g.M = (int)rows; g.N = qw; g.K = d; g.bias = H16(w.qkv_b); g.out16 = qkv; g.ldo = qw;
-    g.qscale = 1.0f / sqrtf((float)hd); g.qcols = Hq * hd;
-    g.pos = r.d_pos; g.rope_cos = m.rope_cos; g.rope_sin = m.rope_sin; g.rope_cols = (Hq + Hkv) * hd; g.hd = hd;
-    if (int rc = launch_gemm(g, s, &clm_gemm_tiles<EP_ROPE>)) return rc;
-    if (int rc = attn(l, qkv, x16)) return rc;
-    g = ClmGemm{};
-    g.A = x16; g.B = H16(w.o_w); g.M = (int)rows; g.N = d; g.K = d; g.resid = resid; g.ldo = d;
-    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
-    if (int rc = rmsnorm(nullptr, rows, w.norm2_w)) return rc;
-    g = ClmGemm{};
-    g.A = x16; g.B = H16(w.gate_up_w); g.M = (int)rows; g.N = 2 * F; g.K = d; g.out16 = hb; g.ldo = F;
-    if (int rc = launch_gemm(g, s, &clm_gemm_tiles<EP_SWIGLU>)) return rc;
-    g = ClmGemm{};
-    g.A = hb; g.B = H16(w.down_w); g.M = (int)rows; g.N = d; g.K = F; g.resid = resid; g.ldo = d;
-    if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
-  }
-  if (r.Mh <= 0) return 0;
-  if (int rc = rmsnorm(r.d_src, r.Mh, m.final_norm_w)) return rc;
-  return clm_head(x16, H16(m.lm_head), m.vocab, d, r, L, base, s);
-}
-
-}  // namespace
 }  // namespace b2t
 
 using namespace b2t;
@@ -151,25 +95,8 @@ extern "C" size_t b2t_clm_llama_ws_bytes(const b2t_clm_llama_t* model, long long
 extern "C" int b2t_clm_llama_score_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                        int n_seq, float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes,
                                        void* stream) {
-  const char* who = "b2t_clm_llama_score_f16";
-  if (int rc = clm_llama_check_model(model)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  const ClmLayout L = llama_layout(model, M, M - n_seq, flat_ints(M, n_seq));
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  const hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  ClmFlatIndex ix;
-  if (int rc = clm_build_flat_index("b2t_clm_llama_score_f16 upload", ids_host, seq_off_host, n_seq,
-                                    reinterpret_cast<int*>(base + L.ints), s, &ix))
-    return rc;
-  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
-    return clm_launch_attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
-  };
-  if (int rc = llama_forward(m, ix.run, L, base, attn, s)) return rc;
-  return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
+  return llama_score<LlamaF16>("b2t_clm_llama_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws,
+                               ws_bytes, stream);
 }
 
 extern "C" size_t b2t_clm_llama_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq) {
@@ -180,28 +107,8 @@ extern "C" size_t b2t_clm_llama_tree_ws_bytes(const b2t_clm_llama_t* model, long
 extern "C" int b2t_clm_llama_score_tree_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                             int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws,
                                             size_t ws_bytes, void* stream) {
-  const char* who = "b2t_clm_llama_score_tree_f16";
-  if (int rc = clm_llama_check_model(model)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);   // a node's rotary position is its depth, node_pos
-  const long long Mn = plan.Mn;
-  if (n_nodes_out) *n_nodes_out = Mn;
-  const ClmLayout L = llama_layout(model, Mn, Mn, tree_ints(Mn, M, n_seq));
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  const hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  ClmTreeIndex ix;
-  if (int rc = clm_build_tree_index("b2t_clm_llama_score_tree_f16 upload", ids_host, seq_off_host, n_seq, plan, 0,
-                                    reinterpret_cast<int*>(base + L.ints), s, &ix))
-    return rc;
-  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
-    return clm_launch_attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
-  };
-  if (int rc = llama_forward(m, ix.run, L, base, attn, s)) return rc;
-  return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
+  return llama_score_tree<LlamaF16>("b2t_clm_llama_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                    tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
 }
 
 extern "C" size_t b2t_clm_llama_cache_kv_bytes(const b2t_clm_llama_t* model, int cap) {
@@ -227,5 +134,5 @@ extern "C" int b2t_clm_llama_score_tree_cached_f16(const b2t_clm_llama_t* model,
       "b2t_clm_llama_score_tree_cached_f16", "b2t_clm_llama_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq,
       scores_out, tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
       [&](long long rows, size_t ints) { return llama_layout(model, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) { return llama_forward(m, r, L, base, attn, s); });
+      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) { return llama_forward<LlamaF16>(m, r, L, base, attn, s); });
 }

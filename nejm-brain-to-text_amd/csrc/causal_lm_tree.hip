@@ -31,46 +31,7 @@
 namespace b2t {
 namespace {
 
-// Causal attention over tree paths, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query positions at a
-// time, starting with the 32-aligned block that holds the sequence's first owned position.  Position i of the sequence is row
-// path[i] = tok_node[seq_off[s] + i] of qkv: K and V are gathered for all positions 0..q, Q is read and the output row is
-// written only for owned positions (fact (a) of the file header).  The arithmetic per query is clm_attn_kernel's: the same
-// attn_block (clm_attn.h) over the same key blocks, on the same row layout q[Hq * D] | k[Hkv * D] | v[Hkv * D].
-// The gather: a lane holds the row of key k0 + (lane & 31) and reads K from it as 16-byte pieces; V's 32 x D block is staged
-// as whole 16-byte row pieces into the wave's own LDS slab and read back transposed, rows of keys beyond the path zeroed.
-// The slab is private to the wave, so the key loop needs no workgroup barrier.
-template <int D>
-__global__ __launch_bounds__(256) void clm_attn_tree_kernel(const _Float16* qkv, _Float16* out, const int* seq_off,
-                                                            const int* tok_node, const int* own_start, int Hq, int Hkv) {
-  __shared__ __attribute__((aligned(16))) _Float16 vslab[4][32 * AttnDims<D>::VP];
-  const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
-  const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, own = own_start[sq];
-  if (own >= L) return;   // every node of this path is owned by an earlier sequence
-  const int* path = tok_node + t0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
-  const long long RS = (long long)(Hq + 2 * Hkv) * D;
-  const _Float16* Qb = qkv + h * D;
-  const _Float16* Kb = qkv + (Hq + hk) * D;
-  const _Float16* Vb = Kb + Hkv * D;
-  _Float16* vs = vslab[wave];
-  const int nqb = (L + 31) / 32;
-  for (int qb = own / 32 + wave; qb < nqb; qb += 4) {
-    const int q = qb * 32 + li;
-    const int qrow = path[min(q, L - 1)];
-    half8 qf[AttnDims<D>::KS];
-    load_q<D>(Qb + (long long)qrow * RS + 8 * hh, qf);
-    float m, l;
-    f32x16 o[AttnDims<D>::NF];
-    attn_zero<D>(m, l, o);
-    for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
-      const int k0 = kb * 32;
-      const int krow = path[min(k0 + li, L - 1)];
-      stage_v<D>(vs, lane, L - k0, [&](int key) { return Vb + (long long)__shfl(krow, key) * RS; });
-      attn_block<D, true>(Kb + (long long)krow * RS + 8 * hh, qf, VSlab<D>{vs}, k0, q, L, li, hh, m, l, o);
-    }
-    if (q >= own && q < L) attn_store<D>(out + ((long long)qrow * Hq + h) * D, o, l, hh);
-  }
-}
+// The attention kernel, clm_attn_tree_kernel, is clm_attn.h's template; this unit instantiates it in fp16 (clm_launch_attn_tree).
 
 // scores[s] = sum of the log-probs along the sequence's path in token order (one thread, as clm_seq_sum_kernel);
 // tok_hrow[t] = the head row of token t's node (unused at a sequence's first token); tok_logp (optional) = per token in the

@@ -1,9 +1,11 @@
 // clm_attn.h — the attention arithmetic of the causal-LM forward, written once (device code, internal linkage).  Every
-// attention kernel -- clm_attn_kernel (causal_lm.hip), clm_attn_tree_kernel (causal_lm_tree.hip), clm_attn_tree_cached_kernel
-// and clm_attn_trunk_kernel (causal_lm_cache.hip) -- walks its own rows and calls attn_block per 32-key block, so a query
-// meets the same operands in the same order on every path: that is what keeps the paths bit-identical.
+// attention kernel -- clm_attn_kernel and clm_attn_tree_kernel (at the end of this file; launched by causal_lm.hip,
+// causal_lm_tree.hip and, in bf16, causal_lm_llama_bf16.hip), clm_attn_tree_cached_kernel and clm_attn_trunk_kernel
+// (causal_lm_cache.hip) -- walks its own rows and calls attn_block per 32-key block, so a query meets the same operands in
+// the same order on every path: that is what keeps the paths bit-identical.  The element type E (ClmElem, clm_internal.h)
+// is deduced from the pointers: _Float16 everywhere but in the bf16 unit.
 //
-// The score tile is computed transposed, S^T = K . Q^T (v_mfma_f32_32x32x16_f16: A = 32 keys, B = 32 queries), so a lane owns
+// The score tile is computed transposed, S^T = K . Q^T (v_mfma_f32_32x32x16_f16 / _bf16: A = 32 keys, B = 32 queries), so a lane owns
 // one query column: its online-softmax state (m, l) is per lane and the row reductions are in-lane plus one swap of the lane
 // halves.  P^T is then the B operand of O^T = V^T . P^T with no data movement (registers 8s..8s+7 of the accumulator are
 // k-step s, keys in the order 16s + 8(j >> 2) + 4h + (j & 3)), and O^T's rescale by exp(m_old - m_new) is per lane too.
@@ -17,9 +19,8 @@
 namespace b2t {
 namespace {
 
-using f32x16 = float __attribute__((ext_vector_type(16)));
 using f32x4 = float __attribute__((ext_vector_type(4)));
-using half8 = _Float16 __attribute__((ext_vector_type(8)));
+using half8 = ClmElem<_Float16>::v8;
 
 template <int D>
 struct AttnDims {
@@ -30,49 +31,51 @@ struct AttnDims {
 
 // Where the V operand of a key block comes from.  at(key, dim): V[key of the block][dim] (key < 32).
 // Global gather (the flat kernel): row k0 + key of Vb at pitch RS, zero beyond the sequence's L rows; nothing to wait for.
+template <class E>
 struct VGather {
-  const _Float16* Vb; long long RS; int k0, L;
+  const E* Vb; long long RS; int k0, L;
   __device__ __forceinline__ void ready() const {}
-  __device__ __forceinline__ _Float16 at(int key, int dim) const {
-    return k0 + key < L ? Vb[(long long)(k0 + key) * RS + dim] : (_Float16)0.f;
+  __device__ __forceinline__ E at(int key, int dim) const {
+    return k0 + key < L ? Vb[(long long)(k0 + key) * RS + dim] : (E)0.f;
   }
 };
 // The wave's own LDS slab (the tree, cached and trunk kernels), staged by stage_v: row pitch VP = D + 8, so that the two lane
 // halves, 4 keys apart, fall on disjoint banks.  The slab is private to the wave: a wave barrier orders its writes and reads.
-template <int D>
+template <int D, class E = _Float16>
 struct VSlab {
-  const _Float16* vs;
+  const E* vs;
   __device__ __forceinline__ void ready() const {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();   // the slab is written
   }
-  __device__ __forceinline__ _Float16 at(int key, int dim) const { return vs[key * AttnDims<D>::VP + dim]; }
+  __device__ __forceinline__ E at(int key, int dim) const { return vs[key * AttnDims<D>::VP + dim]; }
 };
 
 // Stage a 32 x D V block into the slab as whole 16-byte row pieces: piece p = 64 * it + lane is columns 8c .. 8c + 7 of block
 // key p / PCS, whose V row is vrow(key); the rows of keys >= nvalid are zeroed (not read).
-template <int D, class VRow>
-__device__ __forceinline__ void stage_v(_Float16* vs, int lane, int nvalid, VRow&& vrow) {
+template <int D, class E, class VRow>
+__device__ __forceinline__ void stage_v(E* vs, int lane, int nvalid, VRow&& vrow) {
   using A = AttnDims<D>;
+  using vec8 = typename ClmElem<E>::v8;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();   // the previous block's reads of the slab are done
 #pragma unroll
   for (int it = 0; it < A::NIT; ++it) {
     const int p = 64 * it + lane, key = p / A::PCS, c = p % A::PCS;
-    const _Float16* row = vrow(key);
-    half8 v;
+    const E* row = vrow(key);
+    vec8 v;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (_Float16)0.f;
-    if (key < nvalid) v = *reinterpret_cast<const half8*>(row + 8 * c);
-    *reinterpret_cast<half8*>(vs + key * A::VP + 8 * c) = v;
+    for (int j = 0; j < 8; ++j) v[j] = (E)0.f;
+    if (key < nvalid) v = *reinterpret_cast<const vec8*>(row + 8 * c);
+    *reinterpret_cast<vec8*>(vs + key * A::VP + 8 * c) = v;
   }
 }
 
 // the lane's Q fragment: qp = the query row's head + 8 * hh
-template <int D>
-__device__ __forceinline__ void load_q(const _Float16* qp, half8* qf) {
+template <int D, class E>
+__device__ __forceinline__ void load_q(const E* qp, typename ClmElem<E>::v8* qf) {
 #pragma unroll
-  for (int ks = 0; ks < AttnDims<D>::KS; ++ks) qf[ks] = *reinterpret_cast<const half8*>(qp + 16 * ks);
+  for (int ks = 0; ks < AttnDims<D>::KS; ++ks) qf[ks] = *reinterpret_cast<const typename ClmElem<E>::v8*>(qp + 16 * ks);
 }
 
 template <int D>
@@ -85,18 +88,19 @@ __device__ __forceinline__ void attn_zero(float& m, float& l, f32x16* o) {
 }
 
 // One key block of the online softmax: S^T = K . Q^T from the lane's key row kp (+ 8 * hh), the mask (keys beyond the query q
-// or the L keys; MASK false = no key of the block can be either), the per-lane state update, P rounded to fp16,
+// or the L keys; MASK false = no key of the block can be either), the per-lane state update, P rounded to the element type,
 // O^T += V^T . P^T with V from `v`.
-template <int D, bool MASK, class VSrc>
-__device__ __forceinline__ void attn_block(const _Float16* kp, const half8* qf, const VSrc& v, int k0, int q, int L, int li,
-                                           int hh, float& m, float& l, f32x16* o) {
+template <int D, bool MASK, class E, class VSrc>
+__device__ __forceinline__ void attn_block(const E* kp, const typename ClmElem<E>::v8* qf, const VSrc& v, int k0, int q, int L,
+                                           int li, int hh, float& m, float& l, f32x16* o) {
   using A = AttnDims<D>;
+  using vec8 = typename ClmElem<E>::v8;
   f32x16 sacc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
 #pragma unroll
   for (int ks = 0; ks < A::KS; ++ks)
-    sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(kp + 16 * ks), qf[ks], sacc, 0, 0, 0);
+    sacc = ClmElem<E>::mfma(*reinterpret_cast<const vec8*>(kp + 16 * ks), qf[ks], sacc);
   float mx = -INFINITY;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
@@ -115,11 +119,11 @@ __device__ __forceinline__ void attn_block(const _Float16* kp, const half8* qf, 
   ps += __shfl_xor(ps, 32);
   l = l * alpha + ps;
   m = mnew;
-  half8 pb[2];
+  vec8 pb[2];
 #pragma unroll
   for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) pb[s2][j] = (_Float16)sacc[8 * s2 + j];
+    for (int j = 0; j < 8; ++j) pb[s2][j] = (E)sacc[8 * s2 + j];
   v.ready();
 #pragma unroll
   for (int f = 0; f < A::NF; ++f) {
@@ -128,28 +132,103 @@ __device__ __forceinline__ void attn_block(const _Float16* kp, const half8* qf, 
     const int dim = 32 * f + li;
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
-      half8 va;
+      vec8 va;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int key = 16 * s2 + 8 * (j >> 2) + 4 * hh + (j & 3);
-        va[j] = !A::GUARD || dim < D ? v.at(key, dim) : (_Float16)0.f;
+        va[j] = !A::GUARD || dim < D ? v.at(key, dim) : (E)0.f;
       }
-      o[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb[s2], o[f], 0, 0, 0);
+      o[f] = ClmElem<E>::mfma(va, pb[s2], o[f]);
     }
   }
 }
 
 // the lane's query row of the output, o * (1 / l) in the C / D layout: op = the output row's head
-template <int D>
-__device__ __forceinline__ void attn_store(_Float16* op, const f32x16* o, float l, int hh) {
+template <int D, class E>
+__device__ __forceinline__ void attn_store(E* op, const f32x16* o, float l, int hh) {
   const float inv = 1.0f / l;
 #pragma unroll
   for (int f = 0; f < AttnDims<D>::NF; ++f)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int dim = 32 * f + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      if (!AttnDims<D>::GUARD || dim < D) op[dim] = (_Float16)(o[f][e] * inv);
+      if (!AttnDims<D>::GUARD || dim < D) op[dim] = (E)(o[f][e] * inv);
     }
+}
+
+// ---- the flat and the tree kernel ----
+// Templates on the head dim and the element type; a unit instantiates what it launches: causal_lm.hip the flat kernel and
+// causal_lm_tree.hip the tree kernel in fp16 (head dims 64, 80 and 128, behind clm_launch_attn / clm_launch_attn_tree),
+// causal_lm_llama_bf16.hip both in bf16 (64 and 128).
+
+// Causal attention, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query rows at a time and runs the key
+// blocks up to the diagonal through attn_block, V gathered from global memory.  The row is q[Hq * D] | k[Hkv * D] |
+// v[Hkv * D]; query head h reads K / V head h / (Hq / Hkv) (OPT: Hkv = Hq).
+template <int D, class E = _Float16>
+__global__ __launch_bounds__(256) void clm_attn_kernel(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv) {
+  const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
+  const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
+  const long long RS = (long long)(Hq + 2 * Hkv) * D;
+  const E* Qb = qkv + (long long)t0 * RS + h * D;
+  const E* Kb = qkv + (long long)t0 * RS + (Hq + hk) * D;
+  const E* Vb = Kb + Hkv * D;
+  const int nqb = (L + 31) / 32;
+  for (int qb = wave; qb < nqb; qb += 4) {
+    const int q = qb * 32 + li;
+    typename ClmElem<E>::v8 qf[AttnDims<D>::KS];
+    load_q<D>(Qb + (long long)min(q, L - 1) * RS + 8 * hh, qf);
+    float m, l;
+    f32x16 o[AttnDims<D>::NF];
+    attn_zero<D>(m, l, o);
+    for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
+      const int k0 = kb * 32;
+      const E* kp = Kb + (long long)min(k0 + li, L - 1) * RS + 8 * hh;
+      attn_block<D, true>(kp, qf, VGather<E>{Vb, RS, k0, L}, k0, q, L, li, hh, m, l, o);
+    }
+    if (q < L) attn_store<D>(out + ((long long)(t0 + q) * Hq + h) * D, o, l, hh);
+  }
+}
+
+// Causal attention over tree paths, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query positions at a
+// time, starting with the 32-aligned block that holds the sequence's first owned position.  Position i of the sequence is row
+// path[i] = tok_node[seq_off[s] + i] of qkv: K and V are gathered for all positions 0..q, Q is read and the output row is
+// written only for owned positions (fact (a) of causal_lm_tree.hip's header).  The arithmetic per query is clm_attn_kernel's:
+// the same attn_block over the same key blocks, on the same row layout q[Hq * D] | k[Hkv * D] | v[Hkv * D].
+// The gather: a lane holds the row of key k0 + (lane & 31) and reads K from it as 16-byte pieces; V's 32 x D block is staged
+// as whole 16-byte row pieces into the wave's own LDS slab and read back transposed, rows of keys beyond the path zeroed.
+// The slab is private to the wave, so the key loop needs no workgroup barrier.
+template <int D, class E = _Float16>
+__global__ __launch_bounds__(256) void clm_attn_tree_kernel(const E* qkv, E* out, const int* seq_off, const int* tok_node,
+                                                            const int* own_start, int Hq, int Hkv) {
+  __shared__ __attribute__((aligned(16))) E vslab[4][32 * AttnDims<D>::VP];
+  const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
+  const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, own = own_start[sq];
+  if (own >= L) return;   // every node of this path is owned by an earlier sequence
+  const int* path = tok_node + t0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
+  const long long RS = (long long)(Hq + 2 * Hkv) * D;
+  const E* Qb = qkv + h * D;
+  const E* Kb = qkv + (Hq + hk) * D;
+  const E* Vb = Kb + Hkv * D;
+  E* vs = vslab[wave];
+  const int nqb = (L + 31) / 32;
+  for (int qb = own / 32 + wave; qb < nqb; qb += 4) {
+    const int q = qb * 32 + li;
+    const int qrow = path[min(q, L - 1)];
+    typename ClmElem<E>::v8 qf[AttnDims<D>::KS];
+    load_q<D>(Qb + (long long)qrow * RS + 8 * hh, qf);
+    float m, l;
+    f32x16 o[AttnDims<D>::NF];
+    attn_zero<D>(m, l, o);
+    for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
+      const int k0 = kb * 32;
+      const int krow = path[min(k0 + li, L - 1)];
+      stage_v<D>(vs, lane, L - k0, [&](int key) { return Vb + (long long)__shfl(krow, key) * RS; });
+      attn_block<D, true>(Kb + (long long)krow * RS + 8 * hh, qf, VSlab<D, E>{vs}, k0, q, L, li, hh, m, l, o);
+    }
+    if (q >= own && q < L) attn_store<D>(out + ((long long)qrow * Hq + h) * D, o, l, hh);
+  }
 }
 
 }  // namespace

@@ -1,8 +1,11 @@
-// clm_gemm.h — the fp16 tile GEMM of the causal-LM forward with its fused epilogues (the design notes are in the header of
-// causal_lm.hip).  A kernel template with internal linkage: a translation unit instantiates the epilogues it launches --
-// causal_lm.hip the four of the OPT forward (its launch_gemm serves the tree and cache paths too), causal_lm_llama.hip the
-// two of the Llama family (rotary embedding on q | k, SwiGLU).  Which tile a GEMM gets is decided in one place, launch_gemm
-// of causal_lm.hip; clm_gemm_tiles below only launches it.
+// clm_gemm.h — the 16-bit tile GEMM of the causal-LM forward with its fused epilogues (the design notes are in the header of
+// causal_lm.hip).  A kernel template with internal linkage, on the tile, the epilogue and the element type E (_Float16 by
+// default, __bf16: ClmElem of clm_internal.h; only the MFMA and the conversions of bias and out16 depend on it, the 16-byte
+// global and LDS traffic does not): a translation unit instantiates what it launches -- causal_lm.hip the four epilogues of
+// the OPT forward in fp16 (its launch_gemm serves the tree and cache paths too), causal_lm_llama.hip the two of the Llama
+// family in fp16 (rotary embedding on q | k, SwiGLU), causal_lm_llama_bf16.hip the four of the Llama forward in bf16.  Which
+// tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
+// launches it.
 #pragma once
 #include <math.h>
 
@@ -11,10 +14,7 @@
 namespace b2t {
 namespace {
 
-using f32x16 = float __attribute__((ext_vector_type(16)));
-using half8 = _Float16 __attribute__((ext_vector_type(8)));
-
-constexpr int CK = 64, CPITCH = CK + 8;      // k tile; LDS row pitch in fp16 elements (144 B)
+constexpr int CK = 64, CPITCH = CK + 8;      // k tile; LDS row pitch in 2-byte elements (144 B)
 constexpr int ROWPAD = CLM_ROWPAD;                  // A operands and weights are padded to this many rows
 
 // ClmGemm (the GEMM's arguments) and the EP_* epilogue ids: clm_internal.h
@@ -30,15 +30,17 @@ __device__ __forceinline__ float warp32_sum(float v) {
   return v;
 }
 
-// BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.
-template <int BM, int BN, int WGM, int WGN, int EP>
+// BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.  E is the element type of
+// A, B, bias and out16 (ClmElem, clm_internal.h).
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16>
 __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
+  using vec8 = typename ClmElem<E>::v8;
   constexpr int T = 64 * WGM * WGN, WTM = BM / WGM, WTN = BN / WGN, FM = WTM / 32, FN = WTN / 32, RS = T / 8;
   static_assert(WTN == 64, "the head epilogue reduces over 64-column wave slices");
   static_assert(BM * 8 == 4 * T && BN * 8 == 4 * T, "four 16-byte loads per operand and thread per k tile");
-  extern __shared__ __attribute__((aligned(16))) _Float16 clm_lds[];
-  _Float16* As = clm_lds;
-  _Float16* Bs = clm_lds + 2 * BM * CPITCH;
+  extern __shared__ __attribute__((aligned(16))) unsigned char clm_lds[];
+  E* As = reinterpret_cast<E*>(clm_lds);
+  E* Bs = As + 2 * BM * CPITCH;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WGN, wn = wave % WGN;
   const int li = lane & 31, hh = lane >> 5;
   int m0, n0;
@@ -48,8 +50,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
     m0 = (tile % mt) * BM; n0 = (tile / mt) * BN;
   }
   const int K = g.K, nk = K / CK;
-  const _Float16* ag = g.A + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
-  const _Float16* bg = g.B + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
+  const E* ag = static_cast<const E*>(g.A) + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
+  const E* bg = static_cast<const E*>(g.B) + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
   const long long rstep = (long long)RS * K;
   uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
 #define CLM_FETCH(k0)                                                                                                   \
@@ -58,8 +60,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
   rb0 = *reinterpret_cast<const uint4*>(bg + (k0)); rb1 = *reinterpret_cast<const uint4*>(bg + rstep + (k0));             \
   rb2 = *reinterpret_cast<const uint4*>(bg + 2 * rstep + (k0)); rb3 = *reinterpret_cast<const uint4*>(bg + 3 * rstep + (k0));
 #define CLM_STASH(buf)                                                                                                  \
-  { _Float16* ad = As + (buf) * BM * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
-    _Float16* bd = Bs + (buf) * BN * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
+  { E* ad = As + (buf) * BM * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
+    E* bd = Bs + (buf) * BN * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
     *reinterpret_cast<uint4*>(ad) = ra0; *reinterpret_cast<uint4*>(ad + RS * CPITCH) = ra1;                             \
     *reinterpret_cast<uint4*>(ad + 2 * RS * CPITCH) = ra2; *reinterpret_cast<uint4*>(ad + 3 * RS * CPITCH) = ra3;       \
     *reinterpret_cast<uint4*>(bd) = rb0; *reinterpret_cast<uint4*>(bd + RS * CPITCH) = rb1;                             \
@@ -77,19 +79,19 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < nk) { CLM_FETCH((kt + 1) * CK) }
-    const _Float16* ap = As + cur * BM * CPITCH + (wm * WTM + li) * CPITCH + 8 * hh;
-    const _Float16* bp = Bs + cur * BN * CPITCH + (wn * WTN + li) * CPITCH + 8 * hh;
+    const E* ap = As + cur * BM * CPITCH + (wm * WTM + li) * CPITCH + 8 * hh;
+    const E* bp = Bs + cur * BN * CPITCH + (wn * WTN + li) * CPITCH + 8 * hh;
 #pragma unroll
     for (int kk = 0; kk < CK; kk += 16) {
-      half8 a[FM], b[FN];
+      vec8 a[FM], b[FN];
 #pragma unroll
-      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const half8*>(ap + i * 32 * CPITCH + kk);
+      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const vec8*>(ap + i * 32 * CPITCH + kk);
 #pragma unroll
-      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const half8*>(bp + j * 32 * CPITCH + kk);
+      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const vec8*>(bp + j * 32 * CPITCH + kk);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < FN; ++j) acc[i][j] = ClmElem<E>::mfma(a[i], b[j], acc[i][j]);
     }
     if (kt + 1 < nk) { CLM_STASH(cur ^ 1) }
     __syncthreads();
@@ -98,6 +100,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
 #undef CLM_STASH
   // epilogue: C/D layout of the 32x32 MFMAs: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
   const int colw = n0 + wn * WTN;
+  const E* bias = static_cast<const E*>(g.bias);
+  E* out16 = static_cast<E*>(g.out16);
   if (EP == EP_HEAD) {
     if (colw >= g.N) return;   // a 64-column group entirely beyond the vocabulary (wave-uniform)
     const int cg = colw / 64;
@@ -146,12 +150,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
           const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
           if (row >= g.M) continue;
           const float gt = acc[i][0][e], up = acc[i][1][e];
-          g.out16[(long long)row * g.ldo + oc] = (_Float16)(gt / (1.0f + __expf(-gt)) * up);
+          out16[(long long)row * g.ldo + oc] = (E)(gt / (1.0f + __expf(-gt)) * up);
         }
       }
       return;
     }
-    const float b0 = g.bias ? (float)g.bias[c0] : 0.f, b1 = g.bias ? (float)g.bias[c1] : 0.f;
+    const float b0 = bias ? (float)bias[c0] : 0.f, b1 = bias ? (float)bias[c1] : 0.f;
     const float sc = colw < g.qcols ? g.qscale : 1.f;
     const bool rot = colw < g.rope_cols;   // wave-uniform: q | k | v boundaries are multiples of the head dim
     const int half = g.hd >> 1, fi = ((colw % g.hd) >> 1) + li;
@@ -168,9 +172,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
           const float y0 = x0 * cs - x1 * sn, y1 = x1 * cs + x0 * sn;
           x0 = y0; x1 = y1;
         }
-        _Float16* o = g.out16 + (long long)row * g.ldo;
-        o[c0] = (_Float16)(x0 * sc);
-        o[c1] = (_Float16)(x1 * sc);
+        E* o = out16 + (long long)row * g.ldo;
+        o[c0] = (E)(x0 * sc);
+        o[c1] = (E)(x1 * sc);
       }
     }
     return;
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
   for (int j = 0; j < FN; ++j) {
     const int col = colw + j * 32 + li;
     if (col >= g.N) continue;
-    const float bv = g.bias ? (float)g.bias[col] : 0.f;
+    const float bv = bias ? (float)bias[col] : 0.f;
     const float sc = col < g.qcols ? g.qscale : 1.f;
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
@@ -194,30 +198,30 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
         } else {
           if (EP == EP_RELU) v = fmaxf(v, 0.f);
           else v *= sc;
-          g.out16[off] = (_Float16)v;
+          out16[off] = (E)v;
         }
       }
     }
   }
 }
 
-constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * sizeof(_Float16); }
+constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * 2; }   // 2-byte elements
 
 // The launch of one GEMM on the tile the rule chose (ClmGemmTiles of clm_internal.h).
-template <int EP>
+template <int EP, class E = _Float16>
 int clm_gemm_tiles(const ClmGemm& g, hipStream_t s, bool use256) {
   if (use256) {   // one 8-wave workgroup per CU
     const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<256, 256, 2, 4, EP>),
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<256, 256, 2, 4, EP, E>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));
-    hipLaunchKernelGGL((clm_gemm_kernel<256, 256, 2, 4, EP>), dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
+    hipLaunchKernelGGL((clm_gemm_kernel<256, 256, 2, 4, EP, E>), dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
   } else {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<128, 128, 2, 2, EP>),
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<128, 128, 2, 2, EP, E>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(128, 128));
     const int m128 = (g.M + 127) / 128, n128 = (g.N + 127) / 128;
-    hipLaunchKernelGGL((clm_gemm_kernel<128, 128, 2, 2, EP>), dim3(m128 * n128), dim3(256), lds_bytes(128, 128), s, g);
+    hipLaunchKernelGGL((clm_gemm_kernel<128, 128, 2, 2, EP, E>), dim3(m128 * n128), dim3(256), lds_bytes(128, 128), s, g);
   }
   B2T_CHECK_LAUNCH("clm_gemm_kernel");
   return 0;

@@ -1,11 +1,12 @@
-// clm_internal.h — what the four units of the causal-LM forward share.  causal_lm.hip (the flat OPT path) defines the tile rule,
+// clm_internal.h — what the units of the causal-LM forward share (the four fp16 units named below; causal_lm_llama_bf16.hip,
+// the Llama family in bf16, uses the element-type trait ClmElem, ClmGemm, the tile rule, the head and the index builders).  causal_lm.hip (the flat OPT path) defines the tile rule,
 // the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
 // list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
 // and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
 // causal_lm_llama.hip (the Llama family, flat, tree and cached) use them.  All attention launchers serve both families: OPT's
 // row q[d] | k[d] | v[d] is the Llama row q[Hq * D] | k[Hkv * D] | v[Hkv * D] with Hkv = Hq.  The kernels stay private to their
-// files (their arithmetic is clm_attn.h's, the GEMM's template clm_gemm.h's); these are their launchers, so each is
-// instantiated once.  clm_forward, the OPT layer loop of the flat, tree and cached entry points, and clm_score_tree_cached, the
+// files (the flat and tree attention kernels and their arithmetic are clm_attn.h's templates, the GEMM's clm_gemm.h's);
+// these are their fp16 launchers, so each is instantiated once.  clm_forward, the OPT layer loop of the flat, tree and cached entry points, and clm_score_tree_cached, the
 // cached entry point of both families behind their model checks, are at the end.
 #pragma once
 #include <math.h>
@@ -23,12 +24,28 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 //   EP_SWIGLU out16[r][c0 / 2 + i] = silu(C[r][c0 + i]) * C[r][c0 + 32 + i], c0 a multiple of 64, i < 32 (ldo = N / 2).
 enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5 };
 
+using f32x16 = float __attribute__((ext_vector_type(16)));
+
+// The element type E of a forward's 16-bit operands: _Float16 (every fp16 entry point, and the default of every template
+// below and in clm_gemm.h / clm_attn.h) or __bf16 (causal_lm_llama_bf16.hip).  Both are 2 bytes, and the two MFMAs have one
+// shape, operand lane layout and issue rate, so LDS images, workspace sizes and the tile rule do not depend on E.
+template <class E> struct ClmElem;
+template <> struct ClmElem<_Float16> {
+  using v8 = _Float16 __attribute__((ext_vector_type(8)));
+  static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+template <> struct ClmElem<__bf16> {
+  using v8 = __bf16 __attribute__((ext_vector_type(8)));
+  static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+
+// A, B, bias and out16 hold elements of the launched kernel's element type (clm_gemm_kernel's E).
 struct ClmGemm {
-  const _Float16* A;      // [round_up(M, 256)][K]
-  const _Float16* B;      // [round_up(N, 256)][K]
+  const void* A;          // [round_up(M, 256)][K]
+  const void* B;          // [round_up(N, 256)][K]
   int M, N, K;            // K % 64 == 0
-  const _Float16* bias;   // [N] or null
-  _Float16* out16;        // EP_F16 / EP_RELU: [M][ldo]
+  const void* bias;       // [N] or null
+  void* out16;            // EP_F16 / EP_RELU: [M][ldo]
   float* resid;           // EP_RESID: [M][ldo] += C
   int ldo;
   float qscale; int qcols;   // EP_F16: columns < qcols are multiplied by qscale after the bias (OPT's q scaling)
@@ -139,14 +156,16 @@ inline ClmLayout clm_opt_layout(const b2t_clm_t* m, long long rows, long long he
   return clm_layout(m->d_model, 3LL * m->d_model, m->ffn_dim, m->vocab, rows, head_rows, ints);
 }
 
-// Fused LM head over r.Mh rows of x16 (already normalised): logp[i] = log p(r.d_tgt[i]) under the logits x16[i] . W^T
-inline int clm_head(const _Float16* x16, const _Float16* W, int vocab, int d, const ClmRun& r, const ClmLayout& L, char* base,
-                    hipStream_t s) {
+// Fused LM head over r.Mh rows of x16 (already normalised): logp[i] = log p(r.d_tgt[i]) under the logits x16[i] . W^T;
+// `head` launches the EP_HEAD GEMM in the element type of x16 and W (the default: fp16)
+typedef int (*ClmGemmLaunch)(const ClmGemm& g, hipStream_t s);
+inline int clm_head(const void* x16, const void* W, int vocab, int d, const ClmRun& r, const ClmLayout& L, char* base,
+                    hipStream_t s, ClmGemmLaunch head = &launch_gemm<EP_HEAD>) {
   ClmGemm g{};
   g.A = x16; g.B = W; g.M = (int)r.Mh; g.N = vocab; g.K = d;
   g.pmax = reinterpret_cast<float*>(base + L.pmax); g.psum = reinterpret_cast<float*>(base + L.psum);
   g.tlogit = reinterpret_cast<float*>(base + L.tlogit); g.tgt = r.d_tgt; g.ncg = (int)L.ncg;
-  if (int rc = launch_gemm<EP_HEAD>(g, s)) return rc;
+  if (int rc = head(g, s)) return rc;
   return clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, reinterpret_cast<float*>(base + L.logp), r.Mh, s);
 }
 

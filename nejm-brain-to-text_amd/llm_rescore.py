@@ -15,6 +15,11 @@ the device layout of include/b2t.h, scored on packed variable-length token ids (
 b2t_clm_llama_score_tree_cached_f16, csrc/causal_lm_llama.hip: RMSNorm, rotary positions, grouped-query attention, SwiGLU) with
 the same `score` / `token_logprobs` surface and the same opt-in context cache, so the three functions and
 remote_lm.LocalLMService take either.
+
+The Llama family also computes in bfloat16, the format its checkpoints are published in: `dtype="bfloat16"` (or `"auto"`, which
+follows config.json's torch_dtype) on `build_opt` / `build_scorer` / `LlamaScorer` keeps the weights in bf16 and scores
+through b2t_clm_llama_score_bf16 / b2t_clm_llama_score_tree_bf16 (csrc/causal_lm_llama_bf16.hip), on the flat and tree paths.
+The default stays fp16; OPT is fp16 only.
 """
 from __future__ import annotations
 
@@ -459,9 +464,10 @@ class OptScorer(_Scorer):
     _NO_CACHE = "use_cache=True on a scorer built without context_cache_tokens"
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
-                 context_cache_tokens: int = 0):
+                 context_cache_tokens: int = 0, dtype=None):
         import torch
         import b2t_native as N
+        self.dtype = opt_dtype(dtype)   # fp16 alone: bfloat16 is refused
         self.dims = dict(dims)
         self.device = torch.device(device)
         self.share_prefixes = bool(share_prefixes)
@@ -505,6 +511,49 @@ class OptScorer(_Scorer):
                     "b2t_clm_score_tree_f16")
         else:
             N.check(lib.b2t_clm_score_f16(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), "b2t_clm_score_f16")
+
+
+# ---- the compute dtype ----------------------------------------------------------------------------------------------------
+CLM_DTYPES = ("float16", "bfloat16")
+
+
+def clm_dtype(dtype, cfg: Optional[dict] = None):
+    """The torch dtype a scorer computes in, from the `dtype` argument of the scorers and builders: None or "float16" (or
+    torch.float16) -> torch.float16; "bfloat16" (or torch.bfloat16) -> torch.bfloat16; "auto" -> what config.json (cfg) says
+    the checkpoint was saved in, under "torch_dtype" or the newer "dtype": bfloat16 if it says so, float16 for anything
+    else.  Any other value is a ValueError."""
+    import torch
+    if dtype is None:
+        return torch.float16
+    if isinstance(dtype, torch.dtype):
+        dtype = str(dtype).replace("torch.", "")
+    if dtype == "auto":
+        if cfg is None:
+            raise ValueError('dtype "auto" needs the checkpoint\'s config.json (build_scorer / build_opt)')
+        saved = cfg.get("torch_dtype", cfg.get("dtype"))
+        dtype = "bfloat16" if str(saved).replace("torch.", "") == "bfloat16" else "float16"
+    if dtype not in CLM_DTYPES:
+        raise ValueError(f"dtype {dtype!r} is not supported (None, {', '.join(repr(d) for d in CLM_DTYPES)} or 'auto')")
+    return getattr(torch, dtype)
+
+
+def opt_dtype(dtype, cfg: Optional[dict] = None):
+    """clm_dtype for an OPT checkpoint, which computes in fp16 alone ("auto" is fp16 whatever the config says)."""
+    import torch
+    if dtype == "auto":
+        return torch.float16
+    if clm_dtype(dtype, cfg) != torch.float16:
+        raise ValueError("OptScorer: dtype 'bfloat16' is not supported for OPT checkpoints (the reference loads OPT in float16); "
+                         "the Llama family has a bfloat16 mode")
+    return torch.float16
+
+
+def llama_check_dtype_cache(dtype, context_cache_tokens) -> None:
+    """Refuses bfloat16 together with a context cache: the cached path exists in fp16 only."""
+    import torch
+    if dtype == torch.bfloat16 and int(context_cache_tokens) > 0:
+        raise ValueError("LlamaScorer: dtype 'bfloat16' with context_cache_tokens > 0 is not supported yet: the context cache "
+                         "behind bfloat16 is the follow-up to the bfloat16 mode; use dtype 'float16' or context_cache_tokens=0")
 
 
 # ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM) ---------------------------------------
@@ -616,11 +665,14 @@ def gate_up_row_perm(ffn: int) -> np.ndarray:
     return np.concatenate([b, ffn + b], axis=1).reshape(-1)
 
 
-def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray) -> Dict[str, "object"]:
+def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
     """Tensors in the layout of b2t_clm_llama_t from a Llama / Mistral / Qwen2 state dict, on the device the state dict is on
     (the CPU for a checkpoint read from disk): fp16 embed_tokens, lm_head (the same tensor when tied), final_norm_w,
-    layers.<i>.<field> (qkv_b absent when the model has no q / k / v biases), and the fp32 rope_cos / rope_sin tables (CPU)."""
+    layers.<i>.<field> (qkv_b absent when the model has no q / k / v biases), and the fp32 rope_cos / rope_sin tables (CPU).
+    dtype=torch.bfloat16 (clm_dtype's spellings) makes the weights bf16 in the same layout: a bf16 checkpoint's values are
+    kept exactly, an fp32 or fp16 one is rounded to nearest even."""
     import torch
+    wdt = clm_dtype(dtype)
     sd = dict(state)
     d, ffn, V, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"], dims["n_kv_heads"]
     hd = d // Hq
@@ -628,7 +680,7 @@ def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray) -> Dict[s
     def get(name, shape):
         if name not in sd:
             raise KeyError(f"checkpoint lacks {name}")
-        t = sd[name].detach().to(torch.float16).contiguous()
+        t = sd[name].detach().to(wdt).contiguous()
         if tuple(t.shape) != tuple(shape):
             raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
         return t
@@ -655,7 +707,7 @@ def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray) -> Dict[s
                                               0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
              "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
         if any(p + f"self_attn.{n}.bias" in sd for n in widths):
-            zero = lambda w: torch.zeros(w, dtype=torch.float16, device=dev)
+            zero = lambda w: torch.zeros(w, dtype=wdt, device=dev)
             L["qkv_b"] = torch.cat([get(p + f"self_attn.{n}.bias", (w,)) if p + f"self_attn.{n}.bias" in sd else zero(w)
                                     for n, w in widths.items()])[qperm].contiguous()
         for f, t in L.items():
@@ -668,11 +720,12 @@ def load_config(model_dir: str) -> dict:
         return json.load(f)
 
 
-def load_llama_arrays(model_dir: str, max_positions: Optional[int] = None) -> Tuple[dict, Dict[str, "object"]]:
-    """(dims, host tensors in the device layout) of the Llama-family checkpoint in model_dir."""
+def load_llama_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the Llama-family checkpoint in model_dir; dtype as clm_dtype reads it."""
     cfg = load_config(model_dir)
     dims = llama_dims(cfg, max_positions)
-    return dims, llama_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg))
+    wdt = clm_dtype(dtype, cfg)
+    return dims, llama_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
 
 
 class LlamaScorer(_Scorer):
@@ -684,15 +737,23 @@ class LlamaScorer(_Scorer):
     b2t_clm_llama_score_tree_cached_f16, with OptScorer's `use_cache` / `update_cache` / `cache_len` / `cache_ids` /
     `cache_reset` and `last_stats` = {"tokens", "nodes", "reused"}.  With grouped-query K / V a position costs n_layers * 4 *
     n_kv_heads * head_dim bytes: 128 KiB at the Llama-3-8B shape, 256 MiB for 2048.  The cache is GPU memory for kernels that
-    have no CPU path, so on another device context_cache_tokens > 0 raises ValueError."""
+    have no CPU path, so on another device context_cache_tokens > 0 raises ValueError.
+
+    dtype: None or "float16" computes in fp16; "bfloat16" computes in bf16, the format these families are published in
+    (b2t_clm_llama_score_bf16 / b2t_clm_llama_score_tree_bf16: the same contract with bf16 roundings, no fp16 overflow or
+    underflow of weights and activations, about ten times the rounding error).  The arrays must already have that dtype
+    (llama_device_layout(..., dtype=...)); `self.dtype` is the torch dtype.  bfloat16 with a context cache is refused."""
 
     _WS_BYTES = "b2t_clm_llama_ws_bytes"
     _NO_CACHE = "use_cache=True on a scorer built without a context cache (context_cache_tokens)"
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
-                 context_cache_tokens: int = 0):
+                 context_cache_tokens: int = 0, dtype=None):
         import torch
         import b2t_native as N
+        self.dtype = clm_dtype(dtype)
+        self._suffix = "bf16" if self.dtype == torch.bfloat16 else "f16"
+        llama_check_dtype_cache(self.dtype, context_cache_tokens)
         self.dims = dict(dims)
         self.device = torch.device(device)
         self.check_cache_device(self.device, context_cache_tokens)   # before the weights are copied
@@ -702,7 +763,7 @@ class LlamaScorer(_Scorer):
         if dims.get("tied", False) or arrays["lm_head"] is arrays["embed_tokens"]:
             self.w["lm_head"] = self.w["embed_tokens"]
         for k, v in self.w.items():
-            want = torch.float32 if k.startswith("rope_") else torch.float16
+            want = torch.float32 if k.startswith("rope_") else self.dtype
             if v.dtype != want:
                 raise ValueError(f"LlamaScorer: {k} is {v.dtype}, expected {want}")
         self._layers = (N.ClmLlamaLayer * max(1, dims["n_layers"]))()
@@ -749,10 +810,11 @@ class LlamaScorer(_Scorer):
                                                             scores, tok, None, None, ws, ws_bytes, stream),
                     "b2t_clm_llama_score_tree_cached_f16")
         elif path == "tree":
-            N.check(lib.b2t_clm_llama_score_tree_f16(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream),
-                    "b2t_clm_llama_score_tree_f16")
+            name = "b2t_clm_llama_score_tree_" + self._suffix
+            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream), name)
         else:
-            N.check(lib.b2t_clm_llama_score_f16(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), "b2t_clm_llama_score_f16")
+            name = "b2t_clm_llama_score_" + self._suffix
+            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
 
 
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
@@ -788,28 +850,36 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
             "n_after": na.value}
 
 
-def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None):
+def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", LlamaScorer for "llama",
-    "mistral" and "qwen2"; anything else is refused.  max_positions caps a Llama-family model's rotary table."""
-    mt = load_config(model_dir).get("model_type", "opt")
+    "mistral" and "qwen2"; anything else is refused.  max_positions caps a Llama-family model's rotary table.  dtype (clm_dtype):
+    None or "float16", "bfloat16" (the Llama family only, and without a context cache), or "auto" = the dtype config.json says
+    the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
+    refused is refused before any weight is read."""
+    cfg = load_config(model_dir)
+    mt = cfg.get("model_type", "opt")
     if mt == "opt":
+        wdt = opt_dtype(dtype, cfg)
         dims, arrays = load_opt_arrays(model_dir)
-        return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens)
+        return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
     if mt in LLAMA_MODEL_TYPES:
+        wdt = clm_dtype(dtype, cfg)
+        llama_check_dtype_cache(wdt, context_cache_tokens)
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
-        dims, arrays = load_llama_arrays(model_dir, max_positions)
-        return LlamaScorer(dims, arrays, device, share_prefixes, context_cache_tokens)
+        dims, arrays = load_llama_arrays(model_dir, max_positions, wdt)
+        return LlamaScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
     raise ValueError(f"model_type {mt!r} is not supported (opt, {', '.join(LLAMA_MODEL_TYPES)})")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
-              max_positions=None):
-    """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16).  The scorer is an
+              max_positions=None, dtype=None):
+    """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
+    Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
     OptScorer, or a LlamaScorer for a Llama / Mistral / Qwen2 directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)
-    scorer = build_scorer(model_dir, device, share_prefixes, context_cache_tokens, max_positions)
+    scorer = build_scorer(model_dir, device, share_prefixes, context_cache_tokens, max_positions, dtype)
     from transformers import AutoTokenizer
     tok = AutoTokenizer.from_pretrained(model_dir, local_files_only=True)
     tok.padding_side = "right"

@@ -32,6 +32,11 @@ path against HF's LlamaForCausalLM in fp16 on the same weights in this process (
 nbest / --context the flat call against the tree call, with --session the session comparison above.
 
   python tools/bench_llm_rescore.py --arch llama [--tree --context 64 | --session]
+
+`--dtype bfloat16` (with --arch llama) runs the same in bfloat16: b2t_clm_llama_score_bf16 / b2t_clm_llama_score_tree_bf16 on
+bf16 weights against HF's model in bf16.  The cached path has no bf16 form yet, so --session stays float16.
+
+  python tools/bench_llm_rescore.py --arch llama --dtype bfloat16 [--tree --context 64]
 """
 import argparse
 import json
@@ -69,6 +74,8 @@ def nbest_list(rng, V, cands=100, context=()):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", choices=("opt", "llama"), default="opt", help="opt: OPT-6.7b shape; llama: Llama-3-8B shape")
+    ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16",
+                    help="--arch llama: the compute dtype of the scorer and of the HF model beside it")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--d", type=int, default=4096)
     ap.add_argument("--heads", type=int, default=32)
@@ -87,6 +94,8 @@ def main():
     a = ap.parse_args()
     a.ffn = a.ffn or (14336 if a.arch == "llama" else 16384)
     a.vocab = a.vocab or (128256 if a.arch == "llama" else 50272)
+    if a.dtype != "float16" and (a.arch != "llama" or a.session):
+        ap.error("--dtype bfloat16 needs --arch llama and has no --session")
     if a.arch == "llama":
         return main_llama(a)
     import torch
@@ -172,11 +181,13 @@ def main():
 
 
 def main_llama(a):
-    """--arch llama: the lists and the protocol of main() with a LlamaScorer, and HF's fp16 model as the torch side."""
+    """--arch llama: the lists and the protocol of main() with a LlamaScorer, and HF's model in the same dtype (--dtype) as
+    the torch side."""
     import torch
     import transformers
     import llm_rescore as R
     torch.manual_seed(0)
+    dt = R.clm_dtype(a.dtype)
     d, H, Hkv, ffn, V, L = a.d, a.heads, a.kv_heads, a.ffn, a.vocab, a.layers
     dev = "cuda"
     rng = np.random.default_rng(0)
@@ -188,7 +199,7 @@ def main_llama(a):
                                    rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
                                                      original_max_position_embeddings=8192, rope_theta=500000.0))
     old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
+    torch.set_default_dtype(dt)
     try:
         with torch.device(dev):
             model = transformers.LlamaForCausalLM(cfg).eval()
@@ -198,11 +209,11 @@ def main_llama(a):
         for k, p in model.named_parameters():
             if p.dim() == 2:
                 std = 2.0 / d ** 0.5 if ("embed_tokens" in k or "lm_head" in k) else 1.0 / p.shape[1] ** 0.5
-                p.copy_((torch.randn(p.shape, device=dev) * std).half())
+                p.copy_((torch.randn(p.shape, device=dev) * std).to(dt))
     cj = json.loads(cfg.to_json_string())
     dims = R.llama_dims(cj)
-    sc = R.LlamaScorer(dims, R.llama_device_layout(model.state_dict(), dims, R.rope_inv_freq(cj)), dev,
-                       context_cache_tokens=dims["max_pos"] if a.session else 0)
+    sc = R.LlamaScorer(dims, R.llama_device_layout(model.state_dict(), dims, R.rope_inv_freq(cj), dtype=dt), dev,
+                       context_cache_tokens=dims["max_pos"] if a.session else 0, dtype=dt)
     if a.session:
         del model
         torch.cuda.empty_cache()
@@ -219,7 +230,7 @@ def main_llama(a):
         torch.cuda.empty_cache()
         return ab_flat_tree(a, sc, lists, ntok, arch="llama")
 
-    def torch_score(seqs):   # padded batch through the HF model, fp16
+    def torch_score(seqs):   # padded batch through the HF model, in --dtype
         B, T = len(seqs), max(len(s) for s in seqs)
         ids = torch.zeros(B, T, dtype=torch.long, device=dev)
         mask = torch.zeros(B, T, dtype=torch.long, device=dev)
@@ -249,7 +260,7 @@ def main_llama(a):
     flop_tok = 2 * (L * (d * (H + 2 * Hkv) * hd + d * d + 3 * d * ffn) + d * V)
     r2 = lambda x: round(float(x), 2)
     mh, mt = float(np.mean(ms_hip)), float(np.mean(ms_torch))
-    print(json.dumps({"bench": "llm_rescore", "arch": "llama", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn,
+    print(json.dumps({"bench": "llm_rescore", "arch": "llama", "dtype": a.dtype, "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn,
                       "vocab": V, "cands": a.cands, "tokens_per_list": float(np.mean(ntok)), "hip_ms_per_list": r2(mh),
                       "torch_fp16_ms_per_list": r2(mt), "hip_tflops": round(np.mean(ntok) * flop_tok / (mh * 1e-3) / 1e12, 1),
                       "speedup_vs_torch": round(mt / mh, 3), "max_abs_score_diff_vs_torch": round(diff, 4),
