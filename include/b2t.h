@@ -797,6 +797,45 @@ int b2t_clm_llama_score_tree_bf16(const b2t_clm_llama_t* model, const int32_t* i
                                   float* scores_out, float* tok_logp_out, long long* n_nodes_out,
                                   void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Qwen3 (csrc/causal_lm_qwen3.hip): the Llama-family forward with one insertion -----------------------------------------
+ * HF Qwen3ForCausalLM is the forward above plus an RMSNorm over the head dimension of every q head and every k head, after
+ * the projection and before the rotation, with weights self_attn.q_norm.weight / k_norm.weight of shape [hd] and the model's
+ * rms_eps; it has no q / k / v biases.  The model is the same b2t_clm_llama_t in the same layout (qkv_b must be NULL); the norm
+ * weights travel beside it: a HOST array of n_layers entries with DEVICE pointers inside, [hd] each in the call's element
+ * type, for hd == 128 stored in the order of the q / k rows they scale ([0..31, 64..95, 32..63, 96..127]; the mean of squares
+ * does not change under a permutation).
+ * Numerics: the contract above with one insertion.  For each q head and each k head of a row, on the fp32 accumulator of the
+ * QKV GEMM: y[c] = x[c] * rsqrt(mean_c(x[c]^2) + rms_eps) * w[c], w widened from the element type, everything in fp32; then the
+ * rotation, then (q only) the factor hd^-0.5, then the one rounding to the element type.  v is untouched.  No value is rounded
+ * between the GEMM and that rounding and no separate pass over qkv exists: the norm is the QKV GEMM's epilogue
+ * (EP_QKNORM_ROPE, csrc/clm_gemm.h).
+ * The five calls have their Llama twins' argument lists with qk_norm_host inserted after model, their output layout, their
+ * refusals before any launch (the error text carries the entry point's own name) plus: a null qk_norm_host, a null entry in
+ * it, a non-null qkv_b.  Workspace and cache sizes are the Llama size functions' (b2t_clm_llama_ws_bytes,
+ * b2t_clm_llama_tree_ws_bytes, b2t_clm_llama_cache_kv_bytes, b2t_clm_llama_tree_cached_ws_bytes); the cache holds K rows after
+ * norm and rotation.  Tree, cached and flat calls are bit-identical, a sequence scores the same alone or in a batch, and
+ * B2T_CLM_GEMM_256 / B2T_CLM_TRUNK_ATTN do not change the bits.  There is no cached bf16 call. */
+typedef struct {
+  const void *q_norm_w, *k_norm_w;  /* [hd] self_attn.q_norm.weight, self_attn.k_norm.weight */
+} b2t_clm_qknorm_t;
+
+int b2t_clm_qwen3_score_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                            const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                            size_t ws_bytes, void* stream);
+int b2t_clm_qwen3_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                                 const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                 long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_qwen3_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
+                                        b2t_clm_cache_t* cache, int update, const int32_t* ids_host,
+                                        const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                        long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_qwen3_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                             const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                             size_t ws_bytes, void* stream);
+int b2t_clm_qwen3_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                                  const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                  long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,11 @@ class ClmLlamaDesc(C.Structure):
                [("layers_host", C.POINTER(ClmLlamaLayer))]
 
 
+class ClmQkNorm(C.Structure):
+    """Mirror of b2t_clm_qknorm_t (include/b2t.h): device weights [hd] of one Qwen3 layer's q and k RMSNorm."""
+    _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
+
+
 _SIGNATURES = {
     "b2t_version": (C.c_int, []),
     "b2t_last_error": (C.c_char_p, []),
@@ -253,6 +258,11 @@ _SIGNATURES = {
     "b2t_clm_llama_score_tree_cached_f16": (C.c_int, [C.POINTER(ClmLlamaDesc), C.POINTER(ClmCache), C.c_int, VP, VP, C.c_int,
                                                       VP, VP, C.POINTER(LL), C.POINTER(C.c_int), VP, C.c_size_t, VP]),
 }
+# Qwen3: the Llama twin's list with the q / k norm array after the model
+for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16", "score_tree_cached_f16"):
+    _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
+    _SIGNATURES["b2t_clm_qwen3_" + _t] = (_res, [_args[0], C.POINTER(ClmQkNorm)] + _args[1:])
+
 
 
 def header_symbols():

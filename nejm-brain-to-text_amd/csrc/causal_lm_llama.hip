@@ -30,7 +30,8 @@
 // The forward (llama_forward), the bodies of the flat and the tree entry point and the embed / RMSNorm kernels are templates in
 // clm_llama.h, on a per-element-type policy; this unit holds the fp16 policy (LlamaF16: the two GEMM launches of this family
 // through the one tile rule, the OPT paths' residual / head GEMMs and attention launchers) and the model check.  The same
-// forward in bf16 is causal_lm_llama_bf16.hip.
+// forward in bf16 is causal_lm_llama_bf16.hip; Qwen3's, which norms the q and k heads in the QKV GEMM's epilogue, is
+// causal_lm_qwen3.hip, whose policies take every other launch from this unit and the bf16 one (LlamaShared, clm_llama.h).
 #include "clm_llama.h"
 
 namespace b2t {
@@ -58,6 +59,25 @@ bool llama_dims_ok(const b2t_clm_llama_t* m) {
 }
 
 }  // namespace
+
+// LlamaShared<_Float16> (clm_llama.h): this unit's launches for the policy of another family (causal_lm_qwen3.hip)
+template <> int LlamaShared<_Float16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_swiglu(g, s); }
+template <> int LlamaShared<_Float16>::gemm_resid(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_resid(g, s); }
+template <> int LlamaShared<_Float16>::gemm_head(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_head(g, s); }
+template <> int LlamaShared<_Float16>::embed(const int* ids, const E* et, float* resid, int d, long long rows, hipStream_t s) {
+  return LlamaF16::embed(ids, et, resid, d, rows, s);
+}
+template <> int LlamaShared<_Float16>::rmsnorm(const float* x, const int* rowmap, long long n, const E* w, float eps, E* out, int d,
+                                                 hipStream_t s) {
+  return LlamaF16::rmsnorm(x, rowmap, n, w, eps, out, d, s);
+}
+template <> int LlamaShared<_Float16>::attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
+  return LlamaF16::attn(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
+}
+template <> int LlamaShared<_Float16>::attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start,
+                                                   int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
+  return LlamaF16::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
+}
 
 int clm_llama_check_model(const b2t_clm_llama_t* m) {
   B2T_REQUIRE(m, "b2t_clm_llama: null model");

@@ -56,6 +56,26 @@ struct LlamaBf16 : LlamaOps<__bf16> {
 };
 
 }  // namespace
+
+// LlamaShared<__bf16> (clm_llama.h): this unit's launches for the policy of another family (causal_lm_qwen3.hip)
+template <> int LlamaShared<__bf16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_swiglu(g, s); }
+template <> int LlamaShared<__bf16>::gemm_resid(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_resid(g, s); }
+template <> int LlamaShared<__bf16>::gemm_head(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_head(g, s); }
+template <> int LlamaShared<__bf16>::embed(const int* ids, const E* et, float* resid, int d, long long rows, hipStream_t s) {
+  return LlamaBf16::embed(ids, et, resid, d, rows, s);
+}
+template <> int LlamaShared<__bf16>::rmsnorm(const float* x, const int* rowmap, long long n, const E* w, float eps, E* out, int d,
+                                               hipStream_t s) {
+  return LlamaBf16::rmsnorm(x, rowmap, n, w, eps, out, d, s);
+}
+template <> int LlamaShared<__bf16>::attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
+  return LlamaBf16::attn(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
+}
+template <> int LlamaShared<__bf16>::attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start,
+                                                 int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
+  return LlamaBf16::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
+}
+
 }  // namespace b2t
 
 using namespace b2t;

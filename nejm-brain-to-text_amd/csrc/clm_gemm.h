@@ -3,7 +3,8 @@
 // default, __bf16: ClmElem of clm_internal.h; only the MFMA and the conversions of bias and out16 depend on it, the 16-byte
 // global and LDS traffic does not): a translation unit instantiates what it launches -- causal_lm.hip the four epilogues of
 // the OPT forward in fp16 (its launch_gemm serves the tree and cache paths too), causal_lm_llama.hip the two of the Llama
-// family in fp16 (rotary embedding on q | k, SwiGLU), causal_lm_llama_bf16.hip the four of the Llama forward in bf16.  Which
+// family in fp16 (rotary embedding on q | k, SwiGLU), causal_lm_llama_bf16.hip the four of the Llama forward in bf16,
+// causal_lm_qwen3.hip the one Qwen3 adds (EP_QKNORM_ROPE: the per-head q / k RMSNorm in front of the rotation) in both.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -129,6 +130,66 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
           for (int j = 0; j < FN; ++j)
             if (colw + j * 32 + li == t) g.tlogit[row] = v[j];
         }
+      }
+    }
+    return;
+  }
+  if (EP == EP_QKNORM_ROPE) {
+    // EP_ROPE without a bias, behind an RMSNorm over each q and k head of a row (Qwen3), all on the fp32 accumulator.  A lane
+    // holds columns colw + li and colw + 32 + li as below, so a head of 64 is the wave's slice: the sum of squares is a
+    // butterfly over the 32 lanes of a half, which leaves the same bits in every lane.  A head of 128 is the slices of waves
+    // `wave & ~1` and `wave | 1` of this workgroup (n0 and the head boundaries are multiples of 128): each writes its
+    // per-row partial sums to LDS -- the operand tiles are dead after the k loop's last barrier -- and both add the two in one
+    // order, lower 64 columns first, so the result depends neither on the wave nor on the tile.  The barrier is reached by
+    // every wave of the workgroup, the v slices and the slices beyond N included: no wave returns before it.
+    static_assert(FN == 2 && WGN % 2 == 0, "rotary pairs are the two fragments of a lane; a head of 128 is two neighbouring waves");
+    const bool normed = colw < g.rope_cols;   // wave-uniform, and inside the matrix: rope_cols <= N
+    float* part = reinterpret_cast<float*>(clm_lds);   // [waves][WTM]
+    if (g.hd == 128) {
+      if (normed) {
+#pragma unroll
+        for (int i = 0; i < FM; ++i) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const float ss = warp32_sum(__builtin_fmaf(acc[i][0][e], acc[i][0][e], acc[i][1][e] * acc[i][1][e]));
+            if (li == 0) part[wave * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh] = ss;
+          }
+        }
+      }
+      __syncthreads();
+    }
+    if (colw >= g.N) return;
+    const int c0 = colw + li, c1 = c0 + 32;
+    const float sc = colw < g.qcols ? g.qscale : 1.f;
+    const int half = g.hd >> 1, hc = colw % g.hd, fi = (hc >> 1) + li;
+    const float inv_hd = 1.0f / (float)g.hd;
+    float w0 = 1.f, w1 = 1.f;
+    if (normed) {   // stored under the head's row order, like the rows they scale
+      const E* nw = static_cast<const E*>(colw < g.qcols ? g.qnorm_w : g.knorm_w);
+      w0 = (float)nw[hc + li]; w1 = (float)nw[hc + 32 + li];
+    }
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int lr = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh, row = m0 + wm * WTM + lr;
+        float x0 = acc[i][0][e], x1 = acc[i][1][e];
+        float ss = 0.f;
+        if (normed)
+          ss = g.hd == 128 ? part[(wave & ~1) * WTM + lr] + part[(wave | 1) * WTM + lr]
+                           : warp32_sum(__builtin_fmaf(x0, x0, x1 * x1));
+        if (row >= g.M) continue;
+        if (normed) {
+          const float rstd = 1.0f / sqrtf(ss * inv_hd + g.rms_eps);
+          x0 = x0 * rstd * w0; x1 = x1 * rstd * w1;
+          const long long a = (long long)g.pos[row] * half + fi;
+          const float cs = g.rope_cos[a], sn = g.rope_sin[a];
+          const float y0 = x0 * cs - x1 * sn, y1 = x1 * cs + x0 * sn;
+          x0 = y0; x1 = y1;
+        }
+        E* o = out16 + (long long)row * g.ldo;
+        o[c0] = (E)(x0 * sc);
+        o[c1] = (E)(x1 * sc);
       }
     }
     return;

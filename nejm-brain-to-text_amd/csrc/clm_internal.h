@@ -1,5 +1,6 @@
 // clm_internal.h — what the units of the causal-LM forward share (the four fp16 units named below; causal_lm_llama_bf16.hip,
-// the Llama family in bf16, uses the element-type trait ClmElem, ClmGemm, the tile rule, the head and the index builders).  causal_lm.hip (the flat OPT path) defines the tile rule,
+// the Llama family in bf16, uses the element-type trait ClmElem, ClmGemm, the tile rule, the head and the index builders;
+// causal_lm_qwen3.hip, Qwen3 in both formats, the same and clm_score_tree_cached).  causal_lm.hip (the flat OPT path) defines the tile rule,
 // the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
 // list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
 // and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
@@ -22,7 +23,9 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 //   EP_ROPE   out16[r][c], out16[r][c + 32] = the rotation of (C[r][c], C[r][c + 32]) + bias by the angle of row r's position
 //             and frequency (c % hd) / 2 + c % 32 (columns < rope_cols; the others are written as EP_F16 writes them);
 //   EP_SWIGLU out16[r][c0 / 2 + i] = silu(C[r][c0 + i]) * C[r][c0 + 32 + i], c0 a multiple of 64, i < 32 (ldo = N / 2).
-enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5 };
+// EP_QKNORM_ROPE (Qwen3) is EP_ROPE without a bias and with an RMSNorm over every q and k head of a row in front of the rotation:
+//   x[c] * rsqrt(mean over the head of x^2 + rms_eps) * w[c % hd], w = qnorm_w (columns < qcols) or knorm_w (< rope_cols).
+enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6 };
 
 using f32x16 = float __attribute__((ext_vector_type(16)));
 
@@ -54,6 +57,8 @@ struct ClmGemm {
   const int* pos;                           // EP_ROPE: [M] position of each row
   const float* rope_cos; const float* rope_sin;   // EP_ROPE: fp32 [max_pos][hd / 2]
   int rope_cols, hd;                        // EP_ROPE: columns < rope_cols (q | k) are rotated; head dim (64 or 128)
+  const void* qnorm_w; const void* knorm_w; // EP_QKNORM_ROPE: [hd] weights of the q heads' and the k heads' RMSNorm
+  float rms_eps;                            // EP_QKNORM_ROPE
 };
 
 // The tile rule (B2T_CLM_GEMM_256) lives in one definition, causal_lm.hip: it picks the tile and hands the launch to `tiles`,

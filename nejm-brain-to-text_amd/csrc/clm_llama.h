@@ -5,8 +5,11 @@
 //   P::gemm_rope, gemm_swiglu, gemm_resid, gemm_head (g, s)   the four GEMMs, each through the one tile rule launch_gemm
 //   P::embed, P::rmsnorm                        the two kernels below (LlamaOps<E>)
 //   P::attn, P::attn_tree                       the flat and the tree attention launcher
+//   P::qk_norm                                  whether the QKV GEMM's epilogue norms the q and k heads (Qwen3): llama_forward then
+//                                               hands it the layer's weights from the b2t_clm_qknorm_t array and rms_eps
 // causal_lm_llama.hip holds the fp16 policy and the fp16 entry points (the cached one included), causal_lm_llama_bf16.hip the
-// bf16 policy, every bf16 kernel instantiation and the two bf16 entry points.
+// bf16 policy, every bf16 kernel instantiation and the two bf16 entry points.  causal_lm_qwen3.hip holds the two Qwen3
+// policies: gemm_rope with the epilogue EP_QKNORM_ROPE, instantiated there, and every other launch through LlamaShared<E>.
 #pragma once
 #include <math.h>
 #include <string>
@@ -18,6 +21,37 @@ namespace b2t {
 
 // dimensions, head dim and weight pointers of a descriptor (0, or an error with the message set); causal_lm_llama.hip
 int clm_llama_check_model(const b2t_clm_llama_t* m);
+// the q / k norm weights of a checked model for the entry point `who`: a null array or entry and a q / k / v bias (Qwen3 has
+// none, and EP_QKNORM_ROPE adds none) are refused; causal_lm_qwen3.hip
+int clm_qknorm_check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_qknorm_t* qkn);
+
+// The launches of the Llama policy for element type E that another family's policy shares (P's list above without gemm_rope),
+// so that their kernels are instantiated in one unit: the members are defined in causal_lm_llama.hip for _Float16 and in
+// causal_lm_llama_bf16.hip for __bf16, each forwarding to its unit's policy.
+template <class El>
+struct LlamaShared {
+  using E = El;
+  static int gemm_swiglu(const ClmGemm& g, hipStream_t s);
+  static int gemm_resid(const ClmGemm& g, hipStream_t s);
+  static int gemm_head(const ClmGemm& g, hipStream_t s);
+  static int embed(const int* ids, const E* et, float* resid, int d, long long rows, hipStream_t s);
+  static int rmsnorm(const float* x, const int* rowmap, long long n, const E* w, float eps, E* out, int d, hipStream_t s);
+  static int attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s);
+  static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
+                       int Hkv, int hd, hipStream_t s);
+};
+// the specialisations the two units define, declared before any use
+#define B2T_LLAMA_SHARED(EL)                                                                                                  \
+  template <> int LlamaShared<EL>::gemm_swiglu(const ClmGemm&, hipStream_t);                                                  \
+  template <> int LlamaShared<EL>::gemm_resid(const ClmGemm&, hipStream_t);                                                   \
+  template <> int LlamaShared<EL>::gemm_head(const ClmGemm&, hipStream_t);                                                    \
+  template <> int LlamaShared<EL>::embed(const int*, const EL*, float*, int, long long, hipStream_t);                         \
+  template <> int LlamaShared<EL>::rmsnorm(const float*, const int*, long long, const EL*, float, EL*, int, hipStream_t);     \
+  template <> int LlamaShared<EL>::attn(const EL*, EL*, const int*, int, int, int, int, hipStream_t);                         \
+  template <> int LlamaShared<EL>::attn_tree(const EL*, EL*, const int*, const int*, const int*, int, int, int, int, hipStream_t);
+B2T_LLAMA_SHARED(_Float16)
+B2T_LLAMA_SHARED(__bf16)
+#undef B2T_LLAMA_SHARED
 
 namespace {
 
@@ -52,6 +86,7 @@ __global__ __launch_bounds__(256) void clm_llama_rmsnorm_kernel(const float* x, 
 template <class El>
 struct LlamaOps {
   using E = El;
+  static constexpr bool qk_norm = false;
   static int embed(const int* ids, const E* et, float* resid, int d, long long rows, hipStream_t s) {
     hipLaunchKernelGGL(clm_llama_embed_kernel<E>, dim3((unsigned)rows), dim3(256), 0, s, ids, et, resid, d);
     B2T_CHECK_LAUNCH("clm_llama_embed_kernel");
@@ -71,8 +106,10 @@ inline ClmLayout llama_layout(const b2t_clm_llama_t* m, long long rows, long lon
 }
 
 // The forward over r.rows rows up to the per-row log-probs logp[Mh]; attn(layer, qkv, out) enqueues one layer's attention.
+// qkn is the per-layer q / k norm weights of a policy with qk_norm (checked by clm_qknorm_check), unused otherwise.
 template <class P, class Attn>
-int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s) {
+int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
+                  const b2t_clm_qknorm_t* qkn = nullptr) {
   using E = typename P::E;
   const int d = m.d_model, Hq = m.n_heads, Hkv = m.n_kv_heads, hd = d / Hq, F = m.ffn_dim, qw = (Hq + 2 * Hkv) * hd;
   const long long rows = r.rows;
@@ -89,6 +126,7 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
     g.A = x16; g.B = w.qkv_w; g.M = (int)rows; g.N = qw; g.K = d; g.bias = w.qkv_b; g.out16 = qkv; g.ldo = qw;
     g.qscale = 1.0f / sqrtf((float)hd); g.qcols = Hq * hd;
     g.pos = r.d_pos; g.rope_cos = m.rope_cos; g.rope_sin = m.rope_sin; g.rope_cols = (Hq + Hkv) * hd; g.hd = hd;
+    if constexpr (P::qk_norm) { g.qnorm_w = qkn[l].q_norm_w; g.knorm_w = qkn[l].k_norm_w; g.rms_eps = m.rms_eps; }
     if (int rc = P::gemm_rope(g, s)) return rc;
     if (int rc = attn(l, qkv, x16)) return rc;
     g = ClmGemm{};
@@ -110,10 +148,13 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
 // The flat entry point of a policy; `who` is its name.
 template <class P>
 int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
-                float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
+                float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream,
+                const b2t_clm_qknorm_t* qkn = nullptr) {
   using E = typename P::E;
   if (int rc = clm_llama_check_model(model)) return rc;
   const b2t_clm_llama_t& m = *model;
+  if constexpr (P::qk_norm)
+    if (int rc = clm_qknorm_check(who, m, qkn)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
@@ -128,7 +169,7 @@ int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* id
   auto attn = [&](int, const E* qkv, E* out) {
     return P::attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
-  if (int rc = llama_forward<P>(m, ix.run, L, base, attn, s)) return rc;
+  if (int rc = llama_forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
   return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
 }
 
@@ -136,10 +177,12 @@ int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* id
 template <class P>
 int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                      int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
-                     void* stream) {
+                     void* stream, const b2t_clm_qknorm_t* qkn = nullptr) {
   using E = typename P::E;
   if (int rc = clm_llama_check_model(model)) return rc;
   const b2t_clm_llama_t& m = *model;
+  if constexpr (P::qk_norm)
+    if (int rc = clm_qknorm_check(who, m, qkn)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
@@ -157,7 +200,7 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
   auto attn = [&](int, const E* qkv, E* out) {
     return P::attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
-  if (int rc = llama_forward<P>(m, ix.run, L, base, attn, s)) return rc;
+  if (int rc = llama_forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
   return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
 }
 

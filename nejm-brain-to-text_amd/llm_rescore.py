@@ -1,4 +1,4 @@
-"""LLM n-best rescoring (OPT, and the Llama family: Llama, Mistral, Qwen2): the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
+"""LLM n-best rescoring (OPT, and the Llama family: Llama, Mistral, Qwen2, Qwen3): the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
 :127-162, gpt2_lm_decode :165-251, get_string_differences :273-311, augment_nbest :327-411) with the causal-LM forward on the
 HIP path (b2t_clm_score_f16, csrc/causal_lm.hip; opt-in b2t_clm_score_tree_f16, csrc/causal_lm_tree.hip, which computes the
 prefixes the candidates share once; opt-in b2t_clm_score_tree_cached_f16, csrc/causal_lm_cache.hip, which also keeps the
@@ -20,6 +20,11 @@ The Llama family also computes in bfloat16, the format its checkpoints are publi
 follows config.json's torch_dtype) on `build_opt` / `build_scorer` / `LlamaScorer` keeps the weights in bf16 and scores
 through b2t_clm_llama_score_bf16 / b2t_clm_llama_score_tree_bf16 (csrc/causal_lm_llama_bf16.hip), on the flat and tree paths.
 The default stays fp16; OPT is fp16 only.
+
+"qwen3" gives a `LlamaScorer` too: Qwen3 is the same forward with an RMSNorm over every q and k head between the projection
+and the rotation, which runs in the QKV GEMM's epilogue (b2t_clm_qwen3_score_f16 / _tree_f16 / _tree_cached_f16 / _bf16 /
+_tree_bf16, csrc/causal_lm_qwen3.hip).  The loader adds the norm weights to the layout and the scorer takes those entry points
+when its arrays hold them.  Checkpoints whose head_dim is not hidden_size / heads (Qwen3-0.6B, 4B, 32B) are refused.
 """
 from __future__ import annotations
 
@@ -556,8 +561,9 @@ def llama_check_dtype_cache(dtype, context_cache_tokens) -> None:
                          "behind bfloat16 is the follow-up to the bfloat16 mode; use dtype 'float16' or context_cache_tokens=0")
 
 
-# ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM) ---------------------------------------
-LLAMA_MODEL_TYPES = ("llama", "mistral", "qwen2")
+# ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM) ---------------------
+LLAMA_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")
+QK_NORM_MODEL_TYPES = ("qwen3",)   # an RMSNorm over every q and k head in front of the rotation
 LLAMA_HEAD_DIMS = (64, 128)
 LLAMA_MAX_POSITIONS = 8192   # default cap of the rotary cos / sin table: max_pos * head_dim * 4 bytes (4 MiB at head dim 128)
 _LLAMA_LAYER_FIELDS = ("norm1_w", "norm2_w", "qkv_w", "qkv_b", "o_w", "gate_up_w", "down_w")
@@ -621,7 +627,14 @@ def llama_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     if act != "silu":
         raise ValueError(f"{mt} activation {act!r} is not supported (silu only)")
     if d % Hq or d // Hq not in LLAMA_HEAD_DIMS or int(cfg.get("head_dim") or d // Hq) != d // Hq:
-        raise ValueError(f"head dim {cfg.get('head_dim') or d}/{Hq} is not supported (hidden_size / heads, one of {LLAMA_HEAD_DIMS})")
+        hint = ""
+        if mt == "qwen3":
+            hint = ("; Qwen3-1.7B, 8B and 14B have head_dim = hidden_size / heads, Qwen3-0.6B, 4B and 32B a head_dim of its own, "
+                    "which is not supported")
+        raise ValueError(f"head dim {cfg.get('head_dim') or d}/{Hq} is not supported (hidden_size / heads, one of "
+                         f"{LLAMA_HEAD_DIMS}){hint}")
+    if mt in QK_NORM_MODEL_TYPES and cfg.get("attention_bias"):
+        raise ValueError(f"{mt} with attention_bias=True is not supported (the q / k norm epilogue adds no bias)")
     if Hkv < 1 or Hq % Hkv:
         raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
     ffn = int(cfg["intermediate_size"])
@@ -641,7 +654,7 @@ def llama_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
         raise ValueError(f"max_positions {cap} < 1")
     return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
                 vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-6)),
-                tied=bool(cfg.get("tie_word_embeddings", False)))
+                tied=bool(cfg.get("tie_word_embeddings", False)), qk_norm=mt in QK_NORM_MODEL_TYPES)
 
 
 def head_dim_perm(hd: int) -> np.ndarray:
@@ -666,9 +679,11 @@ def gate_up_row_perm(ffn: int) -> np.ndarray:
 
 
 def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
-    """Tensors in the layout of b2t_clm_llama_t from a Llama / Mistral / Qwen2 state dict, on the device the state dict is on
-    (the CPU for a checkpoint read from disk): fp16 embed_tokens, lm_head (the same tensor when tied), final_norm_w,
+    """Tensors in the layout of b2t_clm_llama_t from a Llama / Mistral / Qwen2 / Qwen3 state dict, on the device the state dict
+    is on (the CPU for a checkpoint read from disk): fp16 embed_tokens, lm_head (the same tensor when tied), final_norm_w,
     layers.<i>.<field> (qkv_b absent when the model has no q / k / v biases), and the fp32 rope_cos / rope_sin tables (CPU).
+    With dims["qk_norm"] (Qwen3) also layers.<i>.q_norm_w / k_norm_w, the [hd] weights of b2t_clm_qknorm_t, under
+    head_dim_perm like the q and k rows they scale; q / k / v biases are then refused.
     dtype=torch.bfloat16 (clm_dtype's spellings) makes the weights bf16 in the same layout: a bf16 checkpoint's values are
     kept exactly, an fp32 or fp16 one is rounded to nearest even."""
     import torch
@@ -692,6 +707,8 @@ def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=Non
     cos, sin = rope_tables(inv_freq, dims["max_pos"])
     out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
     qperm = torch.from_numpy(qkv_row_perm(Hq, Hkv, hd)).to(dev)
+    hperm = torch.from_numpy(head_dim_perm(hd)).to(dev)
+    qk_norm = bool(dims.get("qk_norm", False))
     gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
     widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
     for i in range(dims["n_layers"]):
@@ -706,6 +723,13 @@ def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=Non
              "gate_up_w": _pad_rows(torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))],
                                               0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
              "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
+        if qk_norm:
+            if any(p + f"self_attn.{n}.bias" in sd for n in widths):
+                raise ValueError(f"{p}self_attn: q / k / v biases beside q / k norms are not supported")
+            L["q_norm_w"] = get(p + "self_attn.q_norm.weight", (hd,))[hperm].contiguous()
+            L["k_norm_w"] = get(p + "self_attn.k_norm.weight", (hd,))[hperm].contiguous()
+        elif p + "self_attn.q_norm.weight" in sd or p + "self_attn.k_norm.weight" in sd:
+            raise ValueError(f"{p}self_attn: q / k norm weights in a model that is not one of {QK_NORM_MODEL_TYPES}")
         if any(p + f"self_attn.{n}.bias" in sd for n in widths):
             zero = lambda w: torch.zeros(w, dtype=wdt, device=dev)
             L["qkv_b"] = torch.cat([get(p + f"self_attn.{n}.bias", (w,)) if p + f"self_attn.{n}.bias" in sd else zero(w)
@@ -742,7 +766,10 @@ class LlamaScorer(_Scorer):
     dtype: None or "float16" computes in fp16; "bfloat16" computes in bf16, the format these families are published in
     (b2t_clm_llama_score_bf16 / b2t_clm_llama_score_tree_bf16: the same contract with bf16 roundings, no fp16 overflow or
     underflow of weights and activations, about ten times the rounding error).  The arrays must already have that dtype
-    (llama_device_layout(..., dtype=...)); `self.dtype` is the torch dtype.  bfloat16 with a context cache is refused."""
+    (llama_device_layout(..., dtype=...)); `self.dtype` is the torch dtype.  bfloat16 with a context cache is refused.
+
+    Arrays that hold layers.<i>.q_norm_w / k_norm_w (a Qwen3 layout) make the scorer take the b2t_clm_qwen3_* entry points, which
+    norm every q and k head in the QKV GEMM's epilogue, on all those paths; sizes and the cache are the Llama calls'."""
 
     _WS_BYTES = "b2t_clm_llama_ws_bytes"
     _NO_CACHE = "use_cache=True on a scorer built without a context cache (context_cache_tokens)"
@@ -775,6 +802,14 @@ class LlamaScorer(_Scorer):
                                    dims["vocab"], dims["max_pos"], dims["rms_eps"], self.w["embed_tokens"].data_ptr(),
                                    self.w["lm_head"].data_ptr(), self.w["final_norm_w"].data_ptr(),
                                    self.w["rope_cos"].data_ptr(), self.w["rope_sin"].data_ptr(), self._layers)
+        # Qwen3: the per-layer q / k norm weights (b2t_clm_qknorm_t) go in front of the lists
+        self._family, self._qk = "llama", ()
+        if dims["n_layers"] > 0 and "layers.0.q_norm_w" in self.w:
+            self._qkn = (N.ClmQkNorm * dims["n_layers"])()
+            for i in range(dims["n_layers"]):
+                self._qkn[i].q_norm_w = self.w[f"layers.{i}.q_norm_w"].data_ptr()
+                self._qkn[i].k_norm_w = self.w[f"layers.{i}.k_norm_w"].data_ptr()
+            self._family, self._qk = "qwen3", (self._qkn,)
         self._ws = None
         self._alloc_cache(context_cache_tokens)
 
@@ -805,16 +840,17 @@ class LlamaScorer(_Scorer):
         import ctypes as C
         import b2t_native as N
         desc = C.byref(self.desc)
+        pre = f"b2t_clm_{self._family}_score_"
         if path == "cached":
-            N.check(lib.b2t_clm_llama_score_tree_cached_f16(desc, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq,
-                                                            scores, tok, None, None, ws, ws_bytes, stream),
-                    "b2t_clm_llama_score_tree_cached_f16")
+            name = pre + "tree_cached_f16"
+            N.check(getattr(lib, name)(desc, *self._qk, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq,
+                                       scores, tok, None, None, ws, ws_bytes, stream), name)
         elif path == "tree":
-            name = "b2t_clm_llama_score_tree_" + self._suffix
-            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream), name)
+            name = pre + "tree_" + self._suffix
+            N.check(getattr(lib, name)(desc, *self._qk, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream), name)
         else:
-            name = "b2t_clm_llama_score_" + self._suffix
-            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
+            name = pre + self._suffix
+            N.check(getattr(lib, name)(desc, *self._qk, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
 
 
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
@@ -852,7 +888,7 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
 
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", LlamaScorer for "llama",
-    "mistral" and "qwen2"; anything else is refused.  max_positions caps a Llama-family model's rotary table.  dtype (clm_dtype):
+    "mistral", "qwen2" and "qwen3"; anything else is refused.  max_positions caps a Llama-family model's rotary table.  dtype (clm_dtype):
     None or "float16", "bfloat16" (the Llama family only, and without a context cache), or "auto" = the dtype config.json says
     the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
     refused is refused before any weight is read."""
@@ -875,7 +911,7 @@ def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", sha
               max_positions=None, dtype=None):
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
-    OptScorer, or a LlamaScorer for a Llama / Mistral / Qwen2 directory (build_scorer).
+    OptScorer, or a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

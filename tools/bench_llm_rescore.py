@@ -37,6 +37,14 @@ nbest / --context the flat call against the tree call, with --session the sessio
 bf16 weights against HF's model in bf16.  The cached path has no bf16 form yet, so --session stays float16.
 
   python tools/bench_llm_rescore.py --arch llama --dtype bfloat16 [--tree --context 64]
+
+`--arch qwen3` runs Qwen3's path (b2t_clm_qwen3_score_*: the Llama forward with the q / k RMSNorm in the QKV GEMM's epilogue)
+under the protocol of --arch llama, against HF's Qwen3ForCausalLM, at the Qwen3-8B shape: 36 layers, d 4096, 32 query / 8 kv
+heads of 128, ffn 12288, vocab 151936, untied head.  What the norm costs is this run beside --arch llama forced to the same
+dimensions, the two alternating process by process:
+
+  python tools/bench_llm_rescore.py --arch qwen3 --lists 7
+  python tools/bench_llm_rescore.py --arch llama --layers 36 --ffn 12288 --vocab 151936 --lists 7
 """
 import argparse
 import json
@@ -73,15 +81,16 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("opt", "llama"), default="opt", help="opt: OPT-6.7b shape; llama: Llama-3-8B shape")
+    ap.add_argument("--arch", choices=("opt", "llama", "qwen3"), default="opt",
+                    help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape")
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16",
-                    help="--arch llama: the compute dtype of the scorer and of the HF model beside it")
-    ap.add_argument("--layers", type=int, default=32)
+                    help="--arch llama / qwen3: the compute dtype of the scorer and of the HF model beside it")
+    ap.add_argument("--layers", type=int, default=None, help="default 32 (opt, llama), 36 (qwen3)")
     ap.add_argument("--d", type=int, default=4096)
     ap.add_argument("--heads", type=int, default=32)
-    ap.add_argument("--kv-heads", type=int, default=8, help="--arch llama: key / value heads")
-    ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama)")
-    ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama)")
+    ap.add_argument("--kv-heads", type=int, default=8, help="--arch llama / qwen3: key / value heads")
+    ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama), 12288 (qwen3)")
+    ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama), 151936 (qwen3)")
     ap.add_argument("--cands", type=int, default=100)
     ap.add_argument("--lists", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -92,11 +101,12 @@ def main():
     ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
     ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
-    a.ffn = a.ffn or (14336 if a.arch == "llama" else 16384)
-    a.vocab = a.vocab or (128256 if a.arch == "llama" else 50272)
-    if a.dtype != "float16" and (a.arch != "llama" or a.session):
-        ap.error("--dtype bfloat16 needs --arch llama and has no --session")
-    if a.arch == "llama":
+    a.layers = a.layers or (36 if a.arch == "qwen3" else 32)
+    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288}[a.arch]
+    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936}[a.arch]
+    if a.dtype != "float16" and (a.arch == "opt" or a.session):
+        ap.error("--dtype bfloat16 needs --arch llama or qwen3 and has no --session")
+    if a.arch != "opt":
         return main_llama(a)
     import torch
     import torch.nn.functional as F
@@ -181,8 +191,8 @@ def main():
 
 
 def main_llama(a):
-    """--arch llama: the lists and the protocol of main() with a LlamaScorer, and HF's model in the same dtype (--dtype) as
-    the torch side."""
+    """--arch llama / qwen3: the lists and the protocol of main() with a LlamaScorer, and HF's model in the same dtype (--dtype)
+    as the torch side."""
     import torch
     import transformers
     import llm_rescore as R
@@ -193,16 +203,21 @@ def main_llama(a):
     rng = np.random.default_rng(0)
     max_pos = 2048
     calls = session_calls(a, rng, max_pos) if a.session else None   # before the model is built
-    cfg = transformers.LlamaConfig(hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, intermediate_size=ffn,
-                                   vocab_size=V, num_hidden_layers=L, max_position_embeddings=max_pos, rms_norm_eps=1e-5,
-                                   tie_word_embeddings=False, attn_implementation="sdpa",
-                                   rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
-                                                     original_max_position_embeddings=8192, rope_theta=500000.0))
+    if a.arch == "qwen3":
+        cfg = transformers.Qwen3Config(hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, head_dim=d // H,
+                                       intermediate_size=ffn, vocab_size=V, num_hidden_layers=L, max_position_embeddings=max_pos,
+                                       rms_norm_eps=1e-6, tie_word_embeddings=False, attn_implementation="sdpa")
+    else:
+        cfg = transformers.LlamaConfig(hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, intermediate_size=ffn,
+                                       vocab_size=V, num_hidden_layers=L, max_position_embeddings=max_pos, rms_norm_eps=1e-5,
+                                       tie_word_embeddings=False, attn_implementation="sdpa",
+                                       rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                                         original_max_position_embeddings=8192, rope_theta=500000.0))
     old = torch.get_default_dtype()
     torch.set_default_dtype(dt)
     try:
         with torch.device(dev):
-            model = transformers.LlamaForCausalLM(cfg).eval()
+            model = (transformers.Qwen3ForCausalLM if a.arch == "qwen3" else transformers.LlamaForCausalLM)(cfg).eval()
     finally:
         torch.set_default_dtype(old)
     with torch.no_grad():   # HF's init (std 0.02) gives a flat distribution; widths as in the OPT rows
@@ -217,7 +232,7 @@ def main_llama(a):
     if a.session:
         del model
         torch.cuda.empty_cache()
-        return session(a, sc, *calls, arch="llama")
+        return session(a, sc, *calls, arch=a.arch)
     ab = a.tree or a.list != "random" or a.context > 0
     if not ab:
         lists = [random_list(rng, V, a.cands) for _ in range(a.lists)]
@@ -228,7 +243,7 @@ def main_llama(a):
     if ab:
         del model
         torch.cuda.empty_cache()
-        return ab_flat_tree(a, sc, lists, ntok, arch="llama")
+        return ab_flat_tree(a, sc, lists, ntok, arch=a.arch)
 
     def torch_score(seqs):   # padded batch through the HF model, in --dtype
         B, T = len(seqs), max(len(s) for s in seqs)
@@ -260,7 +275,7 @@ def main_llama(a):
     flop_tok = 2 * (L * (d * (H + 2 * Hkv) * hd + d * d + 3 * d * ffn) + d * V)
     r2 = lambda x: round(float(x), 2)
     mh, mt = float(np.mean(ms_hip)), float(np.mean(ms_torch))
-    print(json.dumps({"bench": "llm_rescore", "arch": "llama", "dtype": a.dtype, "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn,
+    print(json.dumps({"bench": "llm_rescore", "arch": a.arch, "dtype": a.dtype, "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn,
                       "vocab": V, "cands": a.cands, "tokens_per_list": float(np.mean(ntok)), "hip_ms_per_list": r2(mh),
                       "torch_fp16_ms_per_list": r2(mt), "hip_tflops": round(np.mean(ntok) * flop_tok / (mh * 1e-3) / 1e12, 1),
                       "speedup_vs_torch": round(mt / mh, 3), "max_abs_score_diff_vs_torch": round(diff, 4),
