@@ -712,6 +712,33 @@ int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache
                                   float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
                                   void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same scoring for GPT-2 (csrc/causal_lm_gpt2.hip) ------------------------------------------------------------
+ * HF GPT2LMHeadModel (distilgpt2, gpt2, gpt2-medium, gpt2-large, gpt2-xl), the family the reference's rescore_with_gpt2 and
+ * gpt2_lm_decode are named after.  Behind the loader GPT-2 is the pre-LN OPT forward above: LayerNorm with eps 1e-5, learned
+ * positions, biased projections, q scaled by head_dim^-0.5, a tied head.  The model is the same b2t_clm_t / b2t_clm_layer_t
+ * in the same layout (nejm-brain-to-text_amd/llm_rescore.py, gpt2_device_layout): the checkpoint's Conv1D weights [in][out]
+ * are transposed to [N][K] rows, c_attn becomes qkv_w with rows q | k | v, c_fc / mlp.c_proj are fc1 / fc2, ln_f the final
+ * LayerNorm, and embed_positions is [max_pos + 2][d] = two zero rows in front of wpe (the embed kernel reads row pos + 2).
+ * One thing differs in arithmetic: the MLP activation.  On the fc1 GEMM's fp32 accumulator plus bias v,
+ *   gelu_new(v) = 0.5 v (1 + tanh(sqrt(2 / pi) (v + 0.044715 v^3)))   ("gelu_new" = "gelu_pytorch_tanh"; not the erf GELU)
+ * in fp32, then the one rounding to fp16, in the GEMM's epilogue.  Saturated pre-activations give v (positive side) or
+ * -0.0 / 0 (negative side), never NaN.  Numerics otherwise as b2t_clm_score_f16; rounded to fp16 once each: the LayerNorm
+ * outputs, q (after bias and head_dim^-0.5), k, v, P per 32-key block, the attention output and gelu_new(fc1).
+ * Arguments, output layout, refusals before any launch, update semantics of the cache, B2T_CLM_GEMM_256 and
+ * B2T_CLM_TRUNK_ATTN are those of b2t_clm_score_f16 / b2t_clm_score_tree_f16 / b2t_clm_score_tree_cached_f16; messages carry
+ * the entry point's own name.  The three calls are bit-identical to each other.  Sizes are the OPT size functions':
+ * b2t_clm_ws_bytes, b2t_clm_tree_ws_bytes, b2t_clm_cache_kv_bytes, b2t_clm_tree_cached_ws_bytes; the plan and the cache rule
+ * are b2t_clm_tree_plan_host and b2t_clm_cache_plan_host; the cache is the same b2t_clm_cache_t. */
+int b2t_clm_gpt2_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                           float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_gpt2_score_tree_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                float* scores_out, float* tok_logp_out, long long* n_nodes_out,
+                                void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_gpt2_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache, int update,
+                                       const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                       float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
+                                       void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the same scoring for the Llama family (csrc/causal_lm_llama.hip; its attention kernels are the OPT paths', ------
  * csrc/causal_lm.hip and csrc/causal_lm_tree.hip, on the row q[Hq hd] | k[Hkv hd] | v[Hkv hd]) ---------------------------
  * HF LlamaForCausalLM, MistralForCausalLM and Qwen2ForCausalLM: RMSNorm, rotary positions (rotate-half convention),

@@ -258,6 +258,9 @@ _SIGNATURES = {
     "b2t_clm_llama_score_tree_cached_f16": (C.c_int, [C.POINTER(ClmLlamaDesc), C.POINTER(ClmCache), C.c_int, VP, VP, C.c_int,
                                                       VP, VP, C.POINTER(LL), C.POINTER(C.c_int), VP, C.c_size_t, VP]),
 }
+# GPT-2: the OPT twin's list (same model, same cache)
+for _t in ("score_f16", "score_tree_f16", "score_tree_cached_f16"):
+    _SIGNATURES["b2t_clm_gpt2_" + _t] = _SIGNATURES["b2t_clm_" + _t]
 # Qwen3: the Llama twin's list with the q / k norm array after the model
 for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16", "score_tree_cached_f16"):
     _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]

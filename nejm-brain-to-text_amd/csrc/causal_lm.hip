@@ -25,7 +25,8 @@
 //
 // The host-side pieces the other paths (causal_lm_tree.hip, causal_lm_cache.hip, causal_lm_llama.hip) reuse -- launch_gemm,
 // the embed / LayerNorm / attention / head launchers, clm_check_model, the list check, the workspace layout and the flat
-// index builder -- have external linkage and are declared in clm_internal.h, which also holds the layer loop (clm_forward).
+// index builder -- have external linkage and are declared in clm_internal.h, which also holds the layer loop (clm_forward)
+// and the body of the flat entry point (clm_score_flat; GPT-2, causal_lm_gpt2.hip, enters it with its own fc1 launcher).
 // The kernels stay private to this file: the GEMM's template is clm_gemm.h, instantiated here for the four epilogues of this
 // forward; the attention's arithmetic and clm_attn_kernel itself are clm_attn.h's templates (instantiated here in fp16 for
 // head dims 64, 80 and 128, behind clm_launch_attn), and the kernel serves the Llama family's row layout too.
@@ -263,23 +264,6 @@ extern "C" size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, i
 
 extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                  float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "b2t_clm_score_f16";
-  if (int rc = clm_check_model(model)) return rc;
-  const b2t_clm_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  const ClmLayout L = clm_opt_layout(model, M, M - n_seq, flat_ints(M, n_seq));
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  const hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  ClmFlatIndex ix;
-  if (int rc = clm_build_flat_index("b2t_clm_score_f16 upload", ids_host, seq_off_host, n_seq, reinterpret_cast<int*>(base + L.ints),
-                                    s, &ix))
-    return rc;
-  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
-    return clm_launch_attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
-  };
-  if (int rc = clm_forward(m, ix.run, L, base, attn, s)) return rc;
-  return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
+  return clm_score_flat("b2t_clm_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws, ws_bytes,
+                        as_stream(stream), &launch_gemm<EP_RELU>);
 }

@@ -169,26 +169,6 @@ extern "C" size_t b2t_clm_tree_ws_bytes(const b2t_clm_t* model, long long n_node
 extern "C" int b2t_clm_score_tree_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                       float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                                       void* stream) {
-  const char* who = "b2t_clm_score_tree_f16";
-  if (int rc = clm_check_model(model)) return rc;
-  const b2t_clm_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);
-  const long long Mn = plan.Mn;
-  if (n_nodes_out) *n_nodes_out = Mn;
-  const ClmLayout L = clm_opt_layout(model, Mn, Mn, tree_ints(Mn, M, n_seq));
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  const hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  ClmTreeIndex ix;
-  if (int rc = clm_build_tree_index("b2t_clm_score_tree_f16 upload", ids_host, seq_off_host, n_seq, plan, 0,
-                                    reinterpret_cast<int*>(base + L.ints), s, &ix))
-    return rc;
-  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
-    return clm_launch_attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
-  };
-  if (int rc = clm_forward(m, ix.run, L, base, attn, s)) return rc;
-  return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
+  return clm_score_tree("b2t_clm_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_nodes_out, ws,
+                        ws_bytes, as_stream(stream), &launch_gemm<EP_RELU>);
 }

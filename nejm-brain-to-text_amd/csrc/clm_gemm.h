@@ -4,7 +4,8 @@
 // global and LDS traffic does not): a translation unit instantiates what it launches -- causal_lm.hip the four epilogues of
 // the OPT forward in fp16 (its launch_gemm serves the tree and cache paths too), causal_lm_llama.hip the two of the Llama
 // family in fp16 (rotary embedding on q | k, SwiGLU), causal_lm_llama_bf16.hip the four of the Llama forward in bf16,
-// causal_lm_qwen3.hip the one Qwen3 adds (EP_QKNORM_ROPE: the per-head q / k RMSNorm in front of the rotation) in both.  Which
+// causal_lm_qwen3.hip the one Qwen3 adds (EP_QKNORM_ROPE: the per-head q / k RMSNorm in front of the rotation) in both,
+// causal_lm_gpt2.hip the one GPT-2 adds (EP_GELU: gelu_new where OPT's fc1 has ReLU) in fp16.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -29,6 +30,15 @@ __device__ __forceinline__ float warp32_sum(float v) {
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// gelu_new (GPT-2's tanh form): 0.5 v (1 + tanh(u)), u = sqrt(2 / pi) (v + 0.044715 v^3), in fp32.  tanh(u) is written
+// 1 - 2 / (exp(2u) + 1): exp(2u) = inf gives 1 and exp(2u) = 0 gives -1, so a saturated pre-activation yields v or -0.0 / 0,
+// never inf / inf; expf is the full-range one (no scratch, no call).
+__device__ __forceinline__ float gelu_new(float v) {
+  const float u = 0.7978845608028654f * (v + 0.044715f * v * v * v);
+  const float th = 1.0f - 2.0f / (expf(2.0f * u) + 1.0f);
+  return 0.5f * v * (1.0f + th);
 }
 
 // BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.  E is the element type of
@@ -258,6 +268,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
           g.resid[off] += v;
         } else {
           if (EP == EP_RELU) v = fmaxf(v, 0.f);
+          else if (EP == EP_GELU) v = gelu_new(v);
           else v *= sc;
           out16[off] = (E)v;
         }

@@ -1,6 +1,7 @@
 // clm_internal.h — what the units of the causal-LM forward share (the four fp16 units named below; causal_lm_llama_bf16.hip,
 // the Llama family in bf16, uses the element-type trait ClmElem, ClmGemm, the tile rule, the head and the index builders;
-// causal_lm_qwen3.hip, Qwen3 in both formats, the same and clm_score_tree_cached).  causal_lm.hip (the flat OPT path) defines the tile rule,
+// causal_lm_qwen3.hip, Qwen3 in both formats, the same and clm_score_tree_cached; causal_lm_gpt2.hip, GPT-2, the OPT forward
+// and entry-point bodies below with its own fc1 GEMM).  causal_lm.hip (the flat OPT path) defines the tile rule,
 // the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
 // list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
 // and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
@@ -11,6 +12,7 @@
 // cached entry point of both families behind their model checks, are at the end.
 #pragma once
 #include <math.h>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -25,7 +27,9 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 //   EP_SWIGLU out16[r][c0 / 2 + i] = silu(C[r][c0 + i]) * C[r][c0 + 32 + i], c0 a multiple of 64, i < 32 (ldo = N / 2).
 // EP_QKNORM_ROPE (Qwen3) is EP_ROPE without a bias and with an RMSNorm over every q and k head of a row in front of the rotation:
 //   x[c] * rsqrt(mean over the head of x^2 + rms_eps) * w[c % hd], w = qnorm_w (columns < qcols) or knorm_w (< rope_cols).
-enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6 };
+// EP_GELU (GPT-2) is EP_RELU with gelu_new in ReLU's place: out16[r][c] = gelu_new(C[r][c] + bias[c]), gelu_new(v) =
+//   0.5 v (1 + tanh(sqrt(2 / pi) (v + 0.044715 v^3))) in fp32, rounded once.
+enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6, EP_GELU = 7 };
 
 using f32x16 = float __attribute__((ext_vector_type(16)));
 
@@ -175,9 +179,12 @@ inline int clm_head(const void* x16, const void* W, int vocab, int d, const ClmR
 }
 
 // The pre-LN OPT forward over r.rows rows up to the per-row log-probs logp[r.Mh] (base + L.logp); attn(layer, qkv, out)
-// enqueues one layer's attention from qkv ([rows][3d]) into out ([rows][d]).
+// enqueues one layer's attention from qkv ([rows][3d]) into out ([rows][d]).  `fc1` launches the fc1 GEMM with the family's
+// activation in its epilogue: OPT's ReLU (the default), or GPT-2's gelu_new (causal_lm_gpt2.hip) -- the families differ in
+// nothing else behind the loader.
 template <class Attn>
-int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s) {
+int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
+                ClmGemmLaunch fc1 = &launch_gemm<EP_RELU>) {
   const int d = m.d_model, hd = d / m.n_heads, F = m.ffn_dim, M = (int)r.rows;
   float* resid = reinterpret_cast<float*>(base + L.resid);
   _Float16* x16 = reinterpret_cast<_Float16*>(base + L.x16);
@@ -199,7 +206,7 @@ int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* b
     if (int rc = clm_launch_layernorm(resid, nullptr, r.rows, H16(w.ln2_w), H16(w.ln2_b), x16, d, s)) return rc;
     g = ClmGemm{};
     g.A = x16; g.B = H16(w.fc1_w); g.M = M; g.N = F; g.K = d; g.bias = H16(w.fc1_b); g.out16 = hb; g.ldo = F;
-    if (int rc = launch_gemm<EP_RELU>(g, s)) return rc;
+    if (int rc = fc1(g, s)) return rc;
     g = ClmGemm{};
     g.A = hb; g.B = H16(w.fc2_w); g.M = M; g.N = d; g.K = F; g.bias = H16(w.fc2_b); g.resid = resid; g.ldo = d;
     if (int rc = launch_gemm<EP_RESID>(g, s)) return rc;
@@ -207,6 +214,56 @@ int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* b
   if (r.Mh <= 0) return 0;
   if (int rc = clm_launch_layernorm(resid, r.d_src, r.Mh, H16(m.final_ln_w), H16(m.final_ln_b), x16, d, s)) return rc;
   return clm_head(x16, H16(m.embed_tokens), m.vocab, d, r, L, base, s);   // the head is tied to embed_tokens
+}
+
+// What the flat and the tree entry point of this forward do behind their names (b2t_clm_score_f16 / b2t_clm_score_tree_f16, and
+// GPT-2's twins with their own fc1): the checks, the index build, the layout, the forward and the sums.  `who` is the entry
+// point's name in every message.
+inline int clm_score_flat(const char* who, const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                          float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, hipStream_t s, ClmGemmLaunch fc1) {
+  if (int rc = clm_check_model(model)) return rc;
+  const b2t_clm_t& m = *model;
+  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
+  const long long M = seq_off_host[n_seq];
+  const ClmLayout L = clm_opt_layout(model, M, M - n_seq, flat_ints(M, n_seq));
+  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
+  char* base = static_cast<char*>(ws);
+  ClmFlatIndex ix;
+  const std::string upload = std::string(who) + " upload";
+  if (int rc = clm_build_flat_index(upload.c_str(), ids_host, seq_off_host, n_seq, reinterpret_cast<int*>(base + L.ints), s, &ix))
+    return rc;
+  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
+    return clm_launch_attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
+  };
+  if (int rc = clm_forward(m, ix.run, L, base, attn, s, fc1)) return rc;
+  return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
+}
+
+inline int clm_score_tree(const char* who, const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                          float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes, hipStream_t s,
+                          ClmGemmLaunch fc1) {
+  if (int rc = clm_check_model(model)) return rc;
+  const b2t_clm_t& m = *model;
+  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
+  const long long M = seq_off_host[n_seq];
+  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);
+  const long long Mn = plan.Mn;
+  if (n_nodes_out) *n_nodes_out = Mn;
+  const ClmLayout L = clm_opt_layout(model, Mn, Mn, tree_ints(Mn, M, n_seq));
+  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
+  char* base = static_cast<char*>(ws);
+  ClmTreeIndex ix;
+  const std::string upload = std::string(who) + " upload";
+  if (int rc = clm_build_tree_index(upload.c_str(), ids_host, seq_off_host, n_seq, plan, 0, reinterpret_cast<int*>(base + L.ints),
+                                    s, &ix))
+    return rc;
+  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
+    return clm_launch_attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
+  };
+  if (int rc = clm_forward(m, ix.run, L, base, attn, s, fc1)) return rc;
+  return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
 }
 
 // ---- the context cache (causal_lm_cache.hip) ----

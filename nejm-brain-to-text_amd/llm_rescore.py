@@ -1,4 +1,4 @@
-"""LLM n-best rescoring (OPT, and the Llama family: Llama, Mistral, Qwen2, Qwen3): the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
+"""LLM n-best rescoring (OPT, GPT-2, and the Llama family: Llama, Mistral, Qwen2, Qwen3): the LLM stage of language_model/language-model-standalone.py (build_opt :92-124, rescore_with_gpt2
 :127-162, gpt2_lm_decode :165-251, get_string_differences :273-311, augment_nbest :327-411) with the causal-LM forward on the
 HIP path (b2t_clm_score_f16, csrc/causal_lm.hip; opt-in b2t_clm_score_tree_f16, csrc/causal_lm_tree.hip, which computes the
 prefixes the candidates share once; opt-in b2t_clm_score_tree_cached_f16, csrc/causal_lm_cache.hip, which also keeps the
@@ -25,6 +25,11 @@ The default stays fp16; OPT is fp16 only.
 and the rotation, which runs in the QKV GEMM's epilogue (b2t_clm_qwen3_score_f16 / _tree_f16 / _tree_cached_f16 / _bf16 /
 _tree_bf16, csrc/causal_lm_qwen3.hip).  The loader adds the norm weights to the layout and the scorer takes those entry points
 when its arrays hold them.  Checkpoints whose head_dim is not hidden_size / heads (Qwen3-0.6B, 4B, 32B) are refused.
+
+"gpt2" (distilgpt2, gpt2, -medium, -large, -xl) gives a `Gpt2Scorer`, an OptScorer on the entry points b2t_clm_gpt2_score_f16 /
+_tree_f16 / _tree_cached_f16 (csrc/causal_lm_gpt2.hip): behind the loader (Conv1D weights transposed, c_attn split into q | k | v
+rows, wpe behind two zero rows) GPT-2 is the OPT forward with gelu_new in the fc1 GEMM's epilogue where OPT has ReLU.  fp16
+only.  The GPT-2 tokenizer prepends no BOS, so a candidate's first token is unscored, as in the reference.
 """
 from __future__ import annotations
 
@@ -467,12 +472,14 @@ class OptScorer(_Scorer):
 
     _WS_BYTES = "b2t_clm_ws_bytes"
     _NO_CACHE = "use_cache=True on a scorer built without context_cache_tokens"
+    _ENTRY = "b2t_clm_"   # the family's entry points: _ENTRY + score_f16 / score_tree_f16 / score_tree_cached_f16
+    _dtype_of = staticmethod(lambda dtype: opt_dtype(dtype))
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0, dtype=None):
         import torch
         import b2t_native as N
-        self.dtype = opt_dtype(dtype)   # fp16 alone: bfloat16 is refused
+        self.dtype = self._dtype_of(dtype)   # fp16 alone: bfloat16 is refused
         self.dims = dict(dims)
         self.device = torch.device(device)
         self.share_prefixes = bool(share_prefixes)
@@ -508,14 +515,15 @@ class OptScorer(_Scorer):
         import b2t_native as N
         desc = C.byref(self.desc)
         if path == "cached":
-            N.check(lib.b2t_clm_score_tree_cached_f16(desc, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq,
-                                                      scores, tok, None, None, ws, ws_bytes, stream),
-                    "b2t_clm_score_tree_cached_f16")
+            name = self._ENTRY + "score_tree_cached_f16"
+            N.check(getattr(lib, name)(desc, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq, scores, tok, None,
+                                       None, ws, ws_bytes, stream), name)
         elif path == "tree":
-            N.check(lib.b2t_clm_score_tree_f16(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream),
-                    "b2t_clm_score_tree_f16")
+            name = self._ENTRY + "score_tree_f16"
+            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream), name)
         else:
-            N.check(lib.b2t_clm_score_f16(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), "b2t_clm_score_f16")
+            name = self._ENTRY + "score_f16"
+            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
 
 
 # ---- the compute dtype ----------------------------------------------------------------------------------------------------
@@ -553,12 +561,116 @@ def opt_dtype(dtype, cfg: Optional[dict] = None):
     return torch.float16
 
 
+def gpt2_dtype(dtype, cfg: Optional[dict] = None):
+    """clm_dtype for a GPT-2 checkpoint, which computes in fp16 alone, as OPT does ("auto" is fp16 whatever the config says)."""
+    import torch
+    if dtype == "auto":
+        return torch.float16
+    if clm_dtype(dtype, cfg) != torch.float16:
+        raise ValueError("Gpt2Scorer: dtype 'bfloat16' is not supported for GPT-2 checkpoints (they are published in float32 and "
+                         "the reference loads them in float16); the Llama family has a bfloat16 mode")
+    return torch.float16
+
+
 def llama_check_dtype_cache(dtype, context_cache_tokens) -> None:
     """Refuses bfloat16 together with a context cache: the cached path exists in fp16 only."""
     import torch
     if dtype == torch.bfloat16 and int(context_cache_tokens) > 0:
         raise ValueError("LlamaScorer: dtype 'bfloat16' with context_cache_tokens > 0 is not supported yet: the context cache "
                          "behind bfloat16 is the follow-up to the bfloat16 mode; use dtype 'float16' or context_cache_tokens=0")
+
+
+# ---- GPT-2 (HF GPT2LMHeadModel) ------------------------------------------------------------------------------------------
+GPT2_ACTIVATIONS = ("gelu_new", "gelu_pytorch_tanh")   # two names of 0.5 v (1 + tanh(sqrt(2 / pi) (v + 0.044715 v^3)))
+
+
+def gpt2_dims(cfg: dict) -> dict:
+    """The dimensions b2t_clm_t needs from a GPT-2 config.json, after refusing what the kernels do not run.  Behind the loader
+    GPT-2 is the pre-LN OPT forward with gelu_new in the fc1 GEMM's epilogue (csrc/causal_lm_gpt2.hip)."""
+    act = cfg.get("activation_function", "gelu_new")
+    if act not in GPT2_ACTIVATIONS:
+        raise ValueError(f"gpt2 activation_function {act!r} is not supported ({' or '.join(GPT2_ACTIVATIONS)}: the tanh form; "
+                         '"gelu", the erf form, is a different function and is not built)')
+    if not cfg.get("scale_attn_weights", True):
+        raise ValueError("gpt2 with scale_attn_weights=False is not supported (q is scaled by head_dim^-0.5)")
+    if cfg.get("scale_attn_by_inverse_layer_idx", False):
+        raise ValueError("gpt2 with scale_attn_by_inverse_layer_idx=True is not supported")
+    if cfg.get("add_cross_attention", False):
+        raise ValueError("gpt2 with add_cross_attention=True is not supported")
+    eps = float(cfg.get("layer_norm_epsilon", 1e-5))
+    if eps != 1e-5:
+        raise ValueError(f"gpt2 layer_norm_epsilon {eps} is not supported (the LayerNorm kernel's eps is the constant 1e-5)")
+    d, heads = int(cfg["n_embd"]), int(cfg["n_head"])
+    if d % heads or d // heads not in HEAD_DIMS:
+        raise ValueError(f"head dim n_embd {d} / n_head {heads} is not supported (one of {HEAD_DIMS})")
+    ffn = int(cfg["n_inner"]) if cfg.get("n_inner") is not None else 4 * d
+    if d % 64 or ffn % 64:
+        raise ValueError(f"n_embd {d} and the ffn width (n_inner) {ffn} must be multiples of 64")
+    # reorder_and_upcast_attn changes where HF scales and in which format it multiplies, not the function: accepted either way
+    return dict(n_layers=int(cfg["n_layer"]), d_model=d, n_heads=heads, ffn_dim=ffn, vocab=int(cfg["vocab_size"]),
+                max_pos=int(cfg["n_positions"]))
+
+
+def gpt2_device_layout(state: dict, dims: dict) -> Dict[str, "object"]:
+    """Host (CPU) fp16 tensors in the layout of b2t_clm_t (device_layout's names) from a GPT2LMHeadModel state dict, keys with
+    or without the 'transformer.' prefix; the attn.bias / attn.masked_bias buffers of old checkpoints are ignored.  The
+    checkpoint's Conv1D weights are [in][out]: c_attn [d][3d] becomes qkv_w [3d][d] with rows q | k | v, and attn.c_proj,
+    mlp.c_fc, mlp.c_proj are transposed the same way to out_w, fc1_w, fc2_w; rows are padded to 256.  embed_positions is wpe
+    behind two zero rows (the embed kernel reads row position + 2, OPT's offset); ln_f is the final LayerNorm; the head is wte
+    (an lm_head that is not wte is refused).  fp32 checkpoints are rounded to fp16 once, as torch_dtype=float16 does."""
+    import torch
+    sd = {}
+    for k, v in state.items():
+        k = k[len("transformer."):] if k.startswith("transformer.") else k
+        if k.endswith(".attn.bias") or k.endswith(".attn.masked_bias"):
+            continue
+        sd[k] = v
+    d, ffn, V = dims["d_model"], dims["ffn_dim"], dims["vocab"]
+
+    def get(name, shape):
+        if name not in sd:
+            raise KeyError(f"GPT-2 checkpoint lacks {name}")
+        t = sd[name].detach().to("cpu", torch.float16).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+
+    def conv1d(name, n_in, n_out):   # Conv1D weight [in][out] -> nn.Linear rows [out][in], padded
+        return _pad_rows(get(name + ".weight", (n_in, n_out)).t().contiguous(), _rup(n_out, ROWPAD))
+    emb = get("wte.weight", (V, d))
+    if "lm_head.weight" in sd and not torch.equal(get("lm_head.weight", (V, d)), emb):
+        raise ValueError("GPT-2 checkpoint with an lm_head that is not wte (untied) is not supported")
+    wpe = get("wpe.weight", (dims["max_pos"], d))
+    out = {"embed_tokens": _pad_rows(emb, _rup(V, ROWPAD)),
+           "embed_positions": torch.cat([wpe.new_zeros((2, d)), wpe], 0).contiguous(),
+           "final_ln_w": get("ln_f.weight", (d,)), "final_ln_b": get("ln_f.bias", (d,))}
+    for i in range(dims["n_layers"]):
+        p = f"h.{i}."
+        L = {"ln1_w": get(p + "ln_1.weight", (d,)), "ln1_b": get(p + "ln_1.bias", (d,)),
+             "qkv_w": conv1d(p + "attn.c_attn", d, 3 * d), "qkv_b": get(p + "attn.c_attn.bias", (3 * d,)),
+             "out_w": conv1d(p + "attn.c_proj", d, d), "out_b": get(p + "attn.c_proj.bias", (d,)),
+             "ln2_w": get(p + "ln_2.weight", (d,)), "ln2_b": get(p + "ln_2.bias", (d,)),
+             "fc1_w": conv1d(p + "mlp.c_fc", d, ffn), "fc1_b": get(p + "mlp.c_fc.bias", (ffn,)),
+             "fc2_w": conv1d(p + "mlp.c_proj", ffn, d), "fc2_b": get(p + "mlp.c_proj.bias", (d,))}
+        for f in _LAYER_FIELDS:
+            out[f"layers.{i}.{f}"] = L[f]
+    return out
+
+
+def load_gpt2_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host fp16 tensors in the device layout) of the GPT-2 checkpoint in model_dir."""
+    dims = gpt2_dims(load_config(model_dir))
+    return dims, gpt2_device_layout(_load_state_dict(model_dir), dims)
+
+
+class Gpt2Scorer(OptScorer):
+    """A GPT-2 decoder on the GPU in the b2t_clm_t layout (gpt2_device_layout): OptScorer's constructor, `score` /
+    `token_logprobs`, share_prefixes and context cache, with the b2t_clm_gpt2_score_f16 / _tree_f16 / _tree_cached_f16 entry
+    points (csrc/causal_lm_gpt2.hip), whose fc1 GEMM applies gelu_new where OPT's applies ReLU.  Sizes and the cache are the
+    OPT calls'.  fp16 only, like OPT."""
+
+    _ENTRY = "b2t_clm_gpt2_"
+    _dtype_of = staticmethod(lambda dtype: gpt2_dtype(dtype))
 
 
 # ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM) ---------------------
@@ -887,7 +999,8 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
 
 
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
-    """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", LlamaScorer for "llama",
+    """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
+    only, like OPT), LlamaScorer for "llama",
     "mistral", "qwen2" and "qwen3"; anything else is refused.  max_positions caps a Llama-family model's rotary table.  dtype (clm_dtype):
     None or "float16", "bfloat16" (the Llama family only, and without a context cache), or "auto" = the dtype config.json says
     the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
@@ -898,20 +1011,25 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         wdt = opt_dtype(dtype, cfg)
         dims, arrays = load_opt_arrays(model_dir)
         return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
+    if mt == "gpt2":
+        wdt = gpt2_dtype(dtype, cfg)
+        dims, arrays = load_gpt2_arrays(model_dir)
+        return Gpt2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
     if mt in LLAMA_MODEL_TYPES:
         wdt = clm_dtype(dtype, cfg)
         llama_check_dtype_cache(wdt, context_cache_tokens)
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_llama_arrays(model_dir, max_positions, wdt)
         return LlamaScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    raise ValueError(f"model_type {mt!r} is not supported (opt, {', '.join(LLAMA_MODEL_TYPES)})")
+    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, {', '.join(LLAMA_MODEL_TYPES)})")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
               max_positions=None, dtype=None):
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
-    OptScorer, or a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory (build_scorer).
+    OptScorer, a Gpt2Scorer for a GPT-2 directory, or a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory
+    (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

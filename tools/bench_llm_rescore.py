@@ -45,6 +45,12 @@ dimensions, the two alternating process by process:
 
   python tools/bench_llm_rescore.py --arch qwen3 --lists 7
   python tools/bench_llm_rescore.py --arch llama --layers 36 --ffn 12288 --vocab 151936 --lists 7
+
+`--arch gpt2` runs GPT-2's path (b2t_clm_gpt2_score_f16 / _tree_f16 / _tree_cached_f16: the OPT forward with gelu_new in the fc1
+GEMM's epilogue) under the protocol of --arch llama, against HF's GPT2LMHeadModel in fp16, at the GPT-2 XL shape: 48 layers,
+d 1600, 25 heads of 64, ffn 6400, vocab 50257, 1024 positions, tied head.
+
+  python tools/bench_llm_rescore.py --arch gpt2 [--tree --context 64 | --session]
 """
 import argparse
 import json
@@ -81,16 +87,16 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("opt", "llama", "qwen3"), default="opt",
-                    help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape")
+    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2"), default="opt",
+                    help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape; gpt2: GPT-2 XL shape")
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16",
                     help="--arch llama / qwen3: the compute dtype of the scorer and of the HF model beside it")
-    ap.add_argument("--layers", type=int, default=None, help="default 32 (opt, llama), 36 (qwen3)")
-    ap.add_argument("--d", type=int, default=4096)
-    ap.add_argument("--heads", type=int, default=32)
+    ap.add_argument("--layers", type=int, default=None, help="default 32 (opt, llama), 36 (qwen3), 48 (gpt2)")
+    ap.add_argument("--d", type=int, default=None, help="default 4096, 1600 (gpt2)")
+    ap.add_argument("--heads", type=int, default=None, help="default 32, 25 (gpt2)")
     ap.add_argument("--kv-heads", type=int, default=8, help="--arch llama / qwen3: key / value heads")
-    ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama), 12288 (qwen3)")
-    ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama), 151936 (qwen3)")
+    ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama), 12288 (qwen3), 6400 (gpt2)")
+    ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama), 151936 (qwen3), 50257 (gpt2)")
     ap.add_argument("--cands", type=int, default=100)
     ap.add_argument("--lists", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -101,11 +107,15 @@ def main():
     ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
     ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
-    a.layers = a.layers or (36 if a.arch == "qwen3" else 32)
-    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288}[a.arch]
-    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936}[a.arch]
-    if a.dtype != "float16" and (a.arch == "opt" or a.session):
+    a.layers = a.layers or {"qwen3": 36, "gpt2": 48}.get(a.arch, 32)
+    a.d = a.d or (1600 if a.arch == "gpt2" else 4096)
+    a.heads = a.heads or (25 if a.arch == "gpt2" else 32)
+    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400}[a.arch]
+    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257}[a.arch]
+    if a.dtype != "float16" and (a.arch in ("opt", "gpt2") or a.session):
         ap.error("--dtype bfloat16 needs --arch llama or qwen3 and has no --session")
+    if a.arch == "gpt2":
+        return main_gpt2(a)
     if a.arch != "opt":
         return main_llama(a)
     import torch
@@ -229,6 +239,47 @@ def main_llama(a):
     dims = R.llama_dims(cj)
     sc = R.LlamaScorer(dims, R.llama_device_layout(model.state_dict(), dims, R.rope_inv_freq(cj), dtype=dt), dev,
                        context_cache_tokens=dims["max_pos"] if a.session else 0, dtype=dt)
+    hd = d // H
+    flop_tok = 2 * (L * (d * (H + 2 * Hkv) * hd + d * d + 3 * d * ffn) + d * V)
+    return against_hf(a, sc, model, calls, rng, flop_tok, {"kv_heads": Hkv})
+
+
+def main_gpt2(a):
+    """--arch gpt2: the lists and the protocol of main_llama() with a Gpt2Scorer and HF's GPT2LMHeadModel in fp16."""
+    import torch
+    import transformers
+    import llm_rescore as R
+    torch.manual_seed(0)
+    d, H, ffn, V, L = a.d, a.heads, a.ffn, a.vocab, a.layers
+    dev = "cuda"
+    rng = np.random.default_rng(0)
+    max_pos = 1024
+    calls = session_calls(a, rng, max_pos) if a.session else None   # before the model is built
+    cfg = transformers.GPT2Config(n_embd=d, n_head=H, n_layer=L, n_inner=ffn, n_positions=max_pos, vocab_size=V,
+                                  activation_function="gelu_new", attn_implementation="sdpa", bos_token_id=2, eos_token_id=2)
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float16)
+    try:
+        with torch.device(dev):
+            model = transformers.GPT2LMHeadModel(cfg).eval()
+    finally:
+        torch.set_default_dtype(old)
+    with torch.no_grad():   # HF's init (std 0.02) gives a flat distribution; widths as in the other rows (Conv1D is [in][out])
+        for k, p in model.named_parameters():
+            if p.dim() == 2:
+                std = 2.0 / d ** 0.5 if "wte" in k else 0.5 if "wpe" in k else 1.0 / p.shape[0] ** 0.5
+                p.copy_((torch.randn(p.shape, device=dev) * std).half())
+    dims = R.gpt2_dims(json.loads(cfg.to_json_string()))
+    sc = R.Gpt2Scorer(dims, R.gpt2_device_layout(model.state_dict(), dims), dev,
+                      context_cache_tokens=dims["max_pos"] if a.session else 0)
+    return against_hf(a, sc, model, calls, rng, 2 * (L * (4 * d * d + 2 * d * ffn) + d * V), {})
+
+
+def against_hf(a, sc, model, calls, rng, flop_tok, extra):
+    """What --arch llama / qwen3 / gpt2 run behind their scorer and HF model: --session, the flat / tree A/B, or the HIP path
+    against the HF model on the same lists; `extra` are the family's own fields of the last row."""
+    import torch
+    dev, V, d, H, ffn, L = "cuda", a.vocab, a.d, a.heads, a.ffn, a.layers
     if a.session:
         del model
         torch.cuda.empty_cache()
@@ -271,11 +322,9 @@ def main_llama(a):
         ms_torch, s_torch = timed(torch_score)
         ms_hip2, _ = timed(lambda l: sc.score(l))      # once more after the torch pass: the order does not decide
     diff = max(float(np.abs(np.asarray(x, np.float64) - np.asarray(y, np.float64)).max()) for x, y in zip(s_hip, s_torch))
-    hd = d // H
-    flop_tok = 2 * (L * (d * (H + 2 * Hkv) * hd + d * d + 3 * d * ffn) + d * V)
     r2 = lambda x: round(float(x), 2)
     mh, mt = float(np.mean(ms_hip)), float(np.mean(ms_torch))
-    print(json.dumps({"bench": "llm_rescore", "arch": a.arch, "dtype": a.dtype, "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn,
+    print(json.dumps({"bench": "llm_rescore", "arch": a.arch, "dtype": a.dtype, "layers": L, "d": d, "heads": H, **extra, "ffn": ffn,
                       "vocab": V, "cands": a.cands, "tokens_per_list": float(np.mean(ntok)), "hip_ms_per_list": r2(mh),
                       "torch_fp16_ms_per_list": r2(mt), "hip_tflops": round(np.mean(ntok) * flop_tok / (mh * 1e-3) / 1e12, 1),
                       "speedup_vs_torch": round(mt / mh, 3), "max_abs_score_diff_vs_torch": round(diff, 4),
