@@ -863,6 +863,66 @@ int b2t_clm_qwen3_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qk
                                   const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                   long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
+ * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
+ * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,
+ * biased projections, multi-head attention with q scaled by hd^-0.5, hd = d_model / n_heads -- so a layer's weights are the
+ * same b2t_clm_layer_t (ln1 = input_layernorm, ln2 = post_attention_layernorm, out = attention.dense, fc1 = dense_h_to_4h,
+ * fc2 = dense_4h_to_h), with three differences in the forward:
+ *   partial rotary positions: only the first rotary_ndims = hd * rotary_pct dims of every q and k head are rotated
+ *     (rotate-half pairs (i, i + rotary_ndims / 2), i < rotary_ndims / 2); the other dims pass through.  rotary_ndims must be
+ *     hd / 4 (Pythia), hd / 2 or hd;
+ *   the MLP activation: act = B2T_CLM_NEOX_ACT_GELU_ERF, gelu(v) = 0.5 v (1 + erf(v / sqrt 2)) ("gelu": Pythia), or
+ *     B2T_CLM_NEOX_ACT_GELU_TANH, the gelu_new of the GPT-2 section (configs with "gelu_new" = "gelu_fast" = "gelu_pytorch_tanh");
+ *   the parallel residual: x + attn(ln1(x)) + mlp(ln2(x)), both LayerNorms reading the layer's input x.
+ * Layout (nejm-brain-to-text_amd/llm_rescore.py, neox_device_layout), fp16 DEVICE arrays with rows padded to 256 as above:
+ *   qkv_w / qkv_b: the checkpoint's query_key_value, whose rows are interleaved per head [h][q | k | v][hd], de-interleaved to
+ *     q | k | v rows; then the rows of every q and k head (and their bias entries) are stored so that each rotary pair sits 32
+ *     rows apart inside one 64-row slice and pass-through rows fill the rest (neox_head_perm): for hd 64 with 16 rotary dims
+ *     [0..7, 16..39, 8..15, 40..63]; for hd 128 with 32 rotary dims [0..15, 32..47, 16..31, 48..63] then 64..127 as they are;
+ *     with rotary_ndims == hd the order of the Llama section.  q . k does not change when both are permuted alike; v and
+ *     attention.dense are stored as they are;
+ *   embed_in [>= vocab][d]; embed_out [round_up(vocab, 256)][d], the head, which may be embed_in (tied) if that is padded so;
+ *   rope_cos / rope_sin: fp32 [max_pos][rotary_ndims / 2], cos and sin of p * inv_freq[i], computed by the host in double.
+ * Numerics: fp16 operands, fp32 accumulation; the residual stream (the fp16 embedding row widened), LayerNorm statistics, the
+ * rotation, the activation, softmax / log-softmax and the sums are fp32.  Rounded to fp16, once each: both LayerNorm outputs;
+ * q, k, v; the attention's probabilities per 32-key block as the P.V operand and its output; gelu(fc1).  The QKV GEMM's
+ * epilogue works on the fp32 accumulator in this order: + bias; rotation of the rotary dims of q and k; the other dims pass
+ * through; q * hd^-0.5; the one rounding (v: + bias, the rounding).  The fc1 GEMM's: + bias; the activation; the one rounding;
+ * a saturated pre-activation gives v or -0.0 / 0, never NaN.  The residual (fp32, +=) receives the attention branch first, then
+ * the MLP branch.  After the last layer: the final LayerNorm, then the head on embed_out.
+ * The seven functions have their OPT twins' argument lists, output layout, update semantics of the cache, B2T_CLM_GEMM_256 and
+ * B2T_CLM_TRUNK_ATTN; the plan and the cache rule are b2t_clm_tree_plan_host and b2t_clm_cache_plan_host, the cache the same
+ * b2t_clm_cache_t (kv [n_layers][cap][2 * d_model]; K rows after bias and rotation, in the stored order).  Refusals before any
+ * launch, under the entry point's own name: the twins', plus a head dim that is not 64 or 128, a rotary_ndims outside
+ * {hd/4, hd/2, hd}, an unknown act, a null rotary table.  The three calls are bit-identical to each other. */
+#define B2T_CLM_NEOX_ACT_GELU_ERF 0
+#define B2T_CLM_NEOX_ACT_GELU_TANH 1
+typedef struct {
+  int n_layers, d_model, n_heads, ffn_dim, vocab, max_pos;
+  int rotary_ndims;                    /* rotated dims of each q / k head: hd / 4, hd / 2 or hd */
+  int act;                             /* B2T_CLM_NEOX_ACT_* */
+  const void* embed_in;                /* fp16 [>= vocab][d] */
+  const void* embed_out;               /* fp16 [round_up(vocab, 256)][d]; may be embed_in (tied) if that is padded so */
+  const void *final_ln_w, *final_ln_b; /* fp16 [d] */
+  const float *rope_cos, *rope_sin;    /* fp32 [max_pos][rotary_ndims / 2] */
+  const b2t_clm_layer_t* layers_host;  /* HOST array of n_layers entries (device pointers inside) */
+} b2t_clm_neox_t;
+
+size_t b2t_clm_neox_ws_bytes(const b2t_clm_neox_t* model, long long n_tokens, int n_seq);
+size_t b2t_clm_neox_tree_ws_bytes(const b2t_clm_neox_t* model, long long n_nodes, long long n_tokens, int n_seq);
+size_t b2t_clm_neox_cache_kv_bytes(const b2t_clm_neox_t* model, int cap);
+size_t b2t_clm_neox_tree_cached_ws_bytes(const b2t_clm_neox_t* model, long long n_rows, long long n_tokens, int n_seq);
+int b2t_clm_neox_score_f16(const b2t_clm_neox_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                           float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_neox_score_tree_f16(const b2t_clm_neox_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                float* scores_out, float* tok_logp_out, long long* n_nodes_out,
+                                void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_neox_score_tree_cached_f16(const b2t_clm_neox_t* model, b2t_clm_cache_t* cache, int update,
+                                       const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                       float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
+                                       void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,16 @@ class ClmQkNorm(C.Structure):
     _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
 
 
+class ClmNeoxDesc(C.Structure):
+    """Mirror of b2t_clm_neox_t (include/b2t.h); the layers are ClmLayer."""
+    _fields_ = [(n, C.c_int) for n in ("n_layers", "d_model", "n_heads", "ffn_dim", "vocab", "max_pos", "rotary_ndims", "act")] + \
+               [(n, VP) for n in ("embed_in", "embed_out", "final_ln_w", "final_ln_b", "rope_cos", "rope_sin")] + \
+               [("layers_host", C.POINTER(ClmLayer))]
+
+
+CLM_NEOX_ACT_GELU_ERF, CLM_NEOX_ACT_GELU_TANH = 0, 1   # B2T_CLM_NEOX_ACT_*
+
+
 _SIGNATURES = {
     "b2t_version": (C.c_int, []),
     "b2t_last_error": (C.c_char_p, []),
@@ -265,7 +275,11 @@ for _t in ("score_f16", "score_tree_f16", "score_tree_cached_f16"):
 for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16", "score_tree_cached_f16"):
     _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
     _SIGNATURES["b2t_clm_qwen3_" + _t] = (_res, [_args[0], C.POINTER(ClmQkNorm)] + _args[1:])
-
+# GPT-NeoX: the OPT twin's list on its own model struct (same cache)
+for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
+           "score_tree_cached_f16"):
+    _res, _args = _SIGNATURES["b2t_clm_" + _t]
+    _SIGNATURES["b2t_clm_neox_" + _t] = (_res, [C.POINTER(ClmNeoxDesc)] + _args[1:])
 
 
 def header_symbols():

@@ -25,6 +25,9 @@ namespace {
 int gpt2_fc1(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_GELU>); }
 
 }  // namespace
+
+int clm_gemm_gelu(const ClmGemm& g, hipStream_t s) { return gpt2_fc1(g, s); }   // GPT-NeoX's gelu_fast / gelu_new is this one
+
 }  // namespace b2t
 
 using namespace b2t;

@@ -5,7 +5,8 @@
 // the OPT forward in fp16 (its launch_gemm serves the tree and cache paths too), causal_lm_llama.hip the two of the Llama
 // family in fp16 (rotary embedding on q | k, SwiGLU), causal_lm_llama_bf16.hip the four of the Llama forward in bf16,
 // causal_lm_qwen3.hip the one Qwen3 adds (EP_QKNORM_ROPE: the per-head q / k RMSNorm in front of the rotation) in both,
-// causal_lm_gpt2.hip the one GPT-2 adds (EP_GELU: gelu_new where OPT's fc1 has ReLU) in fp16.  Which
+// causal_lm_gpt2.hip the one GPT-2 adds (EP_GELU: gelu_new where OPT's fc1 has ReLU) in fp16, causal_lm_neox.hip the two
+// GPT-NeoX adds (EP_ROPE_PART: the rotation of only the first rotary_ndims dims of a head; EP_GELU_ERF) in fp16.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -40,6 +41,10 @@ __device__ __forceinline__ float gelu_new(float v) {
   const float th = 1.0f - 2.0f / (expf(2.0f * u) + 1.0f);
   return 0.5f * v * (1.0f + th);
 }
+
+// the erf GELU (GPT-NeoX / Pythia's "gelu"): 0.5 v (1 + erf(v / sqrt 2)) in fp32.  erff saturates to +-1, so a saturated
+// pre-activation yields v or -0.0 / 0, never NaN.
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.7071067811865476f)); }
 
 // BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.  E is the element type of
 // A, B, bias and out16 (ClmElem, clm_internal.h).
@@ -204,7 +209,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
     }
     return;
   }
-  if (EP == EP_ROPE || EP == EP_SWIGLU) {
+  if (EP == EP_ROPE || EP == EP_ROPE_PART || EP == EP_SWIGLU) {
     // a lane holds columns colw + li (fragment 0) and colw + 32 + li (fragment 1) of every row it owns: the two halves of a
     // rotary pair (head dims of 128 are stored [0..31, 64..95, 32..63, 96..127], so their pairs are 32 columns apart as
     // well), and the gate and up values of one SwiGLU column (the weight's rows are interleaved in blocks of 32).  N is a
@@ -228,8 +233,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
     }
     const float b0 = bias ? (float)bias[c0] : 0.f, b1 = bias ? (float)bias[c1] : 0.f;
     const float sc = colw < g.qcols ? g.qscale : 1.f;
-    const bool rot = colw < g.rope_cols;   // wave-uniform: q | k | v boundaries are multiples of the head dim
-    const int half = g.hd >> 1, fi = ((colw % g.hd) >> 1) + li;
+    // EP_ROPE: wave-uniform (q | k | v boundaries are multiples of the head dim).  EP_ROPE_PART (GPT-NeoX's partial rotary):
+    // the table has rope_half columns, and of the slice at (colw % hd) / 2 = 32 j of them the lanes below rope_half - 32 j
+    // hold a rotary pair; the other lanes' two columns pass through (llm_rescore.neox_head_perm stores the heads so).
+    const bool rot = colw < g.rope_cols && (EP != EP_ROPE_PART || ((colw % g.hd) >> 1) + li < g.rope_half);
+    const int half = EP == EP_ROPE_PART ? g.rope_half : g.hd >> 1, fi = ((colw % g.hd) >> 1) + li;
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
 #pragma unroll
@@ -269,6 +277,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
         } else {
           if (EP == EP_RELU) v = fmaxf(v, 0.f);
           else if (EP == EP_GELU) v = gelu_new(v);
+          else if (EP == EP_GELU_ERF) v = gelu_erf(v);
           else v *= sc;
           out16[off] = (E)v;
         }

@@ -1,7 +1,8 @@
 // clm_internal.h — what the units of the causal-LM forward share (the four fp16 units named below; causal_lm_llama_bf16.hip,
 // the Llama family in bf16, uses the element-type trait ClmElem, ClmGemm, the tile rule, the head and the index builders;
 // causal_lm_qwen3.hip, Qwen3 in both formats, the same and clm_score_tree_cached; causal_lm_gpt2.hip, GPT-2, the OPT forward
-// and entry-point bodies below with its own fc1 GEMM).  causal_lm.hip (the flat OPT path) defines the tile rule,
+// and entry-point bodies below with its own fc1 GEMM; causal_lm_neox.hip, GPT-NeoX, the launchers, the head, the index builders
+// and clm_score_tree_cached around a forward of its own).  causal_lm.hip (the flat OPT path) defines the tile rule,
 // the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
 // list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
 // and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
@@ -29,7 +30,13 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 //   x[c] * rsqrt(mean over the head of x^2 + rms_eps) * w[c % hd], w = qnorm_w (columns < qcols) or knorm_w (< rope_cols).
 // EP_GELU (GPT-2) is EP_RELU with gelu_new in ReLU's place: out16[r][c] = gelu_new(C[r][c] + bias[c]), gelu_new(v) =
 //   0.5 v (1 + tanh(sqrt(2 / pi) (v + 0.044715 v^3))) in fp32, rounded once.
-enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6, EP_GELU = 7 };
+// EP_ROPE_PART (GPT-NeoX) is EP_ROPE with only the first rotary_ndims = 2 * rope_half dims of a head rotated: the loader stores a
+//   head so that in the 64-column slice at 32 * j rows of rope_half the lanes li < clamp(rope_half - 32 j, 0, 32) hold a rotary
+//   pair (frequency 32 j + li) in their two fragments and the other lanes two pass-through columns; the table's row stride is
+//   rope_half.  Bias, rotation or pass-through, the q scale, one rounding, as in EP_ROPE.
+// EP_GELU_ERF (GPT-NeoX) is EP_GELU with the erf form: gelu(v) = 0.5 v (1 + erf(v / sqrt 2)) in fp32, rounded once.
+enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6, EP_GELU = 7,
+       EP_ROPE_PART = 8, EP_GELU_ERF = 9 };
 
 using f32x16 = float __attribute__((ext_vector_type(16)));
 
@@ -63,6 +70,7 @@ struct ClmGemm {
   int rope_cols, hd;                        // EP_ROPE: columns < rope_cols (q | k) are rotated; head dim (64 or 128)
   const void* qnorm_w; const void* knorm_w; // EP_QKNORM_ROPE: [hd] weights of the q heads' and the k heads' RMSNorm
   float rms_eps;                            // EP_QKNORM_ROPE
+  int rope_half;                            // EP_ROPE_PART: rotary_ndims / 2, the row stride of rope_cos / rope_sin (hd/8, hd/4 or hd/2)
 };
 
 // The tile rule (B2T_CLM_GEMM_256) lives in one definition, causal_lm.hip: it picks the tile and hands the launch to `tiles`,
@@ -76,6 +84,8 @@ extern template int launch_gemm<EP_F16>(const ClmGemm&, hipStream_t);
 extern template int launch_gemm<EP_RELU>(const ClmGemm&, hipStream_t);
 extern template int launch_gemm<EP_RESID>(const ClmGemm&, hipStream_t);
 extern template int launch_gemm<EP_HEAD>(const ClmGemm&, hipStream_t);
+// the EP_GELU GEMM through the tile rule, for the families whose fc1 has the tanh GELU (causal_lm_gpt2.hip instantiates it)
+int clm_gemm_gelu(const ClmGemm& g, hipStream_t s);
 
 // resid[r] = embed_tokens[ids[r]] + embed_positions[pos[r] + 2] for r < rows
 int clm_launch_embed(const int* ids, const int* pos, const _Float16* et, const _Float16* ep, float* resid, int d, long long rows,

@@ -30,6 +30,12 @@ when its arrays hold them.  Checkpoints whose head_dim is not hidden_size / head
 _tree_f16 / _tree_cached_f16 (csrc/causal_lm_gpt2.hip): behind the loader (Conv1D weights transposed, c_attn split into q | k | v
 rows, wpe behind two zero rows) GPT-2 is the OPT forward with gelu_new in the fc1 GEMM's epilogue where OPT has ReLU.  fp16
 only.  The GPT-2 tokenizer prepends no BOS, so a candidate's first token is unscored, as in the reference.
+
+"gpt_neox" with head dim 64 or 128 (pythia-70m, 160m, 410m, 1.4b, 6.9b, 12b) gives a `NeoxScorer` on b2t_clm_neox_score_f16 / _tree_f16 / _tree_cached_f16
+(csrc/causal_lm_neox.hip): OPT's LayerNorm, biased projections and attention with rotary positions on the first rotary_pct of
+every head (in the QKV GEMM's epilogue, on rows the loader de-interleaves and permutes: neox_device_layout), the erf GELU (or
+the tanh form, by hidden_act) in the fc1 GEMM's, and the parallel residual.  fp16 only; head dims 64 and 128 (not pythia-1b's
+256, pythia-2.8b's 80 or gpt-neox-20b's 96), parallel residual, biased attention, eps 1e-5 and default rope only.
 """
 from __future__ import annotations
 
@@ -673,6 +679,207 @@ class Gpt2Scorer(OptScorer):
     _dtype_of = staticmethod(lambda dtype: gpt2_dtype(dtype))
 
 
+# ---- GPT-NeoX (HF GPTNeoXForCausalLM with head dim 64 or 128: Pythia) ------------------------------------------------------
+NEOX_HEAD_DIMS = (64, 128)
+NEOX_ACT_GELU_ERF, NEOX_ACT_GELU_TANH = 0, 1   # b2t_clm_neox_t.act (B2T_CLM_NEOX_ACT_*)
+# hidden_act -> act: "gelu" is the erf form; the other three are one tanh function, GPT-2's gelu_new
+NEOX_ACTIVATIONS = {"gelu": NEOX_ACT_GELU_ERF, "gelu_new": NEOX_ACT_GELU_TANH, "gelu_fast": NEOX_ACT_GELU_TANH,
+                    "gelu_pytorch_tanh": NEOX_ACT_GELU_TANH}
+
+
+def neox_dtype(dtype, cfg: Optional[dict] = None):
+    """clm_dtype for a GPT-NeoX checkpoint, which computes in fp16 alone, the format the family is published in ("auto" is
+    fp16 whatever the config says)."""
+    import torch
+    if dtype == "auto":
+        return torch.float16
+    if clm_dtype(dtype, cfg) != torch.float16:
+        raise ValueError("NeoxScorer: dtype 'bfloat16' is not supported for GPT-NeoX checkpoints (the Pythia suite is "
+                         "published in float16); the Llama family has a bfloat16 mode")
+    return torch.float16
+
+
+def _neox_rope(cfg: dict) -> Tuple[float, float, str]:
+    """(partial rotary factor, theta, rope type) of a GPT-NeoX config in either spelling: rotary_pct / rotary_emb_base (the
+    Hub's config.json files, with an optional rope_scaling) or rope_parameters.{partial_rotary_factor, rope_theta, rope_type}."""
+    rp = dict(cfg.get("rope_parameters") or cfg.get("rope_scaling") or {})
+    pct = rp.get("partial_rotary_factor", cfg.get("rotary_pct", cfg.get("partial_rotary_factor", 0.25)))
+    theta = rp.get("rope_theta", cfg.get("rotary_emb_base", cfg.get("rope_theta", 10000)))
+    return float(pct), float(theta), str(rp.get("rope_type", rp.get("type", "default")))
+
+
+def neox_dims(cfg: dict) -> dict:
+    """The dimensions b2t_clm_neox_t needs from a GPT-NeoX config.json, after refusing what the kernels do not run."""
+    if not cfg.get("use_parallel_residual", True):
+        raise ValueError("gpt_neox with use_parallel_residual=False is not supported (the forward is x + attn(ln1(x)) + "
+                         "mlp(ln2(x)); sequential-residual checkpoints are not built)")
+    if not cfg.get("attention_bias", True):
+        raise ValueError("gpt_neox with attention_bias=False is not supported (the projections are biased)")
+    eps = float(cfg.get("layer_norm_eps", 1e-5))
+    if eps != 1e-5:
+        raise ValueError(f"gpt_neox layer_norm_eps {eps} is not supported (the LayerNorm kernel's eps is the constant 1e-5)")
+    pct, _, kind = _neox_rope(cfg)
+    if kind != "default":
+        raise ValueError(f"gpt_neox rope_type {kind!r} is not supported (default only)")
+    act = cfg.get("hidden_act", "gelu")
+    if act not in NEOX_ACTIVATIONS:
+        raise ValueError(f"gpt_neox hidden_act {act!r} is not supported ({', '.join(NEOX_ACTIVATIONS)})")
+    d, heads = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    if d % heads or d // heads not in NEOX_HEAD_DIMS:
+        raise ValueError(f"gpt_neox head dim hidden_size {d} / num_attention_heads {heads} is not supported (one of "
+                         f"{NEOX_HEAD_DIMS}; pythia-2.8b has head dim 80, gpt-neox-20b 96 and pythia-1b 256, which are not built)")
+    hd = d // heads
+    rot = int(hd * pct)
+    if rot not in (hd // 4, hd // 2, hd):
+        raise ValueError(f"gpt_neox rotary_pct {pct} gives {rot} rotary dims of head dim {hd}, which is not supported "
+                         f"({hd // 4}, {hd // 2} or {hd})")
+    ffn = int(cfg["intermediate_size"])
+    if d % 64 or ffn % 64:
+        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=heads, ffn_dim=ffn, vocab=int(cfg["vocab_size"]),
+                max_pos=int(cfg["max_position_embeddings"]), rotary_ndims=rot, act=NEOX_ACTIVATIONS[act],
+                tied=bool(cfg.get("tie_word_embeddings", False)))
+
+
+def neox_inv_freq(cfg: dict) -> np.ndarray:
+    """fp32 inv_freq[rotary_ndims / 2] of a GPT-NeoX config, computed as HF computes it (fp32 torch arithmetic): the default
+    rope over the rotary dims, 1 / theta^(2 i / rotary_ndims)."""
+    import torch
+    pct, theta, _ = _neox_rope(cfg)
+    dim = neox_dims(cfg)["rotary_ndims"]
+    return (1.0 / (theta ** (torch.arange(0, dim, 2, dtype=torch.float) / dim))).numpy().astype(np.float32)
+
+
+def neox_head_perm(hd: int, rotary_ndims: int) -> np.ndarray:
+    """stored row i of a q / k head = original row perm[i], such that every rotary pair (f, f + rotary_ndims / 2) sits 32 rows
+    apart inside one 64-row slice -- pair f in slice f // 32 at rows f % 32 and 32 + f % 32, which is where EP_ROPE_PART
+    (csrc/clm_gemm.h) looks for it -- and the pass-through rows fill the remaining places in order.  hd 64 with 16 rotary dims:
+    [0..7, 16..39, 8..15, 40..63]; hd 128 with 32: [0..15, 32..47, 16..31, 48..63, 64..127]; rotary_ndims == hd: head_dim_perm."""
+    if hd not in NEOX_HEAD_DIMS or rotary_ndims not in (hd // 4, hd // 2, hd):
+        raise ValueError(f"head dim {hd} with {rotary_ndims} rotary dims is not supported")
+    half = rotary_ndims // 2
+    perm = np.full(hd, -1, np.int64)
+    for f in range(half):
+        at = 64 * (f // 32) + f % 32
+        perm[at], perm[at + 32] = f, f + half
+    perm[perm < 0] = np.arange(rotary_ndims, hd)
+    return perm
+
+
+def neox_device_layout(state: dict, dims: dict, inv_freq: np.ndarray) -> Dict[str, "object"]:
+    """Tensors in the layout of b2t_clm_neox_t from a GPTNeoXForCausalLM state dict, on the device the state dict is on (the
+    CPU for a checkpoint read from disk; the rotary tables are CPU tensors either way).  Keys with or without the 'gpt_neox.'
+    prefix; the attention.bias / masked_bias / rotary_emb.inv_freq buffers of old checkpoints are ignored.  fp16
+    embed_in, embed_out (the same tensor when tied), final_ln_w / final_ln_b, layers.<i>.<field> under device_layout's names,
+    and the fp32 rope_cos / rope_sin [max_pos][rotary_ndims / 2].  query_key_value's rows are interleaved per head,
+    [h][q | k | v][hd]: they are de-interleaved to q | k | v rows, then every q and k head's rows (and bias entries) are stored
+    under neox_head_perm.  v and attention.dense are stored as they are; rows are padded to 256."""
+    import torch
+    sd = {}
+    for k, v in state.items():
+        k = k[len("gpt_neox."):] if k.startswith("gpt_neox.") else k
+        if k.endswith((".attention.bias", ".attention.masked_bias", ".rotary_emb.inv_freq")):
+            continue
+        sd["embed_out.weight" if k == "lm_head.weight" else k] = v   # the head's name in memory in recent transformers
+    d, ffn, V, H = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"]
+    hd = d // H
+
+    def get(name, shape):
+        if name not in sd:
+            raise KeyError(f"GPT-NeoX checkpoint lacks {name}")
+        t = sd[name].detach().to(torch.float16).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    emb = _pad_rows(get("embed_in.weight", (V, d)), _rup(V, ROWPAD))
+    dev = emb.device
+    tied = dims.get("tied", False) or "embed_out.weight" not in sd
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    out = {"embed_in": emb, "embed_out": emb if tied else _pad_rows(get("embed_out.weight", (V, d)), _rup(V, ROWPAD)),
+           "final_ln_w": get("final_layer_norm.weight", (d,)), "final_ln_b": get("final_layer_norm.bias", (d,)),
+           "rope_cos": torch.from_numpy(cos), "rope_sin": torch.from_numpy(sin)}
+    hp = neox_head_perm(hd, dims["rotary_ndims"])
+    # stored row i of qkv = de-interleaved row perm[i]: the head permutation inside every q and k head, v as it is
+    perm = torch.from_numpy(np.concatenate([h * hd + hp for h in range(2 * H)] + [np.arange(2 * d, 3 * d)])).to(dev)
+    # de-interleaved row (j, h, c) = checkpoint row (h, j, c), j = q, k, v
+    split = lambda t: t.view(H, 3, hd, *t.shape[1:]).transpose(0, 1).reshape(3 * d, *t.shape[1:])
+    for i in range(dims["n_layers"]):
+        p = f"layers.{i}."
+        L = {"ln1_w": get(p + "input_layernorm.weight", (d,)), "ln1_b": get(p + "input_layernorm.bias", (d,)),
+             "qkv_w": _pad_rows(split(get(p + "attention.query_key_value.weight", (3 * d, d)))[perm].contiguous(), _rup(3 * d, ROWPAD)),
+             "qkv_b": split(get(p + "attention.query_key_value.bias", (3 * d,)))[perm].contiguous(),
+             "out_w": _pad_rows(get(p + "attention.dense.weight", (d, d)), _rup(d, ROWPAD)), "out_b": get(p + "attention.dense.bias", (d,)),
+             "ln2_w": get(p + "post_attention_layernorm.weight", (d,)), "ln2_b": get(p + "post_attention_layernorm.bias", (d,)),
+             "fc1_w": _pad_rows(get(p + "mlp.dense_h_to_4h.weight", (ffn, d)), _rup(ffn, ROWPAD)),
+             "fc1_b": get(p + "mlp.dense_h_to_4h.bias", (ffn,)),
+             "fc2_w": _pad_rows(get(p + "mlp.dense_4h_to_h.weight", (d, ffn)), _rup(d, ROWPAD)),
+             "fc2_b": get(p + "mlp.dense_4h_to_h.bias", (d,))}
+        for f in _LAYER_FIELDS:
+            out[f"layers.{i}.{f}"] = L[f]
+    return out
+
+
+def load_neox_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the GPT-NeoX checkpoint in model_dir."""
+    cfg = load_config(model_dir)
+    dims = neox_dims(cfg)
+    return dims, neox_device_layout(_load_state_dict(model_dir), dims, neox_inv_freq(cfg))
+
+
+class NeoxScorer(_Scorer):
+    """A GPT-NeoX decoder (Pythia; head dim 64 or 128) on the GPU in the b2t_clm_neox_t layout (neox_device_layout), with OptScorer's
+    constructor and scoring surface -- `score` / `token_logprobs`, share_prefixes, the context cache with `use_cache` /
+    `update_cache` / `cache_len` / `cache_ids` / `cache_reset`, `last_stats` -- on the entry points b2t_clm_neox_score_f16 /
+    _tree_f16 / _tree_cached_f16 (csrc/causal_lm_neox.hip): partial rotary positions in the QKV GEMM's epilogue, the erf (or
+    tanh) GELU in the fc1 GEMM's, the parallel residual.  A cached position costs n_layers * 4 * d_model bytes.  fp16 only."""
+
+    _WS_BYTES = "b2t_clm_neox_ws_bytes"
+    _NO_CACHE = "use_cache=True on a scorer built without context_cache_tokens"
+    _ENTRY = "b2t_clm_neox_"
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0, dtype=None):
+        import torch
+        import b2t_native as N
+        self.dtype = neox_dtype(dtype)   # fp16 alone: bfloat16 is refused
+        self.dims = dict(dims)
+        self.device = torch.device(device)
+        self.share_prefixes = bool(share_prefixes)
+        self.last_stats = None
+        tied = dims.get("tied", False) or arrays["embed_out"] is arrays["embed_in"]   # then the head is never copied
+        self.w = {k: v.to(self.device, torch.float32 if k.startswith("rope_") else torch.float16).contiguous()
+                  for k, v in arrays.items() if not (tied and k == "embed_out")}
+        if tied:
+            self.w["embed_out"] = self.w["embed_in"]
+        self._layers = (N.ClmLayer * max(1, dims["n_layers"]))()
+        for i in range(dims["n_layers"]):
+            for f in _LAYER_FIELDS:
+                setattr(self._layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
+        self.desc = N.ClmNeoxDesc(dims["n_layers"], dims["d_model"], dims["n_heads"], dims["ffn_dim"], dims["vocab"], dims["max_pos"],
+                                  dims["rotary_ndims"], dims["act"], self.w["embed_in"].data_ptr(), self.w["embed_out"].data_ptr(),
+                                  self.w["final_ln_w"].data_ptr(), self.w["final_ln_b"].data_ptr(),
+                                  self.w["rope_cos"].data_ptr(), self.w["rope_sin"].data_ptr(), self._layers)
+        self._ws = None
+        self._alloc_cache(context_cache_tokens)
+
+    def _cache_kv_bytes(self, lib, cap):
+        import ctypes as C
+        return lib.b2t_clm_neox_cache_kv_bytes(C.byref(self.desc), cap)
+
+    def _sizes(self, lib, path, ids, off):
+        import ctypes as C
+        desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
+        if path == "cached":
+            plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
+            return plan["rows"], plan["reused"], lib.b2t_clm_neox_tree_cached_ws_bytes(desc, plan["rows"], M, n_seq)
+        if path == "tree":
+            nodes = tree_plan(ids, off)[2]
+            return nodes, 0, lib.b2t_clm_neox_tree_ws_bytes(desc, nodes, M, n_seq)
+        return M, 0, lib.b2t_clm_neox_ws_bytes(desc, M, n_seq)
+
+    _score = OptScorer._score   # the OPT twins' argument lists under this family's _ENTRY
+
+
 # ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM) ---------------------
 LLAMA_MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")
 QK_NORM_MODEL_TYPES = ("qwen3",)   # an RMSNorm over every q and k head in front of the rotation
@@ -1000,7 +1207,7 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
 
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
-    only, like OPT), LlamaScorer for "llama",
+    only, like OPT), NeoxScorer for "gpt_neox" (Pythia; fp16 only), LlamaScorer for "llama",
     "mistral", "qwen2" and "qwen3"; anything else is refused.  max_positions caps a Llama-family model's rotary table.  dtype (clm_dtype):
     None or "float16", "bfloat16" (the Llama family only, and without a context cache), or "auto" = the dtype config.json says
     the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
@@ -1015,13 +1222,17 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         wdt = gpt2_dtype(dtype, cfg)
         dims, arrays = load_gpt2_arrays(model_dir)
         return Gpt2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
+    if mt == "gpt_neox":
+        wdt = neox_dtype(dtype, cfg)
+        dims, arrays = load_neox_arrays(model_dir)
+        return NeoxScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
     if mt in LLAMA_MODEL_TYPES:
         wdt = clm_dtype(dtype, cfg)
         llama_check_dtype_cache(wdt, context_cache_tokens)
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_llama_arrays(model_dir, max_positions, wdt)
         return LlamaScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, {', '.join(LLAMA_MODEL_TYPES)})")
+    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)})")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
