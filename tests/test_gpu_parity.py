@@ -123,7 +123,10 @@ def test_gemm_bf16(akc, bkc, M, N, K):
 @pytest.mark.parametrize("B,H,T,wide", [(17, 80, 9, 0), (64, 512, 12, 0), (40, 768, 6, 0), (64, 512, 12, 1), (23, 96, 7, 1), (40, 768, 6, 1), (64, 768, 20, 1), (64, 512, 180, 1)])
 def test_persistent_sweep_bf16_operands(B, H, T, wide):
     """mode 1 | B2T_GRU_BF16: the recurrent products round their operands (h_{t-1} / dG_{t+1} and the W_hh slice) to bf16
-    and accumulate in fp32.  Reference: the same recurrences in numpy with the operands rounded explicitly."""
+    and accumulate in fp32.  Reference: the same recurrences in numpy with the operands rounded explicitly -- free-running at
+    bf16-ulp scale, then operand-forced (oracle/gru_bf16.py) at M x the float32 roundoff e32 of the same recurrences: M = 16 (out,
+    reserve) / 8 (dG) / 8 (dh_init) = 4 x the largest err / e32 measured on the MI355X, table in NOTES.md 2b "The operand-forced
+    bf16 GRU oracle"; M e32 is capped at 1e-4 resp. 1e-3 of the oracle tensor's rms."""
     import b2t_native as Nn
     import b2t_ops as ops
     lib = Nn.load(); dev = _dev(); p = ops._p
@@ -174,6 +177,14 @@ def test_persistent_sweep_bf16_operands(B, H, T, wide):
     out32 = torch.zeros(T + 1, B, H, device=dev); out32[0] = h0
     Nn.check(lib.b2t_gru_layer_fwd_f32(p(gi), p(w), p(b_), p(out32[0]), p(out32[1:]), None, None, T, B, H, 1, p(sync), ops._stream()), "fwd32")
     assert float((out32 - out).abs().max()) > 1e-5
+    # ... and step by step against the fp64 cell function of the operands the kernel itself wrote (oracle/gru_bf16.py): no rounding
+    # can flip, what is left is fp32 roundoff, bounded by M x that of the float32 restatement (M and the measured ratios: NOTES.md,
+    # "The operand-forced bf16 GRU oracle").  The variants below are bit-identical to this run: one comparison serves them.
+    from oracle import gru_bf16 as G
+    cpu = lambda t: t.cpu().numpy()
+    inputs = dict(gi0=cpu(gi), whh=[cpu(w)], bhh=[cpu(b_)], wih=[None], bih=[None], h0=[cpu(h0)], masks=None, dY=cpu(dY), dhl=cpu(dhl)[None])
+    G.check_kernel(inputs, dict(out=[cpu(out[1:])], outd=[None], res=[cpu(resv)], dG=[cpu(dG)], dh_init=[cpu(dh)]),
+                   f"persistent{' wide' if wide else ''} ({B},{H},{T})")
     if wide:
         # The 32-unit workgroups hand their tiles over as bf16 MFMA fragments through the buffer behind the counters
         # (gru_sync.h); with B2T_HANDOFF16=0 as fp32 tiles that every consumer transposes and rounds itself: the same roundings of
