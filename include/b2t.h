@@ -863,6 +863,53 @@ int b2t_clm_qwen3_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qk
                                   const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                   long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- OLMo-2 (csrc/causal_lm_olmo2.hip): whole-row q / k norms and a post-norm layer ---------------------------------------
+ * HF Olmo2ForCausalLM (OLMo-2 1B, 7B, 13B, 32B) has the Llama family's rotary positions, grouped-query attention, SwiGLU MLP
+ * and head, no biases, and a layer of its own.  With x the residual and no input norm anywhere in the layer:
+ *   q = RMSNorm(x Wq^T; q_norm) over all Hq hd columns, k = RMSNorm(x Wk^T; k_norm) over all Hkv hd columns -- ONE statistic per
+ *     projection row, all heads together (Qwen3 above: one per head) --, v = x Wv^T;
+ *   q and k rotated per head (pairs c, c + hd / 2), q scaled by hd^-0.5, causal grouped-query attention;
+ *   x = x + RMSNorm(attn Wo^T; post_attention_layernorm);
+ *   x = x + RMSNorm((silu(x Wg^T) * x Wu^T) Wd^T; post_feedforward_layernorm);
+ * after the last layer the final RMSNorm, then the head.  The model is the same b2t_clm_llama_t with two differences in the
+ * layout: norm1_w / norm2_w are the two post-norms (post_attention_layernorm, post_feedforward_layernorm), and the q and k
+ * rows of qkv_w are stored in checkpoint order for either head dim (the rotation is not in a GEMM epilogue here); qkv_b must be
+ * NULL.  The q / k norm weights travel in a b2t_clm_qknorm_t array as for Qwen3, with lengths [Hq hd] and [Hkv hd], in checkpoint
+ * order, in the call's element type.
+ * Numerics, E being fp16 or bf16: weights, GEMM and attention operands are E; accumulation, the residual stream, all four
+ * RMSNorm statistics of a layer, the rotation and softmax / log-softmax are fp32.  Rounded to E, once each: the residual as a
+ * GEMM's A operand (layer 0's is the embedding row itself, exact in E); q after norm, rotation and scale; k after norm and
+ * rotation; v; the attention's probabilities per 32-key block as the P.V operand; the attention output; silu(gate) * up; the
+ * final norm's output.  The o_proj and down outputs are never rounded: the GEMM stores its fp32 accumulator, and the post-norm
+ * adds t * rsqrt(mean(t^2) + rms_eps) * w to the residual in fp32.  A row's bits depend only on that row: tree, cached and
+ * flat calls are bit-identical, a sequence scores the same alone or in a batch, and B2T_CLM_GEMM_256 / B2T_CLM_TRUNK_ATTN do not
+ * change the bits.
+ * The workspace is the Llama family's plus one fp32 region of [round_up(rows, 256)][(Hq + Hkv) hd], hence size functions of
+ * their own on the Llama twins' argument lists; b2t_clm_olmo2_cache_kv_bytes equals b2t_clm_llama_cache_kv_bytes, and the cache
+ * holds K rows after norm and rotation in the Llama cache layout.  The five calls have their Qwen3 twins' argument lists and
+ * output layout, and the refusals before any launch of their Llama twins (the error text carries the entry point's own name)
+ * plus: a null qk_norm_host, a null entry in it, a non-null qkv_b.  There is no cached bf16 call. */
+size_t b2t_clm_olmo2_ws_bytes(const b2t_clm_llama_t* model, long long n_tokens, int n_seq);
+size_t b2t_clm_olmo2_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq);
+size_t b2t_clm_olmo2_cache_kv_bytes(const b2t_clm_llama_t* model, int cap);
+size_t b2t_clm_olmo2_tree_cached_ws_bytes(const b2t_clm_llama_t* model, long long n_rows, long long n_tokens, int n_seq);
+int b2t_clm_olmo2_score_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                            const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                            size_t ws_bytes, void* stream);
+int b2t_clm_olmo2_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                                 const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                 long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_olmo2_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
+                                        b2t_clm_cache_t* cache, int update, const int32_t* ids_host,
+                                        const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                        long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_olmo2_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                             const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                             size_t ws_bytes, void* stream);
+int b2t_clm_olmo2_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const int32_t* ids_host,
+                                  const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                  long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
  * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
  * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,

@@ -275,6 +275,11 @@ for _t in ("score_f16", "score_tree_f16", "score_tree_cached_f16"):
 for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16", "score_tree_cached_f16"):
     _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
     _SIGNATURES["b2t_clm_qwen3_" + _t] = (_res, [_args[0], C.POINTER(ClmQkNorm)] + _args[1:])
+# OLMo-2: the Qwen3 twin's list (norm arrays of [Hq * hd] and [Hkv * hd]), and size functions of its own on the Llama twins' lists
+for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16", "score_tree_cached_f16"):
+    _SIGNATURES["b2t_clm_olmo2_" + _t] = _SIGNATURES["b2t_clm_qwen3_" + _t]
+for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes"):
+    _SIGNATURES["b2t_clm_olmo2_" + _t] = _SIGNATURES["b2t_clm_llama_" + _t]
 # GPT-NeoX: the OPT twin's list on its own model struct (same cache)
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
            "score_tree_cached_f16"):

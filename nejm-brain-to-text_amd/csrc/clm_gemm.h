@@ -6,7 +6,8 @@
 // family in fp16 (rotary embedding on q | k, SwiGLU), causal_lm_llama_bf16.hip the four of the Llama forward in bf16,
 // causal_lm_qwen3.hip the one Qwen3 adds (EP_QKNORM_ROPE: the per-head q / k RMSNorm in front of the rotation) in both,
 // causal_lm_gpt2.hip the one GPT-2 adds (EP_GELU: gelu_new where OPT's fc1 has ReLU) in fp16, causal_lm_neox.hip the two
-// GPT-NeoX adds (EP_ROPE_PART: the rotation of only the first rotary_ndims dims of a head; EP_GELU_ERF) in fp16.  Which
+// GPT-NeoX adds (EP_ROPE_PART: the rotation of only the first rotary_ndims dims of a head; EP_GELU_ERF) in fp16, causal_lm_olmo2.hip the two OLMo-2 adds
+// (EP_F32 and EP_QKV_F32: fp32 stores for the norms over a whole output row) in both.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -254,6 +255,28 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
         E* o = out16 + (long long)row * g.ldo;
         o[c0] = (E)(x0 * sc);
         o[c1] = (E)(x1 * sc);
+      }
+    }
+    return;
+  }
+  if (EP == EP_F32 || EP == EP_QKV_F32) {
+    // OLMo-2: the accumulator itself, unrounded, for a norm over the whole output row in a pass of its own.  EP_QKV_F32 keeps
+    // only the q | k columns in fp32 (pitch rope_cols) and rounds the v columns once, where the attention reads them.
+    const int pitch = EP == EP_F32 ? g.ldo : g.rope_cols;
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      const int col = colw + j * 32 + li;
+      if (col >= g.N) continue;
+      const bool f32 = EP == EP_F32 || col < g.rope_cols;
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+          if (row >= g.M) continue;
+          if (f32) g.resid[(long long)row * pitch + col] = acc[i][j][e];
+          else out16[(long long)row * g.ldo + col] = (E)acc[i][j][e];
+        }
       }
     }
     return;

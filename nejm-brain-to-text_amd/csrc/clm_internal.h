@@ -35,8 +35,12 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 //   pair (frequency 32 j + li) in their two fragments and the other lanes two pass-through columns; the table's row stride is
 //   rope_half.  Bias, rotation or pass-through, the q scale, one rounding, as in EP_ROPE.
 // EP_GELU_ERF (GPT-NeoX) is EP_GELU with the erf form: gelu(v) = 0.5 v (1 + erf(v / sqrt 2)) in fp32, rounded once.
+// EP_F32 (OLMo-2) stores the fp32 accumulator unrounded: resid[r][c] = C[r][c] (`=`, no bias; pitch ldo) -- the o_proj and down
+//   outputs, whose whole row a post-norm reads before anything reaches the residual.
+// EP_QKV_F32 (OLMo-2) splits the QKV row: columns < rope_cols (q | k) are stored as EP_F32 stores them, resid[r][c] with pitch
+//   rope_cols, for the whole-row q / k norm that no column tile can hold; the others (v) are rounded once, out16[r][c] (pitch ldo).
 enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6, EP_GELU = 7,
-       EP_ROPE_PART = 8, EP_GELU_ERF = 9 };
+       EP_ROPE_PART = 8, EP_GELU_ERF = 9, EP_F32 = 10, EP_QKV_F32 = 11 };
 
 using f32x16 = float __attribute__((ext_vector_type(16)));
 
@@ -60,7 +64,7 @@ struct ClmGemm {
   int M, N, K;            // K % 64 == 0
   const void* bias;       // [N] or null
   void* out16;            // EP_F16 / EP_RELU: [M][ldo]
-  float* resid;           // EP_RESID: [M][ldo] += C
+  float* resid;           // EP_RESID: [M][ldo] += C; EP_F32: [M][ldo] = C; EP_QKV_F32: [M][rope_cols] = C's q | k columns
   int ldo;
   float qscale; int qcols;   // EP_F16: columns < qcols are multiplied by qscale after the bias (OPT's q scaling)
   float* pmax; float* psum;  // EP_HEAD: [M][ncg] per 64-column group max / sum exp(v - max)

@@ -10,6 +10,8 @@
 // causal_lm_llama.hip holds the fp16 policy and the fp16 entry points (the cached one included), causal_lm_llama_bf16.hip the
 // bf16 policy, every bf16 kernel instantiation and the two bf16 entry points.  causal_lm_qwen3.hip holds the two Qwen3
 // policies: gemm_rope with the epilogue EP_QKNORM_ROPE, instantiated there, and every other launch through LlamaShared<E>.
+// The two entry-point bodies also serve a family with another layer (OLMo-2, clm_olmo2.h): their second template argument
+// supplies the layout, the q / k norm refusals and the forward (LlamaFamily below by default).
 #pragma once
 #include <math.h>
 #include <string>
@@ -145,20 +147,37 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
   return clm_head(x16, m.lm_head, m.vocab, d, r, L, base, s, &P::gemm_head);
 }
 
+// What the two entry-point bodies below take from a family: the workspace layout, the refusals that go with the q / k norm
+// array, and the forward.  This is the Llama family's (Qwen3 included: P::qk_norm); OLMo-2's is Olmo2Family (clm_olmo2.h).
+struct LlamaFamily {
+  static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints) {
+    return llama_layout(m, rows, hrows, ints);
+  }
+  template <class P>
+  static int check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_qknorm_t* qkn) {
+    if constexpr (P::qk_norm) return clm_qknorm_check(who, m, qkn);
+    return 0;
+  }
+  template <class P, class Attn>
+  static int forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
+                     const b2t_clm_qknorm_t* qkn) {
+    return llama_forward<P>(m, r, L, base, attn, s, qkn);
+  }
+};
+
 // The flat entry point of a policy; `who` is its name.
-template <class P>
+template <class P, class Fam = LlamaFamily>
 int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                 float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream,
                 const b2t_clm_qknorm_t* qkn = nullptr) {
   using E = typename P::E;
   if (int rc = clm_llama_check_model(model)) return rc;
   const b2t_clm_llama_t& m = *model;
-  if constexpr (P::qk_norm)
-    if (int rc = clm_qknorm_check(who, m, qkn)) return rc;
+  if (int rc = Fam::template check<P>(who, m, qkn)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
-  const ClmLayout L = llama_layout(model, M, M - n_seq, flat_ints(M, n_seq));
+  const ClmLayout L = Fam::layout(model, M, M - n_seq, flat_ints(M, n_seq));
   B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
   const hipStream_t s = as_stream(stream);
   char* base = static_cast<char*>(ws);
@@ -169,27 +188,26 @@ int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* id
   auto attn = [&](int, const E* qkv, E* out) {
     return P::attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
-  if (int rc = llama_forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
+  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
   return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
 }
 
 // The tree entry point of a policy.
-template <class P>
+template <class P, class Fam = LlamaFamily>
 int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                      int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                      void* stream, const b2t_clm_qknorm_t* qkn = nullptr) {
   using E = typename P::E;
   if (int rc = clm_llama_check_model(model)) return rc;
   const b2t_clm_llama_t& m = *model;
-  if constexpr (P::qk_norm)
-    if (int rc = clm_qknorm_check(who, m, qkn)) return rc;
+  if (int rc = Fam::template check<P>(who, m, qkn)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
   ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);   // a node's rotary position is its depth, node_pos
   const long long Mn = plan.Mn;
   if (n_nodes_out) *n_nodes_out = Mn;
-  const ClmLayout L = llama_layout(model, Mn, Mn, tree_ints(Mn, M, n_seq));
+  const ClmLayout L = Fam::layout(model, Mn, Mn, tree_ints(Mn, M, n_seq));
   B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
   const hipStream_t s = as_stream(stream);
   char* base = static_cast<char*>(ws);
@@ -200,7 +218,7 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
   auto attn = [&](int, const E* qkv, E* out) {
     return P::attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
-  if (int rc = llama_forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
+  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
   return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
 }
 

@@ -1091,6 +1091,7 @@ class LlamaScorer(_Scorer):
     norm every q and k head in the QKV GEMM's epilogue, on all those paths; sizes and the cache are the Llama calls'."""
 
     _WS_BYTES = "b2t_clm_llama_ws_bytes"
+    _SIZES = "b2t_clm_llama_"   # the family's size functions: _SIZES + ws_bytes / tree_ws_bytes / cache_kv_bytes / tree_cached_ws_bytes
     _NO_CACHE = "use_cache=True on a scorer built without a context cache (context_cache_tokens)"
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
@@ -1142,18 +1143,18 @@ class LlamaScorer(_Scorer):
 
     def _cache_kv_bytes(self, lib, cap):
         import ctypes as C
-        return lib.b2t_clm_llama_cache_kv_bytes(C.byref(self.desc), cap)
+        return getattr(lib, self._SIZES + "cache_kv_bytes")(C.byref(self.desc), cap)
 
     def _sizes(self, lib, path, ids, off):
         import ctypes as C
         desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
         if path == "cached":
             plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
-            return plan["rows"], plan["reused"], lib.b2t_clm_llama_tree_cached_ws_bytes(desc, plan["rows"], M, n_seq)
+            return plan["rows"], plan["reused"], getattr(lib, self._SIZES + "tree_cached_ws_bytes")(desc, plan["rows"], M, n_seq)
         if path == "tree":
             nodes = tree_plan(ids, off)[2]
-            return nodes, 0, lib.b2t_clm_llama_tree_ws_bytes(desc, nodes, M, n_seq)
-        return M, 0, lib.b2t_clm_llama_ws_bytes(desc, M, n_seq)
+            return nodes, 0, getattr(lib, self._SIZES + "tree_ws_bytes")(desc, nodes, M, n_seq)
+        return M, 0, getattr(lib, self._SIZES + "ws_bytes")(desc, M, n_seq)
 
     def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
         import ctypes as C
@@ -1170,6 +1171,116 @@ class LlamaScorer(_Scorer):
         else:
             name = pre + self._suffix
             N.check(getattr(lib, name)(desc, *self._qk, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
+
+
+# ---- OLMo-2 (HF Olmo2ForCausalLM): whole-row q / k norms and a post-norm layer ---------------------------------------------
+OLMO2_HEAD_DIMS = (64, 128)
+
+
+def olmo2_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
+    """The dimensions b2t_clm_llama_t needs for an "olmo2" config, after refusing, by the field's name, what the kernels do not
+    run.  max_pos is max_position_embeddings lowered to max_positions (default LLAMA_MAX_POSITIONS), which sizes the rotary
+    table.  "olmo" (no q / k norm, a LayerNorm without weights) and "olmo3" (sliding-window layers) are other forwards."""
+    mt = cfg.get("model_type")
+    if mt != "olmo2":
+        raise ValueError(f"model_type {mt!r} is not 'olmo2'")
+    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    Hkv = int(cfg.get("num_key_value_heads") or Hq)
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise ValueError(f"olmo2 hidden_act {act!r} is not supported (silu only)")
+    if d % Hq or d // Hq not in OLMO2_HEAD_DIMS or int(cfg.get("head_dim") or d // Hq) != d // Hq:
+        raise ValueError(f"head dim {cfg.get('head_dim') or d}/{Hq} is not supported (hidden_size / num_attention_heads, one of "
+                         f"{OLMO2_HEAD_DIMS})")
+    if cfg.get("attention_bias"):
+        raise ValueError("olmo2 with attention_bias=True is not supported (the QKV GEMM's fp32 epilogue adds no bias)")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    ffn = int(cfg["intermediate_size"])
+    if d % 64 or ffn % 64:
+        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    rope_inv_freq(cfg)   # refuses a rope_type other than default / llama3
+    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
+    if cap < 1:
+        raise ValueError(f"max_positions {cap} < 1")
+    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
+                vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg["max_position_embeddings"]), cap),
+                rms_eps=float(cfg.get("rms_norm_eps", 1e-5)), tied=bool(cfg.get("tie_word_embeddings", False)))
+
+
+def olmo2_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
+    """Tensors in the layout of b2t_clm_llama_t / b2t_clm_qknorm_t from an OLMo-2 state dict, as llama_device_layout makes them,
+    with the family's differences: norm1_w / norm2_w are post_attention_layernorm / post_feedforward_layernorm; the q and k rows
+    of qkv_w and the norm weights q_norm_w [Hq * hd] / k_norm_w [Hkv * hd] stay in checkpoint order (the rotation runs in a
+    kernel that sees whole heads, so there is no head_dim_perm); gate / up rows are interleaved as for Llama; any bias is
+    refused."""
+    import torch
+    wdt = clm_dtype(dtype)
+    sd = dict(state)
+    d, ffn, V, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"], dims["n_kv_heads"]
+    hd = d // Hq
+
+    def get(name, shape):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name}")
+        t = sd[name].detach().to(wdt).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
+    tied = dims.get("tied", False) or "lm_head.weight" not in sd
+    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
+           "final_norm_w": get("model.norm.weight", (d,))}
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(emb.device)
+    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    for i in range(dims["n_layers"]):
+        p = f"model.layers.{i}."
+        for n in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
+                  "mlp.down_proj"):
+            if p + n + ".bias" in sd:
+                raise ValueError(f"{p + n}.bias: OLMo-2 biases are not supported")
+        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
+        L = {"norm1_w": get(p + "post_attention_layernorm.weight", (d,)),
+             "norm2_w": get(p + "post_feedforward_layernorm.weight", (d,)),
+             "qkv_w": _pad_rows(qkv, _rup(qkv.shape[0], ROWPAD)),
+             "q_norm_w": get(p + "self_attn.q_norm.weight", (Hq * hd,)),
+             "k_norm_w": get(p + "self_attn.k_norm.weight", (Hkv * hd,)),
+             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, d)), _rup(d, ROWPAD)),
+             "gate_up_w": _pad_rows(torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))],
+                                              0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
+             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
+        for f, t in L.items():
+            out[f"layers.{i}.{f}"] = t
+    return out
+
+
+def load_olmo2_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the OLMo-2 checkpoint in model_dir; dtype as clm_dtype reads it."""
+    cfg = load_config(model_dir)
+    dims = olmo2_dims(cfg, max_positions)
+    wdt = clm_dtype(dtype, cfg)
+    return dims, olmo2_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
+
+
+class Olmo2Scorer(LlamaScorer):
+    """An OLMo-2 decoder on the GPU: a LlamaScorer (same descriptor, scoring surface, context cache in fp16 and dtype rules) whose
+    calls are b2t_clm_olmo2_score_f16 / _tree_f16 / _tree_cached_f16 / _bf16 / _tree_bf16 (csrc/causal_lm_olmo2.hip) with the
+    per-layer q / k norm weights of olmo2_device_layout, and whose workspace sizes are the b2t_clm_olmo2_* size functions'
+    (the Llama workspace plus an fp32 region for the rows the two norms read)."""
+
+    _WS_BYTES = "b2t_clm_olmo2_ws_bytes"
+    _SIZES = "b2t_clm_olmo2_"
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0, dtype=None):
+        if dims["n_layers"] > 0 and "layers.0.q_norm_w" not in arrays:
+            raise KeyError("Olmo2Scorer: the arrays lack layers.<i>.q_norm_w / k_norm_w (olmo2_device_layout makes them)")
+        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
+        self._family = "olmo2"
+        if not self._qk:     # no layers: the calls still take the array argument
+            self._qk = (None,)
 
 
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
@@ -1208,8 +1319,9 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
     only, like OPT), NeoxScorer for "gpt_neox" (Pythia; fp16 only), LlamaScorer for "llama",
-    "mistral", "qwen2" and "qwen3"; anything else is refused.  max_positions caps a Llama-family model's rotary table.  dtype (clm_dtype):
-    None or "float16", "bfloat16" (the Llama family only, and without a context cache), or "auto" = the dtype config.json says
+    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2"; anything else ("olmo" and "olmo3" included) is refused.
+    max_positions caps a Llama-family or OLMo-2 model's rotary table.  dtype (clm_dtype):
+    None or "float16", "bfloat16" (the Llama family and OLMo-2 only, and without a context cache), or "auto" = the dtype config.json says
     the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
     refused is refused before any weight is read."""
     cfg = load_config(model_dir)
@@ -1232,15 +1344,21 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_llama_arrays(model_dir, max_positions, wdt)
         return LlamaScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)})")
+    if mt == "olmo2":
+        wdt = clm_dtype(dtype, cfg)
+        llama_check_dtype_cache(wdt, context_cache_tokens)
+        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
+        dims, arrays = load_olmo2_arrays(model_dir, max_positions, wdt)
+        return Olmo2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
+    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, olmo2)")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
               max_positions=None, dtype=None):
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
-    OptScorer, a Gpt2Scorer for a GPT-2 directory, or a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory
-    (build_scorer).
+    OptScorer, a Gpt2Scorer for a GPT-2 directory, a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory, or an
+    Olmo2Scorer for an OLMo-2 directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

@@ -51,6 +51,15 @@ GEMM's epilogue) under the protocol of --arch llama, against HF's GPT2LMHeadMode
 d 1600, 25 heads of 64, ffn 6400, vocab 50257, 1024 positions, tied head.
 
   python tools/bench_llm_rescore.py --arch gpt2 [--tree --context 64 | --session]
+
+`--arch olmo2` measures what OLMo-2's layer costs beside the Llama layer: an Olmo2Scorer (b2t_clm_olmo2_score_f16 / _tree_f16:
+the whole-row q / k norm and the two post-norms as passes of their own over an fp32 region) and a LlamaScorer of the same
+dimensions on the same random weights, in one process, alternating list by list, each on its flat and its tree path, --reps
+passes over the lists after a warm-up of all four.  The OLMo-2-7B shape: 32 layers, d 4096, 32 query / 32 kv heads of 128, ffn
+11008, vocab 100352, untied head.  The line reports per family and path the per-list medians with their spread, and the
+ratio olmo2 / llama per list.  No HF model is built.
+
+  python tools/bench_llm_rescore.py --arch olmo2 --lists 7 [--list nbest --context 64]
 """
 import argparse
 import json
@@ -87,16 +96,17 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2"), default="opt",
-                    help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape; gpt2: GPT-2 XL shape")
+    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2"), default="opt",
+                    help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape; gpt2: GPT-2 XL shape; "
+                         "olmo2: OLMo-2-7B shape, beside the Llama forward of the same dimensions")
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16",
                     help="--arch llama / qwen3: the compute dtype of the scorer and of the HF model beside it")
     ap.add_argument("--layers", type=int, default=None, help="default 32 (opt, llama), 36 (qwen3), 48 (gpt2)")
     ap.add_argument("--d", type=int, default=None, help="default 4096, 1600 (gpt2)")
     ap.add_argument("--heads", type=int, default=None, help="default 32, 25 (gpt2)")
-    ap.add_argument("--kv-heads", type=int, default=8, help="--arch llama / qwen3: key / value heads")
-    ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama), 12288 (qwen3), 6400 (gpt2)")
-    ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama), 151936 (qwen3), 50257 (gpt2)")
+    ap.add_argument("--kv-heads", type=int, default=None, help="--arch llama / qwen3 / olmo2: key / value heads; default 8, 32 (olmo2)")
+    ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama), 12288 (qwen3), 6400 (gpt2), 11008 (olmo2)")
+    ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama), 151936 (qwen3), 50257 (gpt2), 100352 (olmo2)")
     ap.add_argument("--cands", type=int, default=100)
     ap.add_argument("--lists", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -110,10 +120,15 @@ def main():
     a.layers = a.layers or {"qwen3": 36, "gpt2": 48}.get(a.arch, 32)
     a.d = a.d or (1600 if a.arch == "gpt2" else 4096)
     a.heads = a.heads or (25 if a.arch == "gpt2" else 32)
-    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400}[a.arch]
-    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257}[a.arch]
-    if a.dtype != "float16" and (a.arch in ("opt", "gpt2") or a.session):
+    a.kv_heads = a.kv_heads or (a.heads if a.arch == "olmo2" else 8)
+    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008}[a.arch]
+    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352}[a.arch]
+    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2") or a.session):
         ap.error("--dtype bfloat16 needs --arch llama or qwen3 and has no --session")
+    if a.arch == "olmo2":
+        if a.session:
+            ap.error("--arch olmo2 has no --session")
+        return main_olmo2(a)
     if a.arch == "gpt2":
         return main_gpt2(a)
     if a.arch != "opt":
@@ -273,6 +288,76 @@ def main_gpt2(a):
     sc = R.Gpt2Scorer(dims, R.gpt2_device_layout(model.state_dict(), dims), dev,
                       context_cache_tokens=dims["max_pos"] if a.session else 0)
     return against_hf(a, sc, model, calls, rng, 2 * (L * (4 * d * d + 2 * d * ffn) + d * V), {})
+
+
+def main_olmo2(a):
+    """--arch olmo2: an Olmo2Scorer and a LlamaScorer of the same dimensions on the same random fp16 weights (the Llama model
+    takes post_feedforward_layernorm as its input norm and drops the q / k norms), flat and tree of both alternating list by
+    list in this process."""
+    import torch
+    import llm_rescore as R
+    torch.manual_seed(0)
+    d, H, Hkv, ffn, V, L = a.d, a.heads, a.kv_heads, a.ffn, a.vocab, a.layers
+    hd, dev = d // H, "cuda"
+    rng = np.random.default_rng(0)
+    rn = lambda *s, std: (torch.randn(*s, device=dev) * std).half()
+    nw = lambda n: (1 + 0.2 * torch.randn(n, device=dev)).half()
+    st = {"model.embed_tokens.weight": rn(V, d, std=2.0 / d ** 0.5), "lm_head.weight": rn(V, d, std=2.0 / d ** 0.5),
+          "model.norm.weight": nw(d)}
+    for l in range(L):
+        p = f"model.layers.{l}."
+        for n, (o, i) in {"self_attn.q_proj": (H * hd, d), "self_attn.k_proj": (Hkv * hd, d), "self_attn.v_proj": (Hkv * hd, d),
+                          "self_attn.o_proj": (d, d), "mlp.gate_proj": (ffn, d), "mlp.up_proj": (ffn, d),
+                          "mlp.down_proj": (d, ffn)}.items():
+            st[p + n + ".weight"] = rn(o, i, std=1.0 / i ** 0.5)
+        st[p + "self_attn.q_norm.weight"], st[p + "self_attn.k_norm.weight"] = nw(H * hd), nw(Hkv * hd)
+        st[p + "post_attention_layernorm.weight"], st[p + "post_feedforward_layernorm.weight"] = nw(d), nw(d)
+    cfg = dict(model_type="olmo2", hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, intermediate_size=ffn,
+               vocab_size=V, num_hidden_layers=L, max_position_embeddings=2048, rms_norm_eps=1e-6, rope_theta=500000.0,
+               tie_word_embeddings=False, hidden_act="silu")
+    dims = R.olmo2_dims(cfg)
+    scs = {"olmo2": R.Olmo2Scorer(dims, R.olmo2_device_layout(st, dims, R.rope_inv_freq(cfg)), dev)}
+    lst = {k.replace("post_feedforward_layernorm", "input_layernorm"): v for k, v in st.items() if "_norm.weight" not in k}
+    lcfg = dict(cfg, model_type="llama")
+    ldims = R.llama_dims(lcfg)
+    scs["llama"] = R.LlamaScorer(ldims, R.llama_device_layout(lst, ldims, R.rope_inv_freq(lcfg)), dev)
+    del st, lst
+    torch.cuda.empty_cache()
+    gen = nbest_list if a.list == "nbest" else random_list
+    lists = [gen(rng, V, a.cands, [int(x) for x in rng.integers(4, V, a.context)]) for _ in range(a.lists)]
+    ntok = [sum(len(s) for s in l) for l in lists]
+    fams, paths = ("llama", "olmo2"), (False, True)
+    ms = {(f, t): [[] for _ in lists] for f in fams for t in paths}
+    nodes, same = [0] * len(lists), True
+    with torch.inference_mode():
+        for i in range(max(1, a.warmup)):
+            for f in fams:
+                for t in paths:
+                    scs[f].score(lists[i % len(lists)], share_prefixes=t)
+        torch.cuda.synchronize()
+        for _ in range(max(1, a.reps)):
+            for i, l in enumerate(lists):
+                for f in fams:
+                    out = {}
+                    for t in paths:
+                        t0 = time.perf_counter()
+                        out[t] = scs[f].score(l, share_prefixes=t)   # returns host scores: the call is complete
+                        ms[f, t][i].append((time.perf_counter() - t0) * 1e3)
+                    same = same and out[False].tobytes() == out[True].tobytes()
+                nodes[i] = scs["olmo2"].last_stats["nodes"]
+    r2 = lambda x: round(float(x), 2)
+    per = {k: [float(np.median(v)) for v in ms[k]] for k in ms}   # per list, median over its repeats
+    stat = lambda k: {"median": r2(np.median(per[k])), "min": r2(np.min(per[k])), "max": r2(np.max(per[k])),
+                      "repeat_spread": r2(max(max(v) - min(v) for v in ms[k])), "per_list": [r2(x) for x in per[k]]}
+    ratio = lambda t: [round(o / l, 4) for o, l in zip(per["olmo2", t], per["llama", t])]
+    print(json.dumps({"bench": "llm_rescore_olmo2", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn, "vocab": V,
+                      "cands": a.cands, "list": a.list, "context": a.context, "lists": len(lists), "reps": max(1, a.reps),
+                      "tokens": float(np.mean(ntok)), "nodes": float(np.mean(nodes)), "per_list_tokens": ntok,
+                      "per_list_nodes": nodes, "llama_flat_ms": stat(("llama", False)), "olmo2_flat_ms": stat(("olmo2", False)),
+                      "llama_tree_ms": stat(("llama", True)), "olmo2_tree_ms": stat(("olmo2", True)),
+                      "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
+                      "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
+                      "flat_tree_bit_identical": bool(same)}))
 
 
 def against_hf(a, sc, model, calls, rng, flop_tok, extra):
