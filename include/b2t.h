@@ -910,6 +910,67 @@ int b2t_clm_olmo2_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qk
                                   const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                   long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Mixtral (csrc/causal_lm_mixtral.hip): the Llama layer with routed experts in the dense MLP's place --------------------
+ * HF MixtralForCausalLM (Mixtral-8x7B, 8x22B): attention, norms, rotary positions and head are the Llama forward above, no
+ * biases; the MLP of a layer is n_experts SwiGLU MLPs of which every row runs top_k, chosen by a router.  The model is the same
+ * b2t_clm_llama_t (qkv_b must be NULL) with the experts stacked in a layer's two MLP weights:
+ *   gate_up_w  [n_experts][gate_up_stride][d], gate_up_stride >= round_up(2 F, 256) rows, each expert's rows gate (w1) and up (w3)
+ *              interleaved in blocks of 32 as above and zero-padded;
+ *   down_w     [n_experts][down_stride][F], down_stride >= round_up(d, 256) rows, each expert's w2 zero-padded.
+ * What else the layer needs travels in b2t_clm_moe_t.
+ * The contract, E being the call's element type (fp16 or bf16), x = E(RMSNorm(resid; norm2_w)) the row rounded once -- the
+ * operand of the router and of the experts alike:
+ *   router   l[e] = sum_c x[c] Wg[e][c], e < n_experts: the 16-bit operands widened, accumulated in fp32 in an order that
+ *            depends on the row alone; the logits are never rounded to E;
+ *   choice   top_k experts by repeated argmax with a strict `>`, ties to the lower index.  The ids are top_k distinct values
+ *            in [0, n_experts) whatever the logits hold (NaN, Inf): a NaN shows in the score, never in an address;
+ *   weights  w[j] = exp(l[e_j] - l[e_0]) / sum_{i < top_k} exp(l[e_i] - l[e_0]) in fp32, j in order of choice -- HF's softmax over
+ *            all experts, top-k, renormalise, with the full sum cancelled; never rounded to E;
+ *   experts  h_e = E(silu(x . gate_e) * (x . up_e)) from the two fp32 accumulators, one rounding (the dense layer's epilogue);
+ *            y_e = h_e . down_e, the fp32 accumulator unrounded;
+ *   combine  resid += ((w[0] y_{e_0} + w[1] y_{e_1}) + ...) in fp32, in order of choice, one thread per element, no atomics.
+ * Everything else is the Llama contract above.  Every output element is computed in an order that depends only on its own
+ * row: a sequence scores the same alone or in any batch, flat, tree and cached calls are bit-identical, and B2T_CLM_GEMM_256
+ * does not change a bit.
+ * Limits: 1 <= n_experts <= 64, 1 <= top_k <= min(8, n_experts), ffn_dim % 64 == 0, head dim 64 or 128.
+ * The experts run as one grouped GEMM per projection: the rows are sorted by expert into segments padded to whole 256-row
+ * blocks (S = round_up(rows * top_k, 256) + 256 * n_experts sorted rows always suffice), so the host knows every size before the
+ * first launch and never reads the routing back.  The workspace is the Llama family's, without the dense MLP's hidden rows,
+ * plus one region for the routing and the S sorted rows, hence size functions of their own, which take the MoE descriptor (n_experts and top_k of it); the cache is
+ * the Llama family's (b2t_clm_llama_cache_kv_bytes).  The five calls have their Llama twins' argument lists with `moe` inserted
+ * after model, their output layout and their refusals before any launch (the error text carries the entry point's own name)
+ * plus: a null moe, router_w_host or entry of it; n_experts or top_k outside the limits; a stride below the padded matrix (zero
+ * included); a non-null qkv_b.  There is no cached bf16 call. */
+typedef struct {
+  int n_experts, top_k;
+  const void* const* router_w_host;        /* HOST array of n_layers DEVICE pointers: [n_experts][d] in the call's element type */
+  long long gate_up_stride, down_stride;   /* rows from one expert to the next in gate_up_w and in down_w */
+  int32_t* route_out;                      /* optional DEVICE [n_layers][rows][top_k]: the chosen ids in the call's row order (the
+                                              rows the call computes: tokens, tree nodes, or a cached call's rows); NULL in production */
+} b2t_clm_moe_t;
+
+size_t b2t_clm_mixtral_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_tokens, int n_seq);
+size_t b2t_clm_mixtral_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_nodes, long long n_tokens,
+                                     int n_seq);
+size_t b2t_clm_mixtral_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_rows,
+                                            long long n_tokens, int n_seq);
+int b2t_clm_mixtral_score_f16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
+                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                              size_t ws_bytes, void* stream);
+int b2t_clm_mixtral_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
+                                   const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                   long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_mixtral_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, b2t_clm_cache_t* cache,
+                                          int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                          float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
+                                          void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_mixtral_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
+                               const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                               size_t ws_bytes, void* stream);
+int b2t_clm_mixtral_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
+                                    const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                    long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
  * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
  * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,

@@ -126,6 +126,12 @@ class ClmLlamaDesc(C.Structure):
                [("layers_host", C.POINTER(ClmLlamaLayer))]
 
 
+class ClmMoe(C.Structure):
+    """Mirror of b2t_clm_moe_t (include/b2t.h): the routed experts of a Mixtral model beside its b2t_clm_llama_t."""
+    _fields_ = [("n_experts", C.c_int), ("top_k", C.c_int), ("router_w_host", C.POINTER(VP)), ("gate_up_stride", C.c_longlong),
+                ("down_stride", C.c_longlong), ("route_out", VP)]
+
+
 class ClmQkNorm(C.Structure):
     """Mirror of b2t_clm_qknorm_t (include/b2t.h): device weights [hd] of one Qwen3 layer's q and k RMSNorm."""
     _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
@@ -280,6 +286,11 @@ for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16", "scor
     _SIGNATURES["b2t_clm_olmo2_" + _t] = _SIGNATURES["b2t_clm_qwen3_" + _t]
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes"):
     _SIGNATURES["b2t_clm_olmo2_" + _t] = _SIGNATURES["b2t_clm_llama_" + _t]
+# Mixtral: the Llama twin's list with the MoE descriptor after the model, the size functions included
+for _t in ("ws_bytes", "tree_ws_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16",
+           "score_tree_cached_f16"):
+    _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
+    _SIGNATURES["b2t_clm_mixtral_" + _t] = (_res, [_args[0], C.POINTER(ClmMoe)] + _args[1:])
 # GPT-NeoX: the OPT twin's list on its own model struct (same cache)
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
            "score_tree_cached_f16"):

@@ -61,6 +61,7 @@ bool llama_dims_ok(const b2t_clm_llama_t* m) {
 }  // namespace
 
 // LlamaShared<_Float16> (clm_llama.h): this unit's launches for the policy of another family (causal_lm_qwen3.hip)
+template <> int LlamaShared<_Float16>::gemm_rope(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_rope(g, s); }
 template <> int LlamaShared<_Float16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_swiglu(g, s); }
 template <> int LlamaShared<_Float16>::gemm_resid(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_resid(g, s); }
 template <> int LlamaShared<_Float16>::gemm_head(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_head(g, s); }

@@ -58,6 +58,7 @@ struct LlamaBf16 : LlamaOps<__bf16> {
 }  // namespace
 
 // LlamaShared<__bf16> (clm_llama.h): this unit's launches for the policy of another family (causal_lm_qwen3.hip)
+template <> int LlamaShared<__bf16>::gemm_rope(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_rope(g, s); }
 template <> int LlamaShared<__bf16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_swiglu(g, s); }
 template <> int LlamaShared<__bf16>::gemm_resid(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_resid(g, s); }
 template <> int LlamaShared<__bf16>::gemm_head(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_head(g, s); }

@@ -7,7 +7,8 @@
 // causal_lm_qwen3.hip the one Qwen3 adds (EP_QKNORM_ROPE: the per-head q / k RMSNorm in front of the rotation) in both,
 // causal_lm_gpt2.hip the one GPT-2 adds (EP_GELU: gelu_new where OPT's fc1 has ReLU) in fp16, causal_lm_neox.hip the two
 // GPT-NeoX adds (EP_ROPE_PART: the rotation of only the first rotary_ndims dims of a head; EP_GELU_ERF) in fp16, causal_lm_olmo2.hip the two OLMo-2 adds
-// (EP_F32 and EP_QKV_F32: fp32 stores for the norms over a whole output row) in both.  Which
+// (EP_F32 and EP_QKV_F32: fp32 stores for the norms over a whole output row) in both, causal_lm_mixtral.hip the grouped form of
+// the tile (clm_gemm_grouped_kernel: one B matrix per expert) with EP_SWIGLU and EP_F32 in both.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -48,9 +49,13 @@ __device__ __forceinline__ float gelu_new(float v) {
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.7071067811865476f)); }
 
 // BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.  E is the element type of
-// A, B, bias and out16 (ClmElem, clm_internal.h).
-template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16>
-__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
+// A, B, bias and out16 (ClmElem, clm_internal.h).  This is the body of both kernels below.  GROUPED (routed experts,
+// clm_moe.h): B is a stack of matrices b_stride elements apart and the rows of A are sorted by matrix in segments of whole
+// 256-row blocks, so a tile of either size lies in one segment; it takes its matrix from blk_expert[m0 / 128] and returns, the
+// whole workgroup alike and before any barrier, where that is negative (a block no row was routed to).  Nothing else
+// differs: the k order and the arithmetic of an output element are those of the plain tile.
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16, bool GROUPED = false>
+__device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
   using vec8 = typename ClmElem<E>::v8;
   constexpr int T = 64 * WGM * WGN, WTM = BM / WGM, WTN = BN / WGN, FM = WTM / 32, FN = WTN / 32, RS = T / 8;
   static_assert(WTN == 64, "the head epilogue reduces over 64-column wave slices");
@@ -69,6 +74,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
   const int K = g.K, nk = K / CK;
   const E* ag = static_cast<const E*>(g.A) + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
   const E* bg = static_cast<const E*>(g.B) + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
+  if (GROUPED) {
+    const int ex = g.blk_expert[m0 / 128];   // one value per workgroup: m0 is a multiple of 128
+    if (ex < 0) return;
+    bg += (long long)ex * g.b_stride;
+  }
   const long long rstep = (long long)RS * K;
   uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
 #define CLM_FETCH(k0)                                                                                                   \
@@ -309,23 +319,42 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
   }
 }
 
+// The tile as a kernel of its own: the plain GEMM, and the grouped one of the routed experts.
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16>
+__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_kernel(ClmGemm g) {
+  clm_gemm_tile<BM, BN, WGM, WGN, EP, E>(g);
+}
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16>
+__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_grouped_kernel(ClmGemm g) {
+  clm_gemm_tile<BM, BN, WGM, WGN, EP, E, true>(g);
+}
+
+template <int BM, int BN, int WGM, int WGN, int EP, class E, bool GROUPED>
+constexpr auto clm_gemm_entry() {
+  if constexpr (GROUPED) return &clm_gemm_grouped_kernel<BM, BN, WGM, WGN, EP, E>;
+  else return &clm_gemm_kernel<BM, BN, WGM, WGN, EP, E>;
+}
+
 constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * 2; }   // 2-byte elements
 
-// The launch of one GEMM on the tile the rule chose (ClmGemmTiles of clm_internal.h).
-template <int EP, class E = _Float16>
+// The launch of one GEMM on the tile the rule chose (ClmGemmTiles of clm_internal.h); GROUPED launches the grouped kernel on
+// the same grid (M is then the sorted rows S, a multiple of 256).
+template <int EP, class E = _Float16, bool GROUPED = false>
 int clm_gemm_tiles(const ClmGemm& g, hipStream_t s, bool use256) {
   if (use256) {   // one 8-wave workgroup per CU
+    const auto kern = clm_gemm_entry<256, 256, 2, 4, EP, E, GROUPED>();
     const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<256, 256, 2, 4, EP, E>),
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));
-    hipLaunchKernelGGL((clm_gemm_kernel<256, 256, 2, 4, EP, E>), dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
+    hipLaunchKernelGGL(kern, dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
   } else {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(clm_gemm_kernel<128, 128, 2, 2, EP, E>),
+    const auto kern = clm_gemm_entry<128, 128, 2, 2, EP, E, GROUPED>();
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(128, 128));
     const int m128 = (g.M + 127) / 128, n128 = (g.N + 127) / 128;
-    hipLaunchKernelGGL((clm_gemm_kernel<128, 128, 2, 2, EP, E>), dim3(m128 * n128), dim3(256), lds_bytes(128, 128), s, g);
+    hipLaunchKernelGGL(kern, dim3(m128 * n128), dim3(256), lds_bytes(128, 128), s, g);
   }
   B2T_CHECK_LAUNCH("clm_gemm_kernel");
   return 0;

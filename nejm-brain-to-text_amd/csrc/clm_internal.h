@@ -2,7 +2,8 @@
 // the Llama family in bf16, uses the element-type trait ClmElem, ClmGemm, the tile rule, the head and the index builders;
 // causal_lm_qwen3.hip, Qwen3 in both formats, the same and clm_score_tree_cached; causal_lm_gpt2.hip, GPT-2, the OPT forward
 // and entry-point bodies below with its own fc1 GEMM; causal_lm_neox.hip, GPT-NeoX, the launchers, the head, the index builders
-// and clm_score_tree_cached around a forward of its own).  causal_lm.hip (the flat OPT path) defines the tile rule,
+// and clm_score_tree_cached around a forward of its own; causal_lm_olmo2.hip and causal_lm_mixtral.hip, the Llama family's
+// entry-point bodies around a layer of their own).  causal_lm.hip (the flat OPT path) defines the tile rule,
 // the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
 // list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
 // and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
@@ -75,6 +76,9 @@ struct ClmGemm {
   const void* qnorm_w; const void* knorm_w; // EP_QKNORM_ROPE: [hd] weights of the q heads' and the k heads' RMSNorm
   float rms_eps;                            // EP_QKNORM_ROPE
   int rope_half;                            // EP_ROPE_PART: rotary_ndims / 2, the row stride of rope_cos / rope_sin (hd/8, hd/4 or hd/2)
+  // the grouped kernel only (clm_gemm_grouped_kernel; the routed experts of clm_moe.h): M is a multiple of 256
+  const int* blk_expert;                    // [M / 128] the matrix of B that the 128-row block of A multiplies, -1: no rows, no tile
+  long long b_stride;                       // elements between two consecutive matrices of B
 };
 
 // The tile rule (B2T_CLM_GEMM_256) lives in one definition, causal_lm.hip: it picks the tile and hands the launch to `tiles`,

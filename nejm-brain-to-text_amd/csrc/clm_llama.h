@@ -10,8 +10,9 @@
 // causal_lm_llama.hip holds the fp16 policy and the fp16 entry points (the cached one included), causal_lm_llama_bf16.hip the
 // bf16 policy, every bf16 kernel instantiation and the two bf16 entry points.  causal_lm_qwen3.hip holds the two Qwen3
 // policies: gemm_rope with the epilogue EP_QKNORM_ROPE, instantiated there, and every other launch through LlamaShared<E>.
-// The two entry-point bodies also serve a family with another layer (OLMo-2, clm_olmo2.h): their second template argument
-// supplies the layout, the q / k norm refusals and the forward (LlamaFamily below by default).
+// The two entry-point bodies also serve a family with another layer (OLMo-2, clm_olmo2.h; Mixtral, clm_moe.h): their second
+// template argument supplies the layout, the refusals that go with the family's extra argument and the forward (LlamaFamily
+// below by default).
 #pragma once
 #include <math.h>
 #include <string>
@@ -27,12 +28,14 @@ int clm_llama_check_model(const b2t_clm_llama_t* m);
 // none, and EP_QKNORM_ROPE adds none) are refused; causal_lm_qwen3.hip
 int clm_qknorm_check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_qknorm_t* qkn);
 
-// The launches of the Llama policy for element type E that another family's policy shares (P's list above without gemm_rope),
+// The launches of the Llama policy for element type E that another family's policy shares (P's list above; Qwen3's and OLMo-2's
+// policies put a QKV GEMM of their own in front of gemm_rope, Mixtral's takes it as it is),
 // so that their kernels are instantiated in one unit: the members are defined in causal_lm_llama.hip for _Float16 and in
 // causal_lm_llama_bf16.hip for __bf16, each forwarding to its unit's policy.
 template <class El>
 struct LlamaShared {
   using E = El;
+  static int gemm_rope(const ClmGemm& g, hipStream_t s);
   static int gemm_swiglu(const ClmGemm& g, hipStream_t s);
   static int gemm_resid(const ClmGemm& g, hipStream_t s);
   static int gemm_head(const ClmGemm& g, hipStream_t s);
@@ -44,6 +47,7 @@ struct LlamaShared {
 };
 // the specialisations the two units define, declared before any use
 #define B2T_LLAMA_SHARED(EL)                                                                                                  \
+  template <> int LlamaShared<EL>::gemm_rope(const ClmGemm&, hipStream_t);                                                    \
   template <> int LlamaShared<EL>::gemm_swiglu(const ClmGemm&, hipStream_t);                                                  \
   template <> int LlamaShared<EL>::gemm_resid(const ClmGemm&, hipStream_t);                                                   \
   template <> int LlamaShared<EL>::gemm_head(const ClmGemm&, hipStream_t);                                                    \
@@ -107,18 +111,18 @@ inline ClmLayout llama_layout(const b2t_clm_llama_t* m, long long rows, long lon
   return clm_layout(m->d_model, qw, m->ffn_dim, m->vocab, rows, hrows, ints);
 }
 
-// The forward over r.rows rows up to the per-row log-probs logp[Mh]; attn(layer, qkv, out) enqueues one layer's attention.
+// The forward over r.rows rows up to the per-row log-probs logp[Mh]; attn(layer, qkv, out) enqueues one layer's attention,
+// mlp(layer, x16, resid) one layer's MLP: resid += MLP(x16), x16 being E(RMSNorm(resid; norm2_w)) with its padding rows zero.
 // qkn is the per-layer q / k norm weights of a policy with qk_norm (checked by clm_qknorm_check), unused otherwise.
-template <class P, class Attn>
-int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
-                  const b2t_clm_qknorm_t* qkn = nullptr) {
+template <class P, class Attn, class Mlp>
+int llama_forward_mlp(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
+                      const b2t_clm_qknorm_t* qkn, Mlp&& mlp) {
   using E = typename P::E;
-  const int d = m.d_model, Hq = m.n_heads, Hkv = m.n_kv_heads, hd = d / Hq, F = m.ffn_dim, qw = (Hq + 2 * Hkv) * hd;
+  const int d = m.d_model, Hq = m.n_heads, Hkv = m.n_kv_heads, hd = d / Hq, qw = (Hq + 2 * Hkv) * hd;
   const long long rows = r.rows;
   float* resid = reinterpret_cast<float*>(base + L.resid);
   E* x16 = reinterpret_cast<E*>(base + L.x16);
   E* qkv = reinterpret_cast<E*>(base + L.qkv);
-  E* hb = reinterpret_cast<E*>(base + L.hbuf);
   auto W = [](const void* p) { return static_cast<const E*>(p); };
   if (int rc = P::embed(r.d_ids, W(m.embed_tokens), resid, d, rows, s)) return rc;
   for (int l = 0; l < m.n_layers; ++l) {
@@ -135,23 +139,37 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
     g.A = x16; g.B = w.o_w; g.M = (int)rows; g.N = d; g.K = d; g.resid = resid; g.ldo = d;
     if (int rc = P::gemm_resid(g, s)) return rc;
     if (int rc = P::rmsnorm(resid, nullptr, rows, W(w.norm2_w), m.rms_eps, x16, d, s)) return rc;
-    g = ClmGemm{};
-    g.A = x16; g.B = w.gate_up_w; g.M = (int)rows; g.N = 2 * F; g.K = d; g.out16 = hb; g.ldo = F;
-    if (int rc = P::gemm_swiglu(g, s)) return rc;
-    g = ClmGemm{};
-    g.A = hb; g.B = w.down_w; g.M = (int)rows; g.N = d; g.K = F; g.resid = resid; g.ldo = d;
-    if (int rc = P::gemm_resid(g, s)) return rc;
+    if (int rc = mlp(l, x16, resid)) return rc;
   }
   if (r.Mh <= 0) return 0;
   if (int rc = P::rmsnorm(resid, r.d_src, r.Mh, W(m.final_norm_w), m.rms_eps, x16, d, s)) return rc;
   return clm_head(x16, m.lm_head, m.vocab, d, r, L, base, s, &P::gemm_head);
 }
 
+// The forward with the family's dense SwiGLU MLP: gate / up GEMM (EP_SWIGLU), down GEMM into the residual.
+template <class P, class Attn>
+int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
+                  const b2t_clm_qknorm_t* qkn = nullptr) {
+  using E = typename P::E;
+  const int d = m.d_model, F = m.ffn_dim;
+  E* hb = reinterpret_cast<E*>(base + L.hbuf);
+  auto mlp = [&](int l, const E* x16, float* resid) -> int {
+    const b2t_clm_llama_layer_t& w = m.layers_host[l];
+    ClmGemm g{};
+    g.A = x16; g.B = w.gate_up_w; g.M = (int)r.rows; g.N = 2 * F; g.K = d; g.out16 = hb; g.ldo = F;
+    if (int rc = P::gemm_swiglu(g, s)) return rc;
+    g = ClmGemm{};
+    g.A = hb; g.B = w.down_w; g.M = (int)r.rows; g.N = d; g.K = F; g.resid = resid; g.ldo = d;
+    return P::gemm_resid(g, s);
+  };
+  return llama_forward_mlp<P>(m, r, L, base, attn, s, qkn, mlp);
+}
+
 // What the two entry-point bodies below take from a family: the workspace layout, the refusals that go with the q / k norm
 // array, and the forward.  This is the Llama family's (Qwen3 included: P::qk_norm); OLMo-2's is Olmo2Family (clm_olmo2.h).
 struct LlamaFamily {
-  static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints) {
-    return llama_layout(m, rows, hrows, ints);
+  static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const void* /*extra*/ = nullptr) {
+    return llama_layout(m, rows, hrows, ints);   // the q / k norm array changes no size
   }
   template <class P>
   static int check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_qknorm_t* qkn) {
@@ -165,19 +183,19 @@ struct LlamaFamily {
   }
 };
 
-// The flat entry point of a policy; `who` is its name.
-template <class P, class Fam = LlamaFamily>
+// The flat entry point of a policy; `who` is its name.  `extra` is what the family's layout, check and forward take beside the
+// model, of the family's own type X: the q / k norm array (Qwen3, OLMo-2) or a descriptor (Mixtral's b2t_clm_moe_t, clm_moe.h).
+template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
 int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
-                float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream,
-                const b2t_clm_qknorm_t* qkn = nullptr) {
+                float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream, const X* extra = nullptr) {
   using E = typename P::E;
   if (int rc = clm_llama_check_model(model)) return rc;
   const b2t_clm_llama_t& m = *model;
-  if (int rc = Fam::template check<P>(who, m, qkn)) return rc;
+  if (int rc = Fam::template check<P>(who, m, extra)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
-  const ClmLayout L = Fam::layout(model, M, M - n_seq, flat_ints(M, n_seq));
+  const ClmLayout L = Fam::layout(model, M, M - n_seq, flat_ints(M, n_seq), extra);
   B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
   const hipStream_t s = as_stream(stream);
   char* base = static_cast<char*>(ws);
@@ -188,26 +206,26 @@ int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* id
   auto attn = [&](int, const E* qkv, E* out) {
     return P::attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
-  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
+  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
   return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
 }
 
 // The tree entry point of a policy.
-template <class P, class Fam = LlamaFamily>
+template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
 int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                      int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
-                     void* stream, const b2t_clm_qknorm_t* qkn = nullptr) {
+                     void* stream, const X* extra = nullptr) {
   using E = typename P::E;
   if (int rc = clm_llama_check_model(model)) return rc;
   const b2t_clm_llama_t& m = *model;
-  if (int rc = Fam::template check<P>(who, m, qkn)) return rc;
+  if (int rc = Fam::template check<P>(who, m, extra)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
   ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);   // a node's rotary position is its depth, node_pos
   const long long Mn = plan.Mn;
   if (n_nodes_out) *n_nodes_out = Mn;
-  const ClmLayout L = Fam::layout(model, Mn, Mn, tree_ints(Mn, M, n_seq));
+  const ClmLayout L = Fam::layout(model, Mn, Mn, tree_ints(Mn, M, n_seq), extra);
   B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
   const hipStream_t s = as_stream(stream);
   char* base = static_cast<char*>(ws);
@@ -218,7 +236,7 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
   auto attn = [&](int, const E* qkv, E* out) {
     return P::attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   };
-  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, qkn)) return rc;
+  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
   return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
 }
 

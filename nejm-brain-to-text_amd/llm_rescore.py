@@ -1093,6 +1093,7 @@ class LlamaScorer(_Scorer):
     _WS_BYTES = "b2t_clm_llama_ws_bytes"
     _SIZES = "b2t_clm_llama_"   # the family's size functions: _SIZES + ws_bytes / tree_ws_bytes / cache_kv_bytes / tree_cached_ws_bytes
     _NO_CACHE = "use_cache=True on a scorer built without a context cache (context_cache_tokens)"
+    _size_args = ()   # what the family's workspace size functions take between the model and the sizes (Mixtral: its MoE descriptor)
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0, dtype=None):
@@ -1147,14 +1148,14 @@ class LlamaScorer(_Scorer):
 
     def _sizes(self, lib, path, ids, off):
         import ctypes as C
-        desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
+        desc, M, n_seq = (C.byref(self.desc),) + tuple(self._size_args), len(ids), len(off) - 1
         if path == "cached":
             plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
-            return plan["rows"], plan["reused"], getattr(lib, self._SIZES + "tree_cached_ws_bytes")(desc, plan["rows"], M, n_seq)
+            return plan["rows"], plan["reused"], getattr(lib, self._SIZES + "tree_cached_ws_bytes")(*desc, plan["rows"], M, n_seq)
         if path == "tree":
             nodes = tree_plan(ids, off)[2]
-            return nodes, 0, getattr(lib, self._SIZES + "tree_ws_bytes")(desc, nodes, M, n_seq)
-        return M, 0, getattr(lib, self._SIZES + "ws_bytes")(desc, M, n_seq)
+            return nodes, 0, getattr(lib, self._SIZES + "tree_ws_bytes")(*desc, nodes, M, n_seq)
+        return M, 0, getattr(lib, self._SIZES + "ws_bytes")(*desc, M, n_seq)
 
     def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
         import ctypes as C
@@ -1283,6 +1284,157 @@ class Olmo2Scorer(LlamaScorer):
             self._qk = (None,)
 
 
+# ---- Mixtral (HF MixtralForCausalLM): the Llama layer with routed experts in the dense MLP's place ---------------------------
+MIXTRAL_MAX_EXPERTS, MIXTRAL_MAX_TOP_K = 64, 8
+
+
+def mixtral_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
+    """The dimensions b2t_clm_llama_t and b2t_clm_moe_t need for a "mixtral" config, after refusing, by the field's name, what the
+    kernels do not run.  max_pos is max_position_embeddings lowered to the sliding window where one is configured (as for
+    Mistral: within it full causal attention is what the model computes) and to max_positions (default LLAMA_MAX_POSITIONS)."""
+    mt = cfg.get("model_type")
+    if mt != "mixtral":
+        raise ValueError(f"model_type {mt!r} is not 'mixtral'")
+    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    Hkv = int(cfg.get("num_key_value_heads") or Hq)
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise ValueError(f"mixtral hidden_act {act!r} is not supported (silu only)")
+    if d % Hq or int(cfg.get("head_dim") or d // Hq) != d // Hq:
+        raise ValueError(f"head_dim {cfg.get('head_dim')} is not hidden_size / num_attention_heads = {d}/{Hq}")
+    if d // Hq not in LLAMA_HEAD_DIMS:
+        raise ValueError(f"head_dim {d // Hq} is not supported (one of {LLAMA_HEAD_DIMS})")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    ne, k = int(cfg.get("num_local_experts", 8)), int(cfg.get("num_experts_per_tok", 2))
+    if not 1 <= ne <= MIXTRAL_MAX_EXPERTS:
+        raise ValueError(f"num_local_experts {ne} outside [1, {MIXTRAL_MAX_EXPERTS}]")
+    if not 1 <= k <= min(MIXTRAL_MAX_TOP_K, ne):
+        raise ValueError(f"num_experts_per_tok {k} outside [1, min({MIXTRAL_MAX_TOP_K}, num_local_experts {ne})]")
+    for f in ("attention_bias", "mlp_bias"):
+        if cfg.get(f):
+            raise ValueError(f"mixtral with {f}=True is not supported (no bias anywhere)")
+    ffn = int(cfg["intermediate_size"])
+    if d % 64 or ffn % 64:
+        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    rope_inv_freq(cfg)   # refuses a rope_type other than default / llama3
+    max_pos = int(cfg["max_position_embeddings"])
+    if cfg.get("sliding_window") is not None:
+        max_pos = min(max_pos, int(cfg["sliding_window"]))
+    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
+    if cap < 1:
+        raise ValueError(f"max_positions {cap} < 1")
+    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
+                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-5)),
+                tied=bool(cfg.get("tie_word_embeddings", False)), n_experts=ne, top_k=k)
+
+
+def mixtral_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
+    """Tensors in the layout of b2t_clm_llama_t / b2t_clm_moe_t from a Mixtral state dict.  Embedding, head, norms, qkv_w (under
+    qkv_row_perm), o_w and the rotary tables are llama_device_layout's; per layer also router_w [E][d], gate_up_w
+    [E][round_up(2F, 256)][d] -- every expert's gate (w1) and up (w3) rows interleaved in blocks of 32 (gate_up_row_perm) and
+    zero-padded, so the expert stride is dims-only: mixtral_strides -- and down_w [E][round_up(d, 256)][F] (w2).  Both spellings
+    of a checkpoint are read: the published one (block_sparse_moe.gate.weight, block_sparse_moe.experts.<e>.w1 / w3 / w2.weight)
+    and the fused one (mlp.gate.weight, mlp.experts.gate_up_proj [E][2F][d] with gate rows then up rows, mlp.experts.down_proj
+    [E][d][F]).  Any bias in a layer is refused."""
+    import torch
+    wdt = clm_dtype(dtype)
+    sd = dict(state)
+    d, ffn, V, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"], dims["n_kv_heads"]
+    ne, hd = dims["n_experts"], dims["d_model"] // dims["n_heads"]
+
+    def get(name, shape):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name}")
+        t = sd[name].detach().to(wdt).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
+    dev = emb.device
+    tied = dims.get("tied", False) or "lm_head.weight" not in sd
+    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
+           "final_norm_w": get("model.norm.weight", (d,))}
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    qperm = torch.from_numpy(qkv_row_perm(Hq, Hkv, hd)).to(dev)
+    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
+    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    gus, dns = mixtral_strides(dims)
+    for i in range(dims["n_layers"]):
+        p = f"model.layers.{i}."
+        for n in sd:
+            if n.startswith(p) and n.endswith(".bias"):
+                raise ValueError(f"{n}: Mixtral biases are not supported")
+        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
+        if p + "mlp.experts.gate_up_proj" in sd:     # the fused spelling
+            router = get(p + "mlp.gate.weight", (ne, d))
+            gate_up = get(p + "mlp.experts.gate_up_proj", (ne, 2 * ffn, d))
+            down = get(p + "mlp.experts.down_proj", (ne, d, ffn))
+        else:                                        # the published spelling
+            m = p + "block_sparse_moe."
+            router = get(m + "gate.weight", (ne, d))
+            gate_up = torch.stack([torch.cat([get(m + f"experts.{e}.w1.weight", (ffn, d)), get(m + f"experts.{e}.w3.weight", (ffn, d))], 0)
+                                   for e in range(ne)])
+            down = torch.stack([get(m + f"experts.{e}.w2.weight", (d, ffn)) for e in range(ne)])
+        gu = gate_up.new_zeros((ne, gus, d))
+        gu[:, :2 * ffn] = gate_up[:, gperm]
+        dn = down.new_zeros((ne, dns, ffn))
+        dn[:, :d] = down
+        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
+             "qkv_w": _pad_rows(qkv[qperm].contiguous(), _rup(qkv.shape[0], ROWPAD)),
+             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, d)), _rup(d, ROWPAD)),
+             "router_w": router, "gate_up_w": gu, "down_w": dn}
+        for f, t in L.items():
+            out[f"layers.{i}.{f}"] = t
+    return out
+
+
+def mixtral_strides(dims: dict) -> Tuple[int, int]:
+    """Rows from one expert to the next in gate_up_w and in down_w: round_up(2F, 256) and round_up(d, 256)."""
+    return _rup(2 * dims["ffn_dim"], ROWPAD), _rup(dims["d_model"], ROWPAD)
+
+
+def load_mixtral_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the Mixtral checkpoint in model_dir; dtype as clm_dtype reads it."""
+    cfg = load_config(model_dir)
+    dims = mixtral_dims(cfg, max_positions)
+    wdt = clm_dtype(dtype, cfg)
+    return dims, mixtral_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
+
+
+class MixtralScorer(LlamaScorer):
+    """A Mixtral decoder on the GPU: a LlamaScorer (same descriptor with the experts stacked in gate_up_w / down_w, scoring
+    surface, context cache in fp16 and dtype rules) whose calls are b2t_clm_mixtral_score_f16 / _tree_f16 / _tree_cached_f16 /
+    _bf16 / _tree_bf16 (csrc/causal_lm_mixtral.hip) with the b2t_clm_moe_t of mixtral_device_layout's arrays, and whose
+    workspace sizes are the b2t_clm_mixtral_* size functions' (the Llama workspace plus the routing and the sorted rows); the
+    cache's size is the Llama family's."""
+
+    _WS_BYTES = "b2t_clm_mixtral_ws_bytes"
+    _SIZES = "b2t_clm_mixtral_"
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0, dtype=None):
+        import ctypes as C
+        import b2t_native as N
+        if "n_experts" not in dims or (dims["n_layers"] > 0 and "layers.0.router_w" not in arrays):
+            raise KeyError("MixtralScorer: dims lack n_experts / top_k or the arrays layers.<i>.router_w (mixtral_dims and "
+                           "mixtral_device_layout make them)")
+        # the descriptor first: the cache allocation of the base class does not need it, the size functions do
+        self._routers = (C.c_void_p * max(1, dims["n_layers"]))()
+        gus, dns = mixtral_strides(dims)
+        self._moe = N.ClmMoe(dims["n_experts"], dims["top_k"], self._routers, gus, dns, None)
+        self._size_args = (self._moe,)
+        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
+        for i in range(dims["n_layers"]):
+            self._routers[i] = self.w[f"layers.{i}.router_w"].data_ptr()
+        self._family, self._qk = "mixtral", (self._moe,)
+
+    def _cache_kv_bytes(self, lib, cap):
+        import ctypes as C
+        return lib.b2t_clm_llama_cache_kv_bytes(C.byref(self.desc), cap)
+
+
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
     """b2t_clm_tree_plan_host on packed int32 ids / offsets (host only, no GPU): (node_of_token, parent_of_node, n_nodes).
     A node is a distinct token prefix, numbered by first appearance; parent_of_node is -1 at roots."""
@@ -1319,9 +1471,9 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
     only, like OPT), NeoxScorer for "gpt_neox" (Pythia; fp16 only), LlamaScorer for "llama",
-    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2"; anything else ("olmo" and "olmo3" included) is refused.
-    max_positions caps a Llama-family or OLMo-2 model's rotary table.  dtype (clm_dtype):
-    None or "float16", "bfloat16" (the Llama family and OLMo-2 only, and without a context cache), or "auto" = the dtype config.json says
+    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2", MixtralScorer for "mixtral"; anything else ("olmo" and "olmo3"
+    included) is refused.  max_positions caps a Llama-family, OLMo-2 or Mixtral model's rotary table.  dtype (clm_dtype):
+    None or "float16", "bfloat16" (the Llama family, OLMo-2 and Mixtral only, and without a context cache), or "auto" = the dtype config.json says
     the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
     refused is refused before any weight is read."""
     cfg = load_config(model_dir)
@@ -1350,15 +1502,21 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_olmo2_arrays(model_dir, max_positions, wdt)
         return Olmo2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, olmo2)")
+    if mt == "mixtral":
+        wdt = clm_dtype(dtype, cfg)
+        llama_check_dtype_cache(wdt, context_cache_tokens)
+        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
+        dims, arrays = load_mixtral_arrays(model_dir, max_positions, wdt)
+        return MixtralScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
+    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, olmo2, mixtral)")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
               max_positions=None, dtype=None):
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
-    OptScorer, a Gpt2Scorer for a GPT-2 directory, a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory, or an
-    Olmo2Scorer for an OLMo-2 directory (build_scorer).
+    OptScorer, a Gpt2Scorer for a GPT-2 directory, a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory, an
+    Olmo2Scorer for an OLMo-2 directory, or a MixtralScorer for a Mixtral directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

@@ -60,6 +60,15 @@ passes over the lists after a warm-up of all four.  The OLMo-2-7B shape: 32 laye
 ratio olmo2 / llama per list.  No HF model is built.
 
   python tools/bench_llm_rescore.py --arch olmo2 --lists 7 [--list nbest --context 64]
+
+`--arch mixtral` measures what routing costs: a MixtralScorer (b2t_clm_mixtral_score_f16 / _tree_f16: router, plan, gather, two
+grouped GEMMs over the rows sorted by expert, combine) at the Mixtral-8x7B shape with a few layers -- d 4096, 32 query / 8 kv
+heads of 128, ffn 14336, 8 experts, top-2, vocab 32000 -- beside a dense LlamaScorer with d 4096 and ffn 28672 = top_k x 14336,
+which has the same active FLOPs per row, under the protocol of --arch olmo2.  The line reports the per-list medians and the
+ratio mixtral / llama per list; the sorted rows S = round_up(rows * top_k, 256) + 256 * n_experts against rows * top_k say how much
+of the grouped GEMM is padding at that list length.
+
+  python tools/bench_llm_rescore.py --arch mixtral --layers 4 --lists 7 [--cands 20] [--list nbest --context 64]
 """
 import argparse
 import json
@@ -96,9 +105,10 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2"), default="opt",
+    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2", "mixtral"), default="opt",
                     help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape; gpt2: GPT-2 XL shape; "
-                         "olmo2: OLMo-2-7B shape, beside the Llama forward of the same dimensions")
+                         "olmo2: OLMo-2-7B shape, beside the Llama forward of the same dimensions; mixtral: Mixtral-8x7B shape "
+                         "with 4 layers, beside the dense Llama forward of the same active FLOPs")
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16",
                     help="--arch llama / qwen3: the compute dtype of the scorer and of the HF model beside it")
     ap.add_argument("--layers", type=int, default=None, help="default 32 (opt, llama), 36 (qwen3), 48 (gpt2)")
@@ -117,14 +127,18 @@ def main():
     ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
     ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
-    a.layers = a.layers or {"qwen3": 36, "gpt2": 48}.get(a.arch, 32)
+    a.layers = a.layers or {"qwen3": 36, "gpt2": 48, "mixtral": 4}.get(a.arch, 32)
     a.d = a.d or (1600 if a.arch == "gpt2" else 4096)
     a.heads = a.heads or (25 if a.arch == "gpt2" else 32)
     a.kv_heads = a.kv_heads or (a.heads if a.arch == "olmo2" else 8)
-    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008}[a.arch]
-    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352}[a.arch]
-    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2") or a.session):
+    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008, "mixtral": 14336}[a.arch]
+    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352, "mixtral": 32000}[a.arch]
+    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2", "mixtral") or a.session):
         ap.error("--dtype bfloat16 needs --arch llama or qwen3 and has no --session")
+    if a.arch == "mixtral":
+        if a.session:
+            ap.error("--arch mixtral has no --session")
+        return main_mixtral(a)
     if a.arch == "olmo2":
         if a.session:
             ap.error("--arch olmo2 has no --session")
@@ -355,6 +369,87 @@ def main_olmo2(a):
                       "tokens": float(np.mean(ntok)), "nodes": float(np.mean(nodes)), "per_list_tokens": ntok,
                       "per_list_nodes": nodes, "llama_flat_ms": stat(("llama", False)), "olmo2_flat_ms": stat(("olmo2", False)),
                       "llama_tree_ms": stat(("llama", True)), "olmo2_tree_ms": stat(("olmo2", True)),
+                      "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
+                      "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
+                      "flat_tree_bit_identical": bool(same)}))
+
+
+def main_mixtral(a, n_experts=8, top_k=2):
+    """--arch mixtral: a MixtralScorer and a dense LlamaScorer with ffn top_k x the experts' (the same active FLOPs per row) on
+    random fp16 weights that share everything but the MLP, flat and tree of both alternating list by list in this process."""
+    import torch
+    import llm_rescore as R
+    torch.manual_seed(0)
+    d, H, Hkv, ffn, V, L = a.d, a.heads, a.kv_heads, a.ffn, a.vocab, a.layers
+    hd, dev = d // H, "cuda"
+    rng = np.random.default_rng(0)
+    rn = lambda *s, std: (torch.randn(*s, device=dev) * std).half()
+    nw = lambda n: (1 + 0.2 * torch.randn(n, device=dev)).half()
+    base = dict(hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, vocab_size=V, num_hidden_layers=L,
+                max_position_embeddings=2048, rms_norm_eps=1e-5, rope_theta=1e6, tie_word_embeddings=False, hidden_act="silu")
+    cfg = dict(base, model_type="mixtral", intermediate_size=ffn, num_local_experts=n_experts, num_experts_per_tok=top_k)
+    lcfg = dict(base, model_type="llama", intermediate_size=top_k * ffn)
+    dims, ldims = R.mixtral_dims(cfg), R.llama_dims(lcfg)
+    shared = {"model.embed_tokens.weight": rn(V, d, std=2.0 / d ** 0.5), "lm_head.weight": rn(V, d, std=2.0 / d ** 0.5),
+              "model.norm.weight": nw(d)}
+    for l in range(L):
+        p = f"model.layers.{l}."
+        for n, (o, i) in {"self_attn.q_proj": (H * hd, d), "self_attn.k_proj": (Hkv * hd, d), "self_attn.v_proj": (Hkv * hd, d),
+                          "self_attn.o_proj": (d, d)}.items():
+            shared[p + n + ".weight"] = rn(o, i, std=1.0 / i ** 0.5)
+        shared[p + "input_layernorm.weight"], shared[p + "post_attention_layernorm.weight"] = nw(d), nw(d)
+    st = dict(shared)
+    for l in range(L):
+        p = f"model.layers.{l}.mlp."
+        st[p + "gate.weight"] = rn(n_experts, d, std=1.0 / d ** 0.5)
+        st[p + "experts.gate_up_proj"] = rn(n_experts, 2 * ffn, d, std=1.0 / d ** 0.5)
+        st[p + "experts.down_proj"] = rn(n_experts, d, ffn, std=1.0 / ffn ** 0.5)
+    scs = {"mixtral": R.MixtralScorer(dims, R.mixtral_device_layout(st, dims, R.rope_inv_freq(cfg)), dev)}
+    del st
+    st = dict(shared)
+    for l in range(L):
+        p = f"model.layers.{l}.mlp."
+        st[p + "gate_proj.weight"], st[p + "up_proj.weight"] = (rn(top_k * ffn, d, std=1.0 / d ** 0.5) for _ in range(2))
+        st[p + "down_proj.weight"] = rn(d, top_k * ffn, std=1.0 / (top_k * ffn) ** 0.5)
+    scs["llama"] = R.LlamaScorer(ldims, R.llama_device_layout(st, ldims, R.rope_inv_freq(lcfg)), dev)
+    del st, shared
+    torch.cuda.empty_cache()
+    gen = nbest_list if a.list == "nbest" else random_list
+    lists = [gen(rng, V, a.cands, [int(x) for x in rng.integers(4, V, a.context)]) for _ in range(a.lists)]
+    ntok = [sum(len(s) for s in l) for l in lists]
+    fams, paths = ("llama", "mixtral"), (False, True)
+    ms = {(f, t): [[] for _ in lists] for f in fams for t in paths}
+    nodes, same = [0] * len(lists), True
+    with torch.inference_mode():
+        for i in range(max(1, a.warmup)):
+            for f in fams:
+                for t in paths:
+                    scs[f].score(lists[i % len(lists)], share_prefixes=t)
+        torch.cuda.synchronize()
+        for _ in range(max(1, a.reps)):
+            for i, l in enumerate(lists):
+                for f in fams:
+                    out = {}
+                    for t in paths:
+                        t0 = time.perf_counter()
+                        out[t] = scs[f].score(l, share_prefixes=t)   # returns host scores: the call is complete
+                        ms[f, t][i].append((time.perf_counter() - t0) * 1e3)
+                    same = same and out[False].tobytes() == out[True].tobytes()
+                nodes[i] = scs["mixtral"].last_stats["nodes"]
+    r2 = lambda x: round(float(x), 2)
+    per = {k: [float(np.median(v)) for v in ms[k]] for k in ms}   # per list, median over its repeats
+    stat = lambda k: {"median": r2(np.median(per[k])), "min": r2(np.min(per[k])), "max": r2(np.max(per[k])),
+                      "repeat_spread": r2(max(max(v) - min(v) for v in ms[k])), "per_list": [r2(x) for x in per[k]]}
+    ratio = lambda t: [round(o / l, 4) for o, l in zip(per["mixtral", t], per["llama", t])]
+    sorted_rows = lambda rows: -(-rows * top_k // 256) * 256 + 256 * n_experts
+    print(json.dumps({"bench": "llm_rescore_mixtral", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn, "vocab": V,
+                      "n_experts": n_experts, "top_k": top_k, "dense_ffn": top_k * ffn, "cands": a.cands, "list": a.list,
+                      "context": a.context, "lists": len(lists), "reps": max(1, a.reps), "tokens": float(np.mean(ntok)),
+                      "nodes": float(np.mean(nodes)), "per_list_tokens": ntok, "per_list_nodes": nodes,
+                      "sorted_rows_over_routed_flat": [round(sorted_rows(n) / (n * top_k), 3) for n in ntok],
+                      "sorted_rows_over_routed_tree": [round(sorted_rows(n) / (n * top_k), 3) for n in nodes],
+                      "llama_flat_ms": stat(("llama", False)), "mixtral_flat_ms": stat(("mixtral", False)),
+                      "llama_tree_ms": stat(("llama", True)), "mixtral_tree_ms": stat(("mixtral", True)),
                       "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
                       "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
                       "flat_tree_bit_identical": bool(same)}))
