@@ -126,7 +126,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   const long long i = (long long)c * (CHUNK / 4) + threadIdx.x;
   float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<float4*>(g)[i];
   float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-  const float decay = 1.0f - lr * wd, step = lr / bc1, omb1 = 1.0f - b1, omb2 = 1.0f - b2;
+  // 1 - beta from the doubles, like torch (value = 1 - beta2 in double, then cast): 1.0f - (float)0.999 is 216 fp32 ulps off 0.001
+  const float decay = 1.0f - lr * wd, step = lr / bc1, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
 #define B2T_ADAM1(P, G, M, V)                         \
   {                                                   \
     const float gr = G * coef;                        \

@@ -385,6 +385,52 @@ def test_ctc_oracle_ragged():
     np.testing.assert_allclose(got, dlo, atol=5e-6, rtol=2e-3)
 
 
+@pytest.mark.parametrize("S_max", [0, 20, 100, 200, 300])
+def test_ctc_unstaged_logprobs_and_empty_targets(S_max):
+    """b2t_ctc_loss_f32 where the sentence's log-probabilities do NOT fit the LDS beside the recursion's rows (C = 64, T = 600:
+    4 T C = 153 600 bytes, over the 150 KiB limit for any S), so every emission is read from the logits in HBM: wave widths 2, 4, 8
+    and the thread-per-state recursion (S_max 20, 100, 200, 300), ragged input lengths, one sentence per call with tgt_len = 0
+    (the blank alone), and a call with S_max = 0.  Against the oracle in float64, with test_ctc_oracle_ragged's bound: the
+    gradient's error at most 4 x the fp32 oracle's own (or 5e-6), the loss within 1e-5 relative.  Driven through the C ABI with
+    fresh buffers of the documented sizes, 0xFF scratch, canaries behind each."""
+    import b2t_native as N
+    from test_gpu_elementwise import Buf
+    _dev()
+    rng = np.random.default_rng(40 + S_max)
+    B, T, C, ldd = 3, 600, 64, 68
+    logits = (rng.standard_normal((B, T, C)) * 1.5).astype(np.float32)
+    tg = rng.integers(1, C, (B, S_max)).astype(np.int32)
+    tl = np.array([S_max, 0, S_max // 2], dtype=np.int32)
+    il = np.array([T, 417, 555], dtype=np.int32)
+    if S_max >= 20:
+        tg[0, :6] = [7, 7, 7, 2, 2, 9]
+    for b in range(B):
+        tg[b, tl[b]:] = 0
+    Lx = 2 * S_max + 1
+    bl, bt, bi, bs = Buf(logits), Buf(tg), Buf(il), Buf(tl)
+    loss, ws, dl = Buf(4 * B), Buf(4 * 2 * B * T * Lx), Buf(4 * B * T * ldd)
+    rc = N.load().b2t_ctc_loss_f32(bl.ptr, bt.ptr, bi.ptr, bs.ptr, loss.ptr, ws.ptr, dl.ptr, B, T, C, S_max, ldd, 1.0 / B,
+                                   torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, N.last_error()
+    got_l, got_d = loss.get().copy(), dl.get().reshape(B, T, ldd).copy()
+    ws.get(), bl.get(), bt.get()
+    l32, d32 = O.ctc_loss_fwd_bwd(logits, tg, il, tl)
+    l64, d64 = O.ctc_loss_fwd_bwd(logits, tg, il, tl, dtype=np.float64)
+    assert np.isfinite(l64).all()
+    err_gpu = np.abs(got_d[:, :, :C].astype(np.float64) - d64).max()
+    err_o32 = np.abs(d32.astype(np.float64) - d64).max()
+    print("S_max %d: dlogits error %.3g, fp32 oracle's %.3g; loss rel %.3g" % (S_max, err_gpu, err_o32, np.abs(got_l / l64 - 1).max()))
+    np.testing.assert_allclose(got_l, l64, rtol=1e-5)
+    assert err_gpu <= max(4 * err_o32, 5e-6), (err_gpu, err_o32)
+    assert not got_d[:, :, C:].any()
+    for b in range(B):
+        assert not got_d[b, il[b]:].any()
+    # the empty target: -sum_t log p_t(blank) over its own frames
+    lg1 = logits[1, :il[1]].astype(np.float64)
+    lp_blank = lg1[:, 0] - np.log(np.exp(lg1 - lg1.max(-1, keepdims=True)).sum(-1)) - lg1.max(-1)
+    np.testing.assert_allclose(l64[1], -lp_blank.sum(), rtol=1e-12)
+
+
 def test_train_step_golden(golden_dir):
     """Full fwd + bwd + clip + AdamW for 4 steps vs the reference's step body (rnn_trainer.py:527-558)."""
     from rnn_trainer import TrainStep

@@ -65,6 +65,29 @@ def test_ctc(golden_dir):
     assert np.isinf(li[0]) and np.isinf(zi["loss"][0])
 
 
+def test_ctc_empty_target_is_torchs():
+    """A sentence with tgt_len = 0 (the extended sequence is the blank alone): loss = -sum_t log p_t(blank), and its gradient,
+    as torch.nn.functional.ctc_loss on the CPU gives them, in a batch beside sentences with labels."""
+    import torch
+    rng = np.random.default_rng(8)
+    B, T, C, S = 3, 30, 9, 4
+    logits = (rng.standard_normal((B, T, C)) * 1.5).astype(np.float32)
+    tg = rng.integers(1, C, (B, S)).astype(np.int32)
+    tl, il = np.array([4, 0, 2], dtype=np.int32), np.array([30, 21, 30], dtype=np.int32)
+    tg[1, :], tg[2, 2:] = 0, 0
+    for dtype, tol, atol in ((np.float32, 2e-6, 5e-6), (np.float64, 1e-12, 1e-12)):   # fp32: test_ctc's tolerances
+        loss, dl = O.ctc_loss_fwd_bwd(logits, tg, il, tl, dtype=dtype)
+        x = torch.from_numpy(logits.astype(dtype)).requires_grad_(True)
+        ref = torch.nn.functional.ctc_loss(torch.log_softmax(x, -1).transpose(0, 1), torch.from_numpy(tg).long(), torch.from_numpy(il).long(),
+                                           torch.from_numpy(tl).long(), blank=0, reduction="none", zero_infinity=False)
+        ref.mean().backward()
+        np.testing.assert_allclose(loss, ref.detach().numpy(), rtol=tol)
+        np.testing.assert_allclose(dl, x.grad.numpy(), atol=atol)
+        lp1 = torch.log_softmax(x.detach()[1, :21], -1).numpy()
+        np.testing.assert_allclose(loss[1], -lp1[:, 0].sum(), rtol=tol)
+        assert np.all(dl[1, 21:] == 0)
+
+
 @pytest.mark.parametrize("name", ["train_step.npz", "train_step_patch.npz"])
 def test_train_step(golden_dir, name):
     """Four steps of the reference's step body (rnn_trainer.py:527-558); train_step_patch.npz: patch_size 14 / stride 4
