@@ -971,6 +971,73 @@ int b2t_clm_mixtral_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_
                                     const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                     long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Gemma-2 (csrc/causal_lm_gemma2.hip): head dim 256, soft caps, four norms per layer, GeGLU ----------------------------
+ * HF Gemma2ForCausalLM (gemma-2-2b, 9b, 27b), eager attention.  With x the residual, hd the head dim (a field of its own: Hq hd
+ * != d_model in all three checkpoints) and RMSNorm1p(t; w) = t * rsqrt(mean(t^2) + rms_eps) * (1 + w):
+ *   x  = embed_tokens[id] * embed_scale                                    (embed_scale = sqrt(d_model) rounded to the element type)
+ *   h  = RMSNorm1p(x; input_layernorm);  q | k | v = h Wqkv^T              (no biases)
+ *   q and k rotated over the whole head (pairs c, c + hd / 2), q scaled by q_scale = query_pre_attn_scalar^-0.5
+ *   s  = q . k;  s = attn_cap * tanh(s / attn_cap);  causal softmax;  o = P . V      (grouped-query)
+ *   x += RMSNorm1p(o Wo^T; post_attention_layernorm)
+ *   h  = RMSNorm1p(x; pre_feedforward_layernorm)
+ *   x += RMSNorm1p((gelu_tanh(h Wg^T) * (h Wu^T)) Wd^T; post_feedforward_layernorm)
+ * after the last layer: logits = RMSNorm1p(x; final_norm_w) lm_head^T, logits = final_cap * tanh(logits / final_cap), then the
+ * log-softmax.  A sliding-window layer equals a full one for sequences within the window, so max_pos must not exceed it (the
+ * loader caps it).  The model is the b2t_clm_llama_t above with these differences: hd is b2t_clm_gemma2_t's head_dim, not
+ * d_model / n_heads; qkv_w is [round_up((Hq + 2 Hkv) hd, 256)][d] with every q and k head's rows stored so that stored 32-row
+ * block 2j holds dims [32j, 32j + 32) and block 2j + 1 dims [hd / 2 + 32j, hd / 2 + 32j + 32) (the Llama order at hd 128); o_w is
+ * [round_up(d, 256)][Hq hd]; rope_cos / rope_sin are [max_pos][hd / 2]; norm1_w / norm2_w are input_layernorm and
+ * post_attention_layernorm; qkv_b must be NULL; lm_head is the tied head (embed_tokens padded to 256 rows).  Every norm weight is
+ * the checkpoint's w; the kernels add the 1.  What else the forward needs travels in b2t_clm_gemma2_t.
+ * Required: hd 128 or 256, Hq % Hkv == 0, d_model, ffn_dim and Hq hd multiples of 64, caps >= 0 (0: that cap is off), q_scale
+ * and embed_scale > 0; anything else is refused before any launch.
+ * Numerics, E being fp16 or bf16: weights, GEMM and attention operands are E, accumulation is fp32.  The residual stream, every
+ * norm statistic, the 1 + w (formed in fp32, never stored rounded), the rotation, both tanh caps, softmax / log-softmax and the
+ * sums are fp32; embed_scale is multiplied in fp32 and the residual is not rounded.  Rounded to E, once each: the two pre-norm
+ * outputs and the final norm's output; q after rotation and scale; k after rotation; v; the attention's probabilities per 32-key
+ * block as the P.V operand; the attention output; gelu_tanh(gate) * up from the two fp32 accumulators.  The o_proj and down
+ * outputs are never rounded: the GEMM stores its fp32 accumulator and the post-norm adds to the residual in fp32.  tanh(u) is
+ * computed as 1 - 2 / (exp(2u) + 1): a saturated argument gives +-1, never NaN.  A row's bits depend only on that row: tree,
+ * cached and flat calls are bit-identical, a sequence scores the same alone or in a batch, and B2T_CLM_GEMM_256 /
+ * B2T_CLM_TRUNK_ATTN do not change the bits.
+ * The nine functions have their Mixtral twins' argument lists with the b2t_clm_gemma2_t in the MoE descriptor's place
+ * (b2t_clm_gemma2_cache_kv_bytes takes it too: kv is [n_layers][cap][2 * n_kv_heads * hd] with the real hd), their output
+ * layout and their refusals before any launch under the entry point's own name.  There is no cached bf16 call. */
+typedef struct {
+  const void *pre_ffn_norm_w, *post_ffn_norm_w;  /* [d] pre_feedforward_layernorm, post_feedforward_layernorm */
+} b2t_clm_gemma2_layer_t;
+
+typedef struct {
+  int head_dim;                /* 128 or 256 */
+  float q_scale;               /* query_pre_attn_scalar^-0.5 */
+  float attn_cap, final_cap;   /* attn_logit_softcapping, final_logit_softcapping; 0 = off */
+  float embed_scale;           /* sqrt(d_model) rounded to the call's element type */
+  const b2t_clm_gemma2_layer_t* layers_host;  /* HOST array of n_layers entries (device pointers inside) */
+} b2t_clm_gemma2_t;
+
+size_t b2t_clm_gemma2_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_tokens, int n_seq);
+size_t b2t_clm_gemma2_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_nodes, long long n_tokens,
+                                    int n_seq);
+size_t b2t_clm_gemma2_cache_kv_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, int cap);
+size_t b2t_clm_gemma2_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_rows,
+                                           long long n_tokens, int n_seq);
+int b2t_clm_gemma2_score_f16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
+                             const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                             size_t ws_bytes, void* stream);
+int b2t_clm_gemma2_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
+                                  const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                  long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_gemma2_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, b2t_clm_cache_t* cache,
+                                         int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                         float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
+                                         void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_gemma2_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
+                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                              size_t ws_bytes, void* stream);
+int b2t_clm_gemma2_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
+                                   const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                   long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
  * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
  * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,

@@ -132,6 +132,17 @@ class ClmMoe(C.Structure):
                 ("down_stride", C.c_longlong), ("route_out", VP)]
 
 
+class ClmGemma2Layer(C.Structure):
+    """Mirror of b2t_clm_gemma2_layer_t (include/b2t.h): device weights [d] of one Gemma-2 layer's two feed-forward norms."""
+    _fields_ = [("pre_ffn_norm_w", VP), ("post_ffn_norm_w", VP)]
+
+
+class ClmGemma2(C.Structure):
+    """Mirror of b2t_clm_gemma2_t (include/b2t.h): what a Gemma-2 model adds to its b2t_clm_llama_t."""
+    _fields_ = [("head_dim", C.c_int), ("q_scale", C.c_float), ("attn_cap", C.c_float), ("final_cap", C.c_float),
+                ("embed_scale", C.c_float), ("layers_host", C.POINTER(ClmGemma2Layer))]
+
+
 class ClmQkNorm(C.Structure):
     """Mirror of b2t_clm_qknorm_t (include/b2t.h): device weights [hd] of one Qwen3 layer's q and k RMSNorm."""
     _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
@@ -291,6 +302,11 @@ for _t in ("ws_bytes", "tree_ws_bytes", "tree_cached_ws_bytes", "score_f16", "sc
            "score_tree_cached_f16"):
     _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
     _SIGNATURES["b2t_clm_mixtral_" + _t] = (_res, [_args[0], C.POINTER(ClmMoe)] + _args[1:])
+# Gemma-2: the Llama twin's list with the Gemma-2 descriptor after the model, the four size functions included
+for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16", "score_bf16",
+           "score_tree_bf16", "score_tree_cached_f16"):
+    _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
+    _SIGNATURES["b2t_clm_gemma2_" + _t] = (_res, [_args[0], C.POINTER(ClmGemma2)] + _args[1:])
 # GPT-NeoX: the OPT twin's list on its own model struct (same cache)
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
            "score_tree_cached_f16"):

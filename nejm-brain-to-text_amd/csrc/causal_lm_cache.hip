@@ -36,113 +36,8 @@
 namespace b2t {
 namespace {
 
-// clm_attn_tree_kernel with a two-source gather, on the row layout the flat and tree kernels share (query head h reads K / V
-// head hk = h / (Hq / Hkv); OPT is Hkv = Hq): path node < R is row `node` of the cache's layer slab ([cap][2 * Hkv * D],
-// k[Hkv * D] | v[Hkv * D]), else row node - R of this call's qkv ([rows][(Hq + 2 * Hkv) * D], q | k | v).  In both a row's V
-// sits Hkv * D elements behind its K, so one address per key row serves both; the select is on the address (base and pitch),
-// not around the loads, which are 16-byte pieces (stage_v and attn_block, clm_attn.h).  Queries start at max(own_start, R);
-// out has the computed rows.  With st_o set (stage B) the key loop starts at block kb0 = Rb / 32 from the state
-// clm_attn_trunk_kernel left for the query's row: st_ml [rows][Hq][2], st_o [rows][Hq * D].
-template <int D>
-__global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float16* qkv, const _Float16* slab, _Float16* out,
-                                                                   const int* seq_off, const int* tok_node, const int* own_start,
-                                                                   int Hkv, int R, const float* st_ml, const float* st_o, int kb0) {
-  constexpr int NF = AttnDims<D>::NF;
-  __shared__ __attribute__((aligned(16))) _Float16 vslab[4][32 * AttnDims<D>::VP];
-  const int sq = blockIdx.x, h = blockIdx.y, H = gridDim.y, hk = h / (H / Hkv);
-  const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, start = max(own_start[sq], R);
-  if (start >= L) return;   // every node of this path is owned by an earlier sequence or held by the cache
-  const int* path = tok_node + t0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
-  const int d = H * D, vo = Hkv * D;     // the output row; V behind K in both sources
-  const long long RS = (long long)(H + 2 * Hkv) * D, CS = 2LL * vo;
-  const _Float16* Qb = qkv + h * D;
-  const _Float16* Kq = qkv + (H + hk) * D;   // K of a computed row
-  const _Float16* Kc = slab + hk * D;        // K of a cached row
-  auto krow_of = [&](int node) {
-    const bool c = node < R;
-    return (c ? Kc : Kq) + (long long)(c ? node : node - R) * (c ? CS : RS);
-  };
-  _Float16* vs = vslab[wave];
-  const int nqb = (L + 31) / 32;
-  for (int qb = start / 32 + wave; qb < nqb; qb += 4) {
-    const int q = qb * 32 + li;
-    const bool live = q >= start && q < L;
-    const int qrow = max(path[min(q, L - 1)] - R, 0);   // lanes below R read row 0 and write nothing
-    half8 qf[AttnDims<D>::KS];
-    load_q<D>(Qb + (long long)qrow * RS + 8 * hh, qf);
-    float m, l;
-    f32x16 o[NF];
-    attn_zero<D>(m, l, o);
-    if (st_o) {   // wave-uniform
-      const float* mp = st_ml + ((long long)qrow * H + h) * 2;
-      const float m_in = mp[0], l_in = mp[1];
-      if (live) { m = m_in; l = l_in; }
-      const float* op = st_o + (long long)qrow * d + h * D + 4 * hh;
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          if (32 * f + 8 * g < D) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(op + 32 * f + 8 * g);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[f][4 * g + j] = live ? v[j] : 0.f;
-          }
-        }
-    }
-    for (int kb = kb0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
-      const int k0 = kb * 32;
-      const int knode = path[min(k0 + li, L - 1)];
-      stage_v<D>(vs, lane, L - k0, [&](int key) { return krow_of(__shfl(knode, key)) + vo; });
-      attn_block<D, true>(krow_of(knode) + 8 * hh, qf, VSlab<D>{vs}, k0, q, L, li, hh, m, l, o);
-    }
-    if (live) attn_store<D>(out + (long long)qrow * d + h * D, o, l, hh);
-  }
-}
-
-// Stage B: the cached key blocks 0 .. nkb-1 (keys [0, Rb), contiguous slab rows, no mask) for 32 computed rows at a time, a
-// wave per (row block, query head), reading slab head hk.  Leaves m, l (st_ml [rows][Hq][2]) and the unnormalised o (st_o
-// [rows][Hq * D]) of every row < rows.
-template <int D>
-__global__ __launch_bounds__(64) void clm_attn_trunk_kernel(const _Float16* qkv, const _Float16* slab, int Hkv, int rows, int nkb,
-                                                            float* st_ml, float* st_o) {
-  constexpr int NF = AttnDims<D>::NF;
-  __shared__ __attribute__((aligned(16))) _Float16 vs[32 * AttnDims<D>::VP];
-  const int h = blockIdx.y, H = gridDim.y, hk = h / (H / Hkv);
-  const int lane = threadIdx.x, li = lane & 31, hh = lane >> 5;
-  const int d = H * D, vo = Hkv * D;
-  const long long RS = (long long)(H + 2 * Hkv) * D, CS = 2LL * vo;
-  const int r = blockIdx.x * 32 + li, row = min(r, rows - 1);
-  const _Float16* Kc = slab + hk * D;
-  half8 qf[AttnDims<D>::KS];
-  load_q<D>(qkv + h * D + (long long)row * RS + 8 * hh, qf);
-  float m, l;
-  f32x16 o[NF];
-  attn_zero<D>(m, l, o);
-  for (int kb = 0; kb < nkb; ++kb) {
-    const int k0 = kb * 32;
-    stage_v<D>(vs, lane, 32, [&](int key) { return Kc + (long long)(k0 + key) * CS + vo; });
-    attn_block<D, false>(Kc + (long long)(k0 + li) * CS + 8 * hh, qf, VSlab<D>{vs}, k0, 0, 0, li, hh, m, l, o);
-  }
-  if (r < rows) {
-    if (hh == 0) {
-      float* mp = st_ml + ((long long)row * H + h) * 2;
-      mp[0] = m; mp[1] = l;
-    }
-    float* op = st_o + (long long)row * d + h * D + 4 * hh;
-#pragma unroll
-    for (int f = 0; f < NF; ++f)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (32 * f + 8 * g < D) {
-          f32x4 v;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = o[f][4 * g + j];
-          *reinterpret_cast<f32x4*>(op + 32 * f + 8 * g) = v;
-        }
-      }
-  }
-}
+// The two attention kernels of this path, clm_attn_tree_cached_kernel and clm_attn_trunk_kernel, are templates of clm_attn.h
+// (this unit instantiates them for head dims 64, 80 and 128; causal_lm_gemma2.hip their soft-capped forms).
 
 // cache append: K | V of the trunk's computed rows (qkv rows 0..rows-1 of width rs, columns qc .. qc + cs) -> dst rows 0..
 // ([.][cs], the layer slab at row R), as 16-byte pieces; qc = Hq * D, cs = 2 * Hkv * D, rs = qc + cs
@@ -234,13 +129,13 @@ ClmCachedState clm_cached_state(size_t tree_total, long long rows, int Hq, int d
 // What clm_launch_attn_cached needs for every layer of one call: the index arrays, the shapes, the rows to append, where the
 // state of stage B lives in the workspace, and whether stage B runs.
 ClmCachedAttn clm_cached_attn(const ClmTreeIndex& ix, int n_seq, int Hq, int Hkv, int hd, int R, int app_rows, char* base,
-                              const ClmCachedState& S) {
+                              const ClmCachedState& S, float cap) {
   // B2T_CLM_TRUNK_ATTN, read per call: 0 = every key block in clm_attn_tree_cached_kernel (stage A); 1 = the cached blocks
   // in clm_attn_trunk_kernel (stage B)
   const char* e = getenv("B2T_CLM_TRUNK_ATTN");
   const bool trunk = e && *e ? atoi(e) != 0 : CLM_TRUNK_ATTN_DEFAULT;
   return ClmCachedAttn{ix.d_soff, ix.d_node, ix.d_own, Hq, Hkv, hd, n_seq, R, app_rows, ix.run.rows, trunk,
-                       reinterpret_cast<float*>(base + S.st_ml), reinterpret_cast<float*>(base + S.st_o)};
+                       reinterpret_cast<float*>(base + S.st_ml), reinterpret_cast<float*>(base + S.st_o), cap};
 }
 
 int clm_launch_attn_cached(const ClmCachedAttn& a, const _Float16* qkv, _Float16* slab, _Float16* out, hipStream_t s) {
@@ -251,6 +146,7 @@ int clm_launch_attn_cached(const ClmCachedAttn& a, const _Float16* qkv, _Float16
                        slab + (size_t)a.R * cs, qc, cs, (long long)a.app_rows);
     B2T_CHECK_LAUNCH("clm_cache_append_kernel");
   }
+  if (a.hd == 256 || a.cap > 0.f) return clm_launch_attn_cached_cap(a, qkv, slab, out, s);   // Gemma-2 (causal_lm_gemma2.hip)
   if (a.hd == 64) return launch_attn<64>(a, qkv, slab, out, s);
   if (a.hd == 80) return launch_attn<80>(a, qkv, slab, out, s);
   return launch_attn<128>(a, qkv, slab, out, s);

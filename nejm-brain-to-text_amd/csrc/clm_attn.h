@@ -1,7 +1,7 @@
 // clm_attn.h — the attention arithmetic of the causal-LM forward, written once (device code, internal linkage).  Every
-// attention kernel -- clm_attn_kernel and clm_attn_tree_kernel (at the end of this file; launched by causal_lm.hip,
-// causal_lm_tree.hip and, in bf16, causal_lm_llama_bf16.hip), clm_attn_tree_cached_kernel and clm_attn_trunk_kernel
-// (causal_lm_cache.hip) -- walks its own rows and calls attn_block per 32-key block, so a query meets the same operands in
+// attention kernel -- clm_attn_kernel and clm_attn_tree_kernel (launched by causal_lm.hip, causal_lm_tree.hip and, in bf16,
+// causal_lm_llama_bf16.hip), clm_attn_tree_cached_kernel and clm_attn_trunk_kernel (launched by causal_lm_cache.hip), all at the
+// end of this file, and their soft-capped `_cap_` forms (causal_lm_gemma2.hip) -- walks its own rows and calls attn_block per 32-key block, so a query meets the same operands in
 // the same order on every path: that is what keeps the paths bit-identical.  The element type E (ClmElem, clm_internal.h)
 // is deduced from the pointers: _Float16 everywhere but in the bf16 unit.
 //
@@ -9,8 +9,11 @@
 // one query column: its online-softmax state (m, l) is per lane and the row reductions are in-lane plus one swap of the lane
 // halves.  P^T is then the B operand of O^T = V^T . P^T with no data movement (registers 8s..8s+7 of the accumulator are
 // k-step s, keys in the order 16s + 8(j >> 2) + 4h + (j & 3)), and O^T's rescale by exp(m_old - m_new) is per lane too.
-// Throughout: lane = 32 * hh + li; D is the head dim (64, 80 or 128), KS its k-steps, NF its 32-dim fragments of O^T; the
+// Throughout: lane = 32 * hh + li; D is the head dim (64, 80, 128 or 256), KS its k-steps, NF its 32-dim fragments of O^T; the
 // `dim < D` guards exist only where NF * 32 != D (head dim 80).
+// CAP (Gemma-2, causal_lm_gemma2.hip): the fp32 score tile is soft-capped, s = cap * tanh(s / cap), before the mask and the
+// running max; cap == 0 at run time means off.  CAP is false in every kernel without `_cap_` in its name: the body functions
+// below are inlined into them with the cap's code compiled out.
 #pragma once
 #include <math.h>
 
@@ -89,10 +92,14 @@ __device__ __forceinline__ void attn_zero(float& m, float& l, f32x16* o) {
 
 // One key block of the online softmax: S^T = K . Q^T from the lane's key row kp (+ 8 * hh), the mask (keys beyond the query q
 // or the L keys; MASK false = no key of the block can be either), the per-lane state update, P rounded to the element type,
-// O^T += V^T . P^T with V from `v`.
-template <int D, bool MASK, class E, class VSrc>
+// O^T += V^T . P^T with V from `v`.  CAP: the scores are soft-capped first (soft_cap; cap > 0).
+// tanh(u) is written 1 - 2 / (exp(2u) + 1) like gelu_new's (clm_gemm.h): a saturated argument yields +-1, never inf / inf.
+__device__ __forceinline__ float soft_cap(float v, float cap, float inv_cap) {
+  return cap * (1.0f - 2.0f / (expf(2.0f * (v * inv_cap)) + 1.0f));
+}
+template <int D, bool MASK, bool CAP = false, class E, class VSrc>
 __device__ __forceinline__ void attn_block(const E* kp, const typename ClmElem<E>::v8* qf, const VSrc& v, int k0, int q, int L,
-                                           int li, int hh, float& m, float& l, f32x16* o) {
+                                           int li, int hh, float& m, float& l, f32x16* o, float cap = 0.f) {
   using A = AttnDims<D>;
   using vec8 = typename ClmElem<E>::v8;
   f32x16 sacc;
@@ -101,6 +108,13 @@ __device__ __forceinline__ void attn_block(const E* kp, const typename ClmElem<E
 #pragma unroll
   for (int ks = 0; ks < A::KS; ++ks)
     sacc = ClmElem<E>::mfma(*reinterpret_cast<const vec8*>(kp + 16 * ks), qf[ks], sacc);
+  if (CAP) {
+    if (cap > 0.f) {   // uniform
+      const float inv_cap = 1.0f / cap;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) sacc[e] = soft_cap(sacc[e], cap, inv_cap);
+    }
+  }
   float mx = -INFINITY;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
@@ -164,8 +178,11 @@ __device__ __forceinline__ void attn_store(E* op, const f32x16* o, float l, int 
 // Causal attention, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query rows at a time and runs the key
 // blocks up to the diagonal through attn_block, V gathered from global memory.  The row is q[Hq * D] | k[Hkv * D] |
 // v[Hkv * D]; query head h reads K / V head h / (Hq / Hkv) (OPT: Hkv = Hq).
-template <int D, class E = _Float16>
-__global__ __launch_bounds__(256) void clm_attn_kernel(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv) {
+//
+// clm_attn_flat is the body; SLAB stages V through the wave's LDS slab as the tree kernel does (the same values reach the same
+// MFMAs, so the bits are VGather's) -- the capped kernel at head dim 256 needs the registers the gather holds.
+template <int D, class E, bool CAP, bool SLAB>
+__device__ __forceinline__ void clm_attn_flat(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv, float cap) {
   const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
   const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
@@ -184,10 +201,24 @@ __global__ __launch_bounds__(256) void clm_attn_kernel(const E* qkv, E* out, con
     for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
       const int k0 = kb * 32;
       const E* kp = Kb + (long long)min(k0 + li, L - 1) * RS + 8 * hh;
-      attn_block<D, true>(kp, qf, VGather<E>{Vb, RS, k0, L}, k0, q, L, li, hh, m, l, o);
+      if constexpr (SLAB) {
+        __shared__ __attribute__((aligned(16))) E vslab[4][32 * AttnDims<D>::VP];
+        stage_v<D>(vslab[wave], lane, L - k0, [&](int key) { return Vb + (long long)(k0 + key) * RS; });
+        attn_block<D, true, CAP>(kp, qf, VSlab<D, E>{vslab[wave]}, k0, q, L, li, hh, m, l, o, cap);
+      } else {
+        attn_block<D, true, CAP>(kp, qf, VGather<E>{Vb, RS, k0, L}, k0, q, L, li, hh, m, l, o, cap);
+      }
     }
     if (q < L) attn_store<D>(out + ((long long)(t0 + q) * Hq + h) * D, o, l, hh);
   }
+}
+template <int D, class E = _Float16>
+__global__ __launch_bounds__(256) void clm_attn_kernel(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv) {
+  clm_attn_flat<D, E, false, false>(qkv, out, seq_off, Hq, Hkv, 0.f);
+}
+template <int D, class E, bool SLAB>
+__global__ __launch_bounds__(256) void clm_attn_cap_kernel(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv, float cap) {
+  clm_attn_flat<D, E, true, SLAB>(qkv, out, seq_off, Hq, Hkv, cap);
 }
 
 // Causal attention over tree paths, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query positions at a
@@ -198,9 +229,9 @@ __global__ __launch_bounds__(256) void clm_attn_kernel(const E* qkv, E* out, con
 // The gather: a lane holds the row of key k0 + (lane & 31) and reads K from it as 16-byte pieces; V's 32 x D block is staged
 // as whole 16-byte row pieces into the wave's own LDS slab and read back transposed, rows of keys beyond the path zeroed.
 // The slab is private to the wave, so the key loop needs no workgroup barrier.
-template <int D, class E = _Float16>
-__global__ __launch_bounds__(256) void clm_attn_tree_kernel(const E* qkv, E* out, const int* seq_off, const int* tok_node,
-                                                            const int* own_start, int Hq, int Hkv) {
+template <int D, class E, bool CAP>
+__device__ __forceinline__ void clm_attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start,
+                                              int Hq, int Hkv, float cap) {
   __shared__ __attribute__((aligned(16))) E vslab[4][32 * AttnDims<D>::VP];
   const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
   const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, own = own_start[sq];
@@ -225,10 +256,155 @@ __global__ __launch_bounds__(256) void clm_attn_tree_kernel(const E* qkv, E* out
       const int k0 = kb * 32;
       const int krow = path[min(k0 + li, L - 1)];
       stage_v<D>(vs, lane, L - k0, [&](int key) { return Vb + (long long)__shfl(krow, key) * RS; });
-      attn_block<D, true>(Kb + (long long)krow * RS + 8 * hh, qf, VSlab<D, E>{vs}, k0, q, L, li, hh, m, l, o);
+      attn_block<D, true, CAP>(Kb + (long long)krow * RS + 8 * hh, qf, VSlab<D, E>{vs}, k0, q, L, li, hh, m, l, o, cap);
     }
     if (q >= own && q < L) attn_store<D>(out + ((long long)qrow * Hq + h) * D, o, l, hh);
   }
+}
+template <int D, class E = _Float16>
+__global__ __launch_bounds__(256) void clm_attn_tree_kernel(const E* qkv, E* out, const int* seq_off, const int* tok_node,
+                                                            const int* own_start, int Hq, int Hkv) {
+  clm_attn_tree<D, E, false>(qkv, out, seq_off, tok_node, own_start, Hq, Hkv, 0.f);
+}
+template <int D, class E>
+__global__ __launch_bounds__(256) void clm_attn_tree_cap_kernel(const E* qkv, E* out, const int* seq_off, const int* tok_node,
+                                                                const int* own_start, int Hq, int Hkv, float cap) {
+  clm_attn_tree<D, E, true>(qkv, out, seq_off, tok_node, own_start, Hq, Hkv, cap);
+}
+
+// ---- the cached tree kernel and the trunk kernel (the context cache: causal_lm_cache.hip has the rule and the launches) ----
+
+// clm_attn_tree_kernel with a two-source gather, on the row layout the flat and tree kernels share (query head h reads K / V
+// head hk = h / (Hq / Hkv); OPT is Hkv = Hq): path node < R is row `node` of the cache's layer slab ([cap][2 * Hkv * D],
+// k[Hkv * D] | v[Hkv * D]), else row node - R of this call's qkv ([rows][(Hq + 2 * Hkv) * D], q | k | v).  In both a row's V
+// sits Hkv * D elements behind its K, so one address per key row serves both; the select is on the address (base and pitch),
+// not around the loads, which are 16-byte pieces (stage_v and attn_block, clm_attn.h).  Queries start at max(own_start, R);
+// out has the computed rows.  With st_o set (stage B) the key loop starts at block kb0 = Rb / 32 from the state
+// clm_attn_trunk_kernel left for the query's row: st_ml [rows][Hq][2], st_o [rows][Hq * D].
+// The body is clm_attn_tree_cached; the `_cap_` kernel (Gemma-2) soft-caps the scores in attn_block, the plain one compiles the
+// cap out (clm_attn.h).
+template <int D, bool CAP>
+__device__ __forceinline__ void clm_attn_tree_cached(const _Float16* qkv, const _Float16* slab, _Float16* out, const int* seq_off,
+                                                     const int* tok_node, const int* own_start, int Hkv, int R, const float* st_ml,
+                                                     const float* st_o, int kb0, float cap) {
+  constexpr int NF = AttnDims<D>::NF;
+  __shared__ __attribute__((aligned(16))) _Float16 vslab[4][32 * AttnDims<D>::VP];
+  const int sq = blockIdx.x, h = blockIdx.y, H = gridDim.y, hk = h / (H / Hkv);
+  const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, start = max(own_start[sq], R);
+  if (start >= L) return;   // every node of this path is owned by an earlier sequence or held by the cache
+  const int* path = tok_node + t0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
+  const int d = H * D, vo = Hkv * D;     // the output row; V behind K in both sources
+  const long long RS = (long long)(H + 2 * Hkv) * D, CS = 2LL * vo;
+  const _Float16* Qb = qkv + h * D;
+  const _Float16* Kq = qkv + (H + hk) * D;   // K of a computed row
+  const _Float16* Kc = slab + hk * D;        // K of a cached row
+  auto krow_of = [&](int node) {
+    const bool c = node < R;
+    return (c ? Kc : Kq) + (long long)(c ? node : node - R) * (c ? CS : RS);
+  };
+  _Float16* vs = vslab[wave];
+  const int nqb = (L + 31) / 32;
+  for (int qb = start / 32 + wave; qb < nqb; qb += 4) {
+    const int q = qb * 32 + li;
+    const bool live = q >= start && q < L;
+    const int qrow = max(path[min(q, L - 1)] - R, 0);   // lanes below R read row 0 and write nothing
+    half8 qf[AttnDims<D>::KS];
+    load_q<D>(Qb + (long long)qrow * RS + 8 * hh, qf);
+    float m, l;
+    f32x16 o[NF];
+    attn_zero<D>(m, l, o);
+    if (st_o) {   // wave-uniform
+      const float* mp = st_ml + ((long long)qrow * H + h) * 2;
+      const float m_in = mp[0], l_in = mp[1];
+      if (live) { m = m_in; l = l_in; }
+      const float* op = st_o + (long long)qrow * d + h * D + 4 * hh;
+#pragma unroll
+      for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          if (32 * f + 8 * g < D) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(op + 32 * f + 8 * g);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[f][4 * g + j] = live ? v[j] : 0.f;
+          }
+        }
+    }
+    for (int kb = kb0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
+      const int k0 = kb * 32;
+      const int knode = path[min(k0 + li, L - 1)];
+      stage_v<D>(vs, lane, L - k0, [&](int key) { return krow_of(__shfl(knode, key)) + vo; });
+      attn_block<D, true, CAP>(krow_of(knode) + 8 * hh, qf, VSlab<D>{vs}, k0, q, L, li, hh, m, l, o, cap);
+    }
+    if (live) attn_store<D>(out + (long long)qrow * d + h * D, o, l, hh);
+  }
+}
+template <int D>
+__global__ __launch_bounds__(256) void clm_attn_tree_cached_kernel(const _Float16* qkv, const _Float16* slab, _Float16* out,
+                                                                   const int* seq_off, const int* tok_node, const int* own_start,
+                                                                   int Hkv, int R, const float* st_ml, const float* st_o, int kb0) {
+  clm_attn_tree_cached<D, false>(qkv, slab, out, seq_off, tok_node, own_start, Hkv, R, st_ml, st_o, kb0, 0.f);
+}
+template <int D>
+__global__ __launch_bounds__(256) void clm_attn_tree_cached_cap_kernel(const _Float16* qkv, const _Float16* slab, _Float16* out,
+                                                                       const int* seq_off, const int* tok_node,
+                                                                       const int* own_start, int Hkv, int R, const float* st_ml,
+                                                                       const float* st_o, int kb0, float cap) {
+  clm_attn_tree_cached<D, true>(qkv, slab, out, seq_off, tok_node, own_start, Hkv, R, st_ml, st_o, kb0, cap);
+}
+
+// Stage B: the cached key blocks 0 .. nkb-1 (keys [0, Rb), contiguous slab rows, no mask) for 32 computed rows at a time, a
+// wave per (row block, query head), reading slab head hk.  Leaves m, l (st_ml [rows][Hq][2]) and the unnormalised o (st_o
+// [rows][Hq * D]) of every row < rows.
+template <int D, bool CAP>
+__device__ __forceinline__ void clm_attn_trunk(const _Float16* qkv, const _Float16* slab, int Hkv, int rows, int nkb, float* st_ml,
+                                               float* st_o, float cap) {
+  constexpr int NF = AttnDims<D>::NF;
+  __shared__ __attribute__((aligned(16))) _Float16 vs[32 * AttnDims<D>::VP];
+  const int h = blockIdx.y, H = gridDim.y, hk = h / (H / Hkv);
+  const int lane = threadIdx.x, li = lane & 31, hh = lane >> 5;
+  const int d = H * D, vo = Hkv * D;
+  const long long RS = (long long)(H + 2 * Hkv) * D, CS = 2LL * vo;
+  const int r = blockIdx.x * 32 + li, row = min(r, rows - 1);
+  const _Float16* Kc = slab + hk * D;
+  half8 qf[AttnDims<D>::KS];
+  load_q<D>(qkv + h * D + (long long)row * RS + 8 * hh, qf);
+  float m, l;
+  f32x16 o[NF];
+  attn_zero<D>(m, l, o);
+  for (int kb = 0; kb < nkb; ++kb) {
+    const int k0 = kb * 32;
+    stage_v<D>(vs, lane, 32, [&](int key) { return Kc + (long long)(k0 + key) * CS + vo; });
+    attn_block<D, false, CAP>(Kc + (long long)(k0 + li) * CS + 8 * hh, qf, VSlab<D>{vs}, k0, 0, 0, li, hh, m, l, o, cap);
+  }
+  if (r < rows) {
+    if (hh == 0) {
+      float* mp = st_ml + ((long long)row * H + h) * 2;
+      mp[0] = m; mp[1] = l;
+    }
+    float* op = st_o + (long long)row * d + h * D + 4 * hh;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        if (32 * f + 8 * g < D) {
+          f32x4 v;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = o[f][4 * g + j];
+          *reinterpret_cast<f32x4*>(op + 32 * f + 8 * g) = v;
+        }
+      }
+  }
+}
+template <int D>
+__global__ __launch_bounds__(64) void clm_attn_trunk_kernel(const _Float16* qkv, const _Float16* slab, int Hkv, int rows, int nkb,
+                                                            float* st_ml, float* st_o) {
+  clm_attn_trunk<D, false>(qkv, slab, Hkv, rows, nkb, st_ml, st_o, 0.f);
+}
+template <int D>
+__global__ __launch_bounds__(64) void clm_attn_trunk_cap_kernel(const _Float16* qkv, const _Float16* slab, int Hkv, int rows, int nkb,
+                                                                float* st_ml, float* st_o, float cap) {
+  clm_attn_trunk<D, true>(qkv, slab, Hkv, rows, nkb, st_ml, st_o, cap);
 }
 
 }  // namespace

@@ -8,7 +8,8 @@
 // causal_lm_gpt2.hip the one GPT-2 adds (EP_GELU: gelu_new where OPT's fc1 has ReLU) in fp16, causal_lm_neox.hip the two
 // GPT-NeoX adds (EP_ROPE_PART: the rotation of only the first rotary_ndims dims of a head; EP_GELU_ERF) in fp16, causal_lm_olmo2.hip the two OLMo-2 adds
 // (EP_F32 and EP_QKV_F32: fp32 stores for the norms over a whole output row) in both, causal_lm_mixtral.hip the grouped form of
-// the tile (clm_gemm_grouped_kernel: one B matrix per expert) with EP_SWIGLU and EP_F32 in both.  Which
+// the tile (clm_gemm_grouped_kernel: one B matrix per expert) with EP_SWIGLU and EP_F32 in both, causal_lm_gemma2.hip the two
+// Gemma-2 adds (EP_GEGLU: gelu_new where SwiGLU has silu; EP_HEAD_CAP: the fused head on soft-capped logits) in both.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -129,7 +130,7 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
   const int colw = n0 + wn * WTN;
   const E* bias = static_cast<const E*>(g.bias);
   E* out16 = static_cast<E*>(g.out16);
-  if (EP == EP_HEAD) {
+  if (EP == EP_HEAD || EP == EP_HEAD_CAP) {
     if (colw >= g.N) return;   // a 64-column group entirely beyond the vocabulary (wave-uniform)
     const int cg = colw / 64;
 #pragma unroll
@@ -141,7 +142,9 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
         float mx = -INFINITY;
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
-          v[j] = colw + j * 32 + li < g.N ? acc[i][j][e] : -INFINITY;
+          float a = acc[i][j][e];
+          if (EP == EP_HEAD_CAP) a = g.cap * (1.0f - 2.0f / (expf(2.0f * (a / g.cap)) + 1.0f));   // cap * tanh(a / cap)
+          v[j] = colw + j * 32 + li < g.N ? a : -INFINITY;
           mx = fmaxf(mx, v[j]);
         }
         mx = warp32_max(mx);
@@ -220,15 +223,16 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
     }
     return;
   }
-  if (EP == EP_ROPE || EP == EP_ROPE_PART || EP == EP_SWIGLU) {
+  if (EP == EP_ROPE || EP == EP_ROPE_PART || EP == EP_SWIGLU || EP == EP_GEGLU) {
     // a lane holds columns colw + li (fragment 0) and colw + 32 + li (fragment 1) of every row it owns: the two halves of a
-    // rotary pair (head dims of 128 are stored [0..31, 64..95, 32..63, 96..127], so their pairs are 32 columns apart as
-    // well), and the gate and up values of one SwiGLU column (the weight's rows are interleaved in blocks of 32).  N is a
+    // rotary pair (head dims of 128 are stored [0..31, 64..95, 32..63, 96..127], and in general stored 32-block 2j holds dims
+    // [32j, 32j + 32) and block 2j + 1 dims [hd / 2 + 32j, hd / 2 + 32j + 32), so their pairs are 32 columns apart as
+    // well), and the gate and up values of one SwiGLU / GeGLU column (the weight's rows are interleaved in blocks of 32).  N is a
     // multiple of 64 here, so a wave's slice is inside the matrix or outside it as a whole.
     static_assert(FN == 2, "rotary pairs and gate / up pairs are the two fragments of a lane");
     if (colw >= g.N) return;
     const int c0 = colw + li, c1 = c0 + 32;
-    if (EP == EP_SWIGLU) {
+    if (EP == EP_SWIGLU || EP == EP_GEGLU) {
       const int oc = (colw >> 1) + li;
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
@@ -237,7 +241,8 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
           const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
           if (row >= g.M) continue;
           const float gt = acc[i][0][e], up = acc[i][1][e];
-          out16[(long long)row * g.ldo + oc] = (E)(gt / (1.0f + __expf(-gt)) * up);
+          if (EP == EP_GEGLU) out16[(long long)row * g.ldo + oc] = (E)(gelu_new(gt) * up);
+          else out16[(long long)row * g.ldo + oc] = (E)(gt / (1.0f + __expf(-gt)) * up);
         }
       }
       return;

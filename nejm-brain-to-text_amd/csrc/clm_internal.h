@@ -40,8 +40,11 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 //   outputs, whose whole row a post-norm reads before anything reaches the residual.
 // EP_QKV_F32 (OLMo-2) splits the QKV row: columns < rope_cols (q | k) are stored as EP_F32 stores them, resid[r][c] with pitch
 //   rope_cols, for the whole-row q / k norm that no column tile can hold; the others (v) are rounded once, out16[r][c] (pitch ldo).
+// EP_GEGLU (Gemma-2) is EP_SWIGLU with gelu_new in silu's place: out16[r][c0 / 2 + i] = gelu_new(C[r][c0 + i]) * C[r][c0 + 32 + i].
+// EP_HEAD_CAP (Gemma-2) is EP_HEAD on soft-capped logits: v = cap * tanh(C[r][c] / cap) in fp32 (tanh written as gelu_new's) in
+//   front of the group max, the group sum and the target pick; cap > 0.
 enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6, EP_GELU = 7,
-       EP_ROPE_PART = 8, EP_GELU_ERF = 9, EP_F32 = 10, EP_QKV_F32 = 11 };
+       EP_ROPE_PART = 8, EP_GELU_ERF = 9, EP_F32 = 10, EP_QKV_F32 = 11, EP_GEGLU = 12, EP_HEAD_CAP = 13 };
 
 using f32x16 = float __attribute__((ext_vector_type(16)));
 
@@ -72,13 +75,14 @@ struct ClmGemm {
   float* tlogit; const int* tgt; int ncg;   // EP_HEAD: tlogit[r] = C[r][tgt[r]]
   const int* pos;                           // EP_ROPE: [M] position of each row
   const float* rope_cos; const float* rope_sin;   // EP_ROPE: fp32 [max_pos][hd / 2]
-  int rope_cols, hd;                        // EP_ROPE: columns < rope_cols (q | k) are rotated; head dim (64 or 128)
+  int rope_cols, hd;                        // EP_ROPE: columns < rope_cols (q | k) are rotated; head dim (a multiple of 64)
   const void* qnorm_w; const void* knorm_w; // EP_QKNORM_ROPE: [hd] weights of the q heads' and the k heads' RMSNorm
   float rms_eps;                            // EP_QKNORM_ROPE
   int rope_half;                            // EP_ROPE_PART: rotary_ndims / 2, the row stride of rope_cos / rope_sin (hd/8, hd/4 or hd/2)
   // the grouped kernel only (clm_gemm_grouped_kernel; the routed experts of clm_moe.h): M is a multiple of 256
   const int* blk_expert;                    // [M / 128] the matrix of B that the 128-row block of A multiplies, -1: no rows, no tile
   long long b_stride;                       // elements between two consecutive matrices of B
+  float cap;                                // EP_HEAD_CAP: the soft cap on the logits (> 0)
 };
 
 // The tile rule (B2T_CLM_GEMM_256) lives in one definition, causal_lm.hip: it picks the tile and hands the launch to `tiles`,
@@ -301,10 +305,14 @@ struct ClmCachedAttn {
   long long rows;
   bool trunk;
   float *st_ml, *st_o;
+  float cap;   // Gemma-2: the soft cap on the scores, 0 = none (every other family)
 };
 ClmCachedAttn clm_cached_attn(const ClmTreeIndex& ix, int n_seq, int Hq, int Hkv, int hd, int R, int app_rows, char* base,
-                              const ClmCachedState& S);
+                              const ClmCachedState& S, float cap = 0.f);
 int clm_launch_attn_cached(const ClmCachedAttn& a, const _Float16* qkv, _Float16* slab, _Float16* out, hipStream_t s);
+// the attention of clm_launch_attn_cached (behind its append) with the soft-capped kernels, for head dim 256 or a.cap > 0
+// (Gemma-2: head dim 128 or 256); causal_lm_gemma2.hip
+int clm_launch_attn_cached_cap(const ClmCachedAttn& a, const _Float16* qkv, const _Float16* slab, _Float16* out, hipStream_t s);
 // dst[i] = logp[i], i < n: the trunk's head rows -> the cache's logp at R + 1
 int clm_launch_cache_logp(const float* logp, float* dst, int n, hipStream_t s);
 // clm_launch_seq_sum_tree with the log-probs of positions 1..R taken from cache_logp
@@ -316,7 +324,8 @@ int clm_launch_seq_sum_tree_cached(const float* logp, const float* cache_logp, i
 // cached attention, the appends, the sums and the cache's bookkeeping; `uncached` names the call for callers without a cache.
 // layout(rows, ints) is the family's tree layout; forward(run, L, base, attn, s) its forward, attn(layer, qkv, out) being one
 // layer's attention.  The cache's kv is [n_layers][cap][2 * Hkv * hd].
-struct ClmCacheDims { int vocab, max_pos, Hq, Hkv, hd; };
+// attn_cap: Gemma-2's soft cap on the attention scores (0, the default: none).
+struct ClmCacheDims { int vocab, max_pos, Hq, Hkv, hd; float attn_cap = 0.f; };
 template <class Layout, class Forward>
 int clm_score_tree_cached(const char* who, const char* uncached, const ClmCacheDims& m, b2t_clm_cache_t* cache, int update,
                           const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
@@ -353,7 +362,7 @@ int clm_score_tree_cached(const char* who, const char* uncached, const ClmCacheD
   if (int rc = clm_build_tree_index(who, ids_host, seq_off_host, n_seq, plan, R, reinterpret_cast<int*>(base + L.ints), s, &ix))
     return rc;
   float* logp = reinterpret_cast<float*>(base + L.logp);
-  const ClmCachedAttn ca = clm_cached_attn(ix, n_seq, m.Hq, m.Hkv, m.hd, R, app_rows, base, S);
+  const ClmCachedAttn ca = clm_cached_attn(ix, n_seq, m.Hq, m.Hkv, m.hd, R, app_rows, base, S, m.attn_cap);
   _Float16* kv = static_cast<_Float16*>(cache->kv);
   const size_t slab_elems = (size_t)cache->cap * 2 * m.Hkv * m.hd;
   // a layer's K | V append, then its attention against the layer's slab

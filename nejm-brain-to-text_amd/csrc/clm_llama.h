@@ -12,7 +12,8 @@
 // policies: gemm_rope with the epilogue EP_QKNORM_ROPE, instantiated there, and every other launch through LlamaShared<E>.
 // The two entry-point bodies also serve a family with another layer (OLMo-2, clm_olmo2.h; Mixtral, clm_moe.h): their second
 // template argument supplies the layout, the refusals that go with the family's extra argument and the forward (LlamaFamily
-// below by default).
+// below by default), and -- through LlamaFamilyBase, or on its own for Gemma-2 (clm_gemma2.h), whose head dim is not
+// d_model / n_heads -- the model check and the attention launches.
 #pragma once
 #include <math.h>
 #include <string>
@@ -165,9 +166,27 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
   return llama_forward_mlp<P>(m, r, L, base, attn, s, qkn, mlp);
 }
 
+// What a family whose descriptor obeys the Llama rule hd = d_model / n_heads hands the entry-point bodies beside layout, check
+// and forward: the model check, the head dim and the two attention launches.  Gemma-2 (clm_gemma2.h), whose head dim is a
+// field of its own descriptor and whose attention takes a soft cap, supplies its own.
+struct LlamaFamilyBase {
+  template <class X>
+  static int check_model(const b2t_clm_llama_t* m, const X*) { return clm_llama_check_model(m); }
+  template <class P, class X>
+  static int attn(const b2t_clm_llama_t& m, const X*, const typename P::E* qkv, typename P::E* out, const int* seq_off, int n_seq,
+                  hipStream_t s) {
+    return P::attn(qkv, out, seq_off, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
+  }
+  template <class P, class X>
+  static int attn_tree(const b2t_clm_llama_t& m, const X*, const typename P::E* qkv, typename P::E* out, const int* seq_off,
+                       const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
+    return P::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
+  }
+};
+
 // What the two entry-point bodies below take from a family: the workspace layout, the refusals that go with the q / k norm
 // array, and the forward.  This is the Llama family's (Qwen3 included: P::qk_norm); OLMo-2's is Olmo2Family (clm_olmo2.h).
-struct LlamaFamily {
+struct LlamaFamily : LlamaFamilyBase {
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const void* /*extra*/ = nullptr) {
     return llama_layout(m, rows, hrows, ints);   // the q / k norm array changes no size
   }
@@ -189,7 +208,7 @@ template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
 int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                 float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream, const X* extra = nullptr) {
   using E = typename P::E;
-  if (int rc = clm_llama_check_model(model)) return rc;
+  if (int rc = Fam::check_model(model, extra)) return rc;
   const b2t_clm_llama_t& m = *model;
   if (int rc = Fam::template check<P>(who, m, extra)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
@@ -203,9 +222,7 @@ int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* id
   if (int rc = clm_build_flat_index((std::string(who) + " upload").c_str(), ids_host, seq_off_host, n_seq,
                                     reinterpret_cast<int*>(base + L.ints), s, &ix))
     return rc;
-  auto attn = [&](int, const E* qkv, E* out) {
-    return P::attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
-  };
+  auto attn = [&](int, const E* qkv, E* out) { return Fam::template attn<P>(m, extra, qkv, out, ix.d_soff, n_seq, s); };
   if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
   return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
 }
@@ -216,7 +233,7 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
                      int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                      void* stream, const X* extra = nullptr) {
   using E = typename P::E;
-  if (int rc = clm_llama_check_model(model)) return rc;
+  if (int rc = Fam::check_model(model, extra)) return rc;
   const b2t_clm_llama_t& m = *model;
   if (int rc = Fam::template check<P>(who, m, extra)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
@@ -234,7 +251,7 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
                                     reinterpret_cast<int*>(base + L.ints), s, &ix))
     return rc;
   auto attn = [&](int, const E* qkv, E* out) {
-    return P::attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
+    return Fam::template attn_tree<P>(m, extra, qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, s);
   };
   if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
   return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);

@@ -248,7 +248,7 @@ inline int clm_mixtral_check(const char* who, const b2t_clm_llama_t& m, const b2
 }
 
 // what llama_score / llama_score_tree (clm_llama.h) take from this family
-struct MixtralFamily {
+struct MixtralFamily : LlamaFamilyBase {
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const b2t_clm_moe_t* moe) {
     return mixtral_layout(m, moe, rows, hrows, ints);
   }

@@ -154,7 +154,7 @@ inline int clm_olmo2_check(const char* who, const b2t_clm_llama_t& m, const b2t_
 }
 
 // what llama_score / llama_score_tree (clm_llama.h) take from this family
-struct Olmo2Family {
+struct Olmo2Family : LlamaFamilyBase {
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const void* /*extra*/ = nullptr) {
     return olmo2_layout(m, rows, hrows, ints);
   }

@@ -1435,6 +1435,169 @@ class MixtralScorer(LlamaScorer):
         return lib.b2t_clm_llama_cache_kv_bytes(C.byref(self.desc), cap)
 
 
+# ---- Gemma-2 (HF Gemma2ForCausalLM): a head dim of its own, soft caps, four norms per layer, GeGLU ---------------------------
+GEMMA2_HEAD_DIMS = (128, 256)
+_GEMMA2_LAYER_FIELDS = ("pre_ffn_norm_w", "post_ffn_norm_w")
+
+
+def gemma2_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
+    """The dimensions b2t_clm_llama_t and b2t_clm_gemma2_t need for a "gemma2" config, after refusing, by the field's name, what
+    the kernels do not run.  head_dim is a field of its own (num_attention_heads * head_dim != hidden_size in gemma-2-2b, 9b and
+    27b).  max_pos is max_position_embeddings lowered to sliding_window -- within the window a sliding layer computes what a full
+    one does, as for Mistral -- and to max_positions (default LLAMA_MAX_POSITIONS), which sizes the rotary table.  A cap of None
+    in the config means off (0).  "gemma" and "gemma3" are other forwards."""
+    mt = cfg.get("model_type")
+    if mt != "gemma2":
+        raise ValueError(f"model_type {mt!r} is not 'gemma2'")
+    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    Hkv = int(cfg.get("num_key_value_heads") or Hq)
+    act = cfg.get("hidden_activation", "gelu_pytorch_tanh")
+    if act != "gelu_pytorch_tanh":
+        raise ValueError(f"gemma2 hidden_activation {act!r} is not supported (gelu_pytorch_tanh only)")
+    if cfg.get("attention_bias"):
+        raise ValueError("gemma2 with attention_bias=True is not supported (no bias anywhere)")
+    if cfg.get("use_bidirectional_attention"):
+        raise ValueError("gemma2 with use_bidirectional_attention=True is not supported (causal attention only)")
+    if not cfg.get("tie_word_embeddings", True):
+        raise ValueError("gemma2 with tie_word_embeddings=False is not supported (the head is the embedding)")
+    kind = _rope_parameters(cfg)["rope_type"]
+    if kind != "default":
+        raise ValueError(f"gemma2 rope_type {kind!r} is not supported (default only)")
+    hd = int(cfg.get("head_dim") or 256)
+    if hd not in GEMMA2_HEAD_DIMS:
+        raise ValueError(f"head_dim {hd} is not supported (one of {GEMMA2_HEAD_DIMS})")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    ffn = int(cfg["intermediate_size"])
+    if d % 64 or ffn % 64 or (Hq * hd) % 64:
+        raise ValueError(f"hidden_size {d}, intermediate_size {ffn} and num_attention_heads * head_dim {Hq * hd} must be multiples "
+                         f"of 64")
+    rope_inv_freq(cfg)   # refuses partial rotary embeddings
+    caps = {}
+    for f in ("attn_logit_softcapping", "final_logit_softcapping"):
+        c = cfg.get(f)
+        caps[f] = 0.0 if c is None else float(c)
+        if not caps[f] >= 0.0:
+            raise ValueError(f"{f} {c!r} must be >= 0 or None")
+    qpas = float(cfg.get("query_pre_attn_scalar") or 256)
+    if not qpas > 0:
+        raise ValueError(f"query_pre_attn_scalar {qpas} must be > 0")
+    max_pos = int(cfg["max_position_embeddings"])
+    if cfg.get("sliding_window") is not None:
+        max_pos = min(max_pos, int(cfg["sliding_window"]))
+    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
+    if cap < 1:
+        raise ValueError(f"max_positions {cap} < 1")
+    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
+                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-6)), tied=True,
+                head_dim=hd, q_scale=qpas ** -0.5, attn_cap=caps["attn_logit_softcapping"],
+                final_cap=caps["final_logit_softcapping"])
+
+
+def gemma2_head_perm(hd: int) -> np.ndarray:
+    """stored row i of a q / k head = original row perm[i]: stored 32-row block 2j holds dims [32j, 32j + 32) and block 2j + 1
+    dims [hd / 2 + 32j, hd / 2 + 32j + 32), so that the rotary pair (c, c + hd / 2) is 32 rows apart inside one 64-row slice.  At
+    128 this is head_dim_perm's order."""
+    j = np.arange(hd // 64)[:, None] * 32 + np.arange(32)[None, :]
+    return np.concatenate([j, hd // 2 + j], axis=1).reshape(-1)
+
+
+def gemma2_embed_scale(d_model: int, dtype=None) -> float:
+    """sqrt(hidden_size) rounded once to the compute dtype, as HF's scaled embedding does in that dtype."""
+    import torch
+    return float(torch.tensor(float(d_model) ** 0.5, dtype=torch.float32).to(clm_dtype(dtype)).float())
+
+
+def gemma2_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
+    """Tensors in the layout of b2t_clm_llama_t / b2t_clm_gemma2_t from a Gemma-2 state dict, as llama_device_layout makes them,
+    with the family's differences: the head dim is dims["head_dim"], so qkv_w is [(Hq + 2 Hkv) hd][d] (q and k heads under
+    gemma2_head_perm) and o_w [d][Hq hd]; norm1_w / norm2_w are input_layernorm / post_attention_layernorm and pre_ffn_norm_w /
+    post_ffn_norm_w the two feed-forward norms, all as the checkpoint stores them (the kernels add the 1); gate / up rows are
+    interleaved as for Llama; the head is the embedding; any bias and an lm_head of its own are refused."""
+    import torch
+    wdt = clm_dtype(dtype)
+    sd = dict(state)
+    d, ffn, V, Hq, Hkv, hd = (dims[k] for k in ("d_model", "ffn_dim", "vocab", "n_heads", "n_kv_heads", "head_dim"))
+
+    def get(name, shape):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name}")
+        t = sd[name].detach().to(wdt).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
+    dev = emb.device
+    if "lm_head.weight" in sd and not torch.equal(sd["lm_head.weight"].detach().to(wdt), emb[:V]):
+        raise ValueError("lm_head.weight differs from model.embed_tokens.weight: an untied head is not supported")
+    out = {"embed_tokens": emb, "lm_head": emb, "final_norm_w": get("model.norm.weight", (d,))}
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    hp = gemma2_head_perm(hd)
+    qperm = torch.from_numpy(np.concatenate([h * hd + hp for h in range(Hq + Hkv)] +
+                                            [np.arange((Hq + Hkv) * hd, (Hq + 2 * Hkv) * hd)])).to(dev)
+    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
+    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    for i in range(dims["n_layers"]):
+        p = f"model.layers.{i}."
+        for n in sd:
+            if n.startswith(p) and n.endswith(".bias"):
+                raise ValueError(f"{n}: Gemma-2 biases are not supported")
+        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
+        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)),
+             "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
+             "pre_ffn_norm_w": get(p + "pre_feedforward_layernorm.weight", (d,)),
+             "post_ffn_norm_w": get(p + "post_feedforward_layernorm.weight", (d,)),
+             "qkv_w": _pad_rows(qkv[qperm].contiguous(), _rup(qkv.shape[0], ROWPAD)),
+             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, Hq * hd)), _rup(d, ROWPAD)),
+             "gate_up_w": _pad_rows(torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))],
+                                              0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
+             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
+        for f, t in L.items():
+            out[f"layers.{i}.{f}"] = t
+    return out
+
+
+def load_gemma2_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the Gemma-2 checkpoint in model_dir; dtype as clm_dtype reads it."""
+    cfg = load_config(model_dir)
+    dims = gemma2_dims(cfg, max_positions)
+    wdt = clm_dtype(dtype, cfg)
+    return dims, gemma2_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
+
+
+class Gemma2Scorer(LlamaScorer):
+    """A Gemma-2 decoder on the GPU: a LlamaScorer (same descriptor, scoring surface, context cache in fp16 and dtype rules)
+    whose calls are b2t_clm_gemma2_score_f16 / _tree_f16 / _tree_cached_f16 / _bf16 / _tree_bf16 (csrc/causal_lm_gemma2.hip) with
+    the b2t_clm_gemma2_t of gemma2_dims / gemma2_device_layout (head dim, q scale, the two caps, the embedding scale in the
+    compute dtype, the two feed-forward norms per layer), and whose sizes, the cache's included, are the b2t_clm_gemma2_* size
+    functions'."""
+
+    _WS_BYTES = "b2t_clm_gemma2_ws_bytes"
+    _SIZES = "b2t_clm_gemma2_"
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0, dtype=None):
+        import b2t_native as N
+        if "head_dim" not in dims or (dims["n_layers"] > 0 and "layers.0.pre_ffn_norm_w" not in arrays):
+            raise KeyError("Gemma2Scorer: dims lack head_dim or the arrays layers.<i>.pre_ffn_norm_w / post_ffn_norm_w (gemma2_dims "
+                           "and gemma2_device_layout make them)")
+        # the descriptor first: the cache allocation of the base class sizes the cache with it
+        self._g2_layers = (N.ClmGemma2Layer * max(1, dims["n_layers"]))()
+        self._g2 = N.ClmGemma2(dims["head_dim"], dims["q_scale"], dims["attn_cap"], dims["final_cap"],
+                               gemma2_embed_scale(dims["d_model"], dtype), self._g2_layers)
+        self._size_args = (self._g2,)
+        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
+        for i in range(dims["n_layers"]):
+            for f in _GEMMA2_LAYER_FIELDS:
+                setattr(self._g2_layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
+        self._family, self._qk = "gemma2", (self._g2,)
+
+    def _cache_kv_bytes(self, lib, cap):
+        import ctypes as C
+        return lib.b2t_clm_gemma2_cache_kv_bytes(C.byref(self.desc), self._g2, cap)
+
+
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
     """b2t_clm_tree_plan_host on packed int32 ids / offsets (host only, no GPU): (node_of_token, parent_of_node, n_nodes).
     A node is a distinct token prefix, numbered by first appearance; parent_of_node is -1 at roots."""
@@ -1471,9 +1634,10 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
     only, like OPT), NeoxScorer for "gpt_neox" (Pythia; fp16 only), LlamaScorer for "llama",
-    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2", MixtralScorer for "mixtral"; anything else ("olmo" and "olmo3"
-    included) is refused.  max_positions caps a Llama-family, OLMo-2 or Mixtral model's rotary table.  dtype (clm_dtype):
-    None or "float16", "bfloat16" (the Llama family, OLMo-2 and Mixtral only, and without a context cache), or "auto" = the dtype config.json says
+    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2", MixtralScorer for "mixtral", Gemma2Scorer for "gemma2"; anything else
+    ("olmo", "olmo3", "gemma", "gemma3" and "qwen3_moe" included) is refused.  max_positions caps a Llama-family, OLMo-2, Mixtral
+    or Gemma-2 model's rotary table.  dtype (clm_dtype): None or "float16", "bfloat16" (the Llama family, OLMo-2, Mixtral and
+    Gemma-2 only, and without a context cache), or "auto" = the dtype config.json says
     the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
     refused is refused before any weight is read."""
     cfg = load_config(model_dir)
@@ -1508,7 +1672,14 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_mixtral_arrays(model_dir, max_positions, wdt)
         return MixtralScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, olmo2, mixtral)")
+    if mt == "gemma2":
+        wdt = clm_dtype(dtype, cfg)
+        llama_check_dtype_cache(wdt, context_cache_tokens)
+        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
+        dims, arrays = load_gemma2_arrays(model_dir, max_positions, wdt)
+        return Gemma2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
+    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, olmo2, "
+                     f"mixtral)")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
@@ -1516,7 +1687,8 @@ def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", sha
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
     OptScorer, a Gpt2Scorer for a GPT-2 directory, a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory, an
-    Olmo2Scorer for an OLMo-2 directory, or a MixtralScorer for a Mixtral directory (build_scorer).
+    Olmo2Scorer for an OLMo-2 directory, a MixtralScorer for a Mixtral directory, or a Gemma2Scorer for a Gemma-2 directory
+    (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

@@ -69,6 +69,13 @@ ratio mixtral / llama per list; the sorted rows S = round_up(rows * top_k, 256) 
 of the grouped GEMM is padding at that list length.
 
   python tools/bench_llm_rescore.py --arch mixtral --layers 4 --lists 7 [--cands 20] [--list nbest --context 64]
+
+`--arch gemma2` measures Gemma-2's path (b2t_clm_gemma2_score_f16 / _tree_f16: attention at head dim 256 with the soft cap, at
+one wave per SIMD; four norms per layer; GeGLU; the capped head) at the gemma-2-2b shape -- 26 layers, d 2304, 8 query / 4 kv
+heads of 256, ffn 9216, vocab 256000, tied head -- beside a LlamaScorer of equal active FLOPs per row: the same d, ffn, vocab
+and tied head with 18 query / 6 kv heads of 128, under the protocol of --arch olmo2.
+
+  python tools/bench_llm_rescore.py --arch gemma2 --lists 5 --cands 5|20|100
 """
 import argparse
 import json
@@ -105,10 +112,11 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2", "mixtral"), default="opt",
+    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2", "mixtral", "gemma2"), default="opt",
                     help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape; gpt2: GPT-2 XL shape; "
                          "olmo2: OLMo-2-7B shape, beside the Llama forward of the same dimensions; mixtral: Mixtral-8x7B shape "
-                         "with 4 layers, beside the dense Llama forward of the same active FLOPs")
+                         "with 4 layers, beside the dense Llama forward of the same active FLOPs; gemma2: gemma-2-2b shape, beside "
+                         "a Llama forward of the same active FLOPs")
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16",
                     help="--arch llama / qwen3: the compute dtype of the scorer and of the HF model beside it")
     ap.add_argument("--layers", type=int, default=None, help="default 32 (opt, llama), 36 (qwen3), 48 (gpt2)")
@@ -127,18 +135,22 @@ def main():
     ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
     ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
-    a.layers = a.layers or {"qwen3": 36, "gpt2": 48, "mixtral": 4}.get(a.arch, 32)
-    a.d = a.d or (1600 if a.arch == "gpt2" else 4096)
-    a.heads = a.heads or (25 if a.arch == "gpt2" else 32)
-    a.kv_heads = a.kv_heads or (a.heads if a.arch == "olmo2" else 8)
-    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008, "mixtral": 14336}[a.arch]
-    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352, "mixtral": 32000}[a.arch]
-    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2", "mixtral") or a.session):
+    a.layers = a.layers or {"qwen3": 36, "gpt2": 48, "mixtral": 4, "gemma2": 26}.get(a.arch, 32)
+    a.d = a.d or {"gpt2": 1600, "gemma2": 2304}.get(a.arch, 4096)
+    a.heads = a.heads or {"gpt2": 25, "gemma2": 8}.get(a.arch, 32)
+    a.kv_heads = a.kv_heads or (a.heads if a.arch == "olmo2" else 4 if a.arch == "gemma2" else 8)
+    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008, "mixtral": 14336, "gemma2": 9216}[a.arch]
+    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352, "mixtral": 32000, "gemma2": 256000}[a.arch]
+    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2", "mixtral", "gemma2") or a.session):
         ap.error("--dtype bfloat16 needs --arch llama or qwen3 and has no --session")
     if a.arch == "mixtral":
         if a.session:
             ap.error("--arch mixtral has no --session")
         return main_mixtral(a)
+    if a.arch == "gemma2":
+        if a.session:
+            ap.error("--arch gemma2 has no --session")
+        return main_gemma2(a)
     if a.arch == "olmo2":
         if a.session:
             ap.error("--arch olmo2 has no --session")
@@ -304,6 +316,99 @@ def main_gpt2(a):
     return against_hf(a, sc, model, calls, rng, 2 * (L * (4 * d * d + 2 * d * ffn) + d * V), {})
 
 
+def alternate(a, rng, V, scs, fams):
+    """The protocol of --arch olmo2 / gemma2: the scorers scs[f], f in fams (the new family last), flat and tree of each
+    alternating list by list in this process, --reps passes over --lists lists after a warm-up of all.  Returns (lists, tokens
+    per list, nodes per list, whether flat and tree were bit-identical throughout, per (family, tree) the per-list medians in ms,
+    stat(key) = their summary)."""
+    import torch
+    gen = nbest_list if a.list == "nbest" else random_list
+    lists = [gen(rng, V, a.cands, [int(x) for x in rng.integers(4, V, a.context)]) for _ in range(a.lists)]
+    ntok = [sum(len(s) for s in l) for l in lists]
+    paths = (False, True)
+    ms = {(f, t): [[] for _ in lists] for f in fams for t in paths}
+    nodes, same = [0] * len(lists), True
+    with torch.inference_mode():
+        for i in range(max(1, a.warmup)):
+            for f in fams:
+                for t in paths:
+                    scs[f].score(lists[i % len(lists)], share_prefixes=t)
+        torch.cuda.synchronize()
+        for _ in range(max(1, a.reps)):
+            for i, l in enumerate(lists):
+                for f in fams:
+                    out = {}
+                    for t in paths:
+                        t0 = time.perf_counter()
+                        out[t] = scs[f].score(l, share_prefixes=t)   # returns host scores: the call is complete
+                        ms[f, t][i].append((time.perf_counter() - t0) * 1e3)
+                    same = same and out[False].tobytes() == out[True].tobytes()
+                nodes[i] = scs[fams[-1]].last_stats["nodes"]
+    r2 = lambda x: round(float(x), 2)
+    per = {k: [float(np.median(v)) for v in ms[k]] for k in ms}   # per list, median over its repeats
+    stat = lambda k: {"median": r2(np.median(per[k])), "min": r2(np.min(per[k])), "max": r2(np.max(per[k])),
+                      "repeat_spread": r2(max(max(v) - min(v) for v in ms[k])), "per_list": [r2(x) for x in per[k]]}
+    return lists, ntok, nodes, same, per, stat
+
+
+def main_gemma2(a):
+    """--arch gemma2: a Gemma2Scorer at the gemma-2-2b shape on random fp16 weights beside a LlamaScorer of equal active FLOPs
+    per row (the same d, ffn, vocab and tied head; 18 query / 6 kv heads of 128, whose four projections have gemma-2-2b's
+    2304 x 6144 weights), under the protocol of --arch olmo2."""
+    import torch
+    import llm_rescore as R
+    torch.manual_seed(0)
+    d, H, Hkv, hd, ffn, V, L = a.d, a.heads, a.kv_heads, 256, a.ffn, a.vocab, a.layers
+    lH, lHkv, lhd, dev = 18, 6, 128, "cuda"
+    if d != lH * lhd or (H + 2 * Hkv) * hd + H * hd != (lH + 2 * lHkv) * lhd + lH * lhd:
+        raise SystemExit("--arch gemma2 compares at the gemma-2-2b widths only (d 2304, 8 query / 4 kv heads of 256)")
+    rng = np.random.default_rng(0)
+    rn = lambda *s, std: (torch.randn(*s, device=dev) * std).half()
+    nw = lambda n, one: (one + 0.2 * torch.randn(n, device=dev)).half()
+    emb = rn(V, d, std=2.0 / d ** 0.5)
+    mlp = [{n: rn(o, i, std=1.0 / i ** 0.5) for n, (o, i) in {"mlp.gate_proj": (ffn, d), "mlp.up_proj": (ffn, d),
+                                                               "mlp.down_proj": (d, ffn)}.items()} for _ in range(L)]
+
+    def state(Hq, Hk, h, one, norms):
+        st = {"model.embed_tokens.weight": emb, "model.norm.weight": nw(d, one)}
+        for l in range(L):
+            p = f"model.layers.{l}."
+            for n, (o, i) in {"self_attn.q_proj": (Hq * h, d), "self_attn.k_proj": (Hk * h, d), "self_attn.v_proj": (Hk * h, d),
+                              "self_attn.o_proj": (d, Hq * h)}.items():
+                st[p + n + ".weight"] = rn(o, i, std=1.0 / i ** 0.5)
+            for n, w in mlp[l].items():
+                st[p + n + ".weight"] = w
+            for n in norms:
+                st[p + n + ".weight"] = nw(d, one)
+        return st
+    base = dict(hidden_size=d, intermediate_size=ffn, vocab_size=V, num_hidden_layers=L, max_position_embeddings=8192,
+                rms_norm_eps=1e-6, rope_theta=10000.0, tie_word_embeddings=True)
+    cfg = dict(base, model_type="gemma2", num_attention_heads=H, num_key_value_heads=Hkv, head_dim=hd, sliding_window=4096,
+               query_pre_attn_scalar=256, attn_logit_softcapping=50.0, final_logit_softcapping=30.0,
+               hidden_activation="gelu_pytorch_tanh")
+    dims = R.gemma2_dims(cfg, 2048)
+    st = state(H, Hkv, hd, 0.0, ("input_layernorm", "post_attention_layernorm", "pre_feedforward_layernorm",
+                                 "post_feedforward_layernorm"))
+    scs = {"gemma2": R.Gemma2Scorer(dims, R.gemma2_device_layout(st, dims, R.rope_inv_freq(cfg)), dev)}
+    lcfg = dict(base, model_type="llama", num_attention_heads=lH, num_key_value_heads=lHkv, hidden_act="silu")
+    ldims = R.llama_dims(lcfg, 2048)
+    st = state(lH, lHkv, lhd, 1.0, ("input_layernorm", "post_attention_layernorm"))
+    scs["llama"] = R.LlamaScorer(ldims, R.llama_device_layout(st, ldims, R.rope_inv_freq(lcfg)), dev)
+    del st, mlp, emb
+    torch.cuda.empty_cache()
+    lists, ntok, nodes, same, per, stat = alternate(a, rng, V, scs, ("llama", "gemma2"))
+    ratio = lambda t: [round(o / l, 4) for o, l in zip(per["gemma2", t], per["llama", t])]
+    print(json.dumps({"bench": "llm_rescore_gemma2", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "head_dim": hd, "ffn": ffn,
+                      "vocab": V, "llama_heads": lH, "llama_kv_heads": lHkv, "cands": a.cands, "list": a.list,
+                      "context": a.context, "lists": len(lists), "reps": max(1, a.reps), "tokens": float(np.mean(ntok)),
+                      "nodes": float(np.mean(nodes)), "llama_flat_ms": stat(("llama", False)),
+                      "gemma2_flat_ms": stat(("gemma2", False)), "llama_tree_ms": stat(("llama", True)),
+                      "gemma2_tree_ms": stat(("gemma2", True)),
+                      "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
+                      "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
+                      "flat_tree_bit_identical": bool(same)}))
+
+
 def main_olmo2(a):
     """--arch olmo2: an Olmo2Scorer and a LlamaScorer of the same dimensions on the same random fp16 weights (the Llama model
     takes post_feedforward_layernorm as its input norm and drops the q / k norms), flat and tree of both alternating list by
@@ -337,32 +442,7 @@ def main_olmo2(a):
     scs["llama"] = R.LlamaScorer(ldims, R.llama_device_layout(lst, ldims, R.rope_inv_freq(lcfg)), dev)
     del st, lst
     torch.cuda.empty_cache()
-    gen = nbest_list if a.list == "nbest" else random_list
-    lists = [gen(rng, V, a.cands, [int(x) for x in rng.integers(4, V, a.context)]) for _ in range(a.lists)]
-    ntok = [sum(len(s) for s in l) for l in lists]
-    fams, paths = ("llama", "olmo2"), (False, True)
-    ms = {(f, t): [[] for _ in lists] for f in fams for t in paths}
-    nodes, same = [0] * len(lists), True
-    with torch.inference_mode():
-        for i in range(max(1, a.warmup)):
-            for f in fams:
-                for t in paths:
-                    scs[f].score(lists[i % len(lists)], share_prefixes=t)
-        torch.cuda.synchronize()
-        for _ in range(max(1, a.reps)):
-            for i, l in enumerate(lists):
-                for f in fams:
-                    out = {}
-                    for t in paths:
-                        t0 = time.perf_counter()
-                        out[t] = scs[f].score(l, share_prefixes=t)   # returns host scores: the call is complete
-                        ms[f, t][i].append((time.perf_counter() - t0) * 1e3)
-                    same = same and out[False].tobytes() == out[True].tobytes()
-                nodes[i] = scs["olmo2"].last_stats["nodes"]
-    r2 = lambda x: round(float(x), 2)
-    per = {k: [float(np.median(v)) for v in ms[k]] for k in ms}   # per list, median over its repeats
-    stat = lambda k: {"median": r2(np.median(per[k])), "min": r2(np.min(per[k])), "max": r2(np.max(per[k])),
-                      "repeat_spread": r2(max(max(v) - min(v) for v in ms[k])), "per_list": [r2(x) for x in per[k]]}
+    lists, ntok, nodes, same, per, stat = alternate(a, rng, V, scs, ("llama", "olmo2"))
     ratio = lambda t: [round(o / l, 4) for o, l in zip(per["olmo2", t], per["llama", t])]
     print(json.dumps({"bench": "llm_rescore_olmo2", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "ffn": ffn, "vocab": V,
                       "cands": a.cands, "list": a.list, "context": a.context, "lists": len(lists), "reps": max(1, a.reps),
