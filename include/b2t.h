@@ -1038,6 +1038,55 @@ int b2t_clm_gemma2_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_g
                                    const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                    long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Phi-3 (csrc/causal_lm_phi3.hip): head dim 96, partial rotary ------------------------------------------------------------
+ * HF Phi3ForCausalLM (model_type "phi3": Phi-3-mini, Phi-3.5-mini, Phi-3-medium, Phi-4, Phi-4-mini), eager attention.  The
+ * forward is the Llama section's (pre-norm RMSNorm, grouped-query attention, SwiGLU, no bias anywhere) with hd = b2t_clm_phi3_t's
+ * head_dim, which may be 96, and a rotation of its own:
+ *   of every q and k head the first rot = rotary_dims dims are rotated, pairs (c, c + rot / 2), c < rot / 2, by the angle of
+ *   the row's position; dims rot .. hd - 1 pass through; then every q dim, rotated or not, is multiplied by hd^-0.5.
+ * The model is the b2t_clm_llama_t above with these differences: hd is b2t_clm_phi3_t's head_dim, not d_model / n_heads; qkv_w
+ * is [round_up((Hq + 2 Hkv) hd, 256)][d] with q, k and v rows in checkpoint order (the fused qkv_proj as stored: no permutation
+ * of a head's rows); o_w is [round_up(d, 256)][Hq hd]; rope_cos / rope_sin are [max_pos][rot / 2], and hold LongRoPE's
+ * per-frequency factors and its attention factor where the model has them (nejm-brain-to-text_amd/llm_rescore.py, phi3_rope);
+ * qkv_b must be NULL; gate_up_w is interleaved as in the Llama section.
+ * Required: hd 64, 96 or 128; rot even, 2 <= rot <= hd; Hq % Hkv == 0; d_model, ffn_dim, Hq hd and (Hq + 2 Hkv) hd multiples of
+ * 64; anything else is refused before any launch, under the entry point's own name.
+ * Numerics: the Llama section's, E being fp16 or bf16.  The QKV GEMM keeps the q | k columns as fp32 accumulators; the rotation,
+ * the pass-through and q's factor happen in fp32 on them, then q and k are rounded to E once; v is rounded once by the GEMM.  A
+ * row's bits depend only on that row: tree, cached and flat calls are bit-identical, a sequence scores the same alone or in a
+ * batch, and B2T_CLM_GEMM_256 / B2T_CLM_TRUNK_ATTN do not change the bits.  The cache holds K rows after the rotation.
+ * The nine functions have their Gemma-2 twins' argument lists with the b2t_clm_phi3_t in the Gemma-2 descriptor's place
+ * (b2t_clm_phi3_cache_kv_bytes: kv is [n_layers][cap][2 * n_kv_heads * hd]; 0 if refused), their output layout and their
+ * refusals.  The workspace is the Llama layout with the QKV width (Hq + 2 Hkv) hd plus an fp32 region
+ * [round_up(rows, 256)][(Hq + Hkv) hd].  There is no cached bf16 call. */
+typedef struct {
+  int32_t head_dim;     /* 64, 96 or 128 */
+  int32_t rotary_dims;  /* rotated dims of each q / k head: even, in [2, head_dim] */
+} b2t_clm_phi3_t;
+
+size_t b2t_clm_phi3_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_tokens, int n_seq);
+size_t b2t_clm_phi3_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_nodes, long long n_tokens,
+                                  int n_seq);
+size_t b2t_clm_phi3_cache_kv_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, int cap);
+size_t b2t_clm_phi3_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_rows,
+                                         long long n_tokens, int n_seq);
+int b2t_clm_phi3_score_f16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
+                           const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                           size_t ws_bytes, void* stream);
+int b2t_clm_phi3_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
+                                const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_phi3_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, b2t_clm_cache_t* cache,
+                                       int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                       float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
+                                       void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_phi3_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
+                            const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                            size_t ws_bytes, void* stream);
+int b2t_clm_phi3_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
+                                 const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                 long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
  * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
  * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,

@@ -143,6 +143,11 @@ class ClmGemma2(C.Structure):
                 ("embed_scale", C.c_float), ("layers_host", C.POINTER(ClmGemma2Layer))]
 
 
+class ClmPhi3(C.Structure):
+    """Mirror of b2t_clm_phi3_t (include/b2t.h): what a Phi-3 model adds to its b2t_clm_llama_t."""
+    _fields_ = [("head_dim", C.c_int32), ("rotary_dims", C.c_int32)]
+
+
 class ClmQkNorm(C.Structure):
     """Mirror of b2t_clm_qknorm_t (include/b2t.h): device weights [hd] of one Qwen3 layer's q and k RMSNorm."""
     _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
@@ -307,6 +312,7 @@ for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes"
            "score_tree_bf16", "score_tree_cached_f16"):
     _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
     _SIGNATURES["b2t_clm_gemma2_" + _t] = (_res, [_args[0], C.POINTER(ClmGemma2)] + _args[1:])
+    _SIGNATURES["b2t_clm_phi3_" + _t] = (_res, [_args[0], C.POINTER(ClmPhi3)] + _args[1:])   # Phi-3: the same, on its descriptor
 # GPT-NeoX: the OPT twin's list on its own model struct (same cache)
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
            "score_tree_cached_f16"):

@@ -37,7 +37,8 @@ namespace b2t {
 namespace {
 
 // The two attention kernels of this path, clm_attn_tree_cached_kernel and clm_attn_trunk_kernel, are templates of clm_attn.h
-// (this unit instantiates them for head dims 64, 80 and 128; causal_lm_gemma2.hip their soft-capped forms).
+// (this unit instantiates them for head dims 64, 80 and 128; causal_lm_gemma2.hip their soft-capped forms, causal_lm_phi3.hip
+// head dim 96).
 
 // cache append: K | V of the trunk's computed rows (qkv rows 0..rows-1 of width rs, columns qc .. qc + cs) -> dst rows 0..
 // ([.][cs], the layer slab at row R), as 16-byte pieces; qc = Hq * D, cs = 2 * Hkv * D, rs = qc + cs
@@ -147,6 +148,7 @@ int clm_launch_attn_cached(const ClmCachedAttn& a, const _Float16* qkv, _Float16
     B2T_CHECK_LAUNCH("clm_cache_append_kernel");
   }
   if (a.hd == 256 || a.cap > 0.f) return clm_launch_attn_cached_cap(a, qkv, slab, out, s);   // Gemma-2 (causal_lm_gemma2.hip)
+  if (a.hd == 96) return clm_launch_attn_cached_96(a, qkv, slab, out, s);   // Phi-3 (causal_lm_phi3.hip)
   if (a.hd == 64) return launch_attn<64>(a, qkv, slab, out, s);
   if (a.hd == 80) return launch_attn<80>(a, qkv, slab, out, s);
   return launch_attn<128>(a, qkv, slab, out, s);

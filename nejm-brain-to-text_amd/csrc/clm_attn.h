@@ -1,7 +1,7 @@
 // clm_attn.h — the attention arithmetic of the causal-LM forward, written once (device code, internal linkage).  Every
 // attention kernel -- clm_attn_kernel and clm_attn_tree_kernel (launched by causal_lm.hip, causal_lm_tree.hip and, in bf16,
 // causal_lm_llama_bf16.hip), clm_attn_tree_cached_kernel and clm_attn_trunk_kernel (launched by causal_lm_cache.hip), all at the
-// end of this file, and their soft-capped `_cap_` forms (causal_lm_gemma2.hip) -- walks its own rows and calls attn_block per 32-key block, so a query meets the same operands in
+// end of this file, their soft-capped `_cap_` forms (causal_lm_gemma2.hip) and their head-dim-96 instances (causal_lm_phi3.hip) -- walks its own rows and calls attn_block per 32-key block, so a query meets the same operands in
 // the same order on every path: that is what keeps the paths bit-identical.  The element type E (ClmElem, clm_internal.h)
 // is deduced from the pointers: _Float16 everywhere but in the bf16 unit.
 //
@@ -9,7 +9,7 @@
 // one query column: its online-softmax state (m, l) is per lane and the row reductions are in-lane plus one swap of the lane
 // halves.  P^T is then the B operand of O^T = V^T . P^T with no data movement (registers 8s..8s+7 of the accumulator are
 // k-step s, keys in the order 16s + 8(j >> 2) + 4h + (j & 3)), and O^T's rescale by exp(m_old - m_new) is per lane too.
-// Throughout: lane = 32 * hh + li; D is the head dim (64, 80, 128 or 256), KS its k-steps, NF its 32-dim fragments of O^T; the
+// Throughout: lane = 32 * hh + li; D is the head dim (64, 80, 96, 128 or 256), KS its k-steps, NF its 32-dim fragments of O^T; the
 // `dim < D` guards exist only where NF * 32 != D (head dim 80).
 // CAP (Gemma-2, causal_lm_gemma2.hip): the fp32 score tile is soft-capped, s = cap * tanh(s / cap), before the mask and the
 // running max; cap == 0 at run time means off.  CAP is false in every kernel without `_cap_` in its name: the body functions

@@ -9,7 +9,8 @@
 // GPT-NeoX adds (EP_ROPE_PART: the rotation of only the first rotary_ndims dims of a head; EP_GELU_ERF) in fp16, causal_lm_olmo2.hip the two OLMo-2 adds
 // (EP_F32 and EP_QKV_F32: fp32 stores for the norms over a whole output row) in both, causal_lm_mixtral.hip the grouped form of
 // the tile (clm_gemm_grouped_kernel: one B matrix per expert) with EP_SWIGLU and EP_F32 in both, causal_lm_gemma2.hip the two
-// Gemma-2 adds (EP_GEGLU: gelu_new where SwiGLU has silu; EP_HEAD_CAP: the fused head on soft-capped logits) in both.  Which
+// Gemma-2 adds (EP_GEGLU: gelu_new where SwiGLU has silu; EP_HEAD_CAP: the fused head on soft-capped logits) in both,
+// causal_lm_phi3.hip EP_QKV_F32 again in both (Phi-3's rotation reads the fp32 q | k columns in a kernel of its own).  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once

@@ -38,8 +38,9 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 // EP_GELU_ERF (GPT-NeoX) is EP_GELU with the erf form: gelu(v) = 0.5 v (1 + erf(v / sqrt 2)) in fp32, rounded once.
 // EP_F32 (OLMo-2) stores the fp32 accumulator unrounded: resid[r][c] = C[r][c] (`=`, no bias; pitch ldo) -- the o_proj and down
 //   outputs, whose whole row a post-norm reads before anything reaches the residual.
-// EP_QKV_F32 (OLMo-2) splits the QKV row: columns < rope_cols (q | k) are stored as EP_F32 stores them, resid[r][c] with pitch
-//   rope_cols, for the whole-row q / k norm that no column tile can hold; the others (v) are rounded once, out16[r][c] (pitch ldo).
+// EP_QKV_F32 (OLMo-2, Phi-3) splits the QKV row: columns < rope_cols (q | k) are stored as EP_F32 stores them, resid[r][c] with
+//   pitch rope_cols, for the whole-row q / k norm that no column tile can hold (Phi-3: for the rotation of heads of 96 dims);
+//   the others (v) are rounded once, out16[r][c] (pitch ldo).
 // EP_GEGLU (Gemma-2) is EP_SWIGLU with gelu_new in silu's place: out16[r][c0 / 2 + i] = gelu_new(C[r][c0 + i]) * C[r][c0 + 32 + i].
 // EP_HEAD_CAP (Gemma-2) is EP_HEAD on soft-capped logits: v = cap * tanh(C[r][c] / cap) in fp32 (tanh written as gelu_new's) in
 //   front of the group max, the group sum and the target pick; cap > 0.
@@ -313,6 +314,8 @@ int clm_launch_attn_cached(const ClmCachedAttn& a, const _Float16* qkv, _Float16
 // the attention of clm_launch_attn_cached (behind its append) with the soft-capped kernels, for head dim 256 or a.cap > 0
 // (Gemma-2: head dim 128 or 256); causal_lm_gemma2.hip
 int clm_launch_attn_cached_cap(const ClmCachedAttn& a, const _Float16* qkv, const _Float16* slab, _Float16* out, hipStream_t s);
+// the attention of clm_launch_attn_cached (behind its append) at head dim 96 (Phi-3); causal_lm_phi3.hip
+int clm_launch_attn_cached_96(const ClmCachedAttn& a, const _Float16* qkv, const _Float16* slab, _Float16* out, hipStream_t s);
 // dst[i] = logp[i], i < n: the trunk's head rows -> the cache's logp at R + 1
 int clm_launch_cache_logp(const float* logp, float* dst, int n, hipStream_t s);
 // clm_launch_seq_sum_tree with the log-probs of positions 1..R taken from cache_logp

@@ -13,7 +13,7 @@
 // The two entry-point bodies also serve a family with another layer (OLMo-2, clm_olmo2.h; Mixtral, clm_moe.h): their second
 // template argument supplies the layout, the refusals that go with the family's extra argument and the forward (LlamaFamily
 // below by default), and -- through LlamaFamilyBase, or on its own for Gemma-2 (clm_gemma2.h), whose head dim is not
-// d_model / n_heads -- the model check and the attention launches.
+// d_model / n_heads, and Phi-3 (clm_phi3.h), whose head dim may be 96 -- the model check and the attention launches.
 #pragma once
 #include <math.h>
 #include <string>

@@ -1598,6 +1598,184 @@ class Gemma2Scorer(LlamaScorer):
         return lib.b2t_clm_gemma2_cache_kv_bytes(C.byref(self.desc), self._g2, cap)
 
 
+# ---- Phi-3 (HF Phi3ForCausalLM): head dim 96, partial rotary, LongRoPE, fused qkv_proj / gate_up_proj ------------------------
+PHI3_HEAD_DIMS = (64, 96, 128)
+
+
+def _phi3_rope_parameters(cfg: dict) -> dict:
+    """_rope_parameters with Phi-3's older spellings folded in: type "su" is "longrope", and partial_rotary_factor /
+    original_max_position_embeddings may stand at the config's top level."""
+    rp = _rope_parameters(cfg)
+    if rp["rope_type"] == "su":
+        rp["rope_type"] = "longrope"
+    for f in ("partial_rotary_factor", "original_max_position_embeddings"):
+        if rp.get(f) is None and cfg.get(f) is not None:
+            rp[f] = cfg[f]
+    return rp
+
+
+def _phi3_head_rot(cfg: dict) -> Tuple[int, int]:
+    """(head dim, rotary dims = int(head_dim * partial_rotary_factor), as HF computes them) of a phi3 config"""
+    hd = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // int(cfg["num_attention_heads"]))
+    return hd, int(hd * float(_phi3_rope_parameters(cfg).get("partial_rotary_factor") or 1.0))
+
+
+def phi3_rope(cfg: dict) -> Tuple[np.ndarray, float]:
+    """(fp32 inv_freq[rotary_dims / 2], attention factor) of a "phi3" config, computed as HF's ROPE_INIT_FUNCTIONS compute them
+    (fp32 torch arithmetic, same operation order).  rope_type "default": 1 / base^(arange(0, rot, 2) / rot), factor 1.
+    "longrope" (older spelling "su"): 1 / (short_factor * base^(...)), and the factor that HF multiplies cos and sin by,
+    sqrt(1 + ln(f) / ln(original_max_position_embeddings)) for f = max_position_embeddings / original_max_position_embeddings
+    > 1 (or rope's own "factor"), else 1, unless "attention_factor" is given.  The long factors are never used: phi3_dims keeps
+    every sequence within original_max_position_embeddings.  Every other type is refused."""
+    import math
+    import torch
+    rp = _phi3_rope_parameters(cfg)
+    kind = rp["rope_type"]
+    if kind not in ("default", "longrope"):
+        raise ValueError(f"phi3 rope_type {kind!r} is not supported (default or longrope)")
+    rot = _phi3_head_rot(cfg)[1]
+    base = rp["rope_theta"]
+    if kind == "default":
+        inv = 1.0 / (base ** (torch.arange(0, rot, 2, dtype=torch.float) / rot))
+        return inv.numpy().astype(np.float32), 1.0
+    short = rp.get("short_factor")
+    if short is None or len(short) != rot // 2:
+        raise ValueError(f"short_factor has {0 if short is None else len(short)} entries, rotary dims {rot} need {rot // 2}")
+    orig = int(rp.get("original_max_position_embeddings") or cfg["max_position_embeddings"])
+    factor = rp.get("factor")
+    if factor is None:
+        factor = int(cfg["max_position_embeddings"]) / orig
+    af = rp.get("attention_factor")
+    if af is None:
+        af = 1.0 if factor <= 1.0 else math.sqrt(1 + math.log(factor) / math.log(orig))
+    ext = torch.tensor(short, dtype=torch.float32)
+    shape = torch.arange(0, rot, 2, dtype=torch.int64).float() / rot
+    return (1.0 / (ext * base ** shape)).numpy().astype(np.float32), float(af)
+
+
+def phi3_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
+    """The dimensions b2t_clm_llama_t and b2t_clm_phi3_t need for a "phi3" config, after refusing, by the field's name, what the
+    kernels do not run.  max_pos is max_position_embeddings lowered to sliding_window where one is set (within it full causal
+    attention is what the model computes), for a longrope model to original_max_position_embeddings, and to max_positions
+    (default LLAMA_MAX_POSITIONS), which sizes the rotary table.  Within the original length HF uses short_factor for the whole
+    sequence; beyond it HF switches the whole call to long_factor, so that a row's score would depend on the longest sequence of
+    its batch: such lengths are refused like lengths beyond a sliding window.  "phi", "phimoe" and "phi3small" are other
+    forwards."""
+    mt = cfg.get("model_type")
+    if mt != "phi3":
+        raise ValueError(f"model_type {mt!r} is not 'phi3'")
+    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    Hkv = int(cfg.get("num_key_value_heads") or Hq)
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise ValueError(f"phi3 hidden_act {act!r} is not supported (silu only)")
+    if not cfg.get("head_dim") and d % Hq:
+        raise ValueError(f"hidden_size {d} is not a multiple of num_attention_heads {Hq}")
+    hd, rot = _phi3_head_rot(cfg)
+    if hd not in PHI3_HEAD_DIMS:
+        raise ValueError(f"head_dim {hd} (head_dim, or hidden_size / num_attention_heads) is not supported (one of {PHI3_HEAD_DIMS})")
+    if rot < 2 or rot > hd or rot % 2:
+        raise ValueError(f"partial_rotary_factor gives {rot} rotary dims of head_dim {hd}: not an even number in [2, {hd}]")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    ffn = int(cfg["intermediate_size"])
+    if d % 64 or ffn % 64 or (Hq * hd) % 64 or ((Hq + 2 * Hkv) * hd) % 64:
+        raise ValueError(f"hidden_size {d}, intermediate_size {ffn}, num_attention_heads * head_dim {Hq * hd} and "
+                         f"(num_attention_heads + 2 num_key_value_heads) * head_dim {(Hq + 2 * Hkv) * hd} must be multiples of 64")
+    phi3_rope(cfg)   # refuses the rope types and factor lists the table does not describe
+    rp = _phi3_rope_parameters(cfg)
+    max_pos = int(cfg["max_position_embeddings"])
+    if cfg.get("sliding_window") is not None:
+        max_pos = min(max_pos, int(cfg["sliding_window"]))
+    if rp["rope_type"] == "longrope" and rp.get("original_max_position_embeddings"):
+        max_pos = min(max_pos, int(rp["original_max_position_embeddings"]))
+    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
+    if cap < 1:
+        raise ValueError(f"max_positions {cap} < 1")
+    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
+                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-5)),
+                tied=bool(cfg.get("tie_word_embeddings", False)), head_dim=hd, rotary_dims=rot)
+
+
+def phi3_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float], dtype=None) -> Dict[str, "object"]:
+    """Tensors in the layout of b2t_clm_llama_t / b2t_clm_phi3_t from a Phi-3 state dict, as llama_device_layout makes them, with
+    the family's differences: the head dim is dims["head_dim"]; qkv_w is the fused self_attn.qkv_proj.weight [(Hq + 2 Hkv) hd][d]
+    as stored (q, k and v rows in checkpoint order: the rotation runs in a kernel that sees whole heads, so there is no
+    head_dim_perm); o_w is [d][Hq hd]; gate_up_w is the fused mlp.gate_up_proj.weight (gate rows, then up rows) interleaved in
+    blocks of 32 (gate_up_row_perm); rope_cos / rope_sin are [max_pos][rotary_dims / 2] = rope_tables of rope's inv_freq times
+    its attention factor in fp32 (rope = phi3_rope(cfg)); any bias in a layer is refused; the head is tied or untied as for
+    Llama."""
+    import torch
+    wdt = clm_dtype(dtype)
+    sd = dict(state)
+    d, ffn, V, Hq, Hkv, hd = (dims[k] for k in ("d_model", "ffn_dim", "vocab", "n_heads", "n_kv_heads", "head_dim"))
+    inv_freq, att = rope
+    if len(inv_freq) != dims["rotary_dims"] // 2:
+        raise ValueError(f"inv_freq has {len(inv_freq)} entries, rotary_dims {dims['rotary_dims']} need {dims['rotary_dims'] // 2}")
+
+    def get(name, shape):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name}")
+        t = sd[name].detach().to(wdt).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
+    tied = dims.get("tied", False) or "lm_head.weight" not in sd
+    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
+           "final_norm_w": get("model.norm.weight", (d,))}
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos * np.float32(att)), torch.from_numpy(sin * np.float32(att))
+    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(emb.device)
+    qw = (Hq + 2 * Hkv) * hd
+    for i in range(dims["n_layers"]):
+        p = f"model.layers.{i}."
+        for n in sd:
+            if n.startswith(p) and n.endswith(".bias"):
+                raise ValueError(f"{n}: Phi-3 biases are not supported")
+        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
+             "qkv_w": _pad_rows(get(p + "self_attn.qkv_proj.weight", (qw, d)), _rup(qw, ROWPAD)),
+             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, Hq * hd)), _rup(d, ROWPAD)),
+             "gate_up_w": _pad_rows(get(p + "mlp.gate_up_proj.weight", (2 * ffn, d))[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
+             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
+        for f, t in L.items():
+            out[f"layers.{i}.{f}"] = t
+    return out
+
+
+def load_phi3_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the Phi-3 checkpoint in model_dir; dtype as clm_dtype reads it."""
+    cfg = load_config(model_dir)
+    dims = phi3_dims(cfg, max_positions)
+    wdt = clm_dtype(dtype, cfg)
+    return dims, phi3_device_layout(_load_state_dict(model_dir), dims, phi3_rope(cfg), wdt)
+
+
+class Phi3Scorer(LlamaScorer):
+    """A Phi-3 decoder on the GPU: a LlamaScorer (same descriptor, scoring surface, context cache in fp16 and dtype rules) whose
+    calls are b2t_clm_phi3_score_f16 / _tree_f16 / _tree_cached_f16 / _bf16 / _tree_bf16 (csrc/causal_lm_phi3.hip) with the
+    b2t_clm_phi3_t of phi3_dims (head dim, rotary dims), and whose sizes, the cache's included, are the b2t_clm_phi3_* size
+    functions'."""
+
+    _WS_BYTES = "b2t_clm_phi3_ws_bytes"
+    _SIZES = "b2t_clm_phi3_"
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0, dtype=None):
+        import b2t_native as N
+        if "head_dim" not in dims or "rotary_dims" not in dims:
+            raise KeyError("Phi3Scorer: dims lack head_dim / rotary_dims (phi3_dims makes them)")
+        # the descriptor first: the cache allocation of the base class sizes the cache with it
+        self._phi3 = N.ClmPhi3(dims["head_dim"], dims["rotary_dims"])
+        self._size_args = (self._phi3,)
+        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
+        self._family, self._qk = "phi3", (self._phi3,)
+
+    def _cache_kv_bytes(self, lib, cap):
+        import ctypes as C
+        return lib.b2t_clm_phi3_cache_kv_bytes(C.byref(self.desc), self._phi3, cap)
+
+
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
     """b2t_clm_tree_plan_host on packed int32 ids / offsets (host only, no GPU): (node_of_token, parent_of_node, n_nodes).
     A node is a distinct token prefix, numbered by first appearance; parent_of_node is -1 at roots."""
@@ -1634,10 +1812,11 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
     only, like OPT), NeoxScorer for "gpt_neox" (Pythia; fp16 only), LlamaScorer for "llama",
-    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2", MixtralScorer for "mixtral", Gemma2Scorer for "gemma2"; anything else
-    ("olmo", "olmo3", "gemma", "gemma3" and "qwen3_moe" included) is refused.  max_positions caps a Llama-family, OLMo-2, Mixtral
-    or Gemma-2 model's rotary table.  dtype (clm_dtype): None or "float16", "bfloat16" (the Llama family, OLMo-2, Mixtral and
-    Gemma-2 only, and without a context cache), or "auto" = the dtype config.json says
+    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2", MixtralScorer for "mixtral", Gemma2Scorer for "gemma2", Phi3Scorer for
+    "phi3"; anything else ("olmo", "olmo3", "gemma", "gemma3", "qwen3_moe", "phi", "phimoe" and "phi3small" included) is refused.
+    max_positions caps a Llama-family, OLMo-2, Mixtral, Gemma-2 or Phi-3 model's rotary table.  dtype (clm_dtype): None or
+    "float16", "bfloat16" (the Llama family, OLMo-2, Mixtral, Gemma-2 and Phi-3 only, and without a context cache), or "auto" =
+    the dtype config.json says
     the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
     refused is refused before any weight is read."""
     cfg = load_config(model_dir)
@@ -1678,8 +1857,14 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_gemma2_arrays(model_dir, max_positions, wdt)
         return Gemma2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, olmo2, "
-                     f"mixtral)")
+    if mt == "phi3":
+        wdt = clm_dtype(dtype, cfg)
+        llama_check_dtype_cache(wdt, context_cache_tokens)
+        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
+        dims, arrays = load_phi3_arrays(model_dir, max_positions, wdt)
+        return Phi3Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
+    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, phi3, "
+                     f"olmo2, mixtral)")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
@@ -1687,8 +1872,8 @@ def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", sha
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
     OptScorer, a Gpt2Scorer for a GPT-2 directory, a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory, an
-    Olmo2Scorer for an OLMo-2 directory, a MixtralScorer for a Mixtral directory, or a Gemma2Scorer for a Gemma-2 directory
-    (build_scorer).
+    Olmo2Scorer for an OLMo-2 directory, a MixtralScorer for a Mixtral directory, a Gemma2Scorer for a Gemma-2 directory, or a
+    Phi3Scorer for a Phi-3 / Phi-4 directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

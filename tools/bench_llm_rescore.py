@@ -112,11 +112,12 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2", "mixtral", "gemma2"), default="opt",
+    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2", "mixtral", "gemma2", "phi3"), default="opt",
                     help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape; gpt2: GPT-2 XL shape; "
                          "olmo2: OLMo-2-7B shape, beside the Llama forward of the same dimensions; mixtral: Mixtral-8x7B shape "
                          "with 4 layers, beside the dense Llama forward of the same active FLOPs; gemma2: gemma-2-2b shape, beside "
-                         "a Llama forward of the same active FLOPs")
+                         "a Llama forward of the same active FLOPs; phi3: Phi-3-mini shape (32 heads of 96), beside a Llama forward of "
+                         "the same FLOPs (24 heads of 128)")
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16",
                     help="--arch llama / qwen3: the compute dtype of the scorer and of the HF model beside it")
     ap.add_argument("--layers", type=int, default=None, help="default 32 (opt, llama), 36 (qwen3), 48 (gpt2)")
@@ -135,13 +136,13 @@ def main():
     ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
     ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
-    a.layers = a.layers or {"qwen3": 36, "gpt2": 48, "mixtral": 4, "gemma2": 26}.get(a.arch, 32)
-    a.d = a.d or {"gpt2": 1600, "gemma2": 2304}.get(a.arch, 4096)
+    a.layers = a.layers or {"qwen3": 36, "gpt2": 48, "mixtral": 4, "gemma2": 26}.get(a.arch, 32)   # phi3: 32
+    a.d = a.d or {"gpt2": 1600, "gemma2": 2304, "phi3": 3072}.get(a.arch, 4096)
     a.heads = a.heads or {"gpt2": 25, "gemma2": 8}.get(a.arch, 32)
-    a.kv_heads = a.kv_heads or (a.heads if a.arch == "olmo2" else 4 if a.arch == "gemma2" else 8)
-    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008, "mixtral": 14336, "gemma2": 9216}[a.arch]
-    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352, "mixtral": 32000, "gemma2": 256000}[a.arch]
-    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2", "mixtral", "gemma2") or a.session):
+    a.kv_heads = a.kv_heads or (a.heads if a.arch in ("olmo2", "phi3") else 4 if a.arch == "gemma2" else 8)
+    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008, "mixtral": 14336, "gemma2": 9216, "phi3": 8192}[a.arch]
+    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352, "mixtral": 32000, "gemma2": 256000, "phi3": 32064}[a.arch]
+    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2", "mixtral", "gemma2", "phi3") or a.session):
         ap.error("--dtype bfloat16 needs --arch llama or qwen3 and has no --session")
     if a.arch == "mixtral":
         if a.session:
@@ -151,6 +152,10 @@ def main():
         if a.session:
             ap.error("--arch gemma2 has no --session")
         return main_gemma2(a)
+    if a.arch == "phi3":
+        if a.session:
+            ap.error("--arch phi3 has no --session")
+        return main_phi3(a)
     if a.arch == "olmo2":
         if a.session:
             ap.error("--arch olmo2 has no --session")
@@ -404,6 +409,61 @@ def main_gemma2(a):
                       "nodes": float(np.mean(nodes)), "llama_flat_ms": stat(("llama", False)),
                       "gemma2_flat_ms": stat(("gemma2", False)), "llama_tree_ms": stat(("llama", True)),
                       "gemma2_tree_ms": stat(("gemma2", True)),
+                      "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
+                      "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
+                      "flat_tree_bit_identical": bool(same)}))
+
+
+def main_phi3(a):
+    """--arch phi3: a Phi3Scorer at the Phi-3-mini shape (heads of 96, the fused qkv_proj / gate_up_proj) on random fp16 weights
+    beside a LlamaScorer of equal FLOPs per row (the same weights read as d / 128 heads of 128, rotated in the QKV GEMM's
+    epilogue), under the protocol of --arch gemma2."""
+    import torch
+    import llm_rescore as R
+    torch.manual_seed(0)
+    d, H, Hkv, ffn, V, L = a.d, a.heads, a.kv_heads, a.ffn, a.vocab, a.layers
+    hd, lhd, dev = d // H, 128, "cuda"
+    if hd != 96 or d % lhd or (Hkv * hd) % lhd:
+        raise SystemExit("--arch phi3 compares heads of 96 with heads of 128 over the same widths (d 3072, 32 / 32 heads)")
+    lH, lHkv = d // lhd, Hkv * hd // lhd
+    rng = np.random.default_rng(0)
+    rn = lambda *s, std: (torch.randn(*s, device=dev) * std).half()
+    nw = lambda n: (1 + 0.2 * torch.randn(n, device=dev)).half()
+    st = {"model.embed_tokens.weight": rn(V, d, std=2.0 / d ** 0.5), "lm_head.weight": rn(V, d, std=2.0 / d ** 0.5),
+          "model.norm.weight": nw(d)}
+    for l in range(L):
+        p = f"model.layers.{l}."
+        for n, (o, i) in {"self_attn.qkv_proj": ((H + 2 * Hkv) * hd, d), "self_attn.o_proj": (d, d), "mlp.gate_up_proj": (2 * ffn, d),
+                          "mlp.down_proj": (d, ffn)}.items():
+            st[p + n + ".weight"] = rn(o, i, std=1.0 / i ** 0.5)
+        st[p + "input_layernorm.weight"], st[p + "post_attention_layernorm.weight"] = nw(d), nw(d)
+    base = dict(hidden_size=d, intermediate_size=ffn, vocab_size=V, num_hidden_layers=L, max_position_embeddings=4096,
+                rms_norm_eps=1e-5, rope_theta=10000.0, tie_word_embeddings=False, hidden_act="silu")
+    cfg = dict(base, model_type="phi3", num_attention_heads=H, num_key_value_heads=Hkv, sliding_window=2047)
+    dims = R.phi3_dims(cfg)
+    scs = {"phi3": R.Phi3Scorer(dims, R.phi3_device_layout(st, dims, R.phi3_rope(cfg)), dev)}
+    lst = {}
+    for k, v in st.items():      # the fused tensors split at the same rows
+        if "qkv_proj" in k:
+            for n, t in zip(("q_proj", "k_proj", "v_proj"), v.split((H * hd, Hkv * hd, Hkv * hd))):
+                lst[k.replace("qkv_proj", n)] = t
+        elif "gate_up_proj" in k:
+            lst[k.replace("gate_up_proj", "gate_proj")], lst[k.replace("gate_up_proj", "up_proj")] = v[:ffn], v[ffn:]
+        else:
+            lst[k] = v
+    lcfg = dict(base, model_type="llama", num_attention_heads=lH, num_key_value_heads=lHkv)
+    ldims = R.llama_dims(lcfg, dims["max_pos"])
+    scs["llama"] = R.LlamaScorer(ldims, R.llama_device_layout(lst, ldims, R.rope_inv_freq(lcfg)), dev)
+    del st, lst
+    torch.cuda.empty_cache()
+    lists, ntok, nodes, same, per, stat = alternate(a, rng, V, scs, ("llama", "phi3"))
+    ratio = lambda t: [round(o / l, 4) for o, l in zip(per["phi3", t], per["llama", t])]
+    print(json.dumps({"bench": "llm_rescore_phi3", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "head_dim": hd, "ffn": ffn,
+                      "vocab": V, "llama_heads": lH, "llama_kv_heads": lHkv, "cands": a.cands, "list": a.list,
+                      "context": a.context, "lists": len(lists), "reps": max(1, a.reps), "tokens": float(np.mean(ntok)),
+                      "nodes": float(np.mean(nodes)), "llama_flat_ms": stat(("llama", False)),
+                      "phi3_flat_ms": stat(("phi3", False)), "llama_tree_ms": stat(("llama", True)),
+                      "phi3_tree_ms": stat(("phi3", True)),
                       "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
                       "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
                       "flat_tree_bit_identical": bool(same)}))
