@@ -1087,6 +1087,85 @@ int b2t_clm_phi3_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_phi
                                  const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                  long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- gpt-oss (csrc/causal_lm_gptoss.hip): attention sinks, a sliding window in the kernel, biased routed experts ------------
+ * HF GptOssForCausalLM (model_type "gpt_oss": gpt-oss-20b, gpt-oss-120b), eager attention, eager experts.  With x the fp32
+ * residual, hd = head_dim = 64 (Hq hd != d_model) and E the call's element type (fp16 or bf16), per layer:
+ *   h  = E(RMSNorm(x; norm1_w));  q | k | v = h Wqkv^T + qkv_b
+ *   q and k rotated per head over the pairs (c, c + 32) by the angle of the row's position, cos / sin from the table, which
+ *     already holds YaRN's attention factor; q scaled by hd^-0.5 = 0.125; q, k, v rounded to E once
+ *   attention of query i at head h over the keys j <= i, with a sink and a window:
+ *     sink    sinks[h] is one more logit in the softmax's denominator and in nothing else: the online-softmax state of a query
+ *             starts at (m, l, o) = (sinks[h], 1, 0) where the other families start at (-inf, 0, 0) -- HF's softmax over
+ *             [scores, sink] with the sink's probability dropped.  The sink is compared with scores of the already-scaled q;
+ *     window  with window = W > 0 key j is visible iff i - W < j <= i (HF: q_idx - kv_idx < sliding_window); 0 = full causal.
+ *             The key loop starts at the first 32-key block that holds a visible key of the query block's lowest query (blocks
+ *             and query blocks are aligned to the sequence's start, on a tree path to depth 0) and the invisible keys of the
+ *             blocks that remain are masked to -inf.  m is finite from the start, so a block without a visible key leaves a
+ *             query's state as it was;
+ *   x += E(attn) Wo^T + o_b                                                (fp32, +=)
+ *   h2 = E(RMSNorm(x; norm2_w)), the operand of the router and of the experts alike
+ *   router   l[e] = router_b[e] + sum_c h2[c] router_w[e][c], e < n_experts <= 128: the 16-bit operands widened, summed in fp32
+ *            in an order that depends on the row alone; never rounded to E;
+ *   choice   top_k <= 8 experts by repeated argmax, the larger logit first, the lower index among equals.  The ids are top_k
+ *            distinct values in [0, n_experts) whatever the logits hold (NaN, Inf): a NaN shows in the score, never in an address;
+ *   weights  w[j] = exp(l[e_j] - l[e_0]) / sum_{i < top_k} exp(l[e_i] - l[e_0]) in fp32, the sum in order of choice -- HF's top-k on
+ *            the logits followed by a softmax over the k values; never rounded to E;
+ *   experts  on the two fp32 accumulators of a column of h2 Wgu_e^T: g = min(acc_g + b_g, limit), u = clamp(acc_u + b_u, -limit,
+ *            limit), hs = E((u + 1) * g * (1 / (1 + exp(-1.702 g)))), one rounding; a saturated g gives g or -0, never NaN;
+ *            y_e = hs Wd_e^T + b_d, the fp32 accumulator plus the bias, unrounded;
+ *   combine  x += ((w[0] y_{e_0} + w[1] y_{e_1}) + ...) in fp32, in order of choice, one thread per element, no atomics.
+ * After the last layer: logits = E(RMSNorm(x; final_norm_w)) lm_head^T (untied) and the log-softmax, as in the Llama section.
+ * Every output element is computed in an order that depends only on its own row: the tree call is bit-identical to the flat
+ * one, a sequence scores the same alone or in any batch, and B2T_CLM_GEMM_256 does not change a bit.
+ * The model is the b2t_clm_llama_t above -- qkv_b set; hd is b2t_clm_gptoss_t's head_dim; qkv_w [round_up((Hq + 2 Hkv) hd, 256)][d]
+ * in checkpoint order (at hd 64 the rotary pair is 32 rows apart as stored); o_w [round_up(d, 256)][Hq hd]; rope_cos / rope_sin
+ * [max_pos][32]; gate_up_w [n_experts][gate_up_stride][d], each expert's gate and up rows interleaved in blocks of 32 and
+ * zero-padded; down_w [n_experts][down_stride][F], as in the Mixtral section -- plus a b2t_clm_gptoss_t, whose layers_host is a
+ * HOST array of n_layers records with DEVICE pointers inside.  Biases are in the call's element type, gate_up_b interleaved as
+ * the rows of gate_up_w; the sinks are fp32 and must be finite (the loader refuses others).
+ * Limits: head_dim 64; Hq % Hkv == 0; d_model and ffn_dim multiples of 64; 1 <= n_experts <= 128; 1 <= top_k <= min(8,
+ * n_experts); gate_up_stride >= round_up(2 F, 256), down_stride >= round_up(d, 256); swiglu_limit > 0; window >= 0.  Anything else,
+ * a null pointer of either descriptor included, is refused before any launch.
+ * The experts run as in the Mixtral section: S = round_up(rows * top_k, 256) + 256 * n_experts sorted rows, the routing is never
+ * read back.  The workspace is the Llama layout with the QKV width (Hq + 2 Hkv) hd and no dense hidden rows, plus the
+ * attention output [round_up(rows, 256)][Hq hd] and the Mixtral region.  The six functions have their Mixtral twins' argument
+ * lists with the b2t_clm_gptoss_t in the MoE descriptor's place, their output layout and their refusals.  There is no cached
+ * call: the cached and trunk attention kernels have neither sink nor window. */
+typedef struct {
+  const float* sinks;      /* fp32 [n_heads] */
+  const void* o_b;         /* [d] */
+  const void* router_w;    /* [n_experts][d] */
+  const void* router_b;    /* [n_experts] */
+  const void* gate_up_b;   /* [n_experts][gate_up_stride], interleaved and zero-padded like the rows of gate_up_w */
+  const void* down_b;      /* [n_experts][down_stride], zero-padded */
+  int32_t window;          /* 0 = full causal attention, W > 0 = sliding window of W keys */
+} b2t_clm_gptoss_layer_t;
+
+typedef struct {
+  int32_t head_dim;                        /* 64 */
+  float swiglu_limit;                      /* the clamp of the experts' activation (7 in the published checkpoints) */
+  int32_t n_experts, top_k;
+  long long gate_up_stride, down_stride;   /* rows from one expert to the next in gate_up_w / gate_up_b and in down_w / down_b */
+  int32_t* route_out;                      /* optional DEVICE [n_layers][rows][top_k], as b2t_clm_moe_t's; NULL in production */
+  const b2t_clm_gptoss_layer_t* layers_host;  /* HOST array of n_layers entries (device pointers inside) */
+} b2t_clm_gptoss_t;
+
+size_t b2t_clm_gptoss_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_tokens, int n_seq);
+size_t b2t_clm_gptoss_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_nodes, long long n_tokens,
+                                    int n_seq);
+int b2t_clm_gptoss_score_f16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                             const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                             size_t ws_bytes, void* stream);
+int b2t_clm_gptoss_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                                  const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                  long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_gptoss_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                              size_t ws_bytes, void* stream);
+int b2t_clm_gptoss_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                                   const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                   long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
  * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
  * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,

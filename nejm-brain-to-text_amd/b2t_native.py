@@ -148,6 +148,18 @@ class ClmPhi3(C.Structure):
     _fields_ = [("head_dim", C.c_int32), ("rotary_dims", C.c_int32)]
 
 
+class ClmGptOssLayer(C.Structure):
+    """Mirror of b2t_clm_gptoss_layer_t (include/b2t.h): what one gpt-oss layer adds to its b2t_clm_llama_layer_t."""
+    _fields_ = [(n, VP) for n in ("sinks", "o_b", "router_w", "router_b", "gate_up_b", "down_b")] + [("window", C.c_int32)]
+
+
+class ClmGptOss(C.Structure):
+    """Mirror of b2t_clm_gptoss_t (include/b2t.h): what a gpt-oss model adds to its b2t_clm_llama_t."""
+    _fields_ = [("head_dim", C.c_int32), ("swiglu_limit", C.c_float), ("n_experts", C.c_int32), ("top_k", C.c_int32),
+                ("gate_up_stride", C.c_longlong), ("down_stride", C.c_longlong), ("route_out", VP),
+                ("layers_host", C.POINTER(ClmGptOssLayer))]
+
+
 class ClmQkNorm(C.Structure):
     """Mirror of b2t_clm_qknorm_t (include/b2t.h): device weights [hd] of one Qwen3 layer's q and k RMSNorm."""
     _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
@@ -313,6 +325,10 @@ for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes"
     _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
     _SIGNATURES["b2t_clm_gemma2_" + _t] = (_res, [_args[0], C.POINTER(ClmGemma2)] + _args[1:])
     _SIGNATURES["b2t_clm_phi3_" + _t] = (_res, [_args[0], C.POINTER(ClmPhi3)] + _args[1:])   # Phi-3: the same, on its descriptor
+# gpt-oss: the Llama twin's list with the gpt-oss descriptor after the model; no cached call
+for _t in ("ws_bytes", "tree_ws_bytes", "score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16"):
+    _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
+    _SIGNATURES["b2t_clm_gptoss_" + _t] = (_res, [_args[0], C.POINTER(ClmGptOss)] + _args[1:])
 # GPT-NeoX: the OPT twin's list on its own model struct (same cache)
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
            "score_tree_cached_f16"):

@@ -1,0 +1,154 @@
+// causal_lm_gptoss.hip — the scoring forward of causal_lm_llama.hip for gpt-oss (HF GptOssForCausalLM; gpt-oss-20b, 120b), in fp16
+// and bf16: b2t_clm_gptoss_score_f16 / _bf16 over packed sequences and b2t_clm_gptoss_score_tree_f16 / _bf16 over the shared-prefix
+// token tree.  gpt-oss has the Llama family's pre-norm RMSNorm layer, grouped-query attention, rotary positions over the whole
+// head, embedding and untied head, and differs from its forward in this:
+//   - the head dim is a number of its own (64 heads of 64 dims against d = 2880), as in Gemma-2: the QKV GEMM has N = (Hq + 2 Hkv)
+//     hd, the o_proj K = Hq hd, and the attention output is Hq hd wide;
+//   - q, k, v and o_proj have biases; the rotary table carries YaRN's attention factor (the loader multiplies it in, as for Phi-3);
+//   - every head has a learned sink, one more logit in the softmax's denominator;
+//   - every other layer attends over a sliding window of 128 keys, which binds (a context plus a candidate is longer), so the
+//     window lives in the attention kernel and does not lower max_pos;
+//   - the MLP is n_experts routed experts with a router bias, per-expert gate / up / down biases and the clamped activation
+//     (up + 1) * gate * sigmoid(1.702 gate).
+//
+// The contract (include/b2t.h; what the fp64 restatement ref_logp_gptoss of tests/test_clm_gptoss_host.py rounds), E = fp16 or
+// bf16: causal_lm_llama.hip's, with
+//   - attention: the state of a query at head h starts at (m, l, o) = (sinks[h], 1, 0), the sink in fp32 and compared with the
+//     scores of the already-scaled q; with a window W > 0 key j is visible to query i iff i - W < j <= i; the key loop starts at
+//     the first 32-key block that holds a visible key of the query block's lowest query and the invisible keys of the blocks
+//     that remain are -inf; P is rounded to E per 32-key block as everywhere;
+//   - x += E(attn) Wo^T + o_b in fp32 (EP_RESID with a bias, OPT's epilogue);
+//   - router: l[e] = b[e] + sum_c h2[c] Wr[e][c], 16-bit operands widened, fp32 sums in an order fixed by the row (below), never
+//     rounded; choice by repeated argmax, larger first, lower index among equals, ids always distinct and in range; weights
+//     w[j] = exp(l[e_j] - l[e_0]) / sum_i exp(l[e_i] - l[e_0]) in fp32;
+//   - experts: g = min(acc_g + b_g, limit), u = clamp(acc_u + b_u, -limit, limit), hs = E((u + 1) g / (1 + exp(-1.702 g))) with one
+//     rounding (EP_OSS_GLU); y_e = hs Wd_e^T + b_d unrounded (EP_F32_BIAS); combine in order of choice, no atomics.
+//   Every output element is computed in an order that depends only on its own row: tree and flat calls are byte-identical, a
+//   sequence scores the same alone or in a batch, and B2T_CLM_GEMM_256 does not change a bit.
+// Limits: head dim 64, 1 <= n_experts <= 128, 1 <= top_k <= min(8, n_experts), d_model % 64 == 0, ffn_dim % 64 == 0.
+//
+// Kernels per layer: RMSNorm -> QKV GEMM (EP_ROPE with the bias, the Llama family's) -> clm_attn_sink_kernel /
+// clm_attn_tree_sink_kernel (clm_attn.h with SINK and WIN set) -> o_proj GEMM (EP_RESID with the bias) -> RMSNorm ->
+// clm_gptoss_route_kernel (one workgroup per row; a wave per expert in turn, one barrier) -> clm_moe_plan_kernel ->
+// clm_moe_gather_kernel -> the grouped gate / up GEMM (EP_OSS_GLU) -> the grouped down GEMM (EP_F32_BIAS) ->
+// clm_moe_combine_kernel.  Plan, gather, combine, the region and S = round_up(rows * top_k, 256) + 256 * n_experts are clm_moe.h's.
+//
+// This unit instantiates the two grouped GEMMs (on both tiles), the router kernel, the plan, gather and combine kernels and the
+// two attention kernels, in both element types where they depend on it, and nothing else: every other kernel is reached through
+// LlamaShared<E>, the entry-point bodies are clm_llama.h's under GptOssFamily.  There is no cached call: the cached and trunk
+// attention kernels have neither sink nor window.
+#include "clm_attn.h"
+#include "clm_gptoss.h"
+
+namespace b2t {
+namespace {
+
+template <class El>
+struct GptOssPolicy : LlamaShared<El>, MoeOps<El>, GptOssOps<El> {
+  using E = El;
+  static int gemm_experts_glu(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_OSS_GLU, El, true>); }
+  static int gemm_experts_f32b(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_F32_BIAS, El, true>); }
+  static int attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, const float* sinks, int window,
+                  hipStream_t s) {
+    hipLaunchKernelGGL((clm_attn_sink_kernel<OSS_HEAD_DIM, E>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv, sinks,
+                       window);
+    B2T_CHECK_LAUNCH("clm_attn_sink_kernel");
+    return 0;
+  }
+  static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
+                       int Hkv, const float* sinks, int window, hipStream_t s) {
+    hipLaunchKernelGGL((clm_attn_tree_sink_kernel<OSS_HEAD_DIM, E>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, tok_node,
+                       own_start, Hq, Hkv, sinks, window);
+    B2T_CHECK_LAUNCH("clm_attn_tree_sink_kernel");
+    return 0;
+  }
+};
+using GptOssF16 = GptOssPolicy<_Float16>;
+using GptOssBf16 = GptOssPolicy<__bf16>;
+
+// dimensions a descriptor pair must have for the sizes of gptoss_layout to mean anything (the full check is
+// clm_gptoss_check_model)
+bool gptoss_dims_ok(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) {
+  return m && g && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
+         g->head_dim == OSS_HEAD_DIM && g->n_experts >= 1 && g->n_experts <= OSS_MAX_EXPERTS && g->top_k >= 1 &&
+         g->top_k <= MOE_MAX_TOPK && g->top_k <= g->n_experts;
+}
+
+}  // namespace
+
+int clm_gptoss_check_model(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) {
+  B2T_REQUIRE(m, "b2t_clm_gptoss: null model");
+  B2T_REQUIRE(g, "b2t_clm_gptoss: null gptoss descriptor");
+  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
+              m->max_pos > 0,
+              "b2t_clm_gptoss: bad dimensions (layers %d, d %d, heads %d, kv heads %d, ffn %d, vocab %d, max_pos %d)", m->n_layers,
+              m->d_model, m->n_heads, m->n_kv_heads, m->ffn_dim, m->vocab, m->max_pos);
+  B2T_REQUIRE(g->head_dim == OSS_HEAD_DIM, "b2t_clm_gptoss: unsupported head dim %d (%d)", g->head_dim, OSS_HEAD_DIM);
+  B2T_REQUIRE(m->n_heads % m->n_kv_heads == 0, "b2t_clm_gptoss: n_heads %d is not a multiple of n_kv_heads %d", m->n_heads,
+              m->n_kv_heads);
+  B2T_REQUIRE(m->d_model % 64 == 0 && m->ffn_dim % 64 == 0, "b2t_clm_gptoss: d_model %d and ffn_dim %d must be multiples of 64",
+              m->d_model, m->ffn_dim);
+  B2T_REQUIRE(m->rms_eps >= 0.f && m->rms_eps < 1.f, "b2t_clm_gptoss: rms_eps %g outside [0, 1)", (double)m->rms_eps);
+  B2T_REQUIRE(g->n_experts >= 1 && g->n_experts <= OSS_MAX_EXPERTS, "b2t_clm_gptoss: n_experts %d outside [1, %d]", g->n_experts,
+              OSS_MAX_EXPERTS);
+  B2T_REQUIRE(g->top_k >= 1 && g->top_k <= MOE_MAX_TOPK && g->top_k <= g->n_experts,
+              "b2t_clm_gptoss: top_k %d outside [1, min(%d, n_experts %d)]", g->top_k, MOE_MAX_TOPK, g->n_experts);
+  B2T_REQUIRE(g->gate_up_stride >= rup(2LL * m->ffn_dim, ROWPAD) && g->down_stride >= rup(m->d_model, ROWPAD),
+              "b2t_clm_gptoss: expert strides %lld / %lld rows below round_up(2 ffn_dim, 256) = %lld / round_up(d_model, 256) = %lld",
+              g->gate_up_stride, g->down_stride, rup(2LL * m->ffn_dim, ROWPAD), rup(m->d_model, ROWPAD));
+  B2T_REQUIRE(g->swiglu_limit > 0.f, "b2t_clm_gptoss: swiglu_limit %g must be > 0", (double)g->swiglu_limit);
+  B2T_REQUIRE(m->embed_tokens && m->lm_head && m->final_norm_w && m->rope_cos && m->rope_sin &&
+              (m->n_layers == 0 || (m->layers_host && g->layers_host)), "b2t_clm_gptoss: null weight pointer");
+  for (int l = 0; l < m->n_layers; ++l) {
+    const b2t_clm_llama_layer_t& w = m->layers_host[l];
+    const b2t_clm_gptoss_layer_t& w2 = g->layers_host[l];
+    B2T_REQUIRE(w.norm1_w && w.norm2_w && w.qkv_w && w.o_w && w.gate_up_w && w.down_w && w2.sinks && w2.o_b && w2.router_w &&
+                w2.router_b && w2.gate_up_b && w2.down_b, "b2t_clm_gptoss: null weight pointer in layer %d", l);
+    B2T_REQUIRE(w.qkv_b, "b2t_clm_gptoss: layer %d has no q / k / v biases (qkv_b), which gpt-oss has", l);
+    B2T_REQUIRE(w2.window >= 0, "b2t_clm_gptoss: layer %d has window %d < 0 (0: full attention)", l, w2.window);
+  }
+  return 0;
+}
+
+}  // namespace b2t
+
+using namespace b2t;
+
+extern "C" size_t b2t_clm_gptoss_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_tokens, int n_seq) {
+  if (!gptoss_dims_ok(model, oss) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
+  return gptoss_layout(model, oss, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+}
+
+extern "C" size_t b2t_clm_gptoss_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_nodes,
+                                               long long n_tokens, int n_seq) {
+  if (!gptoss_dims_ok(model, oss) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
+  return gptoss_layout(model, oss, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+}
+
+extern "C" int b2t_clm_gptoss_score_f16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                                        const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                                        size_t ws_bytes, void* stream) {
+  return llama_score<GptOssF16, GptOssFamily>("b2t_clm_gptoss_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                              tok_logp_out, ws, ws_bytes, stream, oss);
+}
+
+extern "C" int b2t_clm_gptoss_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                                             const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                             long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
+  return llama_score_tree<GptOssF16, GptOssFamily>("b2t_clm_gptoss_score_tree_f16", model, ids_host, seq_off_host, n_seq,
+                                                   scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, oss);
+}
+
+extern "C" int b2t_clm_gptoss_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                                         const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
+                                         size_t ws_bytes, void* stream) {
+  return llama_score<GptOssBf16, GptOssFamily>("b2t_clm_gptoss_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                               tok_logp_out, ws, ws_bytes, stream, oss);
+}
+
+extern "C" int b2t_clm_gptoss_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
+                                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                                              long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
+  return llama_score_tree<GptOssBf16, GptOssFamily>("b2t_clm_gptoss_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
+                                                    scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, oss);
+}

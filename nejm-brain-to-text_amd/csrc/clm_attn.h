@@ -1,7 +1,8 @@
 // clm_attn.h — the attention arithmetic of the causal-LM forward, written once (device code, internal linkage).  Every
 // attention kernel -- clm_attn_kernel and clm_attn_tree_kernel (launched by causal_lm.hip, causal_lm_tree.hip and, in bf16,
 // causal_lm_llama_bf16.hip), clm_attn_tree_cached_kernel and clm_attn_trunk_kernel (launched by causal_lm_cache.hip), all at the
-// end of this file, their soft-capped `_cap_` forms (causal_lm_gemma2.hip) and their head-dim-96 instances (causal_lm_phi3.hip) -- walks its own rows and calls attn_block per 32-key block, so a query meets the same operands in
+// end of this file, their soft-capped `_cap_` forms (causal_lm_gemma2.hip), their head-dim-96 instances (causal_lm_phi3.hip) and the
+// flat and tree `_sink_` forms with a sink logit and a sliding window (causal_lm_gptoss.hip) -- walks its own rows and calls attn_block per 32-key block, so a query meets the same operands in
 // the same order on every path: that is what keeps the paths bit-identical.  The element type E (ClmElem, clm_internal.h)
 // is deduced from the pointers: _Float16 everywhere but in the bf16 unit.
 //
@@ -15,6 +16,7 @@
 // running max; cap == 0 at run time means off.  CAP is false in every kernel without `_cap_` in its name: the body functions
 // below are inlined into them with the cap's code compiled out.
 #pragma once
+#include <limits.h>
 #include <math.h>
 
 #include "clm_internal.h"
@@ -97,9 +99,10 @@ __device__ __forceinline__ void attn_zero(float& m, float& l, f32x16* o) {
 __device__ __forceinline__ float soft_cap(float v, float cap, float inv_cap) {
   return cap * (1.0f - 2.0f / (expf(2.0f * (v * inv_cap)) + 1.0f));
 }
-template <int D, bool MASK, bool CAP = false, class E, class VSrc>
+// WIN: keys at or below q - W are masked as well (the sliding window; W >= 1).
+template <int D, bool MASK, bool CAP = false, bool WIN = false, class E, class VSrc>
 __device__ __forceinline__ void attn_block(const E* kp, const typename ClmElem<E>::v8* qf, const VSrc& v, int k0, int q, int L,
-                                           int li, int hh, float& m, float& l, f32x16* o, float cap = 0.f) {
+                                           int li, int hh, float& m, float& l, f32x16* o, float cap = 0.f, int W = 0) {
   using A = AttnDims<D>;
   using vec8 = typename ClmElem<E>::v8;
   f32x16 sacc;
@@ -121,6 +124,9 @@ __device__ __forceinline__ void attn_block(const E* kp, const typename ClmElem<E
     if (MASK) {
       const int key = k0 + (e & 3) + 8 * (e >> 2) + 4 * hh;
       if (key > q || key >= L) sacc[e] = -INFINITY;
+      if (WIN) {
+        if (key <= q - W) sacc[e] = -INFINITY;
+      }
     }
     mx = fmaxf(mx, sacc[e]);
   }
@@ -181,8 +187,15 @@ __device__ __forceinline__ void attn_store(E* op, const f32x16* o, float l, int 
 //
 // clm_attn_flat is the body; SLAB stages V through the wave's LDS slab as the tree kernel does (the same values reach the same
 // MFMAs, so the bits are VGather's) -- the capped kernel at head dim 256 needs the registers the gather holds.
-template <int D, class E, bool CAP, bool SLAB>
-__device__ __forceinline__ void clm_attn_flat(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv, float cap) {
+//
+// SINK / WIN (gpt-oss, causal_lm_gptoss.hip; both false in every other kernel, their code compiled out).  SINK: head h has a
+// learned logit sinks[h] in the softmax's denominator and nowhere else, so a query's state starts at (m, l, o) = (sinks[h], 1, 0)
+// in place of (-inf, 0, 0).  WIN: key j is visible to query i iff i - W < j <= i (W <= 0 at run time: no window); the key loop
+// starts at the first block that holds a visible key of the block's lowest query, 32 qb, and attn_block masks the keys at or
+// below i - W in the blocks that remain.  Which blocks a query meets depends on its position alone, on every path.
+template <int D, class E, bool CAP, bool SLAB, bool SINK = false, bool WIN = false>
+__device__ __forceinline__ void clm_attn_flat(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv, float cap,
+                                              const float* sinks = nullptr, int W = 0) {
   const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
   const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
@@ -191,6 +204,7 @@ __device__ __forceinline__ void clm_attn_flat(const E* qkv, E* out, const int* s
   const E* Kb = qkv + (long long)t0 * RS + (Hq + hk) * D;
   const E* Vb = Kb + Hkv * D;
   const int nqb = (L + 31) / 32;
+  if constexpr (WIN) { if (W <= 0) W = INT_MAX; }   // no window: q - W < 0 for every query
   for (int qb = wave; qb < nqb; qb += 4) {
     const int q = qb * 32 + li;
     typename ClmElem<E>::v8 qf[AttnDims<D>::KS];
@@ -198,15 +212,18 @@ __device__ __forceinline__ void clm_attn_flat(const E* qkv, E* out, const int* s
     float m, l;
     f32x16 o[AttnDims<D>::NF];
     attn_zero<D>(m, l, o);
-    for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
+    if constexpr (SINK) { m = sinks[h]; l = 1.f; }
+    int kb = 0;
+    if constexpr (WIN) kb = max(qb * 32 - W + 1, 0) / 32;   // the block of the lowest query's first visible key
+    for (; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
       const int k0 = kb * 32;
       const E* kp = Kb + (long long)min(k0 + li, L - 1) * RS + 8 * hh;
       if constexpr (SLAB) {
         __shared__ __attribute__((aligned(16))) E vslab[4][32 * AttnDims<D>::VP];
         stage_v<D>(vslab[wave], lane, L - k0, [&](int key) { return Vb + (long long)(k0 + key) * RS; });
-        attn_block<D, true, CAP>(kp, qf, VSlab<D, E>{vslab[wave]}, k0, q, L, li, hh, m, l, o, cap);
+        attn_block<D, true, CAP, WIN>(kp, qf, VSlab<D, E>{vslab[wave]}, k0, q, L, li, hh, m, l, o, cap, W);
       } else {
-        attn_block<D, true, CAP>(kp, qf, VGather<E>{Vb, RS, k0, L}, k0, q, L, li, hh, m, l, o, cap);
+        attn_block<D, true, CAP, WIN>(kp, qf, VGather<E>{Vb, RS, k0, L}, k0, q, L, li, hh, m, l, o, cap, W);
       }
     }
     if (q < L) attn_store<D>(out + ((long long)(t0 + q) * Hq + h) * D, o, l, hh);
@@ -220,6 +237,12 @@ template <int D, class E, bool SLAB>
 __global__ __launch_bounds__(256) void clm_attn_cap_kernel(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv, float cap) {
   clm_attn_flat<D, E, true, SLAB>(qkv, out, seq_off, Hq, Hkv, cap);
 }
+// gpt-oss: sinks fp32 [Hq]; W the layer's window, 0 = full causal attention
+template <int D, class E>
+__global__ __launch_bounds__(256) void clm_attn_sink_kernel(const E* qkv, E* out, const int* seq_off, int Hq, int Hkv,
+                                                            const float* sinks, int W) {
+  clm_attn_flat<D, E, false, false, true, true>(qkv, out, seq_off, Hq, Hkv, 0.f, sinks, W);
+}
 
 // Causal attention over tree paths, one workgroup per (sequence, query head), 4 waves; a wave takes 32 query positions at a
 // time, starting with the 32-aligned block that holds the sequence's first owned position.  Position i of the sequence is row
@@ -229,9 +252,11 @@ __global__ __launch_bounds__(256) void clm_attn_cap_kernel(const E* qkv, E* out,
 // The gather: a lane holds the row of key k0 + (lane & 31) and reads K from it as 16-byte pieces; V's 32 x D block is staged
 // as whole 16-byte row pieces into the wave's own LDS slab and read back transposed, rows of keys beyond the path zeroed.
 // The slab is private to the wave, so the key loop needs no workgroup barrier.
-template <int D, class E, bool CAP>
+// SINK / WIN as in clm_attn_flat: a position is the depth along the path, so the window's rule is the flat kernel's on path
+// positions, and a query at position i meets the key blocks the flat kernel's query i meets.
+template <int D, class E, bool CAP, bool SINK = false, bool WIN = false>
 __device__ __forceinline__ void clm_attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start,
-                                              int Hq, int Hkv, float cap) {
+                                              int Hq, int Hkv, float cap, const float* sinks = nullptr, int W = 0) {
   __shared__ __attribute__((aligned(16))) E vslab[4][32 * AttnDims<D>::VP];
   const int sq = blockIdx.x, h = blockIdx.y, hk = h / (Hq / Hkv);
   const int t0 = seq_off[sq], L = seq_off[sq + 1] - t0, own = own_start[sq];
@@ -244,6 +269,7 @@ __device__ __forceinline__ void clm_attn_tree(const E* qkv, E* out, const int* s
   const E* Vb = Kb + Hkv * D;
   E* vs = vslab[wave];
   const int nqb = (L + 31) / 32;
+  if constexpr (WIN) { if (W <= 0) W = INT_MAX; }   // no window: q - W < 0 for every query
   for (int qb = own / 32 + wave; qb < nqb; qb += 4) {
     const int q = qb * 32 + li;
     const int qrow = path[min(q, L - 1)];
@@ -252,11 +278,14 @@ __device__ __forceinline__ void clm_attn_tree(const E* qkv, E* out, const int* s
     float m, l;
     f32x16 o[AttnDims<D>::NF];
     attn_zero<D>(m, l, o);
-    for (int kb = 0; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
+    if constexpr (SINK) { m = sinks[h]; l = 1.f; }
+    int kb = 0;
+    if constexpr (WIN) kb = max(qb * 32 - W + 1, 0) / 32;   // the block of the lowest query's first visible key
+    for (; kb <= qb; ++kb) {   // key blocks up to the diagonal; key k0 <= q0 < L is valid for every query row
       const int k0 = kb * 32;
       const int krow = path[min(k0 + li, L - 1)];
       stage_v<D>(vs, lane, L - k0, [&](int key) { return Vb + (long long)__shfl(krow, key) * RS; });
-      attn_block<D, true, CAP>(Kb + (long long)krow * RS + 8 * hh, qf, VSlab<D, E>{vs}, k0, q, L, li, hh, m, l, o, cap);
+      attn_block<D, true, CAP, WIN>(Kb + (long long)krow * RS + 8 * hh, qf, VSlab<D, E>{vs}, k0, q, L, li, hh, m, l, o, cap, W);
     }
     if (q >= own && q < L) attn_store<D>(out + ((long long)qrow * Hq + h) * D, o, l, hh);
   }
@@ -270,6 +299,11 @@ template <int D, class E>
 __global__ __launch_bounds__(256) void clm_attn_tree_cap_kernel(const E* qkv, E* out, const int* seq_off, const int* tok_node,
                                                                 const int* own_start, int Hq, int Hkv, float cap) {
   clm_attn_tree<D, E, true>(qkv, out, seq_off, tok_node, own_start, Hq, Hkv, cap);
+}
+template <int D, class E>
+__global__ __launch_bounds__(256) void clm_attn_tree_sink_kernel(const E* qkv, E* out, const int* seq_off, const int* tok_node,
+                                                                 const int* own_start, int Hq, int Hkv, const float* sinks, int W) {
+  clm_attn_tree<D, E, false, true, true>(qkv, out, seq_off, tok_node, own_start, Hq, Hkv, 0.f, sinks, W);
 }
 
 // ---- the cached tree kernel and the trunk kernel (the context cache: causal_lm_cache.hip has the rule and the launches) ----

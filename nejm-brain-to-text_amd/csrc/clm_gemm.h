@@ -10,7 +10,8 @@
 // (EP_F32 and EP_QKV_F32: fp32 stores for the norms over a whole output row) in both, causal_lm_mixtral.hip the grouped form of
 // the tile (clm_gemm_grouped_kernel: one B matrix per expert) with EP_SWIGLU and EP_F32 in both, causal_lm_gemma2.hip the two
 // Gemma-2 adds (EP_GEGLU: gelu_new where SwiGLU has silu; EP_HEAD_CAP: the fused head on soft-capped logits) in both,
-// causal_lm_phi3.hip EP_QKV_F32 again in both (Phi-3's rotation reads the fp32 q | k columns in a kernel of its own).  Which
+// causal_lm_phi3.hip EP_QKV_F32 again in both (Phi-3's rotation reads the fp32 q | k columns in a kernel of its own),
+// causal_lm_gptoss.hip the two gpt-oss adds to the grouped tile (EP_OSS_GLU, EP_F32_BIAS: per-expert biases) in both.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -76,8 +77,9 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
   const int K = g.K, nk = K / CK;
   const E* ag = static_cast<const E*>(g.A) + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
   const E* bg = static_cast<const E*>(g.B) + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
+  int ex = 0;
   if (GROUPED) {
-    const int ex = g.blk_expert[m0 / 128];   // one value per workgroup: m0 is a multiple of 128
+    ex = g.blk_expert[m0 / 128];   // one value per workgroup: m0 is a multiple of 128
     if (ex < 0) return;
     bg += (long long)ex * g.b_stride;
   }
@@ -130,6 +132,7 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
   // epilogue: C/D layout of the 32x32 MFMAs: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
   const int colw = n0 + wn * WTN;
   const E* bias = static_cast<const E*>(g.bias);
+  if (GROUPED && (EP == EP_OSS_GLU || EP == EP_F32_BIAS)) bias += (long long)ex * g.bias_stride;   // the expert's bias
   E* out16 = static_cast<E*>(g.out16);
   if (EP == EP_HEAD || EP == EP_HEAD_CAP) {
     if (colw >= g.N) return;   // a 64-column group entirely beyond the vocabulary (wave-uniform)
@@ -224,7 +227,7 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
     }
     return;
   }
-  if (EP == EP_ROPE || EP == EP_ROPE_PART || EP == EP_SWIGLU || EP == EP_GEGLU) {
+  if (EP == EP_ROPE || EP == EP_ROPE_PART || EP == EP_SWIGLU || EP == EP_GEGLU || EP == EP_OSS_GLU) {
     // a lane holds columns colw + li (fragment 0) and colw + 32 + li (fragment 1) of every row it owns: the two halves of a
     // rotary pair (head dims of 128 are stored [0..31, 64..95, 32..63, 96..127], and in general stored 32-block 2j holds dims
     // [32j, 32j + 32) and block 2j + 1 dims [hd / 2 + 32j, hd / 2 + 32j + 32), so their pairs are 32 columns apart as
@@ -233,6 +236,23 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
     static_assert(FN == 2, "rotary pairs and gate / up pairs are the two fragments of a lane");
     if (colw >= g.N) return;
     const int c0 = colw + li, c1 = c0 + 32;
+    if (EP == EP_OSS_GLU) {
+      // gpt-oss: the two columns' biases, gate clamped from above and up on both sides, (up + 1) * gate * sigmoid(1.702 gate).
+      // expf(-1.702 g) = inf (g far below 0) gives a factor 0 and so g * 0 = -0, never inf / inf.
+      const int oc = (colw >> 1) + li;
+      const float bg0 = (float)bias[c0], bu0 = (float)bias[c1], lim = g.glu_limit;
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+          if (row >= g.M) continue;
+          const float gt = fminf(acc[i][0][e] + bg0, lim), up = fminf(fmaxf(acc[i][1][e] + bu0, -lim), lim);
+          out16[(long long)row * g.ldo + oc] = (E)((up + 1.0f) * gt * (1.0f / (1.0f + expf(-1.702f * gt))));
+        }
+      }
+      return;
+    }
     if (EP == EP_SWIGLU || EP == EP_GEGLU) {
       const int oc = (colw >> 1) + li;
 #pragma unroll
@@ -271,6 +291,25 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
         E* o = out16 + (long long)row * g.ldo;
         o[c0] = (E)(x0 * sc);
         o[c1] = (E)(x1 * sc);
+      }
+    }
+    return;
+  }
+  if (EP == EP_F32_BIAS) {
+    // gpt-oss: EP_F32 with the (expert's) bias on the accumulator
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      const int col = colw + j * 32 + li;
+      if (col >= g.N) continue;
+      const float bv = (float)bias[col];
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int row = m0 + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+          if (row >= g.M) continue;
+          g.resid[(long long)row * g.ldo + col] = acc[i][j][e] + bv;
+        }
       }
     }
     return;

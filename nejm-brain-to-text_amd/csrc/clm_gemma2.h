@@ -176,12 +176,12 @@ struct Gemma2Family {
   template <class P>
   static int check(const char*, const b2t_clm_llama_t&, const b2t_clm_gemma2_t*) { return 0; }   // check_model has it all
   template <class P>
-  static int attn(const b2t_clm_llama_t& m, const b2t_clm_gemma2_t* g2, const typename P::E* qkv, typename P::E* out,
+  static int attn(const b2t_clm_llama_t& m, const b2t_clm_gemma2_t* g2, int /*layer*/, const typename P::E* qkv, typename P::E* out,
                   const int* seq_off, int n_seq, hipStream_t s) {
     return P::attn(qkv, out, seq_off, n_seq, m.n_heads, m.n_kv_heads, g2->head_dim, g2->attn_cap, s);
   }
   template <class P>
-  static int attn_tree(const b2t_clm_llama_t& m, const b2t_clm_gemma2_t* g2, const typename P::E* qkv, typename P::E* out,
+  static int attn_tree(const b2t_clm_llama_t& m, const b2t_clm_gemma2_t* g2, int /*layer*/, const typename P::E* qkv, typename P::E* out,
                        const int* seq_off, const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
     return P::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, m.n_heads, m.n_kv_heads, g2->head_dim, g2->attn_cap, s);
   }

@@ -44,8 +44,14 @@ constexpr int CLM_ROWPAD = 256;   // A operands and weights are padded to this m
 // EP_GEGLU (Gemma-2) is EP_SWIGLU with gelu_new in silu's place: out16[r][c0 / 2 + i] = gelu_new(C[r][c0 + i]) * C[r][c0 + 32 + i].
 // EP_HEAD_CAP (Gemma-2) is EP_HEAD on soft-capped logits: v = cap * tanh(C[r][c] / cap) in fp32 (tanh written as gelu_new's) in
 //   front of the group max, the group sum and the target pick; cap > 0.
+// EP_OSS_GLU (gpt-oss) is EP_SWIGLU with the bias of the two columns and the family's clamped activation: g = min(C[r][c0 + i] +
+//   bias[c0 + i], limit), u = clamp(C[r][c0 + 32 + i] + bias[c0 + 32 + i], -limit, limit), out16[r][c0 / 2 + i] =
+//   (u + 1) * g * (1 / (1 + exp(-1.702 g))) in fp32, rounded once; a saturated g gives g or -0, never inf / inf.
+// EP_F32_BIAS (gpt-oss) is EP_F32 with the bias added to the accumulator: resid[r][c] = C[r][c] + bias[c], unrounded.
+//   In the grouped kernel both take the bias of the tile's expert, bias + expert * bias_stride.
 enum { EP_F16 = 0, EP_RELU = 1, EP_RESID = 2, EP_HEAD = 3, EP_ROPE = 4, EP_SWIGLU = 5, EP_QKNORM_ROPE = 6, EP_GELU = 7,
-       EP_ROPE_PART = 8, EP_GELU_ERF = 9, EP_F32 = 10, EP_QKV_F32 = 11, EP_GEGLU = 12, EP_HEAD_CAP = 13 };
+       EP_ROPE_PART = 8, EP_GELU_ERF = 9, EP_F32 = 10, EP_QKV_F32 = 11, EP_GEGLU = 12, EP_HEAD_CAP = 13,
+       EP_OSS_GLU = 14, EP_F32_BIAS = 15 };
 
 using f32x16 = float __attribute__((ext_vector_type(16)));
 
@@ -84,6 +90,8 @@ struct ClmGemm {
   const int* blk_expert;                    // [M / 128] the matrix of B that the 128-row block of A multiplies, -1: no rows, no tile
   long long b_stride;                       // elements between two consecutive matrices of B
   float cap;                                // EP_HEAD_CAP: the soft cap on the logits (> 0)
+  long long bias_stride;                    // grouped EP_OSS_GLU / EP_F32_BIAS: elements between two consecutive experts' biases
+  float glu_limit;                          // EP_OSS_GLU: the clamp on gate (from above) and up (both sides), > 0
 };
 
 // The tile rule (B2T_CLM_GEMM_256) lives in one definition, causal_lm.hip: it picks the tile and hands the launch to `tiles`,

@@ -167,19 +167,20 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
 }
 
 // What a family whose descriptor obeys the Llama rule hd = d_model / n_heads hands the entry-point bodies beside layout, check
-// and forward: the model check, the head dim and the two attention launches.  Gemma-2 (clm_gemma2.h), whose head dim is a
+// and forward: the model check, the head dim and the two attention launches, which are told the layer (gpt-oss, clm_gptoss.h:
+// a sink per head and a window per layer; nobody else looks at it).  Gemma-2 (clm_gemma2.h), whose head dim is a
 // field of its own descriptor and whose attention takes a soft cap, supplies its own.
 struct LlamaFamilyBase {
   template <class X>
   static int check_model(const b2t_clm_llama_t* m, const X*) { return clm_llama_check_model(m); }
   template <class P, class X>
-  static int attn(const b2t_clm_llama_t& m, const X*, const typename P::E* qkv, typename P::E* out, const int* seq_off, int n_seq,
-                  hipStream_t s) {
+  static int attn(const b2t_clm_llama_t& m, const X*, int /*layer*/, const typename P::E* qkv, typename P::E* out,
+                  const int* seq_off, int n_seq, hipStream_t s) {
     return P::attn(qkv, out, seq_off, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   }
   template <class P, class X>
-  static int attn_tree(const b2t_clm_llama_t& m, const X*, const typename P::E* qkv, typename P::E* out, const int* seq_off,
-                       const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
+  static int attn_tree(const b2t_clm_llama_t& m, const X*, int /*layer*/, const typename P::E* qkv, typename P::E* out,
+                       const int* seq_off, const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
     return P::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads, s);
   }
 };
@@ -222,7 +223,7 @@ int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* id
   if (int rc = clm_build_flat_index((std::string(who) + " upload").c_str(), ids_host, seq_off_host, n_seq,
                                     reinterpret_cast<int*>(base + L.ints), s, &ix))
     return rc;
-  auto attn = [&](int, const E* qkv, E* out) { return Fam::template attn<P>(m, extra, qkv, out, ix.d_soff, n_seq, s); };
+  auto attn = [&](int l, const E* qkv, E* out) { return Fam::template attn<P>(m, extra, l, qkv, out, ix.d_soff, n_seq, s); };
   if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
   return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
 }
@@ -250,8 +251,8 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
   if (int rc = clm_build_tree_index((std::string(who) + " upload").c_str(), ids_host, seq_off_host, n_seq, plan, 0,
                                     reinterpret_cast<int*>(base + L.ints), s, &ix))
     return rc;
-  auto attn = [&](int, const E* qkv, E* out) {
-    return Fam::template attn_tree<P>(m, extra, qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, s);
+  auto attn = [&](int l, const E* qkv, E* out) {
+    return Fam::template attn_tree<P>(m, extra, l, qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, s);
   };
   if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
   return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);

@@ -122,12 +122,12 @@ struct Phi3Family {
   template <class P>
   static int check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_phi3_t* p3) { return clm_phi3_check(who, &m, p3); }
   template <class P>
-  static int attn(const b2t_clm_llama_t& m, const b2t_clm_phi3_t* p3, const typename P::E* qkv, typename P::E* out,
+  static int attn(const b2t_clm_llama_t& m, const b2t_clm_phi3_t* p3, int /*layer*/, const typename P::E* qkv, typename P::E* out,
                   const int* seq_off, int n_seq, hipStream_t s) {
     return P::attn(qkv, out, seq_off, n_seq, m.n_heads, m.n_kv_heads, p3->head_dim, s);
   }
   template <class P>
-  static int attn_tree(const b2t_clm_llama_t& m, const b2t_clm_phi3_t* p3, const typename P::E* qkv, typename P::E* out,
+  static int attn_tree(const b2t_clm_llama_t& m, const b2t_clm_phi3_t* p3, int /*layer*/, const typename P::E* qkv, typename P::E* out,
                        const int* seq_off, const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
     return P::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, m.n_heads, m.n_kv_heads, p3->head_dim, s);
   }

@@ -1776,6 +1776,271 @@ class Phi3Scorer(LlamaScorer):
         return lib.b2t_clm_phi3_cache_kv_bytes(C.byref(self.desc), self._phi3, cap)
 
 
+# ---- gpt-oss (HF GptOssForCausalLM): attention sinks, a sliding window in the kernel, biased routed experts ------------------
+GPTOSS_HEAD_DIM = 64
+GPTOSS_MAX_EXPERTS, GPTOSS_MAX_TOP_K = 128, 8
+GPTOSS_LAYER_TYPES = ("full_attention", "sliding_attention")
+_GPTOSS_LAYER_FIELDS = ("sinks", "o_b", "router_w", "router_b", "gate_up_b", "down_b")
+_FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)   # e2m1
+
+
+def _gptoss_layer_types(cfg: dict) -> list:
+    """layer_types of a gpt_oss config; absent, HF's default: sliding, full, sliding, ..."""
+    n = int(cfg["num_hidden_layers"])
+    lt = cfg.get("layer_types")
+    return ["sliding_attention" if (i + 1) % 2 else "full_attention" for i in range(n)] if lt is None else list(lt)
+
+
+def gptoss_rope(cfg: dict) -> Tuple[np.ndarray, float]:
+    """(fp32 inv_freq[head_dim / 2], attention factor) of a "gpt_oss" config, computed as HF's GptOssRotaryEmbedding computes
+    them (fp32 torch arithmetic, same operation order).  rope_type "default": 1 / base^(arange(0, hd, 2) / hd), factor 1.  "yarn":
+    HF's _compute_yarn_parameters -- the blend of the interpolated and the extrapolated frequencies over the correction range of
+    beta_fast / beta_slow, whose bounds are not rounded to integers when "truncate" is false (the published checkpoints), and the
+    factor that HF multiplies cos and sin by, 0.1 ln(factor) + 1 (or the ratio of the two mscale forms, or "attention_factor").
+    Every other type is refused.  The default rope_theta is 150000 and absent rope parameters are the published yarn ones."""
+    import math
+    import torch
+    rp = dict(cfg.get("rope_parameters") or cfg.get("rope_scaling") or
+              {"rope_type": "yarn", "factor": 32.0, "beta_fast": 32.0, "beta_slow": 1.0, "truncate": False,
+               "original_max_position_embeddings": 4096})
+    if "rope_type" not in rp:
+        rp["rope_type"] = rp.get("type", "default")
+    if "rope_theta" not in rp:
+        rp["rope_theta"] = cfg.get("rope_theta", 150000.0)
+    kind = rp["rope_type"]
+    if kind not in ("default", "yarn"):
+        raise ValueError(f"gpt_oss rope_type {kind!r} is not supported (yarn or default)")
+    dim = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // int(cfg["num_attention_heads"]))
+    base = rp["rope_theta"]
+    if kind == "default":
+        inv = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.float) / dim))
+        return inv.numpy().astype(np.float32), 1.0
+    orig = rp["original_max_position_embeddings"]
+    factor = rp.get("factor")
+    if factor is None:
+        factor = int(cfg["max_position_embeddings"]) / orig
+    mscale_of = lambda scale, m=1: 1.0 if scale <= 1 else 0.1 * m * math.log(scale) + 1.0
+    af = rp.get("attention_factor")
+    if af is None:
+        ms, msa = rp.get("mscale"), rp.get("mscale_all_dim")
+        af = float(mscale_of(factor, ms) / mscale_of(factor, msa)) if ms and msa else mscale_of(factor)
+    beta_fast, beta_slow = rp.get("beta_fast") or 32, rp.get("beta_slow") or 1
+    corr = lambda rot: (dim * math.log(orig / (rot * 2 * math.pi))) / (2 * math.log(base))
+    low, high = corr(beta_fast), corr(beta_slow)
+    if rp.get("truncate", True):
+        low, high = math.floor(low), math.ceil(high)
+    low, high = max(low, 0), min(high, dim - 1)
+    if low == high:
+        high += 0.001
+    pos_freqs = base ** (torch.arange(0, dim, 2).to(dtype=torch.float) / dim)
+    extra, inter = 1.0 / pos_freqs, 1.0 / (factor * pos_freqs)
+    ramp = torch.clamp((torch.arange(dim // 2, dtype=torch.float32) - low) / (high - low), 0, 1)
+    keep = 1 - ramp.to(dtype=torch.float)
+    inv = inter * (1 - keep) + extra * keep
+    return inv.numpy().astype(np.float32), float(af)
+
+
+def gptoss_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
+    """The dimensions b2t_clm_llama_t and b2t_clm_gptoss_t need for a "gpt_oss" config, after refusing, by the field's name, what
+    the kernels do not run.  max_pos is max_position_embeddings lowered to max_positions (default LLAMA_MAX_POSITIONS), which
+    sizes the rotary table; the sliding window does NOT lower it: it binds (128 keys on every other layer), so it is a
+    per-layer argument of the attention kernel, dims["windows"] (0 = a full layer)."""
+    mt = cfg.get("model_type")
+    if mt != "gpt_oss":
+        raise ValueError(f"model_type {mt!r} is not 'gpt_oss'")
+    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    Hkv = int(cfg.get("num_key_value_heads") or Hq)
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise ValueError(f"gpt_oss hidden_act {act!r} is not supported (silu only: the clamped (up + 1) * gate * sigmoid(1.702 gate))")
+    hd = int(cfg.get("head_dim") or d // Hq)
+    if hd != GPTOSS_HEAD_DIM:
+        raise ValueError(f"head_dim {hd} is not supported ({GPTOSS_HEAD_DIM})")
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    ne, k = int(cfg.get("num_local_experts", 128)), int(cfg.get("num_experts_per_tok", 4))
+    if not 1 <= ne <= GPTOSS_MAX_EXPERTS:
+        raise ValueError(f"num_local_experts {ne} outside [1, {GPTOSS_MAX_EXPERTS}]")
+    if not 1 <= k <= min(GPTOSS_MAX_TOP_K, ne):
+        raise ValueError(f"num_experts_per_tok {k} outside [1, min({GPTOSS_MAX_TOP_K}, num_local_experts {ne})]")
+    ffn = int(cfg["intermediate_size"])
+    if d % 64 or ffn % 64:
+        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    if not cfg.get("attention_bias", True):
+        raise ValueError("gpt_oss with attention_bias=False is not supported (the forward adds the q / k / v / o biases)")
+    n_layers = int(cfg["num_hidden_layers"])
+    types = _gptoss_layer_types(cfg)
+    if len(types) != n_layers:
+        raise ValueError(f"layer_types has {len(types)} entries, num_hidden_layers is {n_layers}")
+    for i, t in enumerate(types):
+        if t not in GPTOSS_LAYER_TYPES:
+            raise ValueError(f"layer_types[{i}] {t!r} is not one of {GPTOSS_LAYER_TYPES}")
+    window = cfg.get("sliding_window")
+    if "sliding_attention" in types and (window is None or int(window) < 1):
+        raise ValueError(f"sliding_window {window} < 1 with sliding_attention layers")
+    gptoss_rope(cfg)   # refuses a rope_type other than yarn / default
+    if cfg.get("tie_word_embeddings", False):
+        raise ValueError("gpt_oss with tie_word_embeddings=True is not supported (the head is untied)")
+    limit = float(cfg.get("swiglu_limit", 7.0))
+    if not limit > 0:
+        raise ValueError(f"swiglu_limit {limit} must be > 0")
+    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
+    if cap < 1:
+        raise ValueError(f"max_positions {cap} < 1")
+    return dict(n_layers=n_layers, d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn, vocab=int(cfg["vocab_size"]),
+                max_pos=min(int(cfg["max_position_embeddings"]), cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-5)), tied=False,
+                head_dim=hd, n_experts=ne, top_k=k, swiglu_limit=limit,
+                windows=[int(window) if t == "sliding_attention" else 0 for t in types])
+
+
+def mxfp4_dequant(blocks, scales, name: str = "mxfp4"):
+    """fp32 [..., rows, 32 G] of MXFP4 blocks uint8 [..., rows, G, 16] (two e2m1 values per byte, low nibble first) and scales
+    uint8 [..., rows, G]: value * 2^(scale - 127), exact in fp32 wherever the result is an fp32 number."""
+    import torch
+    if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ValueError(f"{name}: blocks {blocks.dtype} and scales {scales.dtype} must be uint8")
+    if blocks.shape[-1] != 16 or tuple(blocks.shape[:-1]) != tuple(scales.shape):
+        raise ValueError(f"{name}: blocks {tuple(blocks.shape)} do not go with scales {tuple(scales.shape)}")
+    lut = torch.tensor(_FP4_VALUES, dtype=torch.float32, device=blocks.device)
+    b = blocks.long()
+    vals = torch.stack([lut[b & 15], lut[b >> 4]], -1).reshape(*blocks.shape[:-1], 32)      # low nibble first
+    out = torch.ldexp(vals, (scales.to(torch.int32) - 127)[..., None])
+    return out.reshape(*scales.shape[:-1], scales.shape[-1] * 32)
+
+
+def gptoss_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float], dtype=None) -> Dict[str, "object"]:
+    """Tensors in the layout of b2t_clm_llama_t / b2t_clm_gptoss_t from a gpt-oss state dict.  Embedding, untied head, norms and the
+    rotary tables ([max_pos][32], rope_tables of rope's inv_freq times its attention factor in fp32; rope = gptoss_rope(cfg)) are
+    made as for Phi-3; qkv_w / qkv_b are q, k, v rows in checkpoint order (at head dim 64 the rotary pair (c, c + 32) is 32 rows
+    apart as stored); o_w is [round_up(d, 256)][Hq hd].  Per layer also sinks (fp32 [Hq]; a non-finite one is refused by name),
+    o_b, router_w [E][d], router_b [E], gate_up_w [E][round_up(2F, 256)][d], gate_up_b [E][round_up(2F, 256)], down_w
+    [E][round_up(d, 256)][F] and down_b [E][round_up(d, 256)] (mixtral_strides), zero-padded.  Both spellings of a checkpoint are
+    read: the plain one -- mlp.experts.gate_up_proj [E][d][2F] with gate in the even columns and up in the odd ones,
+    gate_up_proj_bias [E][2F] interleaved the same way, down_proj [E][F][d], down_proj_bias [E][d] -- and the published MXFP4 one
+    -- gate_up_proj_blocks / _scales [E][2F][d / 32]([16]) and down_proj_blocks / _scales [E][d][F / 32]([16]), dequantised to
+    fp32 exactly (mxfp4_dequant) and then cast; a value that does not survive the cast as a finite number is refused by name.
+    The expert matrices are transposed to [rows][K], and gate / up are de-interleaved into gate_up_row_perm's blocks of 32."""
+    import torch
+    wdt = clm_dtype(dtype)
+    sd = dict(state)
+    d, ffn, V, Hq, Hkv, hd, ne = (dims[k] for k in ("d_model", "ffn_dim", "vocab", "n_heads", "n_kv_heads", "head_dim", "n_experts"))
+    inv_freq, att = rope
+    if len(inv_freq) != hd // 2:
+        raise ValueError(f"inv_freq has {len(inv_freq)} entries, head_dim {hd} needs {hd // 2}")
+
+    def raw(name):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name}")
+        return sd[name].detach()
+
+    def get(name, shape, to=None):
+        t = raw(name).to(to or wdt).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+
+    def expert_rows(name, rows, K):
+        """[E][rows][K] in wdt of the expert matrix `name`, from either spelling"""
+        if name + "_blocks" in sd:
+            blocks, scales = raw(name + "_blocks"), raw(name + "_scales")
+            if tuple(blocks.shape) != (ne, rows, K // 32, 16) or tuple(scales.shape) != (ne, rows, K // 32) or K % 32:
+                raise ValueError(f"{name}_blocks / _scales: shapes {tuple(blocks.shape)} / {tuple(scales.shape)}, expected "
+                                 f"{(ne, rows, K // 32, 16)} / {(ne, rows, K // 32)}")
+            t = mxfp4_dequant(blocks, scales, name).to(wdt)
+            if not torch.isfinite(t).all():
+                raise ValueError(f"{name}_blocks / _scales: a value is not finite in {wdt}")
+            return t
+        return get(name, (ne, K, rows)).transpose(1, 2).contiguous()
+    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
+    dev = emb.device
+    out = {"embed_tokens": emb, "lm_head": _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
+           "final_norm_w": get("model.norm.weight", (d,))}
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos * np.float32(att)), torch.from_numpy(sin * np.float32(att))
+    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
+    deint = torch.cat([torch.arange(0, 2 * ffn, 2), torch.arange(1, 2 * ffn, 2)]).to(dev)[gperm]   # stored row -> interleaved row
+    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    gus, dns = mixtral_strides(dims)
+    for i in range(dims["n_layers"]):
+        p = f"model.layers.{i}."
+        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
+        sinks = get(p + "self_attn.sinks", (Hq,), torch.float32)
+        if not torch.isfinite(sinks).all():
+            raise ValueError(f"{p}self_attn.sinks: a sink is not finite")
+        gate_up = expert_rows(p + "mlp.experts.gate_up_proj", 2 * ffn, d)        # [E][2F][d], gate rows even, up rows odd
+        down = expert_rows(p + "mlp.experts.down_proj", d, ffn)                  # [E][d][F]
+        gu = gate_up.new_zeros((ne, gus, d))
+        gu[:, :2 * ffn] = gate_up[:, deint]
+        gub = gate_up.new_zeros((ne, gus))
+        gub[:, :2 * ffn] = get(p + "mlp.experts.gate_up_proj_bias", (ne, 2 * ffn))[:, deint]
+        dn = down.new_zeros((ne, dns, ffn))
+        dn[:, :d] = down
+        dnb = down.new_zeros((ne, dns))
+        dnb[:, :d] = get(p + "mlp.experts.down_proj_bias", (ne, d))
+        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
+             "qkv_w": _pad_rows(qkv, _rup(qkv.shape[0], ROWPAD)),
+             "qkv_b": torch.cat([get(p + f"self_attn.{n}.bias", (w,)) for n, w in widths.items()]),
+             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, Hq * hd)), _rup(d, ROWPAD)),
+             "o_b": get(p + "self_attn.o_proj.bias", (d,)), "sinks": sinks,
+             "router_w": get(p + "mlp.router.weight", (ne, d)), "router_b": get(p + "mlp.router.bias", (ne,)),
+             "gate_up_w": gu, "gate_up_b": gub, "down_w": dn, "down_b": dnb}
+        for f, t in L.items():
+            out[f"layers.{i}.{f}"] = t
+    return out
+
+
+def load_gptoss_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the gpt-oss checkpoint in model_dir; dtype as clm_dtype reads it."""
+    cfg = load_config(model_dir)
+    dims = gptoss_dims(cfg, max_positions)
+    wdt = clm_dtype(dtype, cfg)
+    return dims, gptoss_device_layout(_load_state_dict(model_dir), dims, gptoss_rope(cfg), wdt)
+
+
+def gptoss_check_cache(context_cache_tokens) -> None:
+    """Refuses a context cache for gpt-oss: the cached and trunk attention kernels have neither sink nor window."""
+    if int(context_cache_tokens) > 0:
+        raise ValueError("gpt_oss: the context cache (context_cache_tokens > 0) is not supported for this family: the cached "
+                         "attention kernels have neither the sink nor the sliding window (a follow-up)")
+
+
+class GptOssScorer(LlamaScorer):
+    """A gpt-oss decoder on the GPU: a LlamaScorer (same descriptor with the experts stacked in gate_up_w / down_w, scoring surface
+    and dtype rules) whose calls are b2t_clm_gptoss_score_f16 / _tree_f16 / _bf16 / _tree_bf16 (csrc/causal_lm_gptoss.hip) with the
+    b2t_clm_gptoss_t of gptoss_device_layout's arrays, and whose workspace sizes are the b2t_clm_gptoss_* size functions'.  There
+    is no context cache for this family: context_cache_tokens > 0 raises ValueError."""
+
+    _WS_BYTES = "b2t_clm_gptoss_ws_bytes"
+    _SIZES = "b2t_clm_gptoss_"
+
+    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
+                 context_cache_tokens: int = 0, dtype=None):
+        import torch
+        import b2t_native as N
+        gptoss_check_cache(context_cache_tokens)
+        if "windows" not in dims or (dims["n_layers"] > 0 and "layers.0.sinks" not in arrays):
+            raise KeyError("GptOssScorer: dims lack windows / n_experts or the arrays layers.<i>.sinks (gptoss_dims and "
+                           "gptoss_device_layout make them)")
+        # the descriptor first: the size functions need it
+        self._oss_layers = (N.ClmGptOssLayer * max(1, dims["n_layers"]))()
+        gus, dns = mixtral_strides(dims)
+        self._oss = N.ClmGptOss(dims["head_dim"], dims["swiglu_limit"], dims["n_experts"], dims["top_k"], gus, dns, None,
+                                self._oss_layers)
+        self._size_args = (self._oss,)
+        sinks = {k: v for k, v in arrays.items() if k.endswith(".sinks")}
+        rest = {k: v for k, v in arrays.items() if k not in sinks}
+        super().__init__(dims, rest, device, share_prefixes, 0, dtype)
+        for k, v in sinks.items():
+            if v.dtype != torch.float32:
+                raise ValueError(f"GptOssScorer: {k} is {v.dtype}, expected torch.float32")
+            self.w[k] = v.to(self.device).contiguous()
+        for i in range(dims["n_layers"]):
+            for f in _GPTOSS_LAYER_FIELDS:
+                setattr(self._oss_layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
+            self._oss_layers[i].window = dims["windows"][i]
+        self._family, self._qk = "gptoss", (self._oss,)
+
+
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
     """b2t_clm_tree_plan_host on packed int32 ids / offsets (host only, no GPU): (node_of_token, parent_of_node, n_nodes).
     A node is a distinct token prefix, numbered by first appearance; parent_of_node is -1 at roots."""
@@ -1813,7 +2078,8 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
     """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
     only, like OPT), NeoxScorer for "gpt_neox" (Pythia; fp16 only), LlamaScorer for "llama",
     "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2", MixtralScorer for "mixtral", Gemma2Scorer for "gemma2", Phi3Scorer for
-    "phi3"; anything else ("olmo", "olmo3", "gemma", "gemma3", "qwen3_moe", "phi", "phimoe" and "phi3small" included) is refused.
+    "phi3", GptOssScorer for "gpt_oss" (no context cache: context_cache_tokens > 0 is refused before any weight is read);
+    anything else ("olmo", "olmo3", "gemma", "gemma3", "qwen3_moe", "phi", "phimoe" and "phi3small" included) is refused.
     max_positions caps a Llama-family, OLMo-2, Mixtral, Gemma-2 or Phi-3 model's rotary table.  dtype (clm_dtype): None or
     "float16", "bfloat16" (the Llama family, OLMo-2, Mixtral, Gemma-2 and Phi-3 only, and without a context cache), or "auto" =
     the dtype config.json says
@@ -1863,8 +2129,13 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
         LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
         dims, arrays = load_phi3_arrays(model_dir, max_positions, wdt)
         return Phi3Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
+    if mt == "gpt_oss":
+        gptoss_check_cache(context_cache_tokens)   # before the weights are read
+        wdt = clm_dtype(dtype, cfg)
+        dims, arrays = load_gptoss_arrays(model_dir, max_positions, wdt)
+        return GptOssScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
     raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, phi3, "
-                     f"olmo2, mixtral)")
+                     f"gpt_oss, olmo2, mixtral)")
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
@@ -1873,7 +2144,7 @@ def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", sha
     Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
     OptScorer, a Gpt2Scorer for a GPT-2 directory, a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory, an
     Olmo2Scorer for an OLMo-2 directory, a MixtralScorer for a Mixtral directory, a Gemma2Scorer for a Gemma-2 directory, or a
-    Phi3Scorer for a Phi-3 / Phi-4 directory (build_scorer).
+    Phi3Scorer for a Phi-3 / Phi-4 directory, or a GptOssScorer for a gpt-oss directory (build_scorer).
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

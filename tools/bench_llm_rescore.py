@@ -76,6 +76,15 @@ heads of 256, ffn 9216, vocab 256000, tied head -- beside a LlamaScorer of equal
 and tied head with 18 query / 6 kv heads of 128, under the protocol of --arch olmo2.
 
   python tools/bench_llm_rescore.py --arch gemma2 --lists 5 --cands 5|20|100
+
+`--arch gptoss` measures gpt-oss's path (b2t_clm_gptoss_score_bf16 / _tree_bf16: attention with sinks and a window of 128 on every
+other layer, router, plan, gather, two grouped GEMMs with biases, combine) at the gpt-oss-20b shape -- d 2880, 64 query / 8 kv
+heads of 64, F 2880, 32 experts top-4, vocab 201088, --layers of the 24 (default 4) -- on random bf16 weights, beside a dense
+LlamaScorer of equal active matmul FLOPs per row (d 2880, 45 query / 9 kv heads of 64, ffn 12288: 4 x 2880 for the four experts
+and 768 for the wider attention projections), under the protocol of --arch olmo2.  The sorted rows S against rows * top_k say how
+much of the grouped GEMMs is padding.
+
+  python tools/bench_llm_rescore.py --arch gptoss --lists 5 --cands 5|20|100 [--list nbest --context 64]
 """
 import argparse
 import json
@@ -112,7 +121,7 @@ def nbest_list(rng, V, cands=100, context=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2", "mixtral", "gemma2", "phi3"), default="opt",
+    ap.add_argument("--arch", choices=("opt", "llama", "qwen3", "gpt2", "olmo2", "mixtral", "gemma2", "phi3", "gptoss"), default="opt",
                     help="opt: OPT-6.7b shape; llama: Llama-3-8B shape; qwen3: Qwen3-8B shape; gpt2: GPT-2 XL shape; "
                          "olmo2: OLMo-2-7B shape, beside the Llama forward of the same dimensions; mixtral: Mixtral-8x7B shape "
                          "with 4 layers, beside the dense Llama forward of the same active FLOPs; gemma2: gemma-2-2b shape, beside "
@@ -136,14 +145,20 @@ def main():
     ap.add_argument("--session", action="store_true", help="tree against context cache over a growing conversation")
     ap.add_argument("--sentences", type=int, default=12, help="--session: calls of the conversation")
     a = ap.parse_args()
-    a.layers = a.layers or {"qwen3": 36, "gpt2": 48, "mixtral": 4, "gemma2": 26}.get(a.arch, 32)   # phi3: 32
-    a.d = a.d or {"gpt2": 1600, "gemma2": 2304, "phi3": 3072}.get(a.arch, 4096)
-    a.heads = a.heads or {"gpt2": 25, "gemma2": 8}.get(a.arch, 32)
+    a.layers = a.layers or {"qwen3": 36, "gpt2": 48, "mixtral": 4, "gemma2": 26, "gptoss": 4}.get(a.arch, 32)   # phi3: 32
+    a.d = a.d or {"gpt2": 1600, "gemma2": 2304, "phi3": 3072, "gptoss": 2880}.get(a.arch, 4096)
+    a.heads = a.heads or {"gpt2": 25, "gemma2": 8, "gptoss": 64}.get(a.arch, 32)
     a.kv_heads = a.kv_heads or (a.heads if a.arch in ("olmo2", "phi3") else 4 if a.arch == "gemma2" else 8)
-    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008, "mixtral": 14336, "gemma2": 9216, "phi3": 8192}[a.arch]
-    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352, "mixtral": 32000, "gemma2": 256000, "phi3": 32064}[a.arch]
-    if a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2", "mixtral", "gemma2", "phi3") or a.session):
+    a.ffn = a.ffn or {"opt": 16384, "llama": 14336, "qwen3": 12288, "gpt2": 6400, "olmo2": 11008, "mixtral": 14336, "gemma2": 9216, "phi3": 8192, "gptoss": 2880}[a.arch]
+    a.vocab = a.vocab or {"opt": 50272, "llama": 128256, "qwen3": 151936, "gpt2": 50257, "olmo2": 100352, "mixtral": 32000, "gemma2": 256000, "phi3": 32064, "gptoss": 201088}[a.arch]
+    if a.arch == "gptoss":
+        a.dtype = "bfloat16"     # the format the checkpoints are published in
+    elif a.dtype != "float16" and (a.arch in ("opt", "gpt2", "olmo2", "mixtral", "gemma2", "phi3") or a.session):
         ap.error("--dtype bfloat16 needs --arch llama or qwen3 and has no --session")
+    if a.arch == "gptoss":
+        if a.session:
+            ap.error("--arch gptoss has no --session")
+        return main_gptoss(a)
     if a.arch == "mixtral":
         if a.session:
             ap.error("--arch mixtral has no --session")
@@ -409,6 +424,66 @@ def main_gemma2(a):
                       "nodes": float(np.mean(nodes)), "llama_flat_ms": stat(("llama", False)),
                       "gemma2_flat_ms": stat(("gemma2", False)), "llama_tree_ms": stat(("llama", True)),
                       "gemma2_tree_ms": stat(("gemma2", True)),
+                      "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
+                      "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
+                      "flat_tree_bit_identical": bool(same)}))
+
+
+def main_gptoss(a, n_experts=32, top_k=4):
+    """--arch gptoss: a GptOssScorer at the gpt-oss-20b shape on random bf16 weights (sinks and biases N(0, 0.5)) beside a dense
+    LlamaScorer of equal active matmul FLOPs per row, both in bf16, under the protocol of --arch gemma2."""
+    import torch
+    import llm_rescore as R
+    torch.manual_seed(0)
+    d, H, Hkv, hd, ffn, V, L = a.d, a.heads, a.kv_heads, 64, a.ffn, a.vocab, a.layers
+    lH, lHkv, dev, bf = d // 64, 9, "cuda", torch.bfloat16
+    lffn = top_k * ffn + ((H + 2 * Hkv) * hd + H * hd - (lH + 2 * lHkv) * 64 - d) // 3
+    if d % 64 or lH % lHkv or lffn % 64 or 3 * (lffn - top_k * ffn) != (H + 2 * Hkv) * hd + H * hd - (lH + 2 * lHkv) * 64 - d:
+        raise SystemExit("--arch gptoss compares at widths whose dense twin exists (d 2880, 64 / 8 heads of 64, ffn 2880)")
+    rng = np.random.default_rng(0)
+    rn = lambda *s, std: (torch.randn(*s, device=dev) * std).to(bf)
+    nw = lambda n: (1 + 0.2 * torch.randn(n, device=dev)).to(bf)
+    emb, head = rn(V, d, std=2.0 / d ** 0.5), rn(V, d, std=2.0 / d ** 0.5)
+    base = dict(hidden_size=d, vocab_size=V, num_hidden_layers=L, max_position_embeddings=8192, rms_norm_eps=1e-5,
+                tie_word_embeddings=False, hidden_act="silu")
+    cfg = dict(base, model_type="gpt_oss", intermediate_size=ffn, num_attention_heads=H, num_key_value_heads=Hkv, head_dim=hd,
+               num_local_experts=n_experts, num_experts_per_tok=top_k, sliding_window=128)
+    st = {"model.embed_tokens.weight": emb, "lm_head.weight": head, "model.norm.weight": nw(d)}
+    for l in range(L):
+        p = f"model.layers.{l}."
+        for n, (o, i) in {"q_proj": (H * hd, d), "k_proj": (Hkv * hd, d), "v_proj": (Hkv * hd, d), "o_proj": (d, H * hd)}.items():
+            st[p + f"self_attn.{n}.weight"], st[p + f"self_attn.{n}.bias"] = rn(o, i, std=1.0 / i ** 0.5), rn(o, std=0.5)
+        st[p + "self_attn.sinks"] = rn(H, std=0.5)
+        st[p + "mlp.router.weight"], st[p + "mlp.router.bias"] = rn(n_experts, d, std=1.0 / d ** 0.5), rn(n_experts, std=0.5)
+        st[p + "mlp.experts.gate_up_proj"] = rn(n_experts, d, 2 * ffn, std=1.0 / d ** 0.5)
+        st[p + "mlp.experts.gate_up_proj_bias"] = rn(n_experts, 2 * ffn, std=0.5)
+        st[p + "mlp.experts.down_proj"], st[p + "mlp.experts.down_proj_bias"] = rn(n_experts, ffn, d, std=1.0 / ffn ** 0.5), rn(n_experts, d, std=0.5)
+        st[p + "input_layernorm.weight"], st[p + "post_attention_layernorm.weight"] = nw(d), nw(d)
+    dims = R.gptoss_dims(cfg, 2048)
+    scs = {"gptoss": R.GptOssScorer(dims, R.gptoss_device_layout(st, dims, R.gptoss_rope(cfg), bf), dev, dtype=bf)}
+    lst = {"model.embed_tokens.weight": emb, "lm_head.weight": head, "model.norm.weight": nw(d)}
+    for l in range(L):
+        p = f"model.layers.{l}."
+        for n, (o, i) in {"self_attn.q_proj": (lH * 64, d), "self_attn.k_proj": (lHkv * 64, d), "self_attn.v_proj": (lHkv * 64, d),
+                          "self_attn.o_proj": (d, d), "mlp.gate_proj": (lffn, d), "mlp.up_proj": (lffn, d), "mlp.down_proj": (d, lffn)}.items():
+            lst[p + n + ".weight"] = rn(o, i, std=1.0 / i ** 0.5)
+        lst[p + "input_layernorm.weight"], lst[p + "post_attention_layernorm.weight"] = nw(d), nw(d)
+    lcfg = dict(base, model_type="llama", intermediate_size=lffn, num_attention_heads=lH, num_key_value_heads=lHkv, rope_theta=10000.0)
+    ldims = R.llama_dims(lcfg, 2048)
+    scs["llama"] = R.LlamaScorer(ldims, R.llama_device_layout(lst, ldims, R.rope_inv_freq(lcfg), bf), dev, dtype=bf)
+    del st, lst, emb, head
+    torch.cuda.empty_cache()
+    lists, ntok, nodes, same, per, stat = alternate(a, rng, V, scs, ("llama", "gptoss"))
+    ratio = lambda t: [round(o / l, 4) for o, l in zip(per["gptoss", t], per["llama", t])]
+    S = lambda rows: -(-rows * top_k // 256) * 256 + 256 * n_experts
+    print(json.dumps({"bench": "llm_rescore_gptoss", "dtype": "bfloat16", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "head_dim": hd,
+                      "ffn": ffn, "experts": n_experts, "top_k": top_k, "vocab": V, "llama_heads": lH, "llama_kv_heads": lHkv,
+                      "llama_ffn": lffn, "cands": a.cands, "list": a.list, "context": a.context, "lists": len(lists),
+                      "reps": max(1, a.reps), "tokens": float(np.mean(ntok)), "nodes": float(np.mean(nodes)),
+                      "sorted_rows_flat": float(np.mean([S(n) for n in ntok])), "routed_rows_flat": float(np.mean(ntok)) * top_k,
+                      "sorted_rows_tree": float(np.mean([S(n) for n in nodes])), "routed_rows_tree": float(np.mean(nodes)) * top_k,
+                      "llama_flat_ms": stat(("llama", False)), "gptoss_flat_ms": stat(("gptoss", False)),
+                      "llama_tree_ms": stat(("llama", True)), "gptoss_tree_ms": stat(("gptoss", True)),
                       "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
                       "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
                       "flat_tree_bit_identical": bool(same)}))
