@@ -43,7 +43,7 @@ import glob
 import json
 import logging
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -353,6 +353,7 @@ class _Scorer:
     _cache = None
     _WS_BYTES = ""    # the family's flat sizing call, for the message of a refused size
     _NO_CACHE = ""    # the ValueError of use_cache=True on a scorer without a context cache
+    _CONTEXT_CACHE = True   # False: the family has no cached call, and refuses context_cache_tokens > 0 itself
 
     def eval(self):   # the reference calls model.eval(); scoring has no training mode
         return self
@@ -586,6 +587,24 @@ def llama_check_dtype_cache(dtype, context_cache_tokens) -> None:
                          "behind bfloat16 is the follow-up to the bfloat16 mode; use dtype 'float16' or context_cache_tokens=0")
 
 
+def reader(state: dict, wdt, who: str = "", device=None):
+    """get(name, shape, to=None) over a state dict, for every *_device_layout: the tensor `name` cast to `to` (default wdt) on
+    `device` (default: where it is) and contiguous, after checking that it is there (a KeyError that starts with `who` and names
+    the tensor) and, cast, has `shape` (ValueError).  get.raw(name) is the tensor as stored, behind the first check alone."""
+    def raw(name):
+        if name not in state:
+            raise KeyError(f"{who}checkpoint lacks {name}")
+        return state[name].detach()
+
+    def get(name, shape, to=None):
+        t = raw(name).to(device=device, dtype=to or wdt).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    get.raw = raw
+    return get
+
+
 # ---- GPT-2 (HF GPT2LMHeadModel) ------------------------------------------------------------------------------------------
 GPT2_ACTIVATIONS = ("gelu_new", "gelu_pytorch_tanh")   # two names of 0.5 v (1 + tanh(sqrt(2 / pi) (v + 0.044715 v^3)))
 
@@ -633,13 +652,7 @@ def gpt2_device_layout(state: dict, dims: dict) -> Dict[str, "object"]:
         sd[k] = v
     d, ffn, V = dims["d_model"], dims["ffn_dim"], dims["vocab"]
 
-    def get(name, shape):
-        if name not in sd:
-            raise KeyError(f"GPT-2 checkpoint lacks {name}")
-        t = sd[name].detach().to("cpu", torch.float16).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
+    get = reader(sd, torch.float16, "GPT-2 ", device="cpu")
 
     def conv1d(name, n_in, n_out):   # Conv1D weight [in][out] -> nn.Linear rows [out][in], padded
         return _pad_rows(get(name + ".weight", (n_in, n_out)).t().contiguous(), _rup(n_out, ROWPAD))
@@ -665,8 +678,7 @@ def gpt2_device_layout(state: dict, dims: dict) -> Dict[str, "object"]:
 
 def load_gpt2_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host fp16 tensors in the device layout) of the GPT-2 checkpoint in model_dir."""
-    dims = gpt2_dims(load_config(model_dir))
-    return dims, gpt2_device_layout(_load_state_dict(model_dir), dims)
+    return _load_arrays(FAMILIES["gpt2"], model_dir)
 
 
 class Gpt2Scorer(OptScorer):
@@ -784,13 +796,7 @@ def neox_device_layout(state: dict, dims: dict, inv_freq: np.ndarray) -> Dict[st
     d, ffn, V, H = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"]
     hd = d // H
 
-    def get(name, shape):
-        if name not in sd:
-            raise KeyError(f"GPT-NeoX checkpoint lacks {name}")
-        t = sd[name].detach().to(torch.float16).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
+    get = reader(sd, torch.float16, "GPT-NeoX ")
     emb = _pad_rows(get("embed_in.weight", (V, d)), _rup(V, ROWPAD))
     dev = emb.device
     tied = dims.get("tied", False) or "embed_out.weight" not in sd
@@ -821,9 +827,7 @@ def neox_device_layout(state: dict, dims: dict, inv_freq: np.ndarray) -> Dict[st
 
 def load_neox_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host tensors in the device layout) of the GPT-NeoX checkpoint in model_dir."""
-    cfg = load_config(model_dir)
-    dims = neox_dims(cfg)
-    return dims, neox_device_layout(_load_state_dict(model_dir), dims, neox_inv_freq(cfg))
+    return _load_arrays(FAMILIES["gpt_neox"], model_dir)
 
 
 class NeoxScorer(_Scorer):
@@ -933,18 +937,63 @@ def rope_tables(inv_freq: np.ndarray, max_pos: int) -> Tuple[np.ndarray, np.ndar
     return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
 
 
+# What the *_dims of the families on the b2t_clm_llama_t descriptor share.  Each family calls these in the order of its checks:
+# _dims_open, its own head-dim rules, _check_gqa, (_check_moe,) _check_64, its rotary and window rules, _dims_close.
+def _dims_open(cfg: dict, types: Tuple[str, ...], act_field: str = "hidden_act", act: str = "silu", act_word: Optional[str] = None,
+               act_note: str = "") -> Tuple[str, int, int, int]:
+    """(model_type, hidden_size, heads, key / value heads) of a config whose model_type is one of `types` and whose activation
+    (config field act_field, called act_word in the message) is `act`."""
+    mt = cfg.get("model_type")
+    if mt not in types:
+        raise ValueError(f"model_type {mt!r} is not " + (f"one of {types}" if len(types) > 1 else repr(types[0])))
+    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    Hkv = int(cfg.get("num_key_value_heads") or Hq)
+    got = cfg.get(act_field, act)
+    if got != act:
+        raise ValueError(f"{mt} {act_word or act_field} {got!r} is not supported ({act} only{act_note})")
+    return mt, d, Hq, Hkv
+
+
+def _check_gqa(Hq: int, Hkv: int) -> None:
+    if Hkv < 1 or Hq % Hkv:
+        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+
+
+def _check_64(d: int, ffn: int, more: Optional[Dict[str, int]] = None) -> None:
+    """Refuses GEMM widths that are not multiples of 64: hidden_size, intermediate_size and the family's further ones, `more`,
+    which maps the wording of each in the message to its value."""
+    widths = {"hidden_size": d, "intermediate_size": ffn, **(more or {})}
+    if any(w % 64 for w in widths.values()):
+        said = [f"{k} {w}" for k, w in widths.items()]
+        raise ValueError(f"{', '.join(said[:-1])} and {said[-1]} must be multiples of 64")
+
+
+def _check_moe(ne: int, k: int, max_experts: int, max_top_k: int) -> None:
+    if not 1 <= ne <= max_experts:
+        raise ValueError(f"num_local_experts {ne} outside [1, {max_experts}]")
+    if not 1 <= k <= min(max_top_k, ne):
+        raise ValueError(f"num_experts_per_tok {k} outside [1, min({max_top_k}, num_local_experts {ne})]")
+
+
+def _dims_close(cfg: dict, d: int, Hq: int, Hkv: int, ffn: int, max_pos: int, max_positions: Optional[int], rms_eps: float,
+                **own) -> dict:
+    """The dims every family's descriptor starts from, max_pos (already lowered to the family's window) capped by max_positions
+    (default LLAMA_MAX_POSITIONS) and rms_eps the family's default; `own` adds the family's entries (or fixes `tied`)."""
+    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
+    if cap < 1:
+        raise ValueError(f"max_positions {cap} < 1")
+    dims = dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
+                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", rms_eps)),
+                tied=bool(cfg.get("tie_word_embeddings", False)))
+    dims.update(own)
+    return dims
+
+
 def llama_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     """The dimensions b2t_clm_llama_t needs, after refusing what the kernels do not run.  max_pos is the model's
     max_position_embeddings, lowered to the sliding window where one is configured and in use (within it full causal attention
     is what the model computes) and to max_positions (default LLAMA_MAX_POSITIONS), which sizes the rotary table."""
-    mt = cfg.get("model_type")
-    if mt not in LLAMA_MODEL_TYPES:
-        raise ValueError(f"model_type {mt!r} is not one of {LLAMA_MODEL_TYPES}")
-    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
-    Hkv = int(cfg.get("num_key_value_heads") or Hq)
-    act = cfg.get("hidden_act", "silu")
-    if act != "silu":
-        raise ValueError(f"{mt} activation {act!r} is not supported (silu only)")
+    mt, d, Hq, Hkv = _dims_open(cfg, LLAMA_MODEL_TYPES, act_word="activation")
     if d % Hq or d // Hq not in LLAMA_HEAD_DIMS or int(cfg.get("head_dim") or d // Hq) != d // Hq:
         hint = ""
         if mt == "qwen3":
@@ -954,11 +1003,9 @@ def llama_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
                          f"{LLAMA_HEAD_DIMS}){hint}")
     if mt in QK_NORM_MODEL_TYPES and cfg.get("attention_bias"):
         raise ValueError(f"{mt} with attention_bias=True is not supported (the q / k norm epilogue adds no bias)")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    _check_gqa(Hq, Hkv)
     ffn = int(cfg["intermediate_size"])
-    if d % 64 or ffn % 64:
-        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    _check_64(d, ffn)
     if cfg.get("mlp_bias"):
         raise ValueError("mlp_bias=True is not supported")
     rope_inv_freq(cfg)   # refuses the rotary variants the table does not describe
@@ -968,12 +1015,7 @@ def llama_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
                                                          "sliding_attention" in (cfg.get("layer_types") or ["sliding_attention"])))
     if in_use:
         max_pos = min(max_pos, int(window))
-    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
-    if cap < 1:
-        raise ValueError(f"max_positions {cap} < 1")
-    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
-                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-6)),
-                tied=bool(cfg.get("tie_word_embeddings", False)), qk_norm=mt in QK_NORM_MODEL_TYPES)
+    return _dims_close(cfg, d, Hq, Hkv, ffn, max_pos, max_positions, 1e-6, qk_norm=mt in QK_NORM_MODEL_TYPES)
 
 
 def head_dim_perm(hd: int) -> np.ndarray:
@@ -997,6 +1039,82 @@ def gate_up_row_perm(ffn: int) -> np.ndarray:
     return np.concatenate([b, ffn + b], axis=1).reshape(-1)
 
 
+# What the *_device_layout of the families on the b2t_clm_llama_t descriptor share; `get` is reader's, `sd` the state dict.
+def _trunk(sd: dict, get, dims: dict, inv_freq: np.ndarray, att: float = 1.0, head: str = "tied or untied") -> Dict[str, "object"]:
+    """The layout's entries outside the layers: embed_tokens (rows padded to 256), lm_head, final_norm_w and the fp32 rope_cos /
+    rope_sin (CPU) = rope_tables of inv_freq, times the attention factor `att` in fp32 where that is not 1.  head: "tied or
+    untied" -- the embedding itself where dims say tied or the checkpoint has no lm_head.weight, else that tensor; "untied" --
+    always lm_head.weight; "embedding" -- the embedding itself, an lm_head.weight that differs from it refused."""
+    import torch
+    V, d = dims["vocab"], dims["d_model"]
+    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
+    if head == "embedding":
+        tied = True
+        if "lm_head.weight" in sd and not torch.equal(get.raw("lm_head.weight").to(emb.dtype), emb[:V]):
+            raise ValueError("lm_head.weight differs from model.embed_tokens.weight: an untied head is not supported")
+    else:
+        tied = head != "untied" and (dims.get("tied", False) or "lm_head.weight" not in sd)
+    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
+           "final_norm_w": get("model.norm.weight", (d,))}
+    cos, sin = rope_tables(inv_freq, dims["max_pos"])
+    if att != 1.0:
+        cos, sin = cos * np.float32(att), sin * np.float32(att)
+    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    return out
+
+
+def _qkv_widths(dims: dict, hd: int) -> Dict[str, int]:
+    return {"q_proj": dims["n_heads"] * hd, "k_proj": dims["n_kv_heads"] * hd, "v_proj": dims["n_kv_heads"] * hd}
+
+
+def _layer(get, p: str, dims: dict, hd: int, qperm=None, gperm=None, norms=("input_layernorm", "post_attention_layernorm"),
+           fused: bool = False) -> Dict[str, "object"]:
+    """One layer's norm1_w, norm2_w (the checkpoint's `norms`), qkv_w (q | k | v rows, or Phi-3's `fused` qkv_proj, under the
+    row permutation qperm if there is one), o_w [d][Hq hd] and, with gperm = gate_up_row_perm (a layer with a dense MLP),
+    gate_up_w (gate | up rows, or the fused gate_up_proj, under gperm) and down_w; matrix rows padded to 256.  The family puts
+    its own entries around these."""
+    import torch
+    d, ffn = dims["d_model"], dims["ffn_dim"]
+    widths = _qkv_widths(dims, hd)
+    if fused:
+        qkv = get(p + "self_attn.qkv_proj.weight", (sum(widths.values()), d))
+    else:
+        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
+    if qperm is not None:
+        qkv = qkv[qperm].contiguous()
+    L = {"norm1_w": get(p + norms[0] + ".weight", (d,)), "norm2_w": get(p + norms[1] + ".weight", (d,)),
+         "qkv_w": _pad_rows(qkv, _rup(qkv.shape[0], ROWPAD)),
+         "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, widths["q_proj"])), _rup(d, ROWPAD))}
+    if gperm is not None:
+        if fused:
+            gate_up = get(p + "mlp.gate_up_proj.weight", (2 * ffn, d))
+        else:
+            gate_up = torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))], 0)
+        L["gate_up_w"] = _pad_rows(gate_up[gperm].contiguous(), _rup(2 * ffn, ROWPAD))
+        L["down_w"] = _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))
+    return L
+
+
+def _put_layer(out: dict, i: int, L: dict, order: Optional[Tuple[str, ...]] = None) -> None:
+    """Layer i's entries into the layout, in the family's field order (default: L's own)."""
+    for f in order or L:
+        out[f"layers.{i}.{f}"] = L[f]
+
+
+def _refuse_biases(sd: dict, prefix: str, who: str, names: Optional[Sequence[str]] = None) -> None:
+    """Refuses the first bias of a layer: any key behind `prefix` that ends in .bias, or those of `names` alone."""
+    for n in (prefix + n for n in names) if names is not None else (n for n in sd if n.startswith(prefix) and n.endswith(".bias")):
+        if n in sd:
+            raise ValueError(f"{n}: {who} are not supported")
+
+
+def _stack_padded(t, rows: int):
+    """[E][rows](...) of an expert tensor [E][r](...), r <= rows: zeros behind every expert's own rows (mixtral_strides)."""
+    out = t.new_zeros((t.shape[0], rows) + tuple(t.shape[2:]))
+    out[:, :t.shape[1]] = t
+    return out
+
+
 def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
     """Tensors in the layout of b2t_clm_llama_t from a Llama / Mistral / Qwen2 / Qwen3 state dict, on the device the state dict
     is on (the CPU for a checkpoint read from disk): fp16 embed_tokens, lm_head (the same tensor when tied), final_norm_w,
@@ -1008,40 +1126,20 @@ def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=Non
     import torch
     wdt = clm_dtype(dtype)
     sd = dict(state)
-    d, ffn, V, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"], dims["n_kv_heads"]
-    hd = d // Hq
-
-    def get(name, shape):
-        if name not in sd:
-            raise KeyError(f"checkpoint lacks {name}")
-        t = sd[name].detach().to(wdt).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
-    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
-    dev = emb.device
-    tied = dims.get("tied", False) or "lm_head.weight" not in sd
-    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
-           "final_norm_w": get("model.norm.weight", (d,))}
-    cos, sin = rope_tables(inv_freq, dims["max_pos"])
-    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    Hq, Hkv, hd = dims["n_heads"], dims["n_kv_heads"], dims["d_model"] // dims["n_heads"]
+    get = reader(sd, wdt)
+    out = _trunk(sd, get, dims, inv_freq)
+    dev = out["embed_tokens"].device
     qperm = torch.from_numpy(qkv_row_perm(Hq, Hkv, hd)).to(dev)
     hperm = torch.from_numpy(head_dim_perm(hd)).to(dev)
     qk_norm = bool(dims.get("qk_norm", False))
-    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
-    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    gperm = torch.from_numpy(gate_up_row_perm(dims["ffn_dim"])).to(dev)
+    widths = _qkv_widths(dims, hd)
     for i in range(dims["n_layers"]):
         p = f"model.layers.{i}."
-        for n in ("self_attn.o_proj.bias", "mlp.gate_proj.bias", "mlp.up_proj.bias", "mlp.down_proj.bias"):
-            if p + n in sd:
-                raise ValueError(f"{p + n}: biases other than q / k / v's are not supported")
-        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
-        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
-             "qkv_w": _pad_rows(qkv[qperm].contiguous(), _rup(qkv.shape[0], ROWPAD)),
-             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, d)), _rup(d, ROWPAD)),
-             "gate_up_w": _pad_rows(torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))],
-                                              0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
-             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
+        _refuse_biases(sd, p, "biases other than q / k / v's",
+                       ("self_attn.o_proj.bias", "mlp.gate_proj.bias", "mlp.up_proj.bias", "mlp.down_proj.bias"))
+        L = _layer(get, p, dims, hd, qperm, gperm)
         if qk_norm:
             if any(p + f"self_attn.{n}.bias" in sd for n in widths):
                 raise ValueError(f"{p}self_attn: q / k / v biases beside q / k norms are not supported")
@@ -1053,8 +1151,7 @@ def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=Non
             zero = lambda w: torch.zeros(w, dtype=wdt, device=dev)
             L["qkv_b"] = torch.cat([get(p + f"self_attn.{n}.bias", (w,)) if p + f"self_attn.{n}.bias" in sd else zero(w)
                                     for n, w in widths.items()])[qperm].contiguous()
-        for f, t in L.items():
-            out[f"layers.{i}.{f}"] = t
+        _put_layer(out, i, L)
     return out
 
 
@@ -1065,10 +1162,7 @@ def load_config(model_dir: str) -> dict:
 
 def load_llama_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host tensors in the device layout) of the Llama-family checkpoint in model_dir; dtype as clm_dtype reads it."""
-    cfg = load_config(model_dir)
-    dims = llama_dims(cfg, max_positions)
-    wdt = clm_dtype(dtype, cfg)
-    return dims, llama_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
+    return _load_arrays(FAMILIES["llama"], model_dir, max_positions, dtype)
 
 
 class LlamaScorer(_Scorer):
@@ -1094,11 +1188,19 @@ class LlamaScorer(_Scorer):
     _SIZES = "b2t_clm_llama_"   # the family's size functions: _SIZES + ws_bytes / tree_ws_bytes / cache_kv_bytes / tree_cached_ws_bytes
     _NO_CACHE = "use_cache=True on a scorer built without a context cache (context_cache_tokens)"
     _size_args = ()   # what the family's workspace size functions take between the model and the sizes (Mixtral: its MoE descriptor)
+    _CACHE_SIZES = None   # where the cache is another family's (Mixtral: Llama's), that family's _SIZES: its cache_kv_bytes takes
+    #                       the model alone.  None: _SIZES + cache_kv_bytes, with _size_args
+    _OWN_ARRAYS = ()      # suffixes of the arrays that _point copies itself (they are not in the compute dtype)
 
+    # A family is a subclass with class data and two hooks.  The constructor runs, in this order: _describe (which raises the
+    # family's KeyError before anything else happens); the dtype / cache and device refusals; the copy of the weights to the
+    # device, each checked against the dtype; the b2t_clm_llama_t; _point; the cache's allocation, which sizes it through
+    # _size_args.  Every ctypes array and struct a descriptor points at stays an attribute of the scorer.
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0, dtype=None):
         import torch
         import b2t_native as N
+        self._describe(dims, arrays, dtype, context_cache_tokens)
         self.dtype = clm_dtype(dtype)
         self._suffix = "bf16" if self.dtype == torch.bfloat16 else "f16"
         llama_check_dtype_cache(self.dtype, context_cache_tokens)
@@ -1107,7 +1209,7 @@ class LlamaScorer(_Scorer):
         self.check_cache_device(self.device, context_cache_tokens)   # before the weights are copied
         self.share_prefixes = bool(share_prefixes)
         self.last_stats = None
-        self.w = {k: v.to(self.device).contiguous() for k, v in arrays.items()}
+        self.w = {k: v.to(self.device).contiguous() for k, v in arrays.items() if not k.endswith(self._OWN_ARRAYS)}
         if dims.get("tied", False) or arrays["lm_head"] is arrays["embed_tokens"]:
             self.w["lm_head"] = self.w["embed_tokens"]
         for k, v in self.w.items():
@@ -1123,16 +1225,27 @@ class LlamaScorer(_Scorer):
                                    dims["vocab"], dims["max_pos"], dims["rms_eps"], self.w["embed_tokens"].data_ptr(),
                                    self.w["lm_head"].data_ptr(), self.w["final_norm_w"].data_ptr(),
                                    self.w["rope_cos"].data_ptr(), self.w["rope_sin"].data_ptr(), self._layers)
-        # Qwen3: the per-layer q / k norm weights (b2t_clm_qknorm_t) go in front of the lists
-        self._family, self._qk = "llama", ()
-        if dims["n_layers"] > 0 and "layers.0.q_norm_w" in self.w:
-            self._qkn = (N.ClmQkNorm * dims["n_layers"])()
-            for i in range(dims["n_layers"]):
-                self._qkn[i].q_norm_w = self.w[f"layers.{i}.q_norm_w"].data_ptr()
-                self._qkn[i].k_norm_w = self.w[f"layers.{i}.k_norm_w"].data_ptr()
-            self._family, self._qk = "qwen3", (self._qkn,)
+        self._point(arrays)
         self._ws = None
-        self._alloc_cache(context_cache_tokens)
+        self._alloc_cache(context_cache_tokens if self._CONTEXT_CACHE else 0)
+
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
+        """The first hook, before anything is copied: refuses dims / arrays that are not the family's (KeyError), builds the
+        family's descriptor from dims / dtype with its per-layer arrays still empty, and sets _family (the entry points are
+        b2t_clm_<_family>_score_*), _qk (what they take between the model and the lists) and _size_args.
+        Here: arrays that hold layers.<i>.q_norm_w / k_norm_w are Qwen3's, whose b2t_clm_qknorm_t list goes in front of the lists."""
+        import b2t_native as N
+        self._family, self._qk = "llama", ()
+        if dims["n_layers"] > 0 and "layers.0.q_norm_w" in arrays:
+            self._qkn = (N.ClmQkNorm * dims["n_layers"])()
+            self._family, self._qk = "qwen3", (self._qkn,)
+
+    def _point(self, arrays):
+        """The second hook, once self.w holds the weights on the device: fills the family's per-layer pointers (and copies
+        the arrays named by _OWN_ARRAYS into self.w)."""
+        for i in range(len(getattr(self, "_qkn", ()))):
+            self._qkn[i].q_norm_w = self.w[f"layers.{i}.q_norm_w"].data_ptr()
+            self._qkn[i].k_norm_w = self.w[f"layers.{i}.k_norm_w"].data_ptr()
 
     @staticmethod
     def check_cache_device(device, context_cache_tokens) -> None:
@@ -1144,7 +1257,8 @@ class LlamaScorer(_Scorer):
 
     def _cache_kv_bytes(self, lib, cap):
         import ctypes as C
-        return getattr(lib, self._SIZES + "cache_kv_bytes")(C.byref(self.desc), cap)
+        prefix, args = (self._SIZES, self._size_args) if self._CACHE_SIZES is None else (self._CACHE_SIZES, ())
+        return getattr(lib, prefix + "cache_kv_bytes")(C.byref(self.desc), *args, cap)
 
     def _sizes(self, lib, path, ids, off):
         import ctypes as C
@@ -1176,37 +1290,24 @@ class LlamaScorer(_Scorer):
 
 # ---- OLMo-2 (HF Olmo2ForCausalLM): whole-row q / k norms and a post-norm layer ---------------------------------------------
 OLMO2_HEAD_DIMS = (64, 128)
+_OLMO2_ORDER = ("norm1_w", "norm2_w", "qkv_w", "q_norm_w", "k_norm_w", "o_w", "gate_up_w", "down_w")   # the layout's per layer
 
 
 def olmo2_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     """The dimensions b2t_clm_llama_t needs for an "olmo2" config, after refusing, by the field's name, what the kernels do not
     run.  max_pos is max_position_embeddings lowered to max_positions (default LLAMA_MAX_POSITIONS), which sizes the rotary
     table.  "olmo" (no q / k norm, a LayerNorm without weights) and "olmo3" (sliding-window layers) are other forwards."""
-    mt = cfg.get("model_type")
-    if mt != "olmo2":
-        raise ValueError(f"model_type {mt!r} is not 'olmo2'")
-    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
-    Hkv = int(cfg.get("num_key_value_heads") or Hq)
-    act = cfg.get("hidden_act", "silu")
-    if act != "silu":
-        raise ValueError(f"olmo2 hidden_act {act!r} is not supported (silu only)")
+    _, d, Hq, Hkv = _dims_open(cfg, ("olmo2",))
     if d % Hq or d // Hq not in OLMO2_HEAD_DIMS or int(cfg.get("head_dim") or d // Hq) != d // Hq:
         raise ValueError(f"head dim {cfg.get('head_dim') or d}/{Hq} is not supported (hidden_size / num_attention_heads, one of "
                          f"{OLMO2_HEAD_DIMS})")
     if cfg.get("attention_bias"):
         raise ValueError("olmo2 with attention_bias=True is not supported (the QKV GEMM's fp32 epilogue adds no bias)")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    _check_gqa(Hq, Hkv)
     ffn = int(cfg["intermediate_size"])
-    if d % 64 or ffn % 64:
-        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    _check_64(d, ffn)
     rope_inv_freq(cfg)   # refuses a rope_type other than default / llama3
-    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
-    if cap < 1:
-        raise ValueError(f"max_positions {cap} < 1")
-    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
-                vocab=int(cfg["vocab_size"]), max_pos=min(int(cfg["max_position_embeddings"]), cap),
-                rms_eps=float(cfg.get("rms_norm_eps", 1e-5)), tied=bool(cfg.get("tie_word_embeddings", False)))
+    return _dims_close(cfg, d, Hq, Hkv, ffn, int(cfg["max_position_embeddings"]), max_positions, 1e-5)
 
 
 def olmo2_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
@@ -1216,53 +1317,26 @@ def olmo2_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=Non
     kernel that sees whole heads, so there is no head_dim_perm); gate / up rows are interleaved as for Llama; any bias is
     refused."""
     import torch
-    wdt = clm_dtype(dtype)
     sd = dict(state)
-    d, ffn, V, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"], dims["n_kv_heads"]
-    hd = d // Hq
-
-    def get(name, shape):
-        if name not in sd:
-            raise KeyError(f"checkpoint lacks {name}")
-        t = sd[name].detach().to(wdt).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
-    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
-    tied = dims.get("tied", False) or "lm_head.weight" not in sd
-    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
-           "final_norm_w": get("model.norm.weight", (d,))}
-    cos, sin = rope_tables(inv_freq, dims["max_pos"])
-    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
-    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(emb.device)
-    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    Hq, Hkv, hd = dims["n_heads"], dims["n_kv_heads"], dims["d_model"] // dims["n_heads"]
+    get = reader(sd, clm_dtype(dtype))
+    out = _trunk(sd, get, dims, inv_freq)
+    gperm = torch.from_numpy(gate_up_row_perm(dims["ffn_dim"])).to(out["embed_tokens"].device)
     for i in range(dims["n_layers"]):
         p = f"model.layers.{i}."
-        for n in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
-                  "mlp.down_proj"):
-            if p + n + ".bias" in sd:
-                raise ValueError(f"{p + n}.bias: OLMo-2 biases are not supported")
-        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
-        L = {"norm1_w": get(p + "post_attention_layernorm.weight", (d,)),
-             "norm2_w": get(p + "post_feedforward_layernorm.weight", (d,)),
-             "qkv_w": _pad_rows(qkv, _rup(qkv.shape[0], ROWPAD)),
-             "q_norm_w": get(p + "self_attn.q_norm.weight", (Hq * hd,)),
-             "k_norm_w": get(p + "self_attn.k_norm.weight", (Hkv * hd,)),
-             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, d)), _rup(d, ROWPAD)),
-             "gate_up_w": _pad_rows(torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))],
-                                              0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
-             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
-        for f, t in L.items():
-            out[f"layers.{i}.{f}"] = t
+        _refuse_biases(sd, p, "OLMo-2 biases", [n + ".bias" for n in (
+            "self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
+            "mlp.down_proj")])
+        L = _layer(get, p, dims, hd, None, gperm, norms=("post_attention_layernorm", "post_feedforward_layernorm"))
+        L["q_norm_w"] = get(p + "self_attn.q_norm.weight", (Hq * hd,))
+        L["k_norm_w"] = get(p + "self_attn.k_norm.weight", (Hkv * hd,))
+        _put_layer(out, i, L, _OLMO2_ORDER)
     return out
 
 
 def load_olmo2_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host tensors in the device layout) of the OLMo-2 checkpoint in model_dir; dtype as clm_dtype reads it."""
-    cfg = load_config(model_dir)
-    dims = olmo2_dims(cfg, max_positions)
-    wdt = clm_dtype(dtype, cfg)
-    return dims, olmo2_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
+    return _load_arrays(FAMILIES["olmo2"], model_dir, max_positions, dtype)
 
 
 class Olmo2Scorer(LlamaScorer):
@@ -1274,11 +1348,10 @@ class Olmo2Scorer(LlamaScorer):
     _WS_BYTES = "b2t_clm_olmo2_ws_bytes"
     _SIZES = "b2t_clm_olmo2_"
 
-    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
-                 context_cache_tokens: int = 0, dtype=None):
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
         if dims["n_layers"] > 0 and "layers.0.q_norm_w" not in arrays:
             raise KeyError("Olmo2Scorer: the arrays lack layers.<i>.q_norm_w / k_norm_w (olmo2_device_layout makes them)")
-        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
+        super()._describe(dims, arrays, dtype, context_cache_tokens)   # the norm weights' list, which _point fills
         self._family = "olmo2"
         if not self._qk:     # no layers: the calls still take the array argument
             self._qk = (None,)
@@ -1292,41 +1365,24 @@ def mixtral_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     """The dimensions b2t_clm_llama_t and b2t_clm_moe_t need for a "mixtral" config, after refusing, by the field's name, what the
     kernels do not run.  max_pos is max_position_embeddings lowered to the sliding window where one is configured (as for
     Mistral: within it full causal attention is what the model computes) and to max_positions (default LLAMA_MAX_POSITIONS)."""
-    mt = cfg.get("model_type")
-    if mt != "mixtral":
-        raise ValueError(f"model_type {mt!r} is not 'mixtral'")
-    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
-    Hkv = int(cfg.get("num_key_value_heads") or Hq)
-    act = cfg.get("hidden_act", "silu")
-    if act != "silu":
-        raise ValueError(f"mixtral hidden_act {act!r} is not supported (silu only)")
+    _, d, Hq, Hkv = _dims_open(cfg, ("mixtral",))
     if d % Hq or int(cfg.get("head_dim") or d // Hq) != d // Hq:
         raise ValueError(f"head_dim {cfg.get('head_dim')} is not hidden_size / num_attention_heads = {d}/{Hq}")
     if d // Hq not in LLAMA_HEAD_DIMS:
         raise ValueError(f"head_dim {d // Hq} is not supported (one of {LLAMA_HEAD_DIMS})")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    _check_gqa(Hq, Hkv)
     ne, k = int(cfg.get("num_local_experts", 8)), int(cfg.get("num_experts_per_tok", 2))
-    if not 1 <= ne <= MIXTRAL_MAX_EXPERTS:
-        raise ValueError(f"num_local_experts {ne} outside [1, {MIXTRAL_MAX_EXPERTS}]")
-    if not 1 <= k <= min(MIXTRAL_MAX_TOP_K, ne):
-        raise ValueError(f"num_experts_per_tok {k} outside [1, min({MIXTRAL_MAX_TOP_K}, num_local_experts {ne})]")
+    _check_moe(ne, k, MIXTRAL_MAX_EXPERTS, MIXTRAL_MAX_TOP_K)
     for f in ("attention_bias", "mlp_bias"):
         if cfg.get(f):
             raise ValueError(f"mixtral with {f}=True is not supported (no bias anywhere)")
     ffn = int(cfg["intermediate_size"])
-    if d % 64 or ffn % 64:
-        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    _check_64(d, ffn)
     rope_inv_freq(cfg)   # refuses a rope_type other than default / llama3
     max_pos = int(cfg["max_position_embeddings"])
     if cfg.get("sliding_window") is not None:
         max_pos = min(max_pos, int(cfg["sliding_window"]))
-    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
-    if cap < 1:
-        raise ValueError(f"max_positions {cap} < 1")
-    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
-                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-5)),
-                tied=bool(cfg.get("tie_word_embeddings", False)), n_experts=ne, top_k=k)
+    return _dims_close(cfg, d, Hq, Hkv, ffn, max_pos, max_positions, 1e-5, n_experts=ne, top_k=k)
 
 
 def mixtral_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None) -> Dict[str, "object"]:
@@ -1338,35 +1394,19 @@ def mixtral_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=N
     and the fused one (mlp.gate.weight, mlp.experts.gate_up_proj [E][2F][d] with gate rows then up rows, mlp.experts.down_proj
     [E][d][F]).  Any bias in a layer is refused."""
     import torch
-    wdt = clm_dtype(dtype)
     sd = dict(state)
-    d, ffn, V, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["vocab"], dims["n_heads"], dims["n_kv_heads"]
+    d, ffn, Hq, Hkv = dims["d_model"], dims["ffn_dim"], dims["n_heads"], dims["n_kv_heads"]
     ne, hd = dims["n_experts"], dims["d_model"] // dims["n_heads"]
-
-    def get(name, shape):
-        if name not in sd:
-            raise KeyError(f"checkpoint lacks {name}")
-        t = sd[name].detach().to(wdt).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
-    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
-    dev = emb.device
-    tied = dims.get("tied", False) or "lm_head.weight" not in sd
-    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
-           "final_norm_w": get("model.norm.weight", (d,))}
-    cos, sin = rope_tables(inv_freq, dims["max_pos"])
-    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    get = reader(sd, clm_dtype(dtype))
+    out = _trunk(sd, get, dims, inv_freq)
+    dev = out["embed_tokens"].device
     qperm = torch.from_numpy(qkv_row_perm(Hq, Hkv, hd)).to(dev)
     gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
-    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
     gus, dns = mixtral_strides(dims)
     for i in range(dims["n_layers"]):
         p = f"model.layers.{i}."
-        for n in sd:
-            if n.startswith(p) and n.endswith(".bias"):
-                raise ValueError(f"{n}: Mixtral biases are not supported")
-        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
+        _refuse_biases(sd, p, "Mixtral biases")
+        L = _layer(get, p, dims, hd, qperm)
         if p + "mlp.experts.gate_up_proj" in sd:     # the fused spelling
             router = get(p + "mlp.gate.weight", (ne, d))
             gate_up = get(p + "mlp.experts.gate_up_proj", (ne, 2 * ffn, d))
@@ -1377,16 +1417,8 @@ def mixtral_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=N
             gate_up = torch.stack([torch.cat([get(m + f"experts.{e}.w1.weight", (ffn, d)), get(m + f"experts.{e}.w3.weight", (ffn, d))], 0)
                                    for e in range(ne)])
             down = torch.stack([get(m + f"experts.{e}.w2.weight", (d, ffn)) for e in range(ne)])
-        gu = gate_up.new_zeros((ne, gus, d))
-        gu[:, :2 * ffn] = gate_up[:, gperm]
-        dn = down.new_zeros((ne, dns, ffn))
-        dn[:, :d] = down
-        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
-             "qkv_w": _pad_rows(qkv[qperm].contiguous(), _rup(qkv.shape[0], ROWPAD)),
-             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, d)), _rup(d, ROWPAD)),
-             "router_w": router, "gate_up_w": gu, "down_w": dn}
-        for f, t in L.items():
-            out[f"layers.{i}.{f}"] = t
+        L.update(router_w=router, gate_up_w=_stack_padded(gate_up[:, gperm], gus), down_w=_stack_padded(down, dns))
+        _put_layer(out, i, L)
     return out
 
 
@@ -1397,10 +1429,7 @@ def mixtral_strides(dims: dict) -> Tuple[int, int]:
 
 def load_mixtral_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host tensors in the device layout) of the Mixtral checkpoint in model_dir; dtype as clm_dtype reads it."""
-    cfg = load_config(model_dir)
-    dims = mixtral_dims(cfg, max_positions)
-    wdt = clm_dtype(dtype, cfg)
-    return dims, mixtral_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
+    return _load_arrays(FAMILIES["mixtral"], model_dir, max_positions, dtype)
 
 
 class MixtralScorer(LlamaScorer):
@@ -1412,32 +1441,29 @@ class MixtralScorer(LlamaScorer):
 
     _WS_BYTES = "b2t_clm_mixtral_ws_bytes"
     _SIZES = "b2t_clm_mixtral_"
+    _CACHE_SIZES = "b2t_clm_llama_"
 
-    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
-                 context_cache_tokens: int = 0, dtype=None):
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
         import ctypes as C
         import b2t_native as N
         if "n_experts" not in dims or (dims["n_layers"] > 0 and "layers.0.router_w" not in arrays):
             raise KeyError("MixtralScorer: dims lack n_experts / top_k or the arrays layers.<i>.router_w (mixtral_dims and "
                            "mixtral_device_layout make them)")
-        # the descriptor first: the cache allocation of the base class does not need it, the size functions do
         self._routers = (C.c_void_p * max(1, dims["n_layers"]))()
         gus, dns = mixtral_strides(dims)
         self._moe = N.ClmMoe(dims["n_experts"], dims["top_k"], self._routers, gus, dns, None)
         self._size_args = (self._moe,)
-        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
-        for i in range(dims["n_layers"]):
-            self._routers[i] = self.w[f"layers.{i}.router_w"].data_ptr()
         self._family, self._qk = "mixtral", (self._moe,)
 
-    def _cache_kv_bytes(self, lib, cap):
-        import ctypes as C
-        return lib.b2t_clm_llama_cache_kv_bytes(C.byref(self.desc), cap)
+    def _point(self, arrays):
+        for i in range(self.dims["n_layers"]):
+            self._routers[i] = self.w[f"layers.{i}.router_w"].data_ptr()
 
 
 # ---- Gemma-2 (HF Gemma2ForCausalLM): a head dim of its own, soft caps, four norms per layer, GeGLU ---------------------------
 GEMMA2_HEAD_DIMS = (128, 256)
 _GEMMA2_LAYER_FIELDS = ("pre_ffn_norm_w", "post_ffn_norm_w")
+_GEMMA2_ORDER = ("norm1_w", "norm2_w") + _GEMMA2_LAYER_FIELDS + ("qkv_w", "o_w", "gate_up_w", "down_w")   # the layout's per layer
 
 
 def gemma2_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
@@ -1446,14 +1472,7 @@ def gemma2_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     27b).  max_pos is max_position_embeddings lowered to sliding_window -- within the window a sliding layer computes what a full
     one does, as for Mistral -- and to max_positions (default LLAMA_MAX_POSITIONS), which sizes the rotary table.  A cap of None
     in the config means off (0).  "gemma" and "gemma3" are other forwards."""
-    mt = cfg.get("model_type")
-    if mt != "gemma2":
-        raise ValueError(f"model_type {mt!r} is not 'gemma2'")
-    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
-    Hkv = int(cfg.get("num_key_value_heads") or Hq)
-    act = cfg.get("hidden_activation", "gelu_pytorch_tanh")
-    if act != "gelu_pytorch_tanh":
-        raise ValueError(f"gemma2 hidden_activation {act!r} is not supported (gelu_pytorch_tanh only)")
+    _, d, Hq, Hkv = _dims_open(cfg, ("gemma2",), "hidden_activation", "gelu_pytorch_tanh")
     if cfg.get("attention_bias"):
         raise ValueError("gemma2 with attention_bias=True is not supported (no bias anywhere)")
     if cfg.get("use_bidirectional_attention"):
@@ -1466,12 +1485,9 @@ def gemma2_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     hd = int(cfg.get("head_dim") or 256)
     if hd not in GEMMA2_HEAD_DIMS:
         raise ValueError(f"head_dim {hd} is not supported (one of {GEMMA2_HEAD_DIMS})")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    _check_gqa(Hq, Hkv)
     ffn = int(cfg["intermediate_size"])
-    if d % 64 or ffn % 64 or (Hq * hd) % 64:
-        raise ValueError(f"hidden_size {d}, intermediate_size {ffn} and num_attention_heads * head_dim {Hq * hd} must be multiples "
-                         f"of 64")
+    _check_64(d, ffn, {"num_attention_heads * head_dim": Hq * hd})
     rope_inv_freq(cfg)   # refuses partial rotary embeddings
     caps = {}
     for f in ("attn_logit_softcapping", "final_logit_softcapping"):
@@ -1485,13 +1501,8 @@ def gemma2_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     max_pos = int(cfg["max_position_embeddings"])
     if cfg.get("sliding_window") is not None:
         max_pos = min(max_pos, int(cfg["sliding_window"]))
-    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
-    if cap < 1:
-        raise ValueError(f"max_positions {cap} < 1")
-    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
-                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-6)), tied=True,
-                head_dim=hd, q_scale=qpas ** -0.5, attn_cap=caps["attn_logit_softcapping"],
-                final_cap=caps["final_logit_softcapping"])
+    return _dims_close(cfg, d, Hq, Hkv, ffn, max_pos, max_positions, 1e-6, tied=True, head_dim=hd, q_scale=qpas ** -0.5,
+                       attn_cap=caps["attn_logit_softcapping"], final_cap=caps["final_logit_softcapping"])
 
 
 def gemma2_head_perm(hd: int) -> np.ndarray:
@@ -1515,55 +1526,28 @@ def gemma2_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=No
     post_ffn_norm_w the two feed-forward norms, all as the checkpoint stores them (the kernels add the 1); gate / up rows are
     interleaved as for Llama; the head is the embedding; any bias and an lm_head of its own are refused."""
     import torch
-    wdt = clm_dtype(dtype)
     sd = dict(state)
-    d, ffn, V, Hq, Hkv, hd = (dims[k] for k in ("d_model", "ffn_dim", "vocab", "n_heads", "n_kv_heads", "head_dim"))
-
-    def get(name, shape):
-        if name not in sd:
-            raise KeyError(f"checkpoint lacks {name}")
-        t = sd[name].detach().to(wdt).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
-    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
-    dev = emb.device
-    if "lm_head.weight" in sd and not torch.equal(sd["lm_head.weight"].detach().to(wdt), emb[:V]):
-        raise ValueError("lm_head.weight differs from model.embed_tokens.weight: an untied head is not supported")
-    out = {"embed_tokens": emb, "lm_head": emb, "final_norm_w": get("model.norm.weight", (d,))}
-    cos, sin = rope_tables(inv_freq, dims["max_pos"])
-    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos), torch.from_numpy(sin)
+    d, Hq, Hkv, hd = (dims[k] for k in ("d_model", "n_heads", "n_kv_heads", "head_dim"))
+    get = reader(sd, clm_dtype(dtype))
+    out = _trunk(sd, get, dims, inv_freq, head="embedding")
+    dev = out["embed_tokens"].device
     hp = gemma2_head_perm(hd)
     qperm = torch.from_numpy(np.concatenate([h * hd + hp for h in range(Hq + Hkv)] +
                                             [np.arange((Hq + Hkv) * hd, (Hq + 2 * Hkv) * hd)])).to(dev)
-    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
-    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
+    gperm = torch.from_numpy(gate_up_row_perm(dims["ffn_dim"])).to(dev)
     for i in range(dims["n_layers"]):
         p = f"model.layers.{i}."
-        for n in sd:
-            if n.startswith(p) and n.endswith(".bias"):
-                raise ValueError(f"{n}: Gemma-2 biases are not supported")
-        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
-        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)),
-             "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
-             "pre_ffn_norm_w": get(p + "pre_feedforward_layernorm.weight", (d,)),
-             "post_ffn_norm_w": get(p + "post_feedforward_layernorm.weight", (d,)),
-             "qkv_w": _pad_rows(qkv[qperm].contiguous(), _rup(qkv.shape[0], ROWPAD)),
-             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, Hq * hd)), _rup(d, ROWPAD)),
-             "gate_up_w": _pad_rows(torch.cat([get(p + "mlp.gate_proj.weight", (ffn, d)), get(p + "mlp.up_proj.weight", (ffn, d))],
-                                              0)[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
-             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
-        for f, t in L.items():
-            out[f"layers.{i}.{f}"] = t
+        _refuse_biases(sd, p, "Gemma-2 biases")
+        L = _layer(get, p, dims, hd, qperm, gperm)
+        L["pre_ffn_norm_w"] = get(p + "pre_feedforward_layernorm.weight", (d,))
+        L["post_ffn_norm_w"] = get(p + "post_feedforward_layernorm.weight", (d,))
+        _put_layer(out, i, L, _GEMMA2_ORDER)
     return out
 
 
 def load_gemma2_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host tensors in the device layout) of the Gemma-2 checkpoint in model_dir; dtype as clm_dtype reads it."""
-    cfg = load_config(model_dir)
-    dims = gemma2_dims(cfg, max_positions)
-    wdt = clm_dtype(dtype, cfg)
-    return dims, gemma2_device_layout(_load_state_dict(model_dir), dims, rope_inv_freq(cfg), wdt)
+    return _load_arrays(FAMILIES["gemma2"], model_dir, max_positions, dtype)
 
 
 class Gemma2Scorer(LlamaScorer):
@@ -1576,26 +1560,21 @@ class Gemma2Scorer(LlamaScorer):
     _WS_BYTES = "b2t_clm_gemma2_ws_bytes"
     _SIZES = "b2t_clm_gemma2_"
 
-    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
-                 context_cache_tokens: int = 0, dtype=None):
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
         import b2t_native as N
         if "head_dim" not in dims or (dims["n_layers"] > 0 and "layers.0.pre_ffn_norm_w" not in arrays):
             raise KeyError("Gemma2Scorer: dims lack head_dim or the arrays layers.<i>.pre_ffn_norm_w / post_ffn_norm_w (gemma2_dims "
                            "and gemma2_device_layout make them)")
-        # the descriptor first: the cache allocation of the base class sizes the cache with it
         self._g2_layers = (N.ClmGemma2Layer * max(1, dims["n_layers"]))()
         self._g2 = N.ClmGemma2(dims["head_dim"], dims["q_scale"], dims["attn_cap"], dims["final_cap"],
                                gemma2_embed_scale(dims["d_model"], dtype), self._g2_layers)
         self._size_args = (self._g2,)
-        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
-        for i in range(dims["n_layers"]):
-            for f in _GEMMA2_LAYER_FIELDS:
-                setattr(self._g2_layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
         self._family, self._qk = "gemma2", (self._g2,)
 
-    def _cache_kv_bytes(self, lib, cap):
-        import ctypes as C
-        return lib.b2t_clm_gemma2_cache_kv_bytes(C.byref(self.desc), self._g2, cap)
+    def _point(self, arrays):
+        for i in range(self.dims["n_layers"]):
+            for f in _GEMMA2_LAYER_FIELDS:
+                setattr(self._g2_layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
 
 
 # ---- Phi-3 (HF Phi3ForCausalLM): head dim 96, partial rotary, LongRoPE, fused qkv_proj / gate_up_proj ------------------------
@@ -1661,14 +1640,7 @@ def phi3_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     sequence; beyond it HF switches the whole call to long_factor, so that a row's score would depend on the longest sequence of
     its batch: such lengths are refused like lengths beyond a sliding window.  "phi", "phimoe" and "phi3small" are other
     forwards."""
-    mt = cfg.get("model_type")
-    if mt != "phi3":
-        raise ValueError(f"model_type {mt!r} is not 'phi3'")
-    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
-    Hkv = int(cfg.get("num_key_value_heads") or Hq)
-    act = cfg.get("hidden_act", "silu")
-    if act != "silu":
-        raise ValueError(f"phi3 hidden_act {act!r} is not supported (silu only)")
+    _, d, Hq, Hkv = _dims_open(cfg, ("phi3",))
     if not cfg.get("head_dim") and d % Hq:
         raise ValueError(f"hidden_size {d} is not a multiple of num_attention_heads {Hq}")
     hd, rot = _phi3_head_rot(cfg)
@@ -1676,12 +1648,10 @@ def phi3_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
         raise ValueError(f"head_dim {hd} (head_dim, or hidden_size / num_attention_heads) is not supported (one of {PHI3_HEAD_DIMS})")
     if rot < 2 or rot > hd or rot % 2:
         raise ValueError(f"partial_rotary_factor gives {rot} rotary dims of head_dim {hd}: not an even number in [2, {hd}]")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    _check_gqa(Hq, Hkv)
     ffn = int(cfg["intermediate_size"])
-    if d % 64 or ffn % 64 or (Hq * hd) % 64 or ((Hq + 2 * Hkv) * hd) % 64:
-        raise ValueError(f"hidden_size {d}, intermediate_size {ffn}, num_attention_heads * head_dim {Hq * hd} and "
-                         f"(num_attention_heads + 2 num_key_value_heads) * head_dim {(Hq + 2 * Hkv) * hd} must be multiples of 64")
+    _check_64(d, ffn, {"num_attention_heads * head_dim": Hq * hd,
+                       "(num_attention_heads + 2 num_key_value_heads) * head_dim": (Hq + 2 * Hkv) * hd})
     phi3_rope(cfg)   # refuses the rope types and factor lists the table does not describe
     rp = _phi3_rope_parameters(cfg)
     max_pos = int(cfg["max_position_embeddings"])
@@ -1689,12 +1659,7 @@ def phi3_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
         max_pos = min(max_pos, int(cfg["sliding_window"]))
     if rp["rope_type"] == "longrope" and rp.get("original_max_position_embeddings"):
         max_pos = min(max_pos, int(rp["original_max_position_embeddings"]))
-    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
-    if cap < 1:
-        raise ValueError(f"max_positions {cap} < 1")
-    return dict(n_layers=int(cfg["num_hidden_layers"]), d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn,
-                vocab=int(cfg["vocab_size"]), max_pos=min(max_pos, cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-5)),
-                tied=bool(cfg.get("tie_word_embeddings", False)), head_dim=hd, rotary_dims=rot)
+    return _dims_close(cfg, d, Hq, Hkv, ffn, max_pos, max_positions, 1e-5, head_dim=hd, rotary_dims=rot)
 
 
 def phi3_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float], dtype=None) -> Dict[str, "object"]:
@@ -1706,49 +1671,23 @@ def phi3_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float], 
     its attention factor in fp32 (rope = phi3_rope(cfg)); any bias in a layer is refused; the head is tied or untied as for
     Llama."""
     import torch
-    wdt = clm_dtype(dtype)
     sd = dict(state)
-    d, ffn, V, Hq, Hkv, hd = (dims[k] for k in ("d_model", "ffn_dim", "vocab", "n_heads", "n_kv_heads", "head_dim"))
+    get = reader(sd, clm_dtype(dtype))
     inv_freq, att = rope
     if len(inv_freq) != dims["rotary_dims"] // 2:
         raise ValueError(f"inv_freq has {len(inv_freq)} entries, rotary_dims {dims['rotary_dims']} need {dims['rotary_dims'] // 2}")
-
-    def get(name, shape):
-        if name not in sd:
-            raise KeyError(f"checkpoint lacks {name}")
-        t = sd[name].detach().to(wdt).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
-    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
-    tied = dims.get("tied", False) or "lm_head.weight" not in sd
-    out = {"embed_tokens": emb, "lm_head": emb if tied else _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
-           "final_norm_w": get("model.norm.weight", (d,))}
-    cos, sin = rope_tables(inv_freq, dims["max_pos"])
-    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos * np.float32(att)), torch.from_numpy(sin * np.float32(att))
-    gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(emb.device)
-    qw = (Hq + 2 * Hkv) * hd
+    out = _trunk(sd, get, dims, inv_freq, att)
+    gperm = torch.from_numpy(gate_up_row_perm(dims["ffn_dim"])).to(out["embed_tokens"].device)
     for i in range(dims["n_layers"]):
         p = f"model.layers.{i}."
-        for n in sd:
-            if n.startswith(p) and n.endswith(".bias"):
-                raise ValueError(f"{n}: Phi-3 biases are not supported")
-        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
-             "qkv_w": _pad_rows(get(p + "self_attn.qkv_proj.weight", (qw, d)), _rup(qw, ROWPAD)),
-             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, Hq * hd)), _rup(d, ROWPAD)),
-             "gate_up_w": _pad_rows(get(p + "mlp.gate_up_proj.weight", (2 * ffn, d))[gperm].contiguous(), _rup(2 * ffn, ROWPAD)),
-             "down_w": _pad_rows(get(p + "mlp.down_proj.weight", (d, ffn)), _rup(d, ROWPAD))}
-        for f, t in L.items():
-            out[f"layers.{i}.{f}"] = t
+        _refuse_biases(sd, p, "Phi-3 biases")
+        _put_layer(out, i, _layer(get, p, dims, dims["head_dim"], None, gperm, fused=True))
     return out
 
 
 def load_phi3_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host tensors in the device layout) of the Phi-3 checkpoint in model_dir; dtype as clm_dtype reads it."""
-    cfg = load_config(model_dir)
-    dims = phi3_dims(cfg, max_positions)
-    wdt = clm_dtype(dtype, cfg)
-    return dims, phi3_device_layout(_load_state_dict(model_dir), dims, phi3_rope(cfg), wdt)
+    return _load_arrays(FAMILIES["phi3"], model_dir, max_positions, dtype)
 
 
 class Phi3Scorer(LlamaScorer):
@@ -1760,20 +1699,13 @@ class Phi3Scorer(LlamaScorer):
     _WS_BYTES = "b2t_clm_phi3_ws_bytes"
     _SIZES = "b2t_clm_phi3_"
 
-    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
-                 context_cache_tokens: int = 0, dtype=None):
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
         import b2t_native as N
         if "head_dim" not in dims or "rotary_dims" not in dims:
             raise KeyError("Phi3Scorer: dims lack head_dim / rotary_dims (phi3_dims makes them)")
-        # the descriptor first: the cache allocation of the base class sizes the cache with it
         self._phi3 = N.ClmPhi3(dims["head_dim"], dims["rotary_dims"])
         self._size_args = (self._phi3,)
-        super().__init__(dims, arrays, device, share_prefixes, context_cache_tokens, dtype)
-        self._family, self._qk = "phi3", (self._phi3,)
-
-    def _cache_kv_bytes(self, lib, cap):
-        import ctypes as C
-        return lib.b2t_clm_phi3_cache_kv_bytes(C.byref(self.desc), self._phi3, cap)
+        self._family, self._qk = "phi3", (self._phi3,)   # b2t_clm_phi3_t points at nothing: no _point
 
 
 # ---- gpt-oss (HF GptOssForCausalLM): attention sinks, a sliding window in the kernel, biased routed experts ------------------
@@ -1781,6 +1713,8 @@ GPTOSS_HEAD_DIM = 64
 GPTOSS_MAX_EXPERTS, GPTOSS_MAX_TOP_K = 128, 8
 GPTOSS_LAYER_TYPES = ("full_attention", "sliding_attention")
 _GPTOSS_LAYER_FIELDS = ("sinks", "o_b", "router_w", "router_b", "gate_up_b", "down_b")
+_GPTOSS_ORDER = ("norm1_w", "norm2_w", "qkv_w", "qkv_b", "o_w", "o_b", "sinks", "router_w", "router_b", "gate_up_w", "gate_up_b",
+                 "down_w", "down_b")   # the layout's per layer
 _FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)   # e2m1
 
 
@@ -1845,27 +1779,15 @@ def gptoss_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     the kernels do not run.  max_pos is max_position_embeddings lowered to max_positions (default LLAMA_MAX_POSITIONS), which
     sizes the rotary table; the sliding window does NOT lower it: it binds (128 keys on every other layer), so it is a
     per-layer argument of the attention kernel, dims["windows"] (0 = a full layer)."""
-    mt = cfg.get("model_type")
-    if mt != "gpt_oss":
-        raise ValueError(f"model_type {mt!r} is not 'gpt_oss'")
-    d, Hq = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
-    Hkv = int(cfg.get("num_key_value_heads") or Hq)
-    act = cfg.get("hidden_act", "silu")
-    if act != "silu":
-        raise ValueError(f"gpt_oss hidden_act {act!r} is not supported (silu only: the clamped (up + 1) * gate * sigmoid(1.702 gate))")
+    _, d, Hq, Hkv = _dims_open(cfg, ("gpt_oss",), act_note=": the clamped (up + 1) * gate * sigmoid(1.702 gate)")
     hd = int(cfg.get("head_dim") or d // Hq)
     if hd != GPTOSS_HEAD_DIM:
         raise ValueError(f"head_dim {hd} is not supported ({GPTOSS_HEAD_DIM})")
-    if Hkv < 1 or Hq % Hkv:
-        raise ValueError(f"num_attention_heads {Hq} is not a multiple of num_key_value_heads {Hkv}")
+    _check_gqa(Hq, Hkv)
     ne, k = int(cfg.get("num_local_experts", 128)), int(cfg.get("num_experts_per_tok", 4))
-    if not 1 <= ne <= GPTOSS_MAX_EXPERTS:
-        raise ValueError(f"num_local_experts {ne} outside [1, {GPTOSS_MAX_EXPERTS}]")
-    if not 1 <= k <= min(GPTOSS_MAX_TOP_K, ne):
-        raise ValueError(f"num_experts_per_tok {k} outside [1, min({GPTOSS_MAX_TOP_K}, num_local_experts {ne})]")
+    _check_moe(ne, k, GPTOSS_MAX_EXPERTS, GPTOSS_MAX_TOP_K)
     ffn = int(cfg["intermediate_size"])
-    if d % 64 or ffn % 64:
-        raise ValueError(f"hidden_size {d} and intermediate_size {ffn} must be multiples of 64")
+    _check_64(d, ffn)
     if not cfg.get("attention_bias", True):
         raise ValueError("gpt_oss with attention_bias=False is not supported (the forward adds the q / k / v / o biases)")
     n_layers = int(cfg["num_hidden_layers"])
@@ -1884,13 +1806,9 @@ def gptoss_dims(cfg: dict, max_positions: Optional[int] = None) -> dict:
     limit = float(cfg.get("swiglu_limit", 7.0))
     if not limit > 0:
         raise ValueError(f"swiglu_limit {limit} must be > 0")
-    cap = LLAMA_MAX_POSITIONS if max_positions is None else int(max_positions)
-    if cap < 1:
-        raise ValueError(f"max_positions {cap} < 1")
-    return dict(n_layers=n_layers, d_model=d, n_heads=Hq, n_kv_heads=Hkv, ffn_dim=ffn, vocab=int(cfg["vocab_size"]),
-                max_pos=min(int(cfg["max_position_embeddings"]), cap), rms_eps=float(cfg.get("rms_norm_eps", 1e-5)), tied=False,
-                head_dim=hd, n_experts=ne, top_k=k, swiglu_limit=limit,
-                windows=[int(window) if t == "sliding_attention" else 0 for t in types])
+    return _dims_close(cfg, d, Hq, Hkv, ffn, int(cfg["max_position_embeddings"]), max_positions, 1e-5, tied=False, head_dim=hd,
+                       n_experts=ne, top_k=k, swiglu_limit=limit,
+                       windows=[int(window) if t == "sliding_attention" else 0 for t in types])
 
 
 def mxfp4_dequant(blocks, scales, name: str = "mxfp4"):
@@ -1923,21 +1841,12 @@ def gptoss_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float]
     import torch
     wdt = clm_dtype(dtype)
     sd = dict(state)
-    d, ffn, V, Hq, Hkv, hd, ne = (dims[k] for k in ("d_model", "ffn_dim", "vocab", "n_heads", "n_kv_heads", "head_dim", "n_experts"))
+    d, ffn, Hq, hd, ne = (dims[k] for k in ("d_model", "ffn_dim", "n_heads", "head_dim", "n_experts"))
     inv_freq, att = rope
     if len(inv_freq) != hd // 2:
         raise ValueError(f"inv_freq has {len(inv_freq)} entries, head_dim {hd} needs {hd // 2}")
-
-    def raw(name):
-        if name not in sd:
-            raise KeyError(f"checkpoint lacks {name}")
-        return sd[name].detach()
-
-    def get(name, shape, to=None):
-        t = raw(name).to(to or wdt).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-        return t
+    get = reader(sd, wdt)
+    raw = get.raw
 
     def expert_rows(name, rows, K):
         """[E][rows][K] in wdt of the expert matrix `name`, from either spelling"""
@@ -1951,50 +1860,32 @@ def gptoss_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float]
                 raise ValueError(f"{name}_blocks / _scales: a value is not finite in {wdt}")
             return t
         return get(name, (ne, K, rows)).transpose(1, 2).contiguous()
-    emb = _pad_rows(get("model.embed_tokens.weight", (V, d)), _rup(V, ROWPAD))
-    dev = emb.device
-    out = {"embed_tokens": emb, "lm_head": _pad_rows(get("lm_head.weight", (V, d)), _rup(V, ROWPAD)),
-           "final_norm_w": get("model.norm.weight", (d,))}
-    cos, sin = rope_tables(inv_freq, dims["max_pos"])
-    out["rope_cos"], out["rope_sin"] = torch.from_numpy(cos * np.float32(att)), torch.from_numpy(sin * np.float32(att))
+    out = _trunk(sd, get, dims, inv_freq, att, head="untied")
+    dev = out["embed_tokens"].device
     gperm = torch.from_numpy(gate_up_row_perm(ffn)).to(dev)
     deint = torch.cat([torch.arange(0, 2 * ffn, 2), torch.arange(1, 2 * ffn, 2)]).to(dev)[gperm]   # stored row -> interleaved row
-    widths = {"q_proj": Hq * hd, "k_proj": Hkv * hd, "v_proj": Hkv * hd}
     gus, dns = mixtral_strides(dims)
     for i in range(dims["n_layers"]):
         p = f"model.layers.{i}."
-        qkv = torch.cat([get(p + f"self_attn.{n}.weight", (w, d)) for n, w in widths.items()], 0)
-        sinks = get(p + "self_attn.sinks", (Hq,), torch.float32)
-        if not torch.isfinite(sinks).all():
+        L = _layer(get, p, dims, hd)
+        L["sinks"] = get(p + "self_attn.sinks", (Hq,), torch.float32)
+        if not torch.isfinite(L["sinks"]).all():
             raise ValueError(f"{p}self_attn.sinks: a sink is not finite")
         gate_up = expert_rows(p + "mlp.experts.gate_up_proj", 2 * ffn, d)        # [E][2F][d], gate rows even, up rows odd
         down = expert_rows(p + "mlp.experts.down_proj", d, ffn)                  # [E][d][F]
-        gu = gate_up.new_zeros((ne, gus, d))
-        gu[:, :2 * ffn] = gate_up[:, deint]
-        gub = gate_up.new_zeros((ne, gus))
-        gub[:, :2 * ffn] = get(p + "mlp.experts.gate_up_proj_bias", (ne, 2 * ffn))[:, deint]
-        dn = down.new_zeros((ne, dns, ffn))
-        dn[:, :d] = down
-        dnb = down.new_zeros((ne, dns))
-        dnb[:, :d] = get(p + "mlp.experts.down_proj_bias", (ne, d))
-        L = {"norm1_w": get(p + "input_layernorm.weight", (d,)), "norm2_w": get(p + "post_attention_layernorm.weight", (d,)),
-             "qkv_w": _pad_rows(qkv, _rup(qkv.shape[0], ROWPAD)),
-             "qkv_b": torch.cat([get(p + f"self_attn.{n}.bias", (w,)) for n, w in widths.items()]),
-             "o_w": _pad_rows(get(p + "self_attn.o_proj.weight", (d, Hq * hd)), _rup(d, ROWPAD)),
-             "o_b": get(p + "self_attn.o_proj.bias", (d,)), "sinks": sinks,
-             "router_w": get(p + "mlp.router.weight", (ne, d)), "router_b": get(p + "mlp.router.bias", (ne,)),
-             "gate_up_w": gu, "gate_up_b": gub, "down_w": dn, "down_b": dnb}
-        for f, t in L.items():
-            out[f"layers.{i}.{f}"] = t
+        L.update(qkv_b=torch.cat([get(p + f"self_attn.{n}.bias", (w,)) for n, w in _qkv_widths(dims, hd).items()]),
+                 o_b=get(p + "self_attn.o_proj.bias", (d,)),
+                 router_w=get(p + "mlp.router.weight", (ne, d)), router_b=get(p + "mlp.router.bias", (ne,)),
+                 gate_up_w=_stack_padded(gate_up[:, deint], gus),
+                 gate_up_b=_stack_padded(get(p + "mlp.experts.gate_up_proj_bias", (ne, 2 * ffn))[:, deint], gus),
+                 down_w=_stack_padded(down, dns), down_b=_stack_padded(get(p + "mlp.experts.down_proj_bias", (ne, d)), dns))
+        _put_layer(out, i, L, _GPTOSS_ORDER)
     return out
 
 
 def load_gptoss_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
     """(dims, host tensors in the device layout) of the gpt-oss checkpoint in model_dir; dtype as clm_dtype reads it."""
-    cfg = load_config(model_dir)
-    dims = gptoss_dims(cfg, max_positions)
-    wdt = clm_dtype(dtype, cfg)
-    return dims, gptoss_device_layout(_load_state_dict(model_dir), dims, gptoss_rope(cfg), wdt)
+    return _load_arrays(FAMILIES["gpt_oss"], model_dir, max_positions, dtype)
 
 
 def gptoss_check_cache(context_cache_tokens) -> None:
@@ -2012,33 +1903,33 @@ class GptOssScorer(LlamaScorer):
 
     _WS_BYTES = "b2t_clm_gptoss_ws_bytes"
     _SIZES = "b2t_clm_gptoss_"
+    _CONTEXT_CACHE = False
+    _OWN_ARRAYS = (".sinks",)   # fp32 in either compute dtype
 
-    def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
-                 context_cache_tokens: int = 0, dtype=None):
-        import torch
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
         import b2t_native as N
         gptoss_check_cache(context_cache_tokens)
         if "windows" not in dims or (dims["n_layers"] > 0 and "layers.0.sinks" not in arrays):
             raise KeyError("GptOssScorer: dims lack windows / n_experts or the arrays layers.<i>.sinks (gptoss_dims and "
                            "gptoss_device_layout make them)")
-        # the descriptor first: the size functions need it
         self._oss_layers = (N.ClmGptOssLayer * max(1, dims["n_layers"]))()
         gus, dns = mixtral_strides(dims)
         self._oss = N.ClmGptOss(dims["head_dim"], dims["swiglu_limit"], dims["n_experts"], dims["top_k"], gus, dns, None,
                                 self._oss_layers)
         self._size_args = (self._oss,)
-        sinks = {k: v for k, v in arrays.items() if k.endswith(".sinks")}
-        rest = {k: v for k, v in arrays.items() if k not in sinks}
-        super().__init__(dims, rest, device, share_prefixes, 0, dtype)
-        for k, v in sinks.items():
-            if v.dtype != torch.float32:
-                raise ValueError(f"GptOssScorer: {k} is {v.dtype}, expected torch.float32")
-            self.w[k] = v.to(self.device).contiguous()
-        for i in range(dims["n_layers"]):
+        self._family, self._qk = "gptoss", (self._oss,)
+
+    def _point(self, arrays):
+        import torch
+        for k, v in arrays.items():
+            if k.endswith(self._OWN_ARRAYS):
+                if v.dtype != torch.float32:
+                    raise ValueError(f"GptOssScorer: {k} is {v.dtype}, expected torch.float32")
+                self.w[k] = v.to(self.device).contiguous()
+        for i in range(self.dims["n_layers"]):
             for f in _GPTOSS_LAYER_FIELDS:
                 setattr(self._oss_layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
-            self._oss_layers[i].window = dims["windows"][i]
-        self._family, self._qk = "gptoss", (self._oss,)
+            self._oss_layers[i].window = self.dims["windows"][i]
 
 
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
@@ -2074,77 +1965,74 @@ def cache_plan(cache_ids, cap: int, ids, seq_off) -> dict:
             "n_after": na.value}
 
 
+class Family(NamedTuple):
+    """One row of FAMILIES: what build_scorer and the load_*_arrays need to know about a model family."""
+    model_types: Tuple[str, ...]   # config.json's model_type values the family serves
+    dims: Callable                 # config (and, for a LlamaScorer, max_positions) -> dims, refusing what the kernels do not run
+    rope: Optional[Callable]       # config -> the layout's rotary argument (None: the layout takes none)
+    layout: Callable               # state dict, dims (, rope (, dtype)) -> arrays
+    scorer: type
+    dtype: Callable                # the family's reading of the dtype argument: clm_dtype, or an fp16-only rule
+    # whether the family has a context cache is the scorer's: scorer._CONTEXT_CACHE
+
+
+_FAMILY_ROWS = (
+    Family(("opt",), opt_dims, None, device_layout, OptScorer, opt_dtype),
+    Family(("gpt2",), gpt2_dims, None, gpt2_device_layout, Gpt2Scorer, gpt2_dtype),
+    Family(("gpt_neox",), neox_dims, neox_inv_freq, neox_device_layout, NeoxScorer, neox_dtype),
+    Family(LLAMA_MODEL_TYPES, llama_dims, rope_inv_freq, llama_device_layout, LlamaScorer, clm_dtype),
+    Family(("olmo2",), olmo2_dims, rope_inv_freq, olmo2_device_layout, Olmo2Scorer, clm_dtype),
+    Family(("mixtral",), mixtral_dims, rope_inv_freq, mixtral_device_layout, MixtralScorer, clm_dtype),
+    Family(("gemma2",), gemma2_dims, rope_inv_freq, gemma2_device_layout, Gemma2Scorer, clm_dtype),
+    Family(("phi3",), phi3_dims, phi3_rope, phi3_device_layout, Phi3Scorer, clm_dtype),
+    Family(("gpt_oss",), gptoss_dims, gptoss_rope, gptoss_device_layout, GptOssScorer, clm_dtype),
+)
+FAMILIES = {mt: fam for fam in _FAMILY_ROWS for mt in fam.model_types}   # by config.json's model_type
+
+
+def _load_arrays(fam: Family, model_dir: str, max_positions: Optional[int] = None, dtype=None):
+    """(dims, host tensors in the device layout) of the family's checkpoint in model_dir: what every load_*_arrays returns."""
+    cfg = load_config(model_dir)
+    if not issubclass(fam.scorer, LlamaScorer):   # OPT, GPT-2, GPT-NeoX: fp16 alone, positions as the checkpoint has them
+        dims = fam.dims(cfg)
+        return dims, fam.layout(_load_state_dict(model_dir), dims, *([fam.rope(cfg)] if fam.rope else []))
+    dims = fam.dims(cfg, max_positions)
+    wdt = fam.dtype(dtype, cfg)
+    return dims, fam.layout(_load_state_dict(model_dir), dims, fam.rope(cfg), wdt)
+
+
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
-    """The scorer of the checkpoint in model_dir by config.json's model_type: OptScorer for "opt", Gpt2Scorer for "gpt2" (fp16
-    only, like OPT), NeoxScorer for "gpt_neox" (Pythia; fp16 only), LlamaScorer for "llama",
-    "mistral", "qwen2" and "qwen3", Olmo2Scorer for "olmo2", MixtralScorer for "mixtral", Gemma2Scorer for "gemma2", Phi3Scorer for
-    "phi3", GptOssScorer for "gpt_oss" (no context cache: context_cache_tokens > 0 is refused before any weight is read);
-    anything else ("olmo", "olmo3", "gemma", "gemma3", "qwen3_moe", "phi", "phimoe" and "phi3small" included) is refused.
-    max_positions caps a Llama-family, OLMo-2, Mixtral, Gemma-2 or Phi-3 model's rotary table.  dtype (clm_dtype): None or
-    "float16", "bfloat16" (the Llama family, OLMo-2, Mixtral, Gemma-2 and Phi-3 only, and without a context cache), or "auto" =
-    the dtype config.json says
-    the checkpoint was saved in (bfloat16 -> bfloat16, anything else, and every OPT checkpoint -> float16).  A dtype that is
-    refused is refused before any weight is read."""
+    """The scorer of the checkpoint in model_dir by config.json's model_type: the row of FAMILIES that serves it (the one
+    list of the supported families: OPT, GPT-2, GPT-NeoX / Pythia, Llama / Mistral / Qwen2 / Qwen3, OLMo-2, Mixtral, Gemma-2,
+    Phi-3 / Phi-4, gpt-oss, each with its scorer class).  Anything else ("olmo", "olmo3", "gemma", "gemma3", "qwen3_moe", "phi",
+    "phimoe" and "phi3small" included) is refused.
+    max_positions caps the rotary table of every LlamaScorer.  dtype (the family's rule: clm_dtype for every LlamaScorer, fp16
+    alone for OPT, GPT-2 and GPT-NeoX): None or "float16", "bfloat16" (without a context cache), or "auto" = the dtype
+    config.json says the checkpoint was saved in (bfloat16 -> bfloat16; anything else, and every fp16-only family -> float16).
+    A dtype or a context cache that is refused (gpt-oss has no cache, nor has bfloat16, nor a device without GPU memory) is
+    refused before any weight is read."""
     cfg = load_config(model_dir)
     mt = cfg.get("model_type", "opt")
-    if mt == "opt":
-        wdt = opt_dtype(dtype, cfg)
-        dims, arrays = load_opt_arrays(model_dir)
-        return OptScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt == "gpt2":
-        wdt = gpt2_dtype(dtype, cfg)
-        dims, arrays = load_gpt2_arrays(model_dir)
-        return Gpt2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt == "gpt_neox":
-        wdt = neox_dtype(dtype, cfg)
-        dims, arrays = load_neox_arrays(model_dir)
-        return NeoxScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt in LLAMA_MODEL_TYPES:
-        wdt = clm_dtype(dtype, cfg)
+    fam = FAMILIES.get(mt)
+    if fam is None:
+        raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, phi3, "
+                         f"gpt_oss, olmo2, mixtral)")
+    # every refusal that needs no weight, before the weights are read
+    if not fam.scorer._CONTEXT_CACHE:
+        gptoss_check_cache(context_cache_tokens)
+    wdt = fam.dtype(dtype, cfg)
+    if issubclass(fam.scorer, LlamaScorer):
         llama_check_dtype_cache(wdt, context_cache_tokens)
-        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
-        dims, arrays = load_llama_arrays(model_dir, max_positions, wdt)
-        return LlamaScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt == "olmo2":
-        wdt = clm_dtype(dtype, cfg)
-        llama_check_dtype_cache(wdt, context_cache_tokens)
-        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
-        dims, arrays = load_olmo2_arrays(model_dir, max_positions, wdt)
-        return Olmo2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt == "mixtral":
-        wdt = clm_dtype(dtype, cfg)
-        llama_check_dtype_cache(wdt, context_cache_tokens)
-        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
-        dims, arrays = load_mixtral_arrays(model_dir, max_positions, wdt)
-        return MixtralScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt == "gemma2":
-        wdt = clm_dtype(dtype, cfg)
-        llama_check_dtype_cache(wdt, context_cache_tokens)
-        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
-        dims, arrays = load_gemma2_arrays(model_dir, max_positions, wdt)
-        return Gemma2Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt == "phi3":
-        wdt = clm_dtype(dtype, cfg)
-        llama_check_dtype_cache(wdt, context_cache_tokens)
-        LlamaScorer.check_cache_device(device, context_cache_tokens)   # before the weights are read
-        dims, arrays = load_phi3_arrays(model_dir, max_positions, wdt)
-        return Phi3Scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    if mt == "gpt_oss":
-        gptoss_check_cache(context_cache_tokens)   # before the weights are read
-        wdt = clm_dtype(dtype, cfg)
-        dims, arrays = load_gptoss_arrays(model_dir, max_positions, wdt)
-        return GptOssScorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
-    raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, phi3, "
-                     f"gpt_oss, olmo2, mixtral)")
+        LlamaScorer.check_cache_device(device, context_cache_tokens)
+    dims, arrays = _load_arrays(fam, model_dir, max_positions, wdt)
+    return fam.scorer(dims, arrays, device, share_prefixes, context_cache_tokens, wdt)
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
               max_positions=None, dtype=None):
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
-    Llama-family checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto": build_scorer).  The scorer is an
-    OptScorer, a Gpt2Scorer for a GPT-2 directory, a LlamaScorer for a Llama / Mistral / Qwen2 / Qwen3 directory, an
-    Olmo2Scorer for an OLMo-2 directory, a MixtralScorer for a Mixtral directory, a Gemma2Scorer for a Gemma-2 directory, or a
-    Phi3Scorer for a Phi-3 / Phi-4 directory, or a GptOssScorer for a gpt-oss directory (build_scorer).
+    LlamaScorer's checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto").  The scorer is build_scorer's: its
+    docstring lists the families.
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
     model_dir = resolve_model_dir(model_name, cache_dir)

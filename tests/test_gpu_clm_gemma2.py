@@ -12,6 +12,7 @@ restatement, never the kernels).  The tiny models have head dims 256 and 128, an
 residual (128, 192), caps of 2.0 / 3.0 that both matter (tests/test_clm_gemma2_host.py measures it) and a q scale that is not
 head_dim^-0.5.  The measured ratios are in NOTES.md ("LLM")."""
 import ctypes as C
+import functools
 import types
 
 import numpy as np
@@ -21,54 +22,16 @@ import llm_rescore as R
 from test_clm_gemma2_host import E_BF16_MAX, TINY, gemma2_state, ref_logp_gemma2, tiny_gemma2
 from test_clm_llama_host import tiny_seqs
 from test_gpu_clm_cache import SETTINGS, _same_bytes
-from test_gpu_clm_llama import _pack, _prod_list, _same, _tiles
-from test_gpu_clm_llama_cache import Rig
+from test_gpu_clm_llama import _call as _family_call, _prod_list, _same
+from test_gpu_clm_llama_cache import FamilyLib, Rig
 
 pytestmark = pytest.mark.gpu
 LENS = (1, 2, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129)   # 692 rows: crosses the 128- and the 256-row tile boundaries
 
 
-def _call(sc, seqs, tree=False, mode=None, with_tok=True):
-    """(scores, per-sequence token log-probs) of one Gemma-2 C ABI call in the scorer's dtype."""
-    import torch
-    import b2t_native as N
-    lib = N.load()
-    assert sc._family == "gemma2"
-    sfx = "bf16" if sc.dtype is torch.bfloat16 else "f16"
-    ids, off = _pack(seqs)
-    M, S, CAN = int(off[-1]), len(seqs), 4096
-    if tree:
-        nodes = R.tree_plan(ids, off)[2]
-        need = lib.b2t_clm_gemma2_tree_ws_bytes(C.byref(sc.desc), sc._g2, nodes, M, S)
-    else:
-        need = lib.b2t_clm_gemma2_ws_bytes(C.byref(sc.desc), sc._g2, M, S)
-    assert need > 0
-    canary = torch.randint(0, 256, (CAN,), dtype=torch.uint8, device="cuda")
-    ws = torch.empty(need + CAN, dtype=torch.uint8, device="cuda")
-    ws[:need] = 0xFF
-    ws[need:] = canary
-    scores = torch.full((S + 64,), 12345.0, device="cuda")
-    tok = torch.full((M + 64,), 12345.0, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    with _tiles(mode):
-        if tree:
-            nn = C.c_longlong(-1)
-            rc = getattr(lib, "b2t_clm_gemma2_score_tree_" + sfx)(C.byref(sc.desc), sc._g2, ids.ctypes.data, off.ctypes.data, S,
-                                                                  scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                                  C.byref(nn), ws.data_ptr(), need, stream)
-            assert rc != 0 or nn.value == nodes
-        else:
-            rc = getattr(lib, "b2t_clm_gemma2_score_" + sfx)(C.byref(sc.desc), sc._g2, ids.ctypes.data, off.ctypes.data, S,
-                                                             scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                             ws.data_ptr(), need, stream)
-    assert rc == 0, N.last_error()
-    torch.cuda.synchronize()
-    assert torch.equal(ws[need:], canary), "wrote behind the workspace"
-    assert (scores[S:] == 12345.0).all() and (tok[M:] == 12345.0).all()
-    s, t = scores[:S].cpu().numpy(), tok[:M].cpu().numpy()
-    assert np.isfinite(s).all() and np.isfinite(t).all(), "non-finite output"
-    del ws
-    return s, [t[off[i]:off[i + 1]] for i in range(S)]
+# one Gemma-2 C ABI call in the scorer's dtype: tests/test_gpu_clm_llama.py's _call, which takes the entry points, the sizes and
+# their extra arguments from the scorer, on a scorer that must be of this family
+_call = functools.partial(_family_call, family="gemma2")
 
 
 def _flat_and_tree(sc, seqs, mode=None):
@@ -221,23 +184,6 @@ def test_score_alone_equals_score_in_a_batch(name, fmt):
 
 
 # ---- the cached call --------------------------------------------------------------------------------------------------------
-class _Gemma2Lib:
-    """The library as Rig (tests/test_gpu_clm_llama_cache.py) drives it, its cached call and that call's workspace size routed
-    to Gemma-2's with the scorer's descriptor."""
-
-    def __init__(self, lib, g2):
-        self._lib, self._g2 = lib, g2
-
-    def __getattr__(self, name):
-        return getattr(self._lib, name)
-
-    def b2t_clm_llama_tree_cached_ws_bytes(self, desc, *args):
-        return self._lib.b2t_clm_gemma2_tree_cached_ws_bytes(desc, self._g2, *args)
-
-    def b2t_clm_llama_score_tree_cached_f16(self, desc, *args):
-        return self._lib.b2t_clm_gemma2_score_tree_cached_f16(desc, self._g2, *args)
-
-
 class Gemma2Rig(Rig):
     """Rig sizes its slab rows by d_model / n_heads; it is built on the Llama shape of width Hq hd, whose cache rows have
     Gemma-2's size, then pointed at the scorer and at Gemma-2's calls."""
@@ -248,7 +194,7 @@ class Gemma2Rig(Rig):
         wide.d_model = sc.dims["n_heads"] * sc.dims["head_dim"]
         super().__init__(types.SimpleNamespace(dims=dict(sc.dims, d_model=wide.d_model), desc=wide), cap, setting)
         assert self.lib.b2t_clm_gemma2_cache_kv_bytes(C.byref(sc.desc), sc._g2, cap) == self.kv.numel() * 2
-        self.sc, self.lib = sc, _Gemma2Lib(self.lib, sc._g2)
+        self.sc, self.lib = sc, FamilyLib(self.lib, sc, "gemma2")
 
 
 def _rigs(sc, cap):

@@ -11,63 +11,15 @@ The contract bound is the project's own form: e_bf16 = max |bf16-rounded restate
 contract's roundings alone do to the log-probs of that case, and the kernels must be within 3 x e_bf16 of the rounded
 restatement (the margin covers accumulation order and the fast exponentials).  e_bf16 <= 0.1 is asserted first, so the bound
 is never looser than 0.3 on log-probs of magnitude up to 15.  The measured figures are in NOTES.md ("LLM")."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import llm_rescore as R
 from test_clm_llama_bf16_host import E_BF16_MAX, LENS, bf16_model, ref_logp_llama_fmt, scaled_state
 from test_clm_llama_host import TINY, hf_inv_freq, ref_dims, state_of, tiny_seqs
-from test_gpu_clm_llama import WIDTHS, _pack, _prod_list, _same, _tiles
+from test_gpu_clm_llama import WIDTHS, _call, _prod_list, _same
 
 pytestmark = pytest.mark.gpu
-
-
-def _call(sc, seqs, tree=False, mode=None, fill=0xFF, with_tok=True, finite=True):
-    """(scores, per-sequence token log-probs) of one C ABI call in the scorer's dtype on a fresh workspace of exactly the
-    size asked for; finite=False skips the assertion that every output is finite."""
-    import torch
-    import b2t_native as N
-    lib = N.load()
-    sfx = "bf16" if sc.dtype is torch.bfloat16 else "f16"
-    ids, off = _pack(seqs)
-    M, S, CAN = int(off[-1]), len(seqs), 4096
-    if tree:
-        nodes = R.tree_plan(ids, off)[2]
-        need = lib.b2t_clm_llama_tree_ws_bytes(C.byref(sc.desc), nodes, M, S)
-    else:
-        need = lib.b2t_clm_llama_ws_bytes(C.byref(sc.desc), M, S)
-    assert need > 0
-    canary = torch.randint(0, 256, (CAN,), dtype=torch.uint8, device="cuda")
-    ws = torch.empty(need + CAN, dtype=torch.uint8, device="cuda")
-    ws[:need] = fill
-    ws[need:] = canary
-    scores = torch.full((S + 64,), 12345.0, device="cuda")
-    tok = torch.full((M + 64,), 12345.0, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    with _tiles(mode):
-        if tree:
-            nn = C.c_longlong(-1)
-            rc = getattr(lib, "b2t_clm_llama_score_tree_" + sfx)(C.byref(sc.desc), ids.ctypes.data, off.ctypes.data, S,
-                                                                 scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                                 C.byref(nn), ws.data_ptr(), need, stream)
-            assert rc != 0 or nn.value == nodes
-        else:
-            rc = getattr(lib, "b2t_clm_llama_score_" + sfx)(C.byref(sc.desc), ids.ctypes.data, off.ctypes.data, S,
-                                                            scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                            ws.data_ptr(), need, stream)
-    assert rc == 0, N.last_error()
-    torch.cuda.synchronize()
-    assert torch.equal(ws[need:], canary), "wrote behind the workspace"
-    assert (scores[S:] == 12345.0).all() and (tok[M:] == 12345.0).all()
-    if not with_tok:
-        assert (tok == 12345.0).all()
-    s, t = scores[:S].cpu().numpy(), tok[:M].cpu().numpy()
-    if finite:
-        assert np.isfinite(s).all() and np.isfinite(t).all(), "non-finite output"
-    del ws
-    return s, [t[off[i]:off[i + 1]] for i in range(S)]
 
 
 def _flat_and_tree(sc, seqs, mode=None):

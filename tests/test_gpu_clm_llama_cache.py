@@ -118,6 +118,26 @@ class Rig:
         return scores[:S].cpu().numpy(), (_split(tok[:M].cpu().numpy(), off) if with_tok else None), want
 
 
+class FamilyLib:
+    """The library as Rig drives it, for a scorer of another family on the Llama descriptor: Rig's two cached calls,
+    b2t_clm_llama_tree_cached_ws_bytes and b2t_clm_llama_score_tree_cached_f16, go to the family's -- the size by sc._SIZES with
+    sc._size_args, the score to b2t_clm_<family>_score_tree_cached_f16 with sc._qk -- each extra argument right behind the
+    model; every other name is the library's own.  family: what sc._family must be."""
+
+    def __init__(self, lib, sc, family):
+        assert sc._family == family
+        self._lib, self._sc = lib, sc
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+    def b2t_clm_llama_tree_cached_ws_bytes(self, desc, *args):
+        return getattr(self._lib, self._sc._SIZES + "tree_cached_ws_bytes")(desc, *self._sc._size_args, *args)
+
+    def b2t_clm_llama_score_tree_cached_f16(self, desc, *args):
+        return getattr(self._lib, f"b2t_clm_{self._sc._family}_score_tree_cached_f16")(desc, *self._sc._qk, *args)
+
+
 def _check(rigs, sc, seqs, mode=None, update=1, what="", flat=True):
     """Per rig: an independent read-only cached call, then (update on) the updating one, each == the tree call == the flat
     call; returns the plans (one per rig)."""

@@ -26,7 +26,7 @@ from test_clm_mixtral_host import (E_BF16_MAX, SEED, contract_seqs, fused_state,
                                    router_figures, tiny_mixtral)
 from test_gpu_clm_cache import SETTINGS, _same_bytes
 from test_gpu_clm_llama import _pack, _prod_list, _same, _tiles
-from test_gpu_clm_llama_cache import Rig
+from test_gpu_clm_llama_cache import FamilyLib, Rig
 
 pytestmark = pytest.mark.gpu
 
@@ -266,27 +266,10 @@ def test_score_alone_equals_score_in_a_batch(fmt):
     _flat_and_tree(sc, [[2], [2], [3], [2], [4]])                               # one-token sequences: no head rows
 
 
-class _MixtralLib:
-    """The library as Rig (tests/test_gpu_clm_llama_cache.py) drives it, its cached call and that call's workspace size routed
-    to Mixtral's with the scorer's MoE descriptor; the cache's size is the Llama family's either way."""
-
-    def __init__(self, lib, moe):
-        self._lib, self._moe = lib, moe
-
-    def __getattr__(self, name):
-        return getattr(self._lib, name)
-
-    def b2t_clm_llama_tree_cached_ws_bytes(self, desc, *args):
-        return self._lib.b2t_clm_mixtral_tree_cached_ws_bytes(desc, C.byref(self._moe), *args)
-
-    def b2t_clm_llama_score_tree_cached_f16(self, desc, *args):
-        return self._lib.b2t_clm_mixtral_score_tree_cached_f16(desc, C.byref(self._moe), *args)
-
-
 def _rigs(sc, cap):
     rigs = [Rig(sc, cap, s) for s in SETTINGS]
     for rig in rigs:
-        rig.lib = _MixtralLib(rig.lib, sc._moe)
+        rig.lib = FamilyLib(rig.lib, sc, "mixtral")
     return rigs
 
 

@@ -12,7 +12,7 @@ e_bf16 <= 0.1, e16 and e_bf16 being what the contract's roundings alone do to th
 restatement, never the kernels).  In both tiny models the fp32 region's pitch (Hq + Hkv) hd (512, 384) is wider than d (384,
 256), so the QKV GEMM and the o_proj / down GEMMs write it with different pitches; the QKV widths are 640 and 512, the group sizes
 3 and 2, the head dims 128 and 64.  The measured ratios are in NOTES.md ("LLM")."""
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -22,54 +22,16 @@ from test_clm_cache_host import dict_rule  # noqa: F401  (Rig uses it)
 from test_clm_llama_host import tiny_seqs
 from test_clm_olmo2_host import E_BF16_MAX, TINY, olmo2_state, ref_logp_olmo2, tiny_olmo2
 from test_gpu_clm_cache import SETTINGS, _same_bytes
-from test_gpu_clm_llama import _pack, _prod_list, _same, _tiles
-from test_gpu_clm_llama_cache import Rig
+from test_gpu_clm_llama import _call as _family_call, _prod_list, _same
+from test_gpu_clm_llama_cache import FamilyLib, Rig
 
 pytestmark = pytest.mark.gpu
 LENS = (1, 2, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129)   # 692 rows: crosses the 128- and the 256-row tile boundaries
 
 
-def _call(sc, seqs, tree=False, mode=None, with_tok=True):
-    """(scores, per-sequence token log-probs) of one OLMo-2 C ABI call in the scorer's dtype."""
-    import torch
-    import b2t_native as N
-    lib = N.load()
-    assert sc._family == "olmo2"
-    sfx = "bf16" if sc.dtype is torch.bfloat16 else "f16"
-    ids, off = _pack(seqs)
-    M, S, CAN = int(off[-1]), len(seqs), 4096
-    if tree:
-        nodes = R.tree_plan(ids, off)[2]
-        need = lib.b2t_clm_olmo2_tree_ws_bytes(C.byref(sc.desc), nodes, M, S)
-    else:
-        need = lib.b2t_clm_olmo2_ws_bytes(C.byref(sc.desc), M, S)
-    assert need > 0
-    canary = torch.randint(0, 256, (CAN,), dtype=torch.uint8, device="cuda")
-    ws = torch.empty(need + CAN, dtype=torch.uint8, device="cuda")
-    ws[:need] = 0xFF
-    ws[need:] = canary
-    scores = torch.full((S + 64,), 12345.0, device="cuda")
-    tok = torch.full((M + 64,), 12345.0, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    with _tiles(mode):
-        if tree:
-            nn = C.c_longlong(-1)
-            rc = getattr(lib, "b2t_clm_olmo2_score_tree_" + sfx)(C.byref(sc.desc), sc._qkn, ids.ctypes.data, off.ctypes.data, S,
-                                                                 scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                                 C.byref(nn), ws.data_ptr(), need, stream)
-            assert rc != 0 or nn.value == nodes
-        else:
-            rc = getattr(lib, "b2t_clm_olmo2_score_" + sfx)(C.byref(sc.desc), sc._qkn, ids.ctypes.data, off.ctypes.data, S,
-                                                            scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                            ws.data_ptr(), need, stream)
-    assert rc == 0, N.last_error()
-    torch.cuda.synchronize()
-    assert torch.equal(ws[need:], canary), "wrote behind the workspace"
-    assert (scores[S:] == 12345.0).all() and (tok[M:] == 12345.0).all()
-    s, t = scores[:S].cpu().numpy(), tok[:M].cpu().numpy()
-    assert np.isfinite(s).all() and np.isfinite(t).all(), "non-finite output"
-    del ws
-    return s, [t[off[i]:off[i + 1]] for i in range(S)]
+# one OLMo-2 C ABI call in the scorer's dtype: tests/test_gpu_clm_llama.py's _call, which takes the entry points, the sizes and
+# their extra arguments from the scorer, on a scorer that must be of this family
+_call = functools.partial(_family_call, family="olmo2")
 
 
 def _flat_and_tree(sc, seqs, mode=None):
@@ -210,27 +172,10 @@ def test_score_alone_equals_score_in_a_batch(name, fmt):
 
 
 # ---- the cached call --------------------------------------------------------------------------------------------------------
-class _Olmo2Lib:
-    """The library as Rig (tests/test_gpu_clm_llama_cache.py) drives it, its cached call and that call's workspace size routed
-    to OLMo-2's with the scorer's norm weights; the cache's size is the Llama family's either way."""
-
-    def __init__(self, lib, qkn):
-        self._lib, self._qkn = lib, qkn
-
-    def __getattr__(self, name):
-        return getattr(self._lib, name)
-
-    def b2t_clm_llama_tree_cached_ws_bytes(self, *args):
-        return self._lib.b2t_clm_olmo2_tree_cached_ws_bytes(*args)
-
-    def b2t_clm_llama_score_tree_cached_f16(self, desc, *args):
-        return self._lib.b2t_clm_olmo2_score_tree_cached_f16(desc, self._qkn, *args)
-
-
 def _rigs(sc, cap):
     rigs = [Rig(sc, cap, s) for s in SETTINGS]
     for rig in rigs:
-        rig.lib = _Olmo2Lib(rig.lib, sc._qkn)
+        rig.lib = FamilyLib(rig.lib, sc, "olmo2")
     return rigs
 
 

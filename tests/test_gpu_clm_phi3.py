@@ -13,6 +13,7 @@ restatement, never the kernels).  The tiny models are tests/test_clm_phi3_host.p
 queries, 96 of 128 dims rotated under LongRoPE, head dim 128, and a head dim of its own (2 heads of 128 on a residual of 192).
 The measured ratios are in NOTES.md ("LLM")."""
 import ctypes as C
+import functools
 import json
 
 import numpy as np
@@ -22,54 +23,16 @@ import llm_rescore as R
 from test_clm_llama_host import tiny_seqs
 from test_clm_phi3_host import E_BF16_MAX, HEAD_DIM, TINY, phi3_state, ref_logp_phi3, tiny_phi3
 from test_gpu_clm_cache import SETTINGS, _same_bytes
-from test_gpu_clm_llama import _pack, _prod_list, _same, _tiles
-from test_gpu_clm_llama_cache import Rig
+from test_gpu_clm_llama import _call as _family_call, _prod_list, _same
+from test_gpu_clm_llama_cache import FamilyLib, Rig
 
 pytestmark = pytest.mark.gpu
 LENS = (1, 2, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129)   # 692 rows: crosses the 32-key block and the 128- / 256-row tiles
 
 
-def _call(sc, seqs, tree=False, mode=None, with_tok=True):
-    """(scores, per-sequence token log-probs) of one Phi-3 C ABI call in the scorer's dtype."""
-    import torch
-    import b2t_native as N
-    lib = N.load()
-    assert sc._family == "phi3"
-    sfx = "bf16" if sc.dtype is torch.bfloat16 else "f16"
-    ids, off = _pack(seqs)
-    M, S, CAN = int(off[-1]), len(seqs), 4096
-    if tree:
-        nodes = R.tree_plan(ids, off)[2]
-        need = lib.b2t_clm_phi3_tree_ws_bytes(C.byref(sc.desc), sc._phi3, nodes, M, S)
-    else:
-        need = lib.b2t_clm_phi3_ws_bytes(C.byref(sc.desc), sc._phi3, M, S)
-    assert need > 0
-    canary = torch.randint(0, 256, (CAN,), dtype=torch.uint8, device="cuda")
-    ws = torch.empty(need + CAN, dtype=torch.uint8, device="cuda")
-    ws[:need] = 0xFF
-    ws[need:] = canary
-    scores = torch.full((S + 64,), 12345.0, device="cuda")
-    tok = torch.full((M + 64,), 12345.0, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    with _tiles(mode):
-        if tree:
-            nn = C.c_longlong(-1)
-            rc = getattr(lib, "b2t_clm_phi3_score_tree_" + sfx)(C.byref(sc.desc), sc._phi3, ids.ctypes.data, off.ctypes.data, S,
-                                                                scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                                C.byref(nn), ws.data_ptr(), need, stream)
-            assert rc != 0 or nn.value == nodes
-        else:
-            rc = getattr(lib, "b2t_clm_phi3_score_" + sfx)(C.byref(sc.desc), sc._phi3, ids.ctypes.data, off.ctypes.data, S,
-                                                           scores.data_ptr(), tok.data_ptr() if with_tok else None, ws.data_ptr(),
-                                                           need, stream)
-    assert rc == 0, N.last_error()
-    torch.cuda.synchronize()
-    assert torch.equal(ws[need:], canary), "wrote behind the workspace"
-    assert (scores[S:] == 12345.0).all() and (tok[M:] == 12345.0).all()
-    s, t = scores[:S].cpu().numpy(), tok[:M].cpu().numpy()
-    assert np.isfinite(s).all() and np.isfinite(t).all(), "non-finite output"
-    del ws
-    return s, [t[off[i]:off[i + 1]] for i in range(S)]
+# one Phi-3 C ABI call in the scorer's dtype: tests/test_gpu_clm_llama.py's _call, which takes the entry points, the sizes and
+# their extra arguments from the scorer, on a scorer that must be of this family
+_call = functools.partial(_family_call, family="phi3")
 
 
 def _flat_and_tree(sc, seqs, mode=None):
@@ -235,29 +198,12 @@ def test_score_alone_equals_score_in_a_batch(name, fmt):
 CACHED = ("hd96", "hd96gqa", "partial")
 
 
-class _Phi3Lib:
-    """The library as Rig (tests/test_gpu_clm_llama_cache.py) drives it, its cached call and that call's workspace size routed
-    to Phi-3's with the scorer's descriptor.  Rig sizes its slab rows by d_model / n_heads, which is these models' head dim."""
-
-    def __init__(self, lib, phi3):
-        self._lib, self._phi3 = lib, phi3
-
-    def __getattr__(self, name):
-        return getattr(self._lib, name)
-
-    def b2t_clm_llama_tree_cached_ws_bytes(self, desc, *args):
-        return self._lib.b2t_clm_phi3_tree_cached_ws_bytes(desc, self._phi3, *args)
-
-    def b2t_clm_llama_score_tree_cached_f16(self, desc, *args):
-        return self._lib.b2t_clm_phi3_score_tree_cached_f16(desc, self._phi3, *args)
-
-
 def _rigs(sc, cap):
     assert sc.dims["d_model"] // sc.dims["n_heads"] == sc.dims["head_dim"]
     rigs = [Rig(sc, cap, s) for s in SETTINGS]
     for rig in rigs:
         assert rig.lib.b2t_clm_phi3_cache_kv_bytes(C.byref(sc.desc), sc._phi3, cap) == rig.kv.numel() * 2
-        rig.lib = _Phi3Lib(rig.lib, sc._phi3)
+        rig.lib = FamilyLib(rig.lib, sc, "phi3")
     return rigs
 
 

@@ -12,7 +12,7 @@ restatement, never the kernels).  The two tiny models have QKV widths 640 and 38
 N, which must reach the epilogue's barrier; a 256-tile holds a q head beside a k head with other norm weights and v slices
 beside normed ones; group sizes 3 and 4; head dims 128 (the norm's sum crosses two waves through LDS) and 64.  The measured
 ratios are in NOTES.md ("LLM")."""
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -22,54 +22,16 @@ from test_clm_cache_host import dict_rule  # noqa: F401  (Rig uses it)
 from test_clm_llama_host import tiny_seqs
 from test_clm_qwen3_host import E_BF16_MAX, TINY, qwen3_state, ref_logp_qwen3, tiny_qwen3
 from test_gpu_clm_cache import SETTINGS, _same_bytes
-from test_gpu_clm_llama import _pack, _prod_list, _same, _tiles
-from test_gpu_clm_llama_cache import Rig
+from test_gpu_clm_llama import _call as _family_call, _prod_list, _same
+from test_gpu_clm_llama_cache import FamilyLib, Rig
 
 pytestmark = pytest.mark.gpu
 LENS = (1, 2, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129)   # 692 rows: crosses the 128- and the 256-row tile boundaries
 
 
-def _call(sc, seqs, tree=False, mode=None, with_tok=True):
-    """(scores, per-sequence token log-probs) of one Qwen3 C ABI call in the scorer's dtype."""
-    import torch
-    import b2t_native as N
-    lib = N.load()
-    assert sc._family == "qwen3"
-    sfx = "bf16" if sc.dtype is torch.bfloat16 else "f16"
-    ids, off = _pack(seqs)
-    M, S, CAN = int(off[-1]), len(seqs), 4096
-    if tree:
-        nodes = R.tree_plan(ids, off)[2]
-        need = lib.b2t_clm_llama_tree_ws_bytes(C.byref(sc.desc), nodes, M, S)
-    else:
-        need = lib.b2t_clm_llama_ws_bytes(C.byref(sc.desc), M, S)
-    assert need > 0
-    canary = torch.randint(0, 256, (CAN,), dtype=torch.uint8, device="cuda")
-    ws = torch.empty(need + CAN, dtype=torch.uint8, device="cuda")
-    ws[:need] = 0xFF
-    ws[need:] = canary
-    scores = torch.full((S + 64,), 12345.0, device="cuda")
-    tok = torch.full((M + 64,), 12345.0, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    with _tiles(mode):
-        if tree:
-            nn = C.c_longlong(-1)
-            rc = getattr(lib, "b2t_clm_qwen3_score_tree_" + sfx)(C.byref(sc.desc), sc._qkn, ids.ctypes.data, off.ctypes.data, S,
-                                                                 scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                                 C.byref(nn), ws.data_ptr(), need, stream)
-            assert rc != 0 or nn.value == nodes
-        else:
-            rc = getattr(lib, "b2t_clm_qwen3_score_" + sfx)(C.byref(sc.desc), sc._qkn, ids.ctypes.data, off.ctypes.data, S,
-                                                            scores.data_ptr(), tok.data_ptr() if with_tok else None,
-                                                            ws.data_ptr(), need, stream)
-    assert rc == 0, N.last_error()
-    torch.cuda.synchronize()
-    assert torch.equal(ws[need:], canary), "wrote behind the workspace"
-    assert (scores[S:] == 12345.0).all() and (tok[M:] == 12345.0).all()
-    s, t = scores[:S].cpu().numpy(), tok[:M].cpu().numpy()
-    assert np.isfinite(s).all() and np.isfinite(t).all(), "non-finite output"
-    del ws
-    return s, [t[off[i]:off[i + 1]] for i in range(S)]
+# one Qwen3 C ABI call in the scorer's dtype: tests/test_gpu_clm_llama.py's _call, which takes the entry points, the sizes and
+# their extra arguments from the scorer, on a scorer that must be of this family
+_call = functools.partial(_family_call, family="qwen3")
 
 
 def _flat_and_tree(sc, seqs, mode=None):
@@ -202,20 +164,6 @@ def test_tree_equals_flat_at_the_block_edges(name, fmt):
 
 
 # ---- the cached call --------------------------------------------------------------------------------------------------------
-class _Qwen3Lib:
-    """The library as Rig (tests/test_gpu_clm_llama_cache.py) drives it, its cached call routed to Qwen3's with the scorer's
-    norm weights; the size functions are the Llama family's either way."""
-
-    def __init__(self, lib, qkn):
-        self._lib, self._qkn = lib, qkn
-
-    def __getattr__(self, name):
-        return getattr(self._lib, name)
-
-    def b2t_clm_llama_score_tree_cached_f16(self, desc, *args):
-        return self._lib.b2t_clm_qwen3_score_tree_cached_f16(desc, self._qkn, *args)
-
-
 @pytest.mark.parametrize("name", list(TINY))
 def test_cached_session_of_three_growing_contexts(name):
     """Three 20-candidate lists behind a context of 30 tokens that grows by the first candidate of the call before: cached = tree = flat byte for
@@ -226,7 +174,7 @@ def test_cached_session_of_three_growing_contexts(name):
     V, max_pos = rd["vocab"], sc.dims["max_pos"]
     rigs = [Rig(sc, max_pos, s) for s in SETTINGS]
     for rig in rigs:
-        rig.lib = _Qwen3Lib(rig.lib, sc._qkn)
+        rig.lib = FamilyLib(rig.lib, sc, "qwen3")
     rng = np.random.default_rng(V)
     ctx, prev = [int(x) for x in rng.integers(4, V, 30)], None
     for k, mode in enumerate(("0", None, "2")):
