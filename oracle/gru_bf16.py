@@ -20,6 +20,10 @@ Layout (all time-major): gi0 [T,B,3H] (layer 0's input projection, b_ih[0] inclu
 and bih[l] [3H] for l >= 1 (index 0 is None); h0[l] [B,H]; masks None or L - 1 arrays [T,B,H] of keep / (1 - p) factors on out[l];
 dY [T,B,H] (gradient wrt the top layer's outputs); dhl None or [L,B,H].  Gate order r, z, n; reserve = (r, z, n, gh_n) [T,B,4H];
 dG = (dr_pre, dz_pre, dn_pre r, dn_pre) [T,B,4H] as gru_gate_bwd of csrc/gru_cell.h writes it.
+
+The operand rounding is a parameter (`round`, bf16_rne by default).  round = identity gives the same three restatements of the
+EXACT-FP32 sweeps (csrc/gru.hip step-launch, csrc/gru_persistent.hip without GRU_BF16, and the fused forward): only the operand
+rounding differs between the regimes, M and the caps are the same.  tests/test_gru_fp32_oracle_host.py, tests/test_gpu_gru_fp32_oracle.py.
 """
 from __future__ import annotations
 
@@ -37,6 +41,21 @@ CAP_ABS = 1e-4          # out, reserve: 30 x below the free-running comparison's
 CAP_RMS = 1e-3          # dG, dh_init: times the rms of the oracle's tensor
 
 
+# (T, B, H) of the exact-fp32 sweeps' tests, one layer per launch (host and GPU file share them): the smallest shapes that reach
+# every template instance of csrc/gru_persistent.hip's launchers (NCH / NCB = K chunks per wave, forward / backward) and every edge.
+FP32_SWEEP_SHAPES = ((3, 1, 16),       # one row, one workgroup column
+                     (1, 17, 80),      # T = 1: no hand-off, the backward carry is dh_last alone
+                     (2, 5, 48),       # H % 32 != 0: a cache line holds rows of two steps
+                     (4, 17, 128),     # NCH 2 / NCB 6 at their upper edge
+                     (5, 33, 160),     # NCH 4 / NCB 12, three row groups ...
+                     (4, 16, 256),     # ... and exactly one, at the upper edge
+                     (9, 33, 272),     # NCH 8 / NCB 24 just past 256
+                     (6, 64, 512),     # four full row groups; the XCD-local hand-off and the 32-unit workgroups are eligible
+                     (4, 70, 768),     # NCH 12 / NCB 36; B > 64: the XCD-local hand-off is refused
+                     (3, 17, 1024))    # NCH 16 / NCB 48
+fp32_sweep_seed = lambda T, B, H: B * 1000 + H
+
+
 def identity(x):
     return np.asarray(x, dtype=np.float64)
 
@@ -52,6 +71,13 @@ def bf16_trunc(x):
     """fp32 -> bf16 by dropping the low 16 bits (a defect: the `truncate` mutation)."""
     u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
     return (u & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def drop_low_bits(k):
+    """fp32 with its low k mantissa bits cleared (a defect of the exact-fp32 regime: the `drop7` / `drop10` / `drop13` mutations;
+    k = 13 leaves tf32's 10 mantissa bits)."""
+    keep = np.uint32((0xFFFFFFFF << k) & 0xFFFFFFFF)
+    return lambda x: (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & keep).view(np.float32)
 
 
 def random_inputs(L, T, B, H, seed, with_dhl=True):
@@ -132,9 +158,10 @@ def _h_prev(h0_l, out_l):
     return np.concatenate([np.asarray(h0_l, dtype=np.float64)[None], np.asarray(out_l[:-1], dtype=np.float64)])
 
 
-def operand_forced(inputs, kernel):
+def operand_forced(inputs, kernel, round=bf16_rne):
     """The fp64 oracle driven by the tensors a kernel (or the stand-in) wrote: kernel = dict(out, outd, res, dG, dh_init), lists
-    per layer of float32 arrays (outd is read only where inputs['masks'] is set; dh_init is not read at all).
+    per layer of float32 arrays (outd is read only where inputs['masks'] is set; dh_init is not read at all).  `round`: what the
+    kernel does to its matrix operands -- bf16_rne (written bf16() below) for the bf16 sweeps, identity for the exact-fp32 ones.
 
     Forward, layer l, step t (step-local): hp = kernel's out[l][t-1] (h0[l] at t = 0); gh = bf16(hp) W_hh^T + b_hh; gi = gi0 for
     layer 0, else bf16(kernel's outd[l-1][t]) W_ih^T + b_ih (out[l-1] without dropout); r, z, n, h in fp64 -> `out`, `res`.
@@ -142,7 +169,7 @@ def operand_forced(inputs, kernel):
     saved gates and hp are the kernel's; the layer below gets dy = bf16(kernel's dG[l] columns (dr, dz, dn)) bf16(W_ih[l]) times
     masks[l-1] -> `dG`, `dh_init`.  Returns dict(out, res, dG, dh_init), lists per layer of fp64 arrays."""
     I = inputs
-    q = lambda x: bf16_rne(x).astype(np.float64)
+    q = lambda x: round(x).astype(np.float64)
     L = len(I["whh"])
     T, B, _ = I["gi0"].shape
     H = I["whh"][0].shape[1]
@@ -201,12 +228,19 @@ MUTATIONS = ("dr_without_bias",        # dr_pre built from gh_n without its bias
              "swap_z")                 # z and 1 - z swapped in h
 
 
-def standin(inputs, dtype=np.float32, mutate=None):
-    """The recurrences in `dtype` with bf16 operands, in the kernels' layout: dict(out, outd, res [T,B,4H], dG [T,B,4H], dh_init),
-    lists per layer.  Like the kernels, the backward pass reads what the forward pass stored.  `mutate`: one of MUTATIONS."""
-    assert mutate is None or mutate in MUTATIONS, mutate
+# The exact-fp32 regime (round = identity): `truncate` and `carry_unrounded` change nothing there and are left out; what takes their
+# place are matrix operands that silently lose their low mantissa bits (a reduced-precision matrix-core path taken by mistake).
+PRECISION_MUTATIONS = {"drop7": 7, "drop10": 10, "drop13": 13}
+MUTATIONS_FP32 = tuple(m for m in MUTATIONS if m not in ("truncate", "carry_unrounded")) + tuple(PRECISION_MUTATIONS)
+
+
+def standin(inputs, dtype=np.float32, mutate=None, round=bf16_rne):
+    """The recurrences in `dtype` with `round`-ed operands (bf16 by default, identity: the exact-fp32 sweeps), in the kernels'
+    layout: dict(out, outd, res [T,B,4H], dG [T,B,4H], dh_init), lists per layer.  Like the kernels, the backward pass reads what
+    the forward pass stored.  `mutate`: one of MUTATIONS, or of MUTATIONS_FP32 with round = identity."""
+    assert mutate is None or mutate in (MUTATIONS_FP32 if round is identity else MUTATIONS), mutate
     I = inputs
-    rnd = bf16_trunc if mutate == "truncate" else bf16_rne
+    rnd = bf16_trunc if mutate == "truncate" else drop_low_bits(PRECISION_MUTATIONS[mutate]) if mutate in PRECISION_MUTATIONS else round
     q = lambda x: rnd(x).astype(dtype)
     c = lambda x: np.asarray(x, dtype=dtype)
     L = len(I["whh"])
@@ -267,10 +301,10 @@ def max_errors(kernel, forced):
     return {k: [float(np.abs(np.asarray(kernel[k][l], dtype=np.float64) - forced[k][l]).max()) for l in range(len(forced[k]))] for k in KINDS}
 
 
-def floor_e32(inputs):
+def floor_e32(inputs, round=bf16_rne):
     """e32: the float32 stand-in against the oracle driven by the stand-in's own tensors, per kind and layer."""
-    s = standin(inputs)
-    return max_errors(s, operand_forced(inputs, s))
+    s = standin(inputs, round=round)
+    return max_errors(s, operand_forced(inputs, s, round=round))
 
 
 def caps(forced):
@@ -281,14 +315,16 @@ def caps(forced):
             "dG": [CAP_RMS * rms(forced["dG"][l]) for l in range(L)], "dh_init": [CAP_RMS * rms(forced["dh_init"][l]) for l in range(L)]}
 
 
-def check_kernel(inputs, kernel, label):
+def check_kernel(inputs, kernel, label, round=bf16_rne, e32=None):
     """The operand-forced comparison of a kernel's tensors: prints err, e32 and err / e32 per kind and layer, then asserts the caps
-    on M * e32 and err <= M * e32.  Returns the table's rows."""
-    forced = operand_forced(inputs, kernel)
-    err, e32, cap = max_errors(kernel, forced), floor_e32(inputs), caps(forced)
+    on M * e32 and err <= M * e32.  Returns the table's rows.  `round`: the kernel's operand rounding (identity: the exact-fp32
+    sweeps; the same M); `e32`: floor_e32(inputs, round) where the caller already has it (several kernels on one set of inputs)."""
+    forced = operand_forced(inputs, kernel, round=round)
+    err, e32, cap = max_errors(kernel, forced), floor_e32(inputs, round=round) if e32 is None else e32, caps(forced)
     rows = [(k, l, err[k][l], e32[k][l], cap[k][l]) for k in KINDS for l in range(len(forced[k]))]
+    tag = "fp32 oracle" if round is identity else "bf16 oracle"
     for k, l, e, f, c_ in rows:
-        print(f"[bf16 oracle] {label} {k}[{l}]: err {e:.3e}  e32 {f:.3e}  ratio {e / f if f > 0 else float('inf'):.2f}  bound {M[k] * f:.3e}  cap {c_:.3e}")
+        print(f"[{tag}] {label} {k}[{l}]: err {e:.3e}  e32 {f:.3e}  ratio {e / f if f > 0 else float('inf'):.2f}  bound {M[k] * f:.3e}  cap {c_:.3e}")
     for k, l, e, f, c_ in rows:
         assert f > 0, f"{label} {k}[{l}]: the stand-in's floor is zero"
         assert M[k] * f <= c_, f"{label} {k}[{l}]: bound {M[k] * f:.3e} above its cap {c_:.3e}"
