@@ -1166,6 +1166,51 @@ int b2t_clm_gptoss_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_g
                                    const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                    long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- gpt-oss with the experts kept in MXFP4 (csrc/causal_lm_gptoss_mx.hip) ---------------------------------------------------
+ * The published gpt-oss checkpoints hold the expert matrices in MXFP4 (OCP Microscaling: blocks of 32 e2m1 values -- 0, 0.5, 1,
+ * 1.5, 2, 3, 4, 6 and their negatives, two a byte, the low nibble first -- with one E8M0 scale byte, value * 2^(scale - 127);
+ * HF GptOssForCausalLM dequantises them the same way), 4.25 bits a weight.  These calls keep them so in device memory and
+ * unpack in the grouped GEMM: where the dense tile loads 16 bytes of B, the packed one loads the 4 bytes and the scale byte
+ * that hold the same eight elements and expands them, in registers, to the call's element type E, rounded to nearest even
+ * (fp16 subnormals included; every finite value is exact in bf16) -- the bits that the loader's dequantise-then-cast puts into
+ * gate_up_w / down_w.  From there on the kernel is the dense one, the k order included, so scores, token log-probs and
+ * route_out are BYTE-IDENTICAL to the b2t_clm_gptoss_* call on the expanded model, on both tiles (B2T_CLM_GEMM_256).
+ * The model and the b2t_clm_gptoss_t are the section's above, except that every layer's gate_up_w and down_w must be NULL (a
+ * caller holds one form of the experts, not both); mx is a HOST array of n_layers records with DEVICE pointers inside:
+ *   gate_up_q uint8 [n_experts][gate_up_stride][d / 2]    gate_up_s uint8 [n_experts][gate_up_stride][d / 32]
+ *   down_q    uint8 [n_experts][down_stride][F / 2]       down_s    uint8 [n_experts][down_stride][F / 32]
+ * in the rows of the dense stacks (gate and up rows interleaved in blocks of 32; element k of a row is nibble k & 1 of byte
+ * k / 2 and is scaled by byte k / 32 of the row's scales), the rows behind an expert's own filled with zero bytes, which unpack
+ * to zero.  A value that is not finite in E (a scale byte of 255; above 65504 in fp16) has no defined result: the loader
+ * (llm_rescore.gptoss_mx_device_layout) refuses such a block by name, as the dense loader does.
+ * The four score calls have the b2t_clm_gptoss_* twins' argument lists with mx after oss, their outputs, their route_out, their
+ * workspace (the size functions are the twins': b2t_clm_gptoss_ws_bytes / _tree_ws_bytes) and their refusals, under the entry
+ * point's own name where the twin has its own; they also refuse a null mx, a null pointer inside it, and a layer whose
+ * gate_up_w or down_w is not NULL.  Their names are declared in parentheses, so that a search for "b2t_clm_gptoss_<call>("
+ * finds the six calls of the dense section alone.
+ * b2t_clm_mxfp4_unpack_f16 / _bf16 write rows packed rows of K elements (q [rows][K / 2], s [rows][K / 32], K % 32 == 0, DEVICE)
+ * to the dense out [rows][K] through the same device function as the GEMM: a public utility, and the way to test the
+ * expansion exhaustively. */
+typedef struct {
+  const void *gate_up_q, *gate_up_s;   /* uint8 [n_experts][gate_up_stride][d / 2], [n_experts][gate_up_stride][d / 32] */
+  const void *down_q, *down_s;         /* uint8 [n_experts][down_stride][F / 2], [n_experts][down_stride][F / 32] */
+} b2t_clm_gptoss_mx_t;
+
+int (b2t_clm_gptoss_mx_score_f16)(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const b2t_clm_gptoss_mx_t* mx,
+                                  const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                  float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+int (b2t_clm_gptoss_mx_score_tree_f16)(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const b2t_clm_gptoss_mx_t* mx,
+                                       const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                       float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int (b2t_clm_gptoss_mx_score_bf16)(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const b2t_clm_gptoss_mx_t* mx,
+                                   const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                   float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+int (b2t_clm_gptoss_mx_score_tree_bf16)(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const b2t_clm_gptoss_mx_t* mx,
+                                        const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                        float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_mxfp4_unpack_f16(const void* q, const void* s, long long rows, int K, void* out, void* stream);
+int b2t_clm_mxfp4_unpack_bf16(const void* q, const void* s, long long rows, int K, void* out, void* stream);
+
 /* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
  * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
  * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,

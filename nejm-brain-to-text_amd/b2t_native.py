@@ -160,6 +160,11 @@ class ClmGptOss(C.Structure):
                 ("layers_host", C.POINTER(ClmGptOssLayer))]
 
 
+class ClmGptOssMx(C.Structure):
+    """Mirror of b2t_clm_gptoss_mx_t (include/b2t.h): one gpt-oss layer's experts kept in MXFP4, nibbles and scale bytes."""
+    _fields_ = [(n, VP) for n in ("gate_up_q", "gate_up_s", "down_q", "down_s")]
+
+
 class ClmQkNorm(C.Structure):
     """Mirror of b2t_clm_qknorm_t (include/b2t.h): device weights [hd] of one Qwen3 layer's q and k RMSNorm."""
     _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
@@ -329,6 +334,13 @@ for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes"
 for _t in ("ws_bytes", "tree_ws_bytes", "score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16"):
     _res, _args = _SIGNATURES["b2t_clm_llama_" + _t]
     _SIGNATURES["b2t_clm_gptoss_" + _t] = (_res, [_args[0], C.POINTER(ClmGptOss)] + _args[1:])
+# gpt-oss with the experts kept in MXFP4: the gpt-oss twin's list with the per-layer array of packed experts after the
+# descriptor (the size functions are the twins'), and the unpack utility
+for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16"):
+    _res, _args = _SIGNATURES["b2t_clm_gptoss_" + _t]
+    _SIGNATURES["b2t_clm_gptoss_mx_" + _t] = (_res, _args[:2] + [C.POINTER(ClmGptOssMx)] + _args[2:])
+for _t in ("f16", "bf16"):
+    _SIGNATURES["b2t_clm_mxfp4_unpack_" + _t] = (C.c_int, [VP, VP, LL, C.c_int, VP, VP])
 # GPT-NeoX: the OPT twin's list on its own model struct (same cache)
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
            "score_tree_cached_f16"):
@@ -337,11 +349,11 @@ for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes"
 
 
 def header_symbols():
-    """Every function name declared in include/b2t.h."""
+    """Every function name declared in include/b2t.h, as `name(` or `(name)(` (a function pointer type, `(*name)(`, is none)."""
     with open(HEADER_PATH) as f:
         txt = f.read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(b2t_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"(?<!\*)\b(b2t_[a-z0-9_]+)\s*\)?\s*\(", txt)))
 
 
 def load():

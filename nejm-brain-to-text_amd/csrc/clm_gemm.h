@@ -11,7 +11,8 @@
 // the tile (clm_gemm_grouped_kernel: one B matrix per expert) with EP_SWIGLU and EP_F32 in both, causal_lm_gemma2.hip the two
 // Gemma-2 adds (EP_GEGLU: gelu_new where SwiGLU has silu; EP_HEAD_CAP: the fused head on soft-capped logits) in both,
 // causal_lm_phi3.hip EP_QKV_F32 again in both (Phi-3's rotation reads the fp32 q | k columns in a kernel of its own),
-// causal_lm_gptoss.hip the two gpt-oss adds to the grouped tile (EP_OSS_GLU, EP_F32_BIAS: per-expert biases) in both.  Which
+// causal_lm_gptoss.hip the two gpt-oss adds to the grouped tile (EP_OSS_GLU, EP_F32_BIAS: per-expert biases) in both,
+// causal_lm_gptoss_mx.hip those two on the packed form of the grouped tile (clm_gemm_grouped_mx_kernel: B in MXFP4).  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -51,14 +52,85 @@ __device__ __forceinline__ float gelu_new(float v) {
 // pre-activation yields v or -0.0 / 0, never NaN.
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.7071067811865476f)); }
 
+// MXFP4 -> E: the eight values of 4 bytes of e2m1 nibbles (low nibble first: element 2i is byte i's low nibble) times
+// 2^(sb - 127), sb the block's E8M0 scale byte, as eight E in element order -- the uint4 that the dense path loads from a matrix
+// of (E)(float)(value * 2^(sb - 127)), rounded to nearest even.  No table in memory and no per-element branch: a byte permute
+// looks the magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 up as the high byte of an fp16 (the low byte is 0), four at a time; the sign
+// bit is or-ed in; a second permute interleaves the even and the odd elements into four fp16 pairs.  Those pairs are exact,
+// and one multiplication by a power of two, whose one rounding is the contract's, does the rest:
+//   fp16  a packed fp16 multiply.  2^(sb - 127) is an fp16 only for sb in [103, 142], so the table holds the values times 2^-13
+//         (sb <= 128; 0.5 * 2^-13 is the smallest normal) or times 4 (sb > 128) and the factor is 2^(sb - 114) or 2^(sb - 129),
+//         a normal fp16 for 100 <= sb <= 144.  Below 100 the largest value, 6 * 2^-28, rounds to zero, and the factor is 0, which
+//         keeps the signs; above 144 only zero nibbles are finite, and the factor stays 2^15.  The subnormal results (sb < 114)
+//         are the multiplier's own rounding to nearest even (fp16 denormals are never flushed on this target).
+//   bf16  the pair widened to fp32 (exact) times 2^(sb - 127) in fp32 (exact: at most two significant bits, and bf16 has fp32's
+//         exponent range, its subnormals included), of which the upper halves are the bf16s.
+// A scale byte of 255 (NaN) has no defined result: the loader refuses it.  The one definition: the packed grouped tile below
+// and b2t_clm_mxfp4_unpack_f16 / _bf16 (causal_lm_gptoss_mx.hip) call it.
+template <int REF>   // the table: values * 2^-13 (0), * 4 (1) or * 1 (2), as fp16 pairs (element 2i, element 2i + 1) of byte i
+__device__ __forceinline__ void mxfp4_pairs_f16(unsigned q, unsigned (&p)[4], bool hi = false) {
+  constexpr unsigned T0[3] = {0x0A080400u, 0x46444000u, 0x3E3C3800u}, T1[3] = {0x12100E0Cu, 0x4E4C4A48u, 0x46444240u};
+  unsigned t0 = T0[REF], t1 = T1[REF];
+  if (REF == 0 && hi) { t0 = T0[1]; t1 = T1[1]; }
+  const unsigned ev = q & 0x0F0F0F0Fu, od = (q >> 4) & 0x0F0F0F0Fu;   // elements 0, 2, 4, 6 and 1, 3, 5, 7, one a byte
+  const unsigned he = __builtin_amdgcn_perm(t1, t0, ev & 0x07070707u) | ((ev & 0x08080808u) << 4);
+  const unsigned ho = __builtin_amdgcn_perm(t1, t0, od & 0x07070707u) | ((od & 0x08080808u) << 4);
+  p[0] = __builtin_amdgcn_perm(ho, he, 0x040C000Cu); p[1] = __builtin_amdgcn_perm(ho, he, 0x050C010Cu);
+  p[2] = __builtin_amdgcn_perm(ho, he, 0x060C020Cu); p[3] = __builtin_amdgcn_perm(ho, he, 0x070C030Cu);
+}
+template <class E>
+__device__ __forceinline__ uint4 mxfp4_unpack8(unsigned q, unsigned sb);
+template <>
+__device__ __forceinline__ uint4 mxfp4_unpack8<_Float16>(unsigned q, unsigned sb) {
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  const bool hi = sb > 128u;
+  const unsigned ex = hi ? (sb < 144u ? sb : 144u) - 114u : (sb > 99u ? sb - 99u : 0u);   // the factor's exponent field
+  const unsigned f = (ex << 10) * 0x10001u;
+  unsigned p[4];
+  mxfp4_pairs_f16<0>(q, p, hi);
+  uint4 r;
+  unsigned* o = &r.x;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const h2 v = __builtin_bit_cast(h2, p[i]) * __builtin_bit_cast(h2, f);
+    o[i] = __builtin_bit_cast(unsigned, v);
+  }
+  return r;
+}
+template <>
+__device__ __forceinline__ uint4 mxfp4_unpack8<__bf16>(unsigned q, unsigned sb) {
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  const float f = __builtin_bit_cast(float, sb ? sb << 23 : 0x00400000u);   // 2^(sb - 127); 2^-127 is an fp32 subnormal
+  unsigned p[4];
+  mxfp4_pairs_f16<2>(q, p);
+  uint4 r;
+  unsigned* o = &r.x;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const h2 v = __builtin_bit_cast(h2, p[i]);
+    const unsigned lo = __builtin_bit_cast(unsigned, (float)v[0] * f), up = __builtin_bit_cast(unsigned, (float)v[1] * f);
+    o[i] = __builtin_amdgcn_perm(up, lo, 0x07060302u);
+  }
+  return r;
+}
+
 // BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.  E is the element type of
 // A, B, bias and out16 (ClmElem, clm_internal.h).  This is the body of both kernels below.  GROUPED (routed experts,
 // clm_moe.h): B is a stack of matrices b_stride elements apart and the rows of A are sorted by matrix in segments of whole
 // 256-row blocks, so a tile of either size lies in one segment; it takes its matrix from blk_expert[m0 / 128] and returns, the
 // whole workgroup alike and before any barrier, where that is negative (a block no row was routed to).  Nothing else
-// differs: the k order and the arithmetic of an output element are those of the plain tile.
-template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16, bool GROUPED = false>
+// differs: the k order and the arithmetic of an output element are those of the plain tile.  MX (with GROUPED: gpt-oss experts
+// kept in MXFP4) reads B packed: g.B holds K / 2 bytes of nibbles a row and g.b_scale K / 32 scale bytes a row, in the rows and
+// the strides (b_stride, in elements) of the dense stack.  A thread fetches, where the dense tile fetches 16 bytes of B, the 4
+// bytes that hold the same eight elements and their block's scale byte -- a thread's piece never crosses a row's end or a
+// block of 32 -- and unpacks them (mxfp4_unpack8) into the uint4 the dense tile would have loaded, on its way into the same LDS
+// layout: from the LDS reads on the kernel is the dense one, operand bits and k order included.  The unpacking of tile kt + 1 is
+// spread over the last three of tile kt's four MFMA steps, so that its VALU work issues under the matrix pipe and not, with every
+// wave of the workgroup at once, between the k loop's last MFMA and the barrier (in the last tile it expands stale registers,
+// which nothing reads).
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16, bool GROUPED = false, bool MX = false>
 __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
+  static_assert(!MX || GROUPED, "the packed B operand is the grouped tile's");
   using vec8 = typename ClmElem<E>::v8;
   constexpr int T = 64 * WGM * WGN, WTM = BM / WGM, WTN = BN / WGN, FM = WTM / 32, FN = WTN / 32, RS = T / 8;
   static_assert(WTN == 64, "the head epilogue reduces over 64-column wave slices");
@@ -77,19 +149,33 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
   const int K = g.K, nk = K / CK;
   const E* ag = static_cast<const E*>(g.A) + (long long)(m0 + (tid >> 3)) * K + (tid & 7) * 8;
   const E* bg = static_cast<const E*>(g.B) + (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;
+  long long boff = (long long)(n0 + (tid >> 3)) * K + (tid & 7) * 8;   // MX: the element bg points at, counted from g.B
   int ex = 0;
   if (GROUPED) {
     ex = g.blk_expert[m0 / 128];   // one value per workgroup: m0 is a multiple of 128
     if (ex < 0) return;
     bg += (long long)ex * g.b_stride;
+    boff += (long long)ex * g.b_stride;
   }
   const long long rstep = (long long)RS * K;
   uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
+  // MX: element e of B is nibble e & 1 of byte e / 2 and belongs to scale byte e / 32; boff, rstep and k0 are multiples of 8
+  const unsigned char* bq = static_cast<const unsigned char*>(g.B);
+  const unsigned char* bs = static_cast<const unsigned char*>(g.b_scale);
+  unsigned rq0, rq1, rq2, rq3, rs0, rs1, rs2, rs3;
+#define CLM_FETCH_MX(rq, rs, e) rq = *reinterpret_cast<const unsigned*>(bq + ((e) >> 1)); rs = bs[(e) >> 5];
+  // an empty statement that keeps an unpacked piece where it was computed: without it the compiler moves the unpacking, whose
+  // results only the stash reads, behind the k tile's last MFMA
+#define CLM_PIN(r) asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
 #define CLM_FETCH(k0)                                                                                                   \
   ra0 = *reinterpret_cast<const uint4*>(ag + (k0)); ra1 = *reinterpret_cast<const uint4*>(ag + rstep + (k0));             \
   ra2 = *reinterpret_cast<const uint4*>(ag + 2 * rstep + (k0)); ra3 = *reinterpret_cast<const uint4*>(ag + 3 * rstep + (k0)); \
+  if constexpr (MX) {                                                                                                   \
+    CLM_FETCH_MX(rq0, rs0, boff + (k0)) CLM_FETCH_MX(rq1, rs1, boff + rstep + (k0))                                     \
+    CLM_FETCH_MX(rq2, rs2, boff + 2 * rstep + (k0)) CLM_FETCH_MX(rq3, rs3, boff + 3 * rstep + (k0))                     \
+  } else {                                                                                                              \
   rb0 = *reinterpret_cast<const uint4*>(bg + (k0)); rb1 = *reinterpret_cast<const uint4*>(bg + rstep + (k0));             \
-  rb2 = *reinterpret_cast<const uint4*>(bg + 2 * rstep + (k0)); rb3 = *reinterpret_cast<const uint4*>(bg + 3 * rstep + (k0));
+  rb2 = *reinterpret_cast<const uint4*>(bg + 2 * rstep + (k0)); rb3 = *reinterpret_cast<const uint4*>(bg + 3 * rstep + (k0)); }
 #define CLM_STASH(buf)                                                                                                  \
   { E* ad = As + (buf) * BM * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
     E* bd = Bs + (buf) * BN * CPITCH + (tid >> 3) * CPITCH + (tid & 7) * 8;                                      \
@@ -105,6 +191,10 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
   CLM_FETCH(0)
+  if constexpr (MX) {
+    rb0 = mxfp4_unpack8<E>(rq0, rs0); rb1 = mxfp4_unpack8<E>(rq1, rs1);
+    rb2 = mxfp4_unpack8<E>(rq2, rs2); rb3 = mxfp4_unpack8<E>(rq3, rs3);
+  }
   CLM_STASH(0)
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
@@ -123,11 +213,18 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
       for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = ClmElem<E>::mfma(a[i], b[j], acc[i][j]);
+      if constexpr (MX) {   // the next tile's pieces are expanded between this tile's MFMAs, behind the step that hid their loads
+        if (kk == 16) { rb0 = mxfp4_unpack8<E>(rq0, rs0); CLM_PIN(rb0) }
+        if (kk == 32) { rb1 = mxfp4_unpack8<E>(rq1, rs1); CLM_PIN(rb1) }
+        if (kk == 48) { rb2 = mxfp4_unpack8<E>(rq2, rs2); CLM_PIN(rb2) rb3 = mxfp4_unpack8<E>(rq3, rs3); CLM_PIN(rb3) }
+      }
     }
     if (kt + 1 < nk) { CLM_STASH(cur ^ 1) }
     __syncthreads();
   }
 #undef CLM_FETCH
+#undef CLM_FETCH_MX
+#undef CLM_PIN
 #undef CLM_STASH
   // epilogue: C/D layout of the 32x32 MFMAs: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
   const int colw = n0 + wn * WTN;
@@ -374,27 +471,34 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_grouped_kernel(ClmGem
   clm_gemm_tile<BM, BN, WGM, WGN, EP, E, true>(g);
 }
 
-template <int BM, int BN, int WGM, int WGN, int EP, class E, bool GROUPED>
+// the grouped tile over experts kept in MXFP4 (ClmGemm::b_scale)
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16>
+__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_grouped_mx_kernel(ClmGemm g) {
+  clm_gemm_tile<BM, BN, WGM, WGN, EP, E, true, true>(g);
+}
+
+template <int BM, int BN, int WGM, int WGN, int EP, class E, bool GROUPED, bool MX = false>
 constexpr auto clm_gemm_entry() {
-  if constexpr (GROUPED) return &clm_gemm_grouped_kernel<BM, BN, WGM, WGN, EP, E>;
+  if constexpr (MX) return &clm_gemm_grouped_mx_kernel<BM, BN, WGM, WGN, EP, E>;
+  else if constexpr (GROUPED) return &clm_gemm_grouped_kernel<BM, BN, WGM, WGN, EP, E>;
   else return &clm_gemm_kernel<BM, BN, WGM, WGN, EP, E>;
 }
 
 constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * 2; }   // 2-byte elements
 
 // The launch of one GEMM on the tile the rule chose (ClmGemmTiles of clm_internal.h); GROUPED launches the grouped kernel on
-// the same grid (M is then the sorted rows S, a multiple of 256).
-template <int EP, class E = _Float16, bool GROUPED = false>
+// the same grid (M is then the sorted rows S, a multiple of 256), MX the packed grouped one.
+template <int EP, class E = _Float16, bool GROUPED = false, bool MX = false>
 int clm_gemm_tiles(const ClmGemm& g, hipStream_t s, bool use256) {
   if (use256) {   // one 8-wave workgroup per CU
-    const auto kern = clm_gemm_entry<256, 256, 2, 4, EP, E, GROUPED>();
+    const auto kern = clm_gemm_entry<256, 256, 2, 4, EP, E, GROUPED, MX>();
     const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));
     hipLaunchKernelGGL(kern, dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
   } else {
-    const auto kern = clm_gemm_entry<128, 128, 2, 2, EP, E, GROUPED>();
+    const auto kern = clm_gemm_entry<128, 128, 2, 2, EP, E, GROUPED, MX>();
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(128, 128));

@@ -115,10 +115,12 @@ inline ClmLayout gptoss_layout(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t*
 
 // One layer's MLP over `rows` rows, x16 = E(RMSNorm(resid; norm2_w)) the operand of the router and of the experts alike:
 // resid += sum_j w[j] (glu_{e_j}(x16) down_{e_j}^T + b_down_{e_j}), in order of choice.  moe_mlp of clm_moe.h with this family's
-// router, the per-expert biases and EP_OSS_GLU; the plan, the gather, S and the combine are that file's.
+// router, the per-expert biases and EP_OSS_GLU; the plan, the gather, S and the combine are that file's.  With mx (the experts
+// kept in MXFP4, causal_lm_gptoss_mx.hip) gate_up_w / down_w of the layer are the packed nibbles and mx[l] has their scale bytes;
+// P's two grouped GEMMs are then the packed ones.
 template <class P>
 int gptoss_mlp(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t& g, int l, long long rows, const ClmLayout& L, char* base,
-               const typename P::E* x16, float* resid, hipStream_t s) {
+               const typename P::E* x16, float* resid, hipStream_t s, const b2t_clm_gptoss_mx_t* mx = nullptr) {
   using E = typename P::E;
   const int d = m.d_model, F = m.ffn_dim, ne = g.n_experts, k = g.top_k;
   const b2t_clm_moe_t moe = gptoss_moe(&g);
@@ -147,11 +149,13 @@ int gptoss_mlp(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t& g, int l, long 
   gm.A = xs; gm.B = w.gate_up_w; gm.M = (int)R.S; gm.N = 2 * F; gm.K = d; gm.out16 = hs; gm.ldo = F;
   gm.blk_expert = blk_expert; gm.b_stride = g.gate_up_stride * d;
   gm.bias = w2.gate_up_b; gm.bias_stride = g.gate_up_stride; gm.glu_limit = g.swiglu_limit;
+  gm.b_scale = mx ? mx[l].gate_up_s : nullptr;
   if (int rc = P::gemm_experts_glu(gm, s)) return rc;
   gm = ClmGemm{};
   gm.A = hs; gm.B = w.down_w; gm.M = (int)R.S; gm.N = d; gm.K = F; gm.resid = ys; gm.ldo = d;
   gm.blk_expert = blk_expert; gm.b_stride = g.down_stride * F;
   gm.bias = w2.down_b; gm.bias_stride = g.down_stride;
+  gm.b_scale = mx ? mx[l].down_s : nullptr;
   if (int rc = P::gemm_experts_f32b(gm, s)) return rc;
   const long long elems = rows * d;
   hipLaunchKernelGGL(clm_moe_combine_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, ys, slot_of, route_w, k, resid,
@@ -161,10 +165,10 @@ int gptoss_mlp(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t& g, int l, long 
 }
 
 // The forward over r.rows rows up to the per-row log-probs; attn(layer, qkv, out) enqueues one layer's attention, out being
-// [rows][Hq hd].
+// [rows][Hq hd].  mx: gptoss_mlp's.
 template <class P, class Attn>
 int gptoss_forward(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t& g, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn,
-                   hipStream_t s) {
+                   hipStream_t s, const b2t_clm_gptoss_mx_t* mx = nullptr) {
   using E = typename P::E;
   const int d = m.d_model, Hq = m.n_heads, Hkv = m.n_kv_heads, hd = g.head_dim, qw = (Hq + 2 * Hkv) * hd;
   const long long rows = r.rows;
@@ -188,7 +192,7 @@ int gptoss_forward(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t& g, const Cl
     gm.A = ao; gm.B = w.o_w; gm.M = (int)rows; gm.N = d; gm.K = Hq * hd; gm.bias = g.layers_host[l].o_b; gm.resid = resid; gm.ldo = d;
     if (int rc = P::gemm_resid(gm, s)) return rc;
     if (int rc = P::rmsnorm(resid, nullptr, rows, W(w.norm2_w), m.rms_eps, x16, d, s)) return rc;
-    if (int rc = gptoss_mlp<P>(m, g, l, rows, L, base, x16, resid, s)) return rc;
+    if (int rc = gptoss_mlp<P>(m, g, l, rows, L, base, x16, resid, s, mx)) return rc;
   }
   if (r.Mh <= 0) return 0;
   if (int rc = P::rmsnorm(resid, r.d_src, r.Mh, W(m.final_norm_w), m.rms_eps, x16, d, s)) return rc;

@@ -92,6 +92,8 @@ struct ClmGemm {
   float cap;                                // EP_HEAD_CAP: the soft cap on the logits (> 0)
   long long bias_stride;                    // grouped EP_OSS_GLU / EP_F32_BIAS: elements between two consecutive experts' biases
   float glu_limit;                          // EP_OSS_GLU: the clamp on gate (from above) and up (both sides), > 0
+  // the packed grouped kernel only (clm_gemm_grouped_mx_kernel): B is MXFP4 nibbles, K / 2 bytes a row, low nibble first
+  const void* b_scale;                      // E8M0 scale bytes, K / 32 a row, in the rows and strides of B
 };
 
 // The tile rule (B2T_CLM_GEMM_256) lives in one definition, causal_lm.hip: it picks the tile and hands the launch to `tiles`,

@@ -1716,6 +1716,9 @@ _GPTOSS_LAYER_FIELDS = ("sinks", "o_b", "router_w", "router_b", "gate_up_b", "do
 _GPTOSS_ORDER = ("norm1_w", "norm2_w", "qkv_w", "qkv_b", "o_w", "o_b", "sinks", "router_w", "router_b", "gate_up_w", "gate_up_b",
                  "down_w", "down_b")   # the layout's per layer
 _FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)   # e2m1
+EXPERT_WEIGHTS = ("dense", "mxfp4")   # build_scorer's expert_weights: expanded to the compute dtype, or kept as the checkpoint has them
+_GPTOSS_MX_FIELDS = ("gate_up_q", "gate_up_s", "down_q", "down_s")   # b2t_clm_gptoss_mx_t
+_GPTOSS_MX_ORDER = tuple(g for f in _GPTOSS_ORDER for g in ({"gate_up_w": ("gate_up_q", "gate_up_s"), "down_w": ("down_q", "down_s")}.get(f, (f,))))
 
 
 def _gptoss_layer_types(cfg: dict) -> list:
@@ -1826,6 +1829,17 @@ def mxfp4_dequant(blocks, scales, name: str = "mxfp4"):
     return out.reshape(*scales.shape[:-1], scales.shape[-1] * 32)
 
 
+def mxfp4_block_finite(blocks, scales, wdt):
+    """Per block (bool, the shape of scales): whether every value of the block is finite after mxfp4_dequant(...).to(wdt),
+    decided from the block's largest nibble magnitude and its scale byte without expanding anything: the magnitudes are
+    monotone in the 3-bit code, a value has at most two significant bits (so no rounding carries it over the dtype's largest
+    number), and a scale byte of 255 is 0 * 2^128 = NaN at best."""
+    import torch
+    code = torch.maximum(blocks & 7, (blocks >> 4) & 7).amax(-1).long()                    # the largest magnitude's code, 0..7
+    top = torch.ldexp(torch.tensor(_FP4_VALUES[:8], dtype=torch.float32, device=blocks.device)[code], scales.to(torch.int32) - 127)
+    return (top <= torch.finfo(wdt).max) & (scales != 255)
+
+
 def gptoss_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float], dtype=None) -> Dict[str, "object"]:
     """Tensors in the layout of b2t_clm_llama_t / b2t_clm_gptoss_t from a gpt-oss state dict.  Embedding, untied head, norms and the
     rotary tables ([max_pos][32], rope_tables of rope's inv_freq times its attention factor in fp32; rope = gptoss_rope(cfg)) are
@@ -1838,9 +1852,36 @@ def gptoss_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float]
     -- gate_up_proj_blocks / _scales [E][2F][d / 32]([16]) and down_proj_blocks / _scales [E][d][F / 32]([16]), dequantised to
     fp32 exactly (mxfp4_dequant) and then cast; a value that does not survive the cast as a finite number is refused by name.
     The expert matrices are transposed to [rows][K], and gate / up are de-interleaved into gate_up_row_perm's blocks of 32."""
+    return _gptoss_layout(state, dims, rope, dtype, False)
+
+
+def gptoss_mx_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float], dtype=None) -> Dict[str, "object"]:
+    """gptoss_device_layout for build_scorer(..., expert_weights="mxfp4"): every tensor but the expert matrices is that layout's,
+    made by the same code, and in place of gate_up_w / down_w the layers have the checkpoint's MXFP4 bytes as the kernels of
+    csrc/causal_lm_gptoss_mx.hip read them (b2t_clm_gptoss_mx_t): gate_up_q uint8 [E][round_up(2F, 256)][d / 2] and gate_up_s
+    uint8 [E][round_up(2F, 256)][d / 32], the blocks and scale bytes of gate_up_proj under the row order of gate_up_w
+    (de-interleaved into gate_up_row_perm's blocks of 32), down_q [E][round_up(d, 256)][F / 2] and down_s [E][round_up(d,
+    256)][F / 32]; the rows behind an expert's own are zero bytes, which unpack to zero.  The bytes are permuted by row and
+    padded, never expanded: 4.25 bits a weight here and on the device.  mxfp4_dequant(q, s).to(dtype) of these arrays is
+    gate_up_w / down_w of gptoss_device_layout to the byte.
+    A checkpoint in the plain spelling is refused with the name of the first _blocks tensor it lacks, before anything else is
+    read; a block with a value that is not finite in the compute dtype is refused as the dense loader refuses it (same
+    message, same tensor), decided by mxfp4_block_finite."""
+    return _gptoss_layout(state, dims, rope, dtype, True)
+
+
+def _gptoss_layout(state: dict, dims: dict, rope, dtype, packed: bool) -> Dict[str, "object"]:
+    """gptoss_device_layout (packed False) and gptoss_mx_device_layout (True)"""
     import torch
     wdt = clm_dtype(dtype)
     sd = dict(state)
+    if packed:
+        for i in range(dims["n_layers"]):
+            for n in ("gate_up_proj", "down_proj"):
+                name = f"model.layers.{i}.mlp.experts.{n}_blocks"
+                if name not in sd:
+                    raise ValueError(f"expert_weights='mxfp4': the checkpoint lacks {name} (its experts are not in the MXFP4 "
+                                     f"spelling; quantising a plain checkpoint is not built: use expert_weights='dense')")
     d, ffn, Hq, hd, ne = (dims[k] for k in ("d_model", "ffn_dim", "n_heads", "head_dim", "n_experts"))
     inv_freq, att = rope
     if len(inv_freq) != hd // 2:
@@ -1849,12 +1890,19 @@ def gptoss_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float]
     raw = get.raw
 
     def expert_rows(name, rows, K):
-        """[E][rows][K] in wdt of the expert matrix `name`, from either spelling"""
+        """[E][rows][K] in wdt of the expert matrix `name`, from either spelling; packed: (its blocks as [E][rows][K / 2], its
+        scale bytes [E][rows][K / 32]), as stored"""
         if name + "_blocks" in sd:
             blocks, scales = raw(name + "_blocks"), raw(name + "_scales")
             if tuple(blocks.shape) != (ne, rows, K // 32, 16) or tuple(scales.shape) != (ne, rows, K // 32) or K % 32:
                 raise ValueError(f"{name}_blocks / _scales: shapes {tuple(blocks.shape)} / {tuple(scales.shape)}, expected "
                                  f"{(ne, rows, K // 32, 16)} / {(ne, rows, K // 32)}")
+            if packed:
+                if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
+                    raise ValueError(f"{name}: blocks {blocks.dtype} and scales {scales.dtype} must be uint8")
+                if not mxfp4_block_finite(blocks, scales, wdt).all():
+                    raise ValueError(f"{name}_blocks / _scales: a value is not finite in {wdt}")
+                return blocks.reshape(ne, rows, K // 2), scales
             t = mxfp4_dequant(blocks, scales, name).to(wdt)
             if not torch.isfinite(t).all():
                 raise ValueError(f"{name}_blocks / _scales: a value is not finite in {wdt}")
@@ -1876,16 +1924,22 @@ def gptoss_device_layout(state: dict, dims: dict, rope: Tuple[np.ndarray, float]
         L.update(qkv_b=torch.cat([get(p + f"self_attn.{n}.bias", (w,)) for n, w in _qkv_widths(dims, hd).items()]),
                  o_b=get(p + "self_attn.o_proj.bias", (d,)),
                  router_w=get(p + "mlp.router.weight", (ne, d)), router_b=get(p + "mlp.router.bias", (ne,)),
-                 gate_up_w=_stack_padded(gate_up[:, deint], gus),
                  gate_up_b=_stack_padded(get(p + "mlp.experts.gate_up_proj_bias", (ne, 2 * ffn))[:, deint], gus),
-                 down_w=_stack_padded(down, dns), down_b=_stack_padded(get(p + "mlp.experts.down_proj_bias", (ne, d)), dns))
-        _put_layer(out, i, L, _GPTOSS_ORDER)
+                 down_b=_stack_padded(get(p + "mlp.experts.down_proj_bias", (ne, d)), dns))
+        if packed:
+            L.update(gate_up_q=_stack_padded(gate_up[0][:, deint], gus), gate_up_s=_stack_padded(gate_up[1][:, deint], gus),
+                     down_q=_stack_padded(down[0], dns), down_s=_stack_padded(down[1], dns))
+        else:
+            L.update(gate_up_w=_stack_padded(gate_up[:, deint], gus), down_w=_stack_padded(down, dns))
+        _put_layer(out, i, L, _GPTOSS_MX_ORDER if packed else _GPTOSS_ORDER)
     return out
 
 
-def load_gptoss_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None) -> Tuple[dict, Dict[str, "object"]]:
-    """(dims, host tensors in the device layout) of the gpt-oss checkpoint in model_dir; dtype as clm_dtype reads it."""
-    return _load_arrays(FAMILIES["gpt_oss"], model_dir, max_positions, dtype)
+def load_gptoss_arrays(model_dir: str, max_positions: Optional[int] = None, dtype=None,
+                       expert_weights: str = "dense") -> Tuple[dict, Dict[str, "object"]]:
+    """(dims, host tensors in the device layout) of the gpt-oss checkpoint in model_dir; dtype as clm_dtype reads it;
+    expert_weights="mxfp4": gptoss_mx_device_layout's."""
+    return _load_arrays(_family_for(FAMILIES["gpt_oss"], expert_weights), model_dir, max_positions, dtype)
 
 
 def gptoss_check_cache(context_cache_tokens) -> None:
@@ -1905,6 +1959,7 @@ class GptOssScorer(LlamaScorer):
     _SIZES = "b2t_clm_gptoss_"
     _CONTEXT_CACHE = False
     _OWN_ARRAYS = (".sinks",)   # fp32 in either compute dtype
+    _PACKED = ()                # those of _OWN_ARRAYS that are uint8 (GptOssMxScorer)
 
     def _describe(self, dims, arrays, dtype, context_cache_tokens):
         import b2t_native as N
@@ -1923,13 +1978,44 @@ class GptOssScorer(LlamaScorer):
         import torch
         for k, v in arrays.items():
             if k.endswith(self._OWN_ARRAYS):
-                if v.dtype != torch.float32:
-                    raise ValueError(f"GptOssScorer: {k} is {v.dtype}, expected torch.float32")
+                want = torch.uint8 if k.endswith(self._PACKED) else torch.float32
+                if v.dtype != want:
+                    raise ValueError(f"GptOssScorer: {k} is {v.dtype}, expected {want}")
                 self.w[k] = v.to(self.device).contiguous()
         for i in range(self.dims["n_layers"]):
             for f in _GPTOSS_LAYER_FIELDS:
                 setattr(self._oss_layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
             self._oss_layers[i].window = self.dims["windows"][i]
+
+
+class GptOssMxScorer(GptOssScorer):
+    """A GptOssScorer that keeps the experts in MXFP4 on the device (build_scorer(..., expert_weights="mxfp4")): `w` holds
+    gptoss_mx_device_layout's uint8 layers.<i>.gate_up_q / gate_up_s / down_q / down_s, 4.25 bits a weight, and no gate_up_w /
+    down_w (the model descriptor's are NULL); the calls are b2t_clm_gptoss_mx_score_f16 / _tree_f16 / _bf16 / _tree_bf16
+    (csrc/causal_lm_gptoss_mx.hip) with the b2t_clm_gptoss_mx_t array of those tensors, which unpack in the grouped GEMM.  Scores,
+    token log-probs and last_stats are the GptOssScorer's of the same checkpoint to the byte; the workspace is the same."""
+
+    _OWN_ARRAYS = (".sinks",) + tuple("." + f for f in _GPTOSS_MX_FIELDS)
+    _PACKED = tuple("." + f for f in _GPTOSS_MX_FIELDS)
+
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
+        import b2t_native as N
+        super()._describe(dims, arrays, dtype, context_cache_tokens)
+        if dims["n_layers"] > 0 and ("layers.0.gate_up_q" not in arrays or "layers.0.gate_up_w" in arrays):
+            raise KeyError("GptOssMxScorer: the arrays lack layers.<i>.gate_up_q / gate_up_s / down_q / down_s or hold gate_up_w "
+                           "beside them (gptoss_mx_device_layout makes them)")
+        self._mx = (N.ClmGptOssMx * max(1, dims["n_layers"]))()
+        self._family, self._qk = "gptoss_mx", (self._oss, self._mx)   # the size functions are the dense twins': _size_args stays
+
+    def _point(self, arrays):
+        super()._point(arrays)
+        for i in range(self.dims["n_layers"]):
+            for f in _GPTOSS_MX_FIELDS:
+                setattr(self._mx[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
+
+    def expert_bytes(self) -> int:
+        """bytes of the packed experts held: n_layers E (gate_up_stride (d / 2 + d / 32) + down_stride (F / 2 + F / 32))"""
+        return sum(v.numel() for k, v in self.w.items() if k.endswith(self._PACKED))
 
 
 def tree_plan(ids, seq_off, cap: Optional[int] = None):
@@ -1990,6 +2076,19 @@ _FAMILY_ROWS = (
 FAMILIES = {mt: fam for fam in _FAMILY_ROWS for mt in fam.model_types}   # by config.json's model_type
 
 
+def _family_for(fam: Family, expert_weights: str) -> Family:
+    """The family's row for build_scorer's expert_weights: itself for "dense"; for "mxfp4" gpt-oss with the packed layout and
+    scorer, any other family refused.  Reads no weight."""
+    if expert_weights not in EXPERT_WEIGHTS:
+        raise ValueError(f"expert_weights {expert_weights!r} is not one of {EXPERT_WEIGHTS}")
+    if expert_weights == "dense":
+        return fam
+    if fam.scorer is not GptOssScorer:
+        raise ValueError(f"expert_weights='mxfp4' is for gpt_oss checkpoints, whose experts are published in MXFP4; model_type "
+                         f"{fam.model_types[0]!r} has none")
+    return fam._replace(layout=gptoss_mx_device_layout, scorer=GptOssMxScorer)
+
+
 def _load_arrays(fam: Family, model_dir: str, max_positions: Optional[int] = None, dtype=None):
     """(dims, host tensors in the device layout) of the family's checkpoint in model_dir: what every load_*_arrays returns."""
     cfg = load_config(model_dir)
@@ -2001,7 +2100,8 @@ def _load_arrays(fam: Family, model_dir: str, max_positions: Optional[int] = Non
     return dims, fam.layout(_load_state_dict(model_dir), dims, fam.rope(cfg), wdt)
 
 
-def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, dtype=None):
+def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, *,
+                 expert_weights="dense", dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: the row of FAMILIES that serves it (the one
     list of the supported families: OPT, GPT-2, GPT-NeoX / Pythia, Llama / Mistral / Qwen2 / Qwen3, OLMo-2, Mixtral, Gemma-2,
     Phi-3 / Phi-4, gpt-oss, each with its scorer class).  Anything else ("olmo", "olmo3", "gemma", "gemma3", "qwen3_moe", "phi",
@@ -2010,13 +2110,18 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
     alone for OPT, GPT-2 and GPT-NeoX): None or "float16", "bfloat16" (without a context cache), or "auto" = the dtype
     config.json says the checkpoint was saved in (bfloat16 -> bfloat16; anything else, and every fp16-only family -> float16).
     A dtype or a context cache that is refused (gpt-oss has no cache, nor has bfloat16, nor a device without GPU memory) is
-    refused before any weight is read."""
+    refused before any weight is read.
+    expert_weights (by keyword, like dtype behind it): "dense" (the default) expands a gpt-oss checkpoint's MXFP4 experts to the compute dtype, four times their
+    published size; "mxfp4" keeps them packed in host and device memory and unpacks them in the grouped GEMM (GptOssMxScorer:
+    the same scores to the byte).  "mxfp4" for another family, or for a gpt-oss checkpoint in the plain spelling (by the name of
+    the _blocks tensor it lacks), is refused before any weight is expanded."""
     cfg = load_config(model_dir)
     mt = cfg.get("model_type", "opt")
     fam = FAMILIES.get(mt)
     if fam is None:
         raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, phi3, "
                          f"gpt_oss, olmo2, mixtral)")
+    fam = _family_for(fam, expert_weights)
     # every refusal that needs no weight, before the weights are read
     if not fam.scorer._CONTEXT_CACHE:
         gptoss_check_cache(context_cache_tokens)
@@ -2029,14 +2134,16 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
-              max_positions=None, dtype=None):
+              max_positions=None, *, expert_weights="dense", dtype=None):
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     LlamaScorer's checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto").  The scorer is build_scorer's: its
     docstring lists the families.
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
-    context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory)."""
+    context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory).
+    expert_weights="mxfp4" keeps a gpt-oss checkpoint's experts packed (build_scorer)."""
     model_dir = resolve_model_dir(model_name, cache_dir)
-    scorer = build_scorer(model_dir, device, share_prefixes, context_cache_tokens, max_positions, dtype)
+    scorer = build_scorer(model_dir, device, share_prefixes, context_cache_tokens, max_positions, expert_weights=expert_weights,
+                          dtype=dtype)
     from transformers import AutoTokenizer
     tok = AutoTokenizer.from_pretrained(model_dir, local_files_only=True)
     tok.padding_side = "right"

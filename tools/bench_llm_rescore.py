@@ -82,9 +82,10 @@ other layer, router, plan, gather, two grouped GEMMs with biases, combine) at th
 heads of 64, F 2880, 32 experts top-4, vocab 201088, --layers of the 24 (default 4) -- on random bf16 weights, beside a dense
 LlamaScorer of equal active matmul FLOPs per row (d 2880, 45 query / 9 kv heads of 64, ffn 12288: 4 x 2880 for the four experts
 and 768 for the wider attention projections), under the protocol of --arch olmo2.  The sorted rows S against rows * top_k say how
-much of the grouped GEMMs is padding.
+much of the grouped GEMMs is padding.  `--experts mxfp4` makes the experts an MXFP4 checkpoint's and adds the scorer that keeps
+them packed (b2t_clm_gptoss_mx_score_bf16 / _tree_bf16), alternating with the dense scorer of the same checkpoint.
 
-  python tools/bench_llm_rescore.py --arch gptoss --lists 5 --cands 5|20|100 [--list nbest --context 64]
+  python tools/bench_llm_rescore.py --arch gptoss --lists 5 --cands 5|20|100 [--list nbest --context 64] [--experts mxfp4]
 """
 import argparse
 import json
@@ -135,6 +136,9 @@ def main():
     ap.add_argument("--kv-heads", type=int, default=None, help="--arch llama / qwen3 / olmo2: key / value heads; default 8, 32 (olmo2)")
     ap.add_argument("--ffn", type=int, default=None, help="default 16384 (opt), 14336 (llama), 12288 (qwen3), 6400 (gpt2), 11008 (olmo2)")
     ap.add_argument("--vocab", type=int, default=None, help="default 50272 (opt), 128256 (llama), 151936 (qwen3), 50257 (gpt2), 100352 (olmo2)")
+    ap.add_argument("--experts", choices=("dense", "mxfp4"), default="dense",
+                    help="--arch gptoss: mxfp4 makes the experts an MXFP4 checkpoint's and runs the scorer that keeps them packed "
+                         "(expert_weights='mxfp4') beside the dense scorer of the same checkpoint")
     ap.add_argument("--cands", type=int, default=100)
     ap.add_argument("--lists", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -431,7 +435,11 @@ def main_gemma2(a):
 
 def main_gptoss(a, n_experts=32, top_k=4):
     """--arch gptoss: a GptOssScorer at the gpt-oss-20b shape on random bf16 weights (sinks and biases N(0, 0.5)) beside a dense
-    LlamaScorer of equal active matmul FLOPs per row, both in bf16, under the protocol of --arch gemma2."""
+    LlamaScorer of equal active matmul FLOPs per row, both in bf16, under the protocol of --arch gemma2.
+    --experts mxfp4: the expert matrices are an MXFP4 checkpoint's (random nibbles, scale bytes 119 to 121: about the same spread of
+    values) and a third scorer, the GptOssMxScorer that keeps them packed, alternates with the other two list by list; the line
+    then also has its times, their ratio to the dense scorer's per list, whether its scores were the dense scorer's bytes, and the
+    device bytes that either scorer's construction allocated."""
     import torch
     import llm_rescore as R
     torch.manual_seed(0)
@@ -455,12 +463,30 @@ def main_gptoss(a, n_experts=32, top_k=4):
             st[p + f"self_attn.{n}.weight"], st[p + f"self_attn.{n}.bias"] = rn(o, i, std=1.0 / i ** 0.5), rn(o, std=0.5)
         st[p + "self_attn.sinks"] = rn(H, std=0.5)
         st[p + "mlp.router.weight"], st[p + "mlp.router.bias"] = rn(n_experts, d, std=1.0 / d ** 0.5), rn(n_experts, std=0.5)
-        st[p + "mlp.experts.gate_up_proj"] = rn(n_experts, d, 2 * ffn, std=1.0 / d ** 0.5)
         st[p + "mlp.experts.gate_up_proj_bias"] = rn(n_experts, 2 * ffn, std=0.5)
-        st[p + "mlp.experts.down_proj"], st[p + "mlp.experts.down_proj_bias"] = rn(n_experts, ffn, d, std=1.0 / ffn ** 0.5), rn(n_experts, d, std=0.5)
+        st[p + "mlp.experts.down_proj_bias"] = rn(n_experts, d, std=0.5)
+        if a.experts == "mxfp4":
+            for n, rows, K in (("gate_up_proj", 2 * ffn, d), ("down_proj", d, ffn)):
+                st[p + f"mlp.experts.{n}_blocks"] = torch.randint(0, 256, (n_experts, rows, K // 32, 16), dtype=torch.uint8, device=dev)
+                st[p + f"mlp.experts.{n}_scales"] = torch.randint(119, 122, (n_experts, rows, K // 32), dtype=torch.uint8, device=dev)
+        else:
+            st[p + "mlp.experts.gate_up_proj"] = rn(n_experts, d, 2 * ffn, std=1.0 / d ** 0.5)
+            st[p + "mlp.experts.down_proj"] = rn(n_experts, ffn, d, std=1.0 / ffn ** 0.5)
         st[p + "input_layernorm.weight"], st[p + "post_attention_layernorm.weight"] = nw(d), nw(d)
     dims = R.gptoss_dims(cfg, 2048)
-    scs = {"gptoss": R.GptOssScorer(dims, R.gptoss_device_layout(st, dims, R.gptoss_rope(cfg), bf), dev, dtype=bf)}
+    def built(make):   # (the scorer, the device bytes its construction left allocated)
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
+        sc = make()
+        torch.cuda.synchronize()
+        return sc, torch.cuda.memory_allocated() - before
+    scs, held = {}, {}
+    scs["gptoss"], held["gptoss"] = built(lambda: R.GptOssScorer(dims, R.gptoss_device_layout(st, dims, R.gptoss_rope(cfg), bf), dev, dtype=bf))
+    fams = ("llama", "gptoss")
+    if a.experts == "mxfp4":
+        scs["gptoss_mx"], held["gptoss_mx"] = built(
+            lambda: R.GptOssMxScorer(dims, R.gptoss_mx_device_layout(st, dims, R.gptoss_rope(cfg), bf), dev, dtype=bf))
+        fams += ("gptoss_mx",)
     lst = {"model.embed_tokens.weight": emb, "lm_head.weight": head, "model.norm.weight": nw(d)}
     for l in range(L):
         p = f"model.layers.{l}."
@@ -473,8 +499,19 @@ def main_gptoss(a, n_experts=32, top_k=4):
     scs["llama"] = R.LlamaScorer(ldims, R.llama_device_layout(lst, ldims, R.rope_inv_freq(lcfg), bf), dev, dtype=bf)
     del st, lst, emb, head
     torch.cuda.empty_cache()
-    lists, ntok, nodes, same, per, stat = alternate(a, rng, V, scs, ("llama", "gptoss"))
+    lists, ntok, nodes, same, per, stat = alternate(a, rng, V, scs, fams)
     ratio = lambda t: [round(o / l, 4) for o, l in zip(per["gptoss", t], per["llama", t])]
+    mx = {}
+    if a.experts == "mxfp4":
+        mx_ratio = lambda t: [round(o / l, 4) for o, l in zip(per["gptoss_mx", t], per["gptoss", t])]
+        with torch.inference_mode():
+            equal = all(scs["gptoss_mx"].score(l, share_prefixes=t).tobytes() == scs["gptoss"].score(l, share_prefixes=t).tobytes()
+                        for l in lists for t in (False, True))
+        mx = {"experts": "mxfp4", "gptoss_mx_flat_ms": stat(("gptoss_mx", False)), "gptoss_mx_tree_ms": stat(("gptoss_mx", True)),
+              "mx_over_dense_flat": {"median": round(float(np.median(mx_ratio(False))), 4), "per_list": mx_ratio(False)},
+              "mx_over_dense_tree": {"median": round(float(np.median(mx_ratio(True))), 4), "per_list": mx_ratio(True)},
+              "mx_scores_are_dense_bytes": bool(equal), "dense_device_bytes": held["gptoss"], "mx_device_bytes": held["gptoss_mx"],
+              "mx_expert_bytes": scs["gptoss_mx"].expert_bytes()}
     S = lambda rows: -(-rows * top_k // 256) * 256 + 256 * n_experts
     print(json.dumps({"bench": "llm_rescore_gptoss", "dtype": "bfloat16", "layers": L, "d": d, "heads": H, "kv_heads": Hkv, "head_dim": hd,
                       "ffn": ffn, "experts": n_experts, "top_k": top_k, "vocab": V, "llama_heads": lH, "llama_kv_heads": lHkv,
@@ -486,7 +523,7 @@ def main_gptoss(a, n_experts=32, top_k=4):
                       "llama_tree_ms": stat(("llama", True)), "gptoss_tree_ms": stat(("gptoss", True)),
                       "ratio_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
                       "ratio_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
-                      "flat_tree_bit_identical": bool(same)}))
+                      "flat_tree_bit_identical": bool(same), **mx}))
 
 
 def main_phi3(a):
