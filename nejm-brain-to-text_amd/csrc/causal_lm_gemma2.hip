@@ -48,8 +48,9 @@
 // (tests/test_clm_gemma2_host.py checks it).
 //
 // This unit instantiates the three GEMM epilogues (on both tiles), the three kernels of clm_gemma2.h and the capped flat and tree
-// attention, in both element types, and the capped cached and trunk attention in fp16; the QKV and the uncapped head GEMM are reached through LlamaShared<E>, the entry-point bodies
-// are clm_llama.h's under Gemma2Family, the cached call is clm_score_tree_cached.  The workspace is gemma2_layout (clm_gemma2.h).
+// attention, in both element types, and the capped cached and trunk attention in fp16; the QKV and the uncapped head GEMM are
+// reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's under Gemma2Family.  The
+// workspace is gemma2_layout (clm_gemma2.h).
 #include "clm_attn.h"
 #include "clm_gemma2.h"
 
@@ -85,13 +86,6 @@ struct Gemma2Policy : LlamaShared<El>, Gemma2Ops<El> {
 using Gemma2F16 = Gemma2Policy<_Float16>;
 using Gemma2Bf16 = Gemma2Policy<__bf16>;
 
-// dimensions a descriptor pair must have for the sizes of gemma2_layout to mean anything (the full check is
-// clm_gemma2_check_model)
-bool gemma2_dims_ok(const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2) {
-  return m && g2 && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-         (g2->head_dim == 128 || g2->head_dim == 256);
-}
-
 // launch_attn of causal_lm_cache.hip with the `_cap_` kernels: stage B over the whole cached blocks, then the tree walk
 template <int D>
 int launch_attn_cap(const ClmCachedAttn& a, const _Float16* qkv, const _Float16* slab, _Float16* out, hipStream_t s) {
@@ -115,32 +109,25 @@ int clm_launch_attn_cached_cap(const ClmCachedAttn& a, const _Float16* qkv, cons
 }
 
 int clm_gemma2_check_model(const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2) {
-  B2T_REQUIRE(m, "b2t_clm_gemma2: null model");
-  B2T_REQUIRE(g2, "b2t_clm_gemma2: null gemma2 descriptor");
-  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-              m->max_pos > 0,
-              "b2t_clm_gemma2: bad dimensions (layers %d, d %d, heads %d, kv heads %d, ffn %d, vocab %d, max_pos %d)", m->n_layers,
-              m->d_model, m->n_heads, m->n_kv_heads, m->ffn_dim, m->vocab, m->max_pos);
+  const char* pre = "b2t_clm_gemma2";
+  B2T_REQUIRE(!m || g2, "b2t_clm_gemma2: null gemma2 descriptor");   // behind the null model, in front of the dimensions
+  if (int rc = clm_check_dims(pre, m)) return rc;
   const int hd = g2->head_dim;
   B2T_REQUIRE(hd == 128 || hd == 256, "b2t_clm_gemma2: unsupported head dim %d (128 or 256)", hd);
-  B2T_REQUIRE(m->n_heads % m->n_kv_heads == 0, "b2t_clm_gemma2: n_heads %d is not a multiple of n_kv_heads %d", m->n_heads,
-              m->n_kv_heads);
+  if (int rc = clm_check_gqa(pre, *m)) return rc;
   B2T_REQUIRE(m->d_model % 64 == 0 && m->ffn_dim % 64 == 0 && ((long long)m->n_heads * hd) % 64 == 0,
               "b2t_clm_gemma2: d_model %d, ffn_dim %d and n_heads * head_dim %lld must be multiples of 64", m->d_model, m->ffn_dim,
               (long long)m->n_heads * hd);
-  B2T_REQUIRE(m->rms_eps >= 0.f && m->rms_eps < 1.f, "b2t_clm_gemma2: rms_eps %g outside [0, 1)", (double)m->rms_eps);
+  if (int rc = clm_check_eps(pre, *m)) return rc;
   B2T_REQUIRE(g2->attn_cap >= 0.f && g2->final_cap >= 0.f, "b2t_clm_gemma2: caps %g and %g must be >= 0 (0: off)",
               (double)g2->attn_cap, (double)g2->final_cap);
   B2T_REQUIRE(g2->q_scale > 0.f && g2->embed_scale > 0.f, "b2t_clm_gemma2: q_scale %g and embed_scale %g must be > 0",
               (double)g2->q_scale, (double)g2->embed_scale);
-  B2T_REQUIRE(m->embed_tokens && m->lm_head && m->final_norm_w && m->rope_cos && m->rope_sin &&
-              (m->n_layers == 0 || (m->layers_host && g2->layers_host)), "b2t_clm_gemma2: null weight pointer");
+  if (int rc = clm_check_pointers(pre, *m, g2->layers_host != nullptr)) return rc;
   for (int l = 0; l < m->n_layers; ++l) {
-    const b2t_clm_llama_layer_t& w = m->layers_host[l];
     const b2t_clm_gemma2_layer_t& w2 = g2->layers_host[l];
-    B2T_REQUIRE(w.norm1_w && w.norm2_w && w.qkv_w && w.o_w && w.gate_up_w && w.down_w && w2.pre_ffn_norm_w && w2.post_ffn_norm_w,
-                "b2t_clm_gemma2: null weight pointer in layer %d", l);
-    B2T_REQUIRE(!w.qkv_b, "b2t_clm_gemma2: layer %d has q / k / v biases (qkv_b), which Gemma-2 does not", l);
+    if (int rc = clm_check_layer(pre, m->layers_host[l], l, w2.pre_ffn_norm_w && w2.post_ffn_norm_w)) return rc;
+    B2T_REQUIRE(!m->layers_host[l].qkv_b, "b2t_clm_gemma2: layer %d has q / k / v biases (qkv_b), which Gemma-2 does not", l);
   }
   return 0;
 }
@@ -150,26 +137,21 @@ int clm_gemma2_check_model(const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2)
 using namespace b2t;
 
 extern "C" size_t b2t_clm_gemma2_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_tokens, int n_seq) {
-  if (!gemma2_dims_ok(model, g2) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return gemma2_layout(model, g2, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+  return llama_ws_bytes<Gemma2Family>(model, n_tokens, n_seq, g2);
 }
 
 extern "C" size_t b2t_clm_gemma2_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_nodes,
                                                long long n_tokens, int n_seq) {
-  if (!gemma2_dims_ok(model, g2) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return gemma2_layout(model, g2, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+  return llama_tree_ws_bytes<Gemma2Family>(model, n_nodes, n_tokens, n_seq, g2);
 }
 
 extern "C" size_t b2t_clm_gemma2_cache_kv_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, int cap) {
-  if (!gemma2_dims_ok(model, g2) || cap < 1 || cap > model->max_pos || model->n_layers < 1) return 0;
-  return (size_t)model->n_layers * (size_t)cap * 2 * (size_t)model->n_kv_heads * (size_t)g2->head_dim * sizeof(_Float16);
+  return llama_cache_kv_bytes<Gemma2Family>(model, cap, g2);
 }
 
 extern "C" size_t b2t_clm_gemma2_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_rows,
                                                       long long n_tokens, int n_seq) {
-  if (!gemma2_dims_ok(model, g2) || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  const size_t tree = gemma2_layout(model, g2, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
-  return clm_cached_state(tree, n_rows, model->n_heads, model->n_heads * g2->head_dim).total;
+  return llama_tree_cached_ws_bytes<Gemma2Family>(model, n_rows, n_tokens, n_seq, g2);
 }
 
 extern "C" int b2t_clm_gemma2_score_f16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
@@ -190,16 +172,9 @@ extern "C" int b2t_clm_gemma2_score_tree_cached_f16(const b2t_clm_llama_t* model
                                                     int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                     float* scores_out, float* tok_logp_out, long long* n_rows_out,
                                                     int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = clm_gemma2_check_model(model, g2)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, g2->head_dim, g2->attn_cap};
-  return clm_score_tree_cached(
-      "b2t_clm_gemma2_score_tree_cached_f16", "b2t_clm_gemma2_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq,
-      scores_out, tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return gemma2_layout(model, g2, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
-        return gemma2_forward<Gemma2F16>(m, *g2, r, L, base, attn, s);
-      });
+  return llama_score_tree_cached<Gemma2F16, Gemma2Family>("b2t_clm_gemma2_score_tree_cached_f16", "b2t_clm_gemma2_score_tree_f16", model,
+                                                          cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
+                                                          n_rows_out, n_reused_out, ws, ws_bytes, stream, g2);
 }
 
 extern "C" int b2t_clm_gemma2_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,

@@ -34,8 +34,9 @@
 // clm_moe_combine_kernel.  Plan, gather, combine, the region and S = round_up(rows * top_k, 256) + 256 * n_experts are clm_moe.h's.
 //
 // This unit instantiates the two grouped GEMMs (on both tiles), the router kernel, the plan, gather and combine kernels and the
-// two attention kernels, in both element types where they depend on it, and nothing else: every other kernel is reached through
-// LlamaShared<E>, the entry-point bodies are clm_llama.h's under GptOssFamily.  There is no cached call: the cached and trunk
+// two attention kernels (through GptOssOps<E>, clm_gptoss.h), in both element types where they depend on it, and nothing else:
+// every other kernel is reached through LlamaShared<E>, the flat and the tree entry-point body and the two size rules are
+// clm_llama.h's under GptOssFamily.  There is no cached call: the cached and trunk
 // attention kernels have neither sink nor window.
 #include "clm_attn.h"
 #include "clm_gptoss.h"
@@ -45,50 +46,23 @@ namespace {
 
 template <class El>
 struct GptOssPolicy : LlamaShared<El>, MoeOps<El>, GptOssOps<El> {
-  using E = El;
   static int gemm_experts_glu(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_OSS_GLU, El, true>); }
   static int gemm_experts_f32b(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_F32_BIAS, El, true>); }
-  static int attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, const float* sinks, int window,
-                  hipStream_t s) {
-    hipLaunchKernelGGL((clm_attn_sink_kernel<OSS_HEAD_DIM, E>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv, sinks,
-                       window);
-    B2T_CHECK_LAUNCH("clm_attn_sink_kernel");
-    return 0;
-  }
-  static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
-                       int Hkv, const float* sinks, int window, hipStream_t s) {
-    hipLaunchKernelGGL((clm_attn_tree_sink_kernel<OSS_HEAD_DIM, E>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, tok_node,
-                       own_start, Hq, Hkv, sinks, window);
-    B2T_CHECK_LAUNCH("clm_attn_tree_sink_kernel");
-    return 0;
-  }
 };
 using GptOssF16 = GptOssPolicy<_Float16>;
 using GptOssBf16 = GptOssPolicy<__bf16>;
 
-// dimensions a descriptor pair must have for the sizes of gptoss_layout to mean anything (the full check is
-// clm_gptoss_check_model)
-bool gptoss_dims_ok(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) {
-  return m && g && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-         g->head_dim == OSS_HEAD_DIM && g->n_experts >= 1 && g->n_experts <= OSS_MAX_EXPERTS && g->top_k >= 1 &&
-         g->top_k <= MOE_MAX_TOPK && g->top_k <= g->n_experts;
-}
-
 }  // namespace
 
 int clm_gptoss_check_model(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) {
-  B2T_REQUIRE(m, "b2t_clm_gptoss: null model");
-  B2T_REQUIRE(g, "b2t_clm_gptoss: null gptoss descriptor");
-  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-              m->max_pos > 0,
-              "b2t_clm_gptoss: bad dimensions (layers %d, d %d, heads %d, kv heads %d, ffn %d, vocab %d, max_pos %d)", m->n_layers,
-              m->d_model, m->n_heads, m->n_kv_heads, m->ffn_dim, m->vocab, m->max_pos);
+  const char* pre = "b2t_clm_gptoss";
+  B2T_REQUIRE(!m || g, "b2t_clm_gptoss: null gptoss descriptor");   // behind the null model, in front of the dimensions
+  if (int rc = clm_check_dims(pre, m)) return rc;
   B2T_REQUIRE(g->head_dim == OSS_HEAD_DIM, "b2t_clm_gptoss: unsupported head dim %d (%d)", g->head_dim, OSS_HEAD_DIM);
-  B2T_REQUIRE(m->n_heads % m->n_kv_heads == 0, "b2t_clm_gptoss: n_heads %d is not a multiple of n_kv_heads %d", m->n_heads,
-              m->n_kv_heads);
+  if (int rc = clm_check_gqa(pre, *m)) return rc;
   B2T_REQUIRE(m->d_model % 64 == 0 && m->ffn_dim % 64 == 0, "b2t_clm_gptoss: d_model %d and ffn_dim %d must be multiples of 64",
               m->d_model, m->ffn_dim);
-  B2T_REQUIRE(m->rms_eps >= 0.f && m->rms_eps < 1.f, "b2t_clm_gptoss: rms_eps %g outside [0, 1)", (double)m->rms_eps);
+  if (int rc = clm_check_eps(pre, *m)) return rc;
   B2T_REQUIRE(g->n_experts >= 1 && g->n_experts <= OSS_MAX_EXPERTS, "b2t_clm_gptoss: n_experts %d outside [1, %d]", g->n_experts,
               OSS_MAX_EXPERTS);
   B2T_REQUIRE(g->top_k >= 1 && g->top_k <= MOE_MAX_TOPK && g->top_k <= g->n_experts,
@@ -97,14 +71,13 @@ int clm_gptoss_check_model(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) 
               "b2t_clm_gptoss: expert strides %lld / %lld rows below round_up(2 ffn_dim, 256) = %lld / round_up(d_model, 256) = %lld",
               g->gate_up_stride, g->down_stride, rup(2LL * m->ffn_dim, ROWPAD), rup(m->d_model, ROWPAD));
   B2T_REQUIRE(g->swiglu_limit > 0.f, "b2t_clm_gptoss: swiglu_limit %g must be > 0", (double)g->swiglu_limit);
-  B2T_REQUIRE(m->embed_tokens && m->lm_head && m->final_norm_w && m->rope_cos && m->rope_sin &&
-              (m->n_layers == 0 || (m->layers_host && g->layers_host)), "b2t_clm_gptoss: null weight pointer");
+  if (int rc = clm_check_pointers(pre, *m, g->layers_host != nullptr)) return rc;
   for (int l = 0; l < m->n_layers; ++l) {
-    const b2t_clm_llama_layer_t& w = m->layers_host[l];
     const b2t_clm_gptoss_layer_t& w2 = g->layers_host[l];
-    B2T_REQUIRE(w.norm1_w && w.norm2_w && w.qkv_w && w.o_w && w.gate_up_w && w.down_w && w2.sinks && w2.o_b && w2.router_w &&
-                w2.router_b && w2.gate_up_b && w2.down_b, "b2t_clm_gptoss: null weight pointer in layer %d", l);
-    B2T_REQUIRE(w.qkv_b, "b2t_clm_gptoss: layer %d has no q / k / v biases (qkv_b), which gpt-oss has", l);
+    if (int rc = clm_check_layer(pre, m->layers_host[l], l,
+                                 w2.sinks && w2.o_b && w2.router_w && w2.router_b && w2.gate_up_b && w2.down_b))
+      return rc;
+    B2T_REQUIRE(m->layers_host[l].qkv_b, "b2t_clm_gptoss: layer %d has no q / k / v biases (qkv_b), which gpt-oss has", l);
     B2T_REQUIRE(w2.window >= 0, "b2t_clm_gptoss: layer %d has window %d < 0 (0: full attention)", l, w2.window);
   }
   return 0;
@@ -115,14 +88,12 @@ int clm_gptoss_check_model(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) 
 using namespace b2t;
 
 extern "C" size_t b2t_clm_gptoss_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_tokens, int n_seq) {
-  if (!gptoss_dims_ok(model, oss) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return gptoss_layout(model, oss, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+  return llama_ws_bytes<GptOssFamily>(model, n_tokens, n_seq, oss);
 }
 
 extern "C" size_t b2t_clm_gptoss_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_nodes,
                                                long long n_tokens, int n_seq) {
-  if (!gptoss_dims_ok(model, oss) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return gptoss_layout(model, oss, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+  return llama_tree_ws_bytes<GptOssFamily>(model, n_nodes, n_tokens, n_seq, oss);
 }
 
 extern "C" int b2t_clm_gptoss_score_f16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,

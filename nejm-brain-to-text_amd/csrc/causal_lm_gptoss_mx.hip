@@ -25,23 +25,8 @@ namespace {
 
 template <class El>
 struct GptOssMxPolicy : LlamaShared<El>, MoeOps<El>, GptOssOps<El> {
-  using E = El;
   static int gemm_experts_glu(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_OSS_GLU, El, true, true>); }
   static int gemm_experts_f32b(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_F32_BIAS, El, true, true>); }
-  static int attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, const float* sinks, int window,
-                  hipStream_t s) {
-    hipLaunchKernelGGL((clm_attn_sink_kernel<OSS_HEAD_DIM, E>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv, sinks,
-                       window);
-    B2T_CHECK_LAUNCH("clm_attn_sink_kernel");
-    return 0;
-  }
-  static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
-                       int Hkv, const float* sinks, int window, hipStream_t s) {
-    hipLaunchKernelGGL((clm_attn_tree_sink_kernel<OSS_HEAD_DIM, E>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, tok_node,
-                       own_start, Hq, Hkv, sinks, window);
-    B2T_CHECK_LAUNCH("clm_attn_tree_sink_kernel");
-    return 0;
-  }
 };
 
 // what the entry-point bodies of clm_llama.h carry beside the model: the gpt-oss descriptor and the packed experts
@@ -50,24 +35,8 @@ struct GptOssMxArg {
   const b2t_clm_gptoss_mx_t* mx;
 };
 
-// GptOssFamily on that pair
-struct GptOssMxFamily {
-  static int check_model(const b2t_clm_llama_t* m, const GptOssMxArg* x) { return clm_gptoss_check_model(m, x->g); }
-  static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const GptOssMxArg* x) {
-    return gptoss_layout(m, x->g, rows, hrows, ints);
-  }
-  template <class P>
-  static int check(const char*, const b2t_clm_llama_t&, const GptOssMxArg*) { return 0; }
-  template <class P>
-  static int attn(const b2t_clm_llama_t& m, const GptOssMxArg* x, int l, const typename P::E* qkv, typename P::E* out,
-                  const int* seq_off, int n_seq, hipStream_t s) {
-    return GptOssFamily::attn<P>(m, x->g, l, qkv, out, seq_off, n_seq, s);
-  }
-  template <class P>
-  static int attn_tree(const b2t_clm_llama_t& m, const GptOssMxArg* x, int l, const typename P::E* qkv, typename P::E* out,
-                       const int* seq_off, const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
-    return GptOssFamily::attn_tree<P>(m, x->g, l, qkv, out, seq_off, tok_node, own_start, n_seq, s);
-  }
+// GptOssFamily on that pair: check, layout and the attention are its own on x->g (gptoss_of); the forward gets the scale bytes
+struct GptOssMxFamily : GptOssFamily {
   template <class P, class Attn>
   static int forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
                      const GptOssMxArg* x) {

@@ -27,133 +27,100 @@
 // of 32, and for head dim 128 the q / k rows of each head in the order [0..31, 64..95, 32..63, 96..127] (q . k is invariant
 // under one permutation of both; V and o_proj are untouched).
 //
-// The forward (llama_forward), the bodies of the flat and the tree entry point and the embed / RMSNorm kernels are templates in
-// clm_llama.h, on a per-element-type policy; this unit holds the fp16 policy (LlamaF16: the two GEMM launches of this family
-// through the one tile rule, the OPT paths' residual / head GEMMs and attention launchers) and the model check.  The same
-// forward in bf16 is causal_lm_llama_bf16.hip; Qwen3's, which norms the q and k heads in the QKV GEMM's epilogue, is
-// causal_lm_qwen3.hip, whose policies take every other launch from this unit and the bf16 one (LlamaShared, clm_llama.h).
+// The forward (llama_forward), the bodies of the flat, the tree and the cached entry point, the size rules and the embed /
+// RMSNorm kernels are templates in clm_llama.h, on a per-element-type policy and a family; this unit holds the fp16 launches of
+// the Llama policy (LlamaShared<_Float16>: the two GEMM launches of this family through the one tile rule, the OPT paths'
+// residual / head GEMMs and attention launchers, embed and RMSNorm), which every other family's fp16 policy shares, and the
+// model check.  The same forward in bf16 is causal_lm_llama_bf16.hip; Qwen3's, which norms the q and k heads in the QKV GEMM's
+// epilogue, is causal_lm_qwen3.hip.
 #include "clm_llama.h"
 
 namespace b2t {
-namespace {
 
-// The fp16 policy of the forward (clm_llama.h): the attention kernels are causal_lm.hip's and causal_lm_tree.hip's.
-struct LlamaF16 : LlamaOps<_Float16> {
-  static int gemm_rope(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_ROPE>); }
-  static int gemm_swiglu(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_SWIGLU>); }
-  static int gemm_resid(const ClmGemm& g, hipStream_t s) { return launch_gemm<EP_RESID>(g, s); }
-  static int gemm_head(const ClmGemm& g, hipStream_t s) { return launch_gemm<EP_HEAD>(g, s); }
-  static int attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
-    return clm_launch_attn(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
-  }
-  static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
-                       int Hkv, int hd, hipStream_t s) {
-    return clm_launch_attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
-  }
-};
-
-// dimensions a descriptor must have for the sizes of llama_layout (clm_llama.h) to mean anything (the full check is clm_llama_check_model)
-bool llama_dims_ok(const b2t_clm_llama_t* m) {
-  return m && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-         m->d_model % m->n_heads == 0;
+// LlamaShared<_Float16> (clm_llama.h); the attention kernels are causal_lm.hip's and causal_lm_tree.hip's
+template <> int LlamaShared<_Float16>::gemm_rope(const ClmGemm& g, hipStream_t s) {
+  return launch_gemm(g, s, &clm_gemm_tiles<EP_ROPE>);
 }
-
-}  // namespace
-
-// LlamaShared<_Float16> (clm_llama.h): this unit's launches for the policy of another family (causal_lm_qwen3.hip)
-template <> int LlamaShared<_Float16>::gemm_rope(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_rope(g, s); }
-template <> int LlamaShared<_Float16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_swiglu(g, s); }
-template <> int LlamaShared<_Float16>::gemm_resid(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_resid(g, s); }
-template <> int LlamaShared<_Float16>::gemm_head(const ClmGemm& g, hipStream_t s) { return LlamaF16::gemm_head(g, s); }
+template <> int LlamaShared<_Float16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) {
+  return launch_gemm(g, s, &clm_gemm_tiles<EP_SWIGLU>);
+}
+template <> int LlamaShared<_Float16>::gemm_resid(const ClmGemm& g, hipStream_t s) { return launch_gemm<EP_RESID>(g, s); }
+template <> int LlamaShared<_Float16>::gemm_head(const ClmGemm& g, hipStream_t s) { return launch_gemm<EP_HEAD>(g, s); }
 template <> int LlamaShared<_Float16>::embed(const int* ids, const E* et, float* resid, int d, long long rows, hipStream_t s) {
-  return LlamaF16::embed(ids, et, resid, d, rows, s);
+  hipLaunchKernelGGL(clm_llama_embed_kernel<E>, dim3((unsigned)rows), dim3(256), 0, s, ids, et, resid, d);
+  B2T_CHECK_LAUNCH("clm_llama_embed_kernel");
+  return 0;
 }
 template <> int LlamaShared<_Float16>::rmsnorm(const float* x, const int* rowmap, long long n, const E* w, float eps, E* out, int d,
                                                  hipStream_t s) {
-  return LlamaF16::rmsnorm(x, rowmap, n, w, eps, out, d, s);
+  hipLaunchKernelGGL(clm_llama_rmsnorm_kernel<E>, dim3((unsigned)rup(n, ROWPAD)), dim3(256), 0, s, x, rowmap, (int)n, w, eps, out, d);
+  B2T_CHECK_LAUNCH("clm_llama_rmsnorm_kernel");
+  return 0;
 }
 template <> int LlamaShared<_Float16>::attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
-  return LlamaF16::attn(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
+  return clm_launch_attn(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
 }
 template <> int LlamaShared<_Float16>::attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start,
                                                    int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
-  return LlamaF16::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
+  return clm_launch_attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
 }
 
 int clm_llama_check_model(const b2t_clm_llama_t* m) {
-  B2T_REQUIRE(m, "b2t_clm_llama: null model");
-  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-              m->max_pos > 0,
-              "b2t_clm_llama: bad dimensions (layers %d, d %d, heads %d, kv heads %d, ffn %d, vocab %d, max_pos %d)", m->n_layers,
-              m->d_model, m->n_heads, m->n_kv_heads, m->ffn_dim, m->vocab, m->max_pos);
+  const char* pre = "b2t_clm_llama";
+  if (int rc = clm_check_dims(pre, m)) return rc;
   B2T_REQUIRE(m->d_model % m->n_heads == 0, "b2t_clm_llama: d_model %d is not a multiple of n_heads %d", m->d_model, m->n_heads);
   const int hd = m->d_model / m->n_heads;
   B2T_REQUIRE(hd == 64 || hd == 128, "b2t_clm_llama: unsupported head dim %d (64 or 128)", hd);
-  B2T_REQUIRE(m->n_heads % m->n_kv_heads == 0, "b2t_clm_llama: n_heads %d is not a multiple of n_kv_heads %d", m->n_heads,
-              m->n_kv_heads);
+  if (int rc = clm_check_gqa(pre, *m)) return rc;
   B2T_REQUIRE(m->d_model % 64 == 0 && m->ffn_dim % 64 == 0, "b2t_clm_llama: d_model %d and ffn_dim %d must be multiples of 64",
               m->d_model, m->ffn_dim);
-  B2T_REQUIRE(m->rms_eps >= 0.f && m->rms_eps < 1.f, "b2t_clm_llama: rms_eps %g outside [0, 1)", (double)m->rms_eps);
-  B2T_REQUIRE(m->embed_tokens && m->lm_head && m->final_norm_w && m->rope_cos && m->rope_sin && (m->n_layers == 0 || m->layers_host),
-              "b2t_clm_llama: null weight pointer");
-  for (int l = 0; l < m->n_layers; ++l) {
-    const b2t_clm_llama_layer_t& w = m->layers_host[l];   // qkv_b may be null (no q / k / v biases)
-    B2T_REQUIRE(w.norm1_w && w.norm2_w && w.qkv_w && w.o_w && w.gate_up_w && w.down_w,
-                "b2t_clm_llama: null weight pointer in layer %d", l);
-  }
+  if (int rc = clm_check_eps(pre, *m)) return rc;
+  if (int rc = clm_check_pointers(pre, *m)) return rc;
+  for (int l = 0; l < m->n_layers; ++l)
+    if (int rc = clm_check_layer(pre, m->layers_host[l], l)) return rc;
   return 0;
 }
 
 }  // namespace b2t
 
 using namespace b2t;
+using LlamaF = LlamaPolicy<_Float16>;
 
 extern "C" size_t b2t_clm_llama_ws_bytes(const b2t_clm_llama_t* model, long long n_tokens, int n_seq) {
-  if (!llama_dims_ok(model) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return llama_layout(model, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+  return llama_ws_bytes<LlamaFamily>(model, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_llama_score_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                        int n_seq, float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes,
                                        void* stream) {
-  return llama_score<LlamaF16>("b2t_clm_llama_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws,
-                               ws_bytes, stream);
+  return llama_score<LlamaF>("b2t_clm_llama_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws,
+                             ws_bytes, stream);
 }
 
 extern "C" size_t b2t_clm_llama_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq) {
-  if (!llama_dims_ok(model) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return llama_layout(model, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+  return llama_tree_ws_bytes<LlamaFamily>(model, n_nodes, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_llama_score_tree_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                             int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws,
                                             size_t ws_bytes, void* stream) {
-  return llama_score_tree<LlamaF16>("b2t_clm_llama_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                    tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
+  return llama_score_tree<LlamaF>("b2t_clm_llama_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
+                                  n_nodes_out, ws, ws_bytes, stream);
 }
 
 extern "C" size_t b2t_clm_llama_cache_kv_bytes(const b2t_clm_llama_t* model, int cap) {
-  if (!llama_dims_ok(model) || cap < 1 || cap > model->max_pos || model->n_layers < 1) return 0;
-  return (size_t)model->n_layers * (size_t)cap * 2 * (size_t)model->n_kv_heads * (size_t)(model->d_model / model->n_heads) *
-         sizeof(_Float16);
+  return llama_cache_kv_bytes<LlamaFamily>(model, cap);
 }
 
 extern "C" size_t b2t_clm_llama_tree_cached_ws_bytes(const b2t_clm_llama_t* model, long long n_rows, long long n_tokens, int n_seq) {
-  if (!llama_dims_ok(model) || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  const size_t tree = llama_layout(model, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
-  return clm_cached_state(tree, n_rows, model->n_heads, model->d_model).total;
+  return llama_tree_cached_ws_bytes<LlamaFamily>(model, n_rows, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_llama_score_tree_cached_f16(const b2t_clm_llama_t* model, b2t_clm_cache_t* cache, int update,
                                                    const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                    float* scores_out, float* tok_logp_out, long long* n_rows_out,
                                                    int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = clm_llama_check_model(model)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads};
-  return clm_score_tree_cached(
-      "b2t_clm_llama_score_tree_cached_f16", "b2t_clm_llama_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq,
-      scores_out, tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return llama_layout(model, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) { return llama_forward<LlamaF16>(m, r, L, base, attn, s); });
+  return llama_score_tree_cached<LlamaF>("b2t_clm_llama_score_tree_cached_f16", "b2t_clm_llama_score_tree_f16", model, cache, update,
+                                         ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out, n_reused_out, ws,
+                                         ws_bytes, stream);
 }

@@ -1,7 +1,8 @@
 // causal_lm_llama_bf16.hip — the Llama-family scoring forward of causal_lm_llama.hip in bfloat16, the format Llama-3, Mistral
 // and Qwen2 are trained and published in: b2t_clm_llama_score_bf16 over packed sequences and b2t_clm_llama_score_tree_bf16
 // over the shared-prefix token tree.  The forward, the entry points' bodies and every kernel are the fp16 path's templates
-// (clm_llama.h, clm_gemm.h, clm_attn.h) instantiated for __bf16; this unit holds the bf16 policy and all bf16 instantiations:
+// (clm_llama.h, clm_gemm.h, clm_attn.h) instantiated for __bf16; this unit holds the bf16 launches of the Llama policy
+// (LlamaShared<__bf16>) and with them all bf16 instantiations:
 // the GEMM with the epilogues EP_ROPE, EP_SWIGLU, EP_RESID and EP_HEAD on both tiles, the flat and the tree attention kernel
 // for head dims 64 and 128, embed and RMSNorm.  No fp16 unit instantiates a bf16 kernel.
 //
@@ -21,60 +22,45 @@
 #include "clm_llama.h"
 
 namespace b2t {
-namespace {
 
-int launch_attn_bf16(const __bf16* qkv, __bf16* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
-  const dim3 grid(n_seq, Hq);
-  if (hd == 64) hipLaunchKernelGGL((clm_attn_kernel<64, __bf16>), grid, dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv);
-  else hipLaunchKernelGGL((clm_attn_kernel<128, __bf16>), grid, dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv);   // 64 or 128: clm_llama_check_model
-  B2T_CHECK_LAUNCH("clm_attn_kernel");
-  return 0;
+// LlamaShared<__bf16> (clm_llama.h): the launches every family's bf16 policy shares
+template <> int LlamaShared<__bf16>::gemm_rope(const ClmGemm& g, hipStream_t s) {
+  return launch_gemm(g, s, &clm_gemm_tiles<EP_ROPE, __bf16>);
 }
-
-int launch_attn_tree_bf16(const __bf16* qkv, __bf16* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq,
-                          int Hq, int Hkv, int hd, hipStream_t s) {
-  const dim3 grid(n_seq, Hq);
-  if (hd == 64) hipLaunchKernelGGL((clm_attn_tree_kernel<64, __bf16>), grid, dim3(256), 0, s, qkv, out, seq_off, tok_node, own_start, Hq, Hkv);
-  else hipLaunchKernelGGL((clm_attn_tree_kernel<128, __bf16>), grid, dim3(256), 0, s, qkv, out, seq_off, tok_node, own_start, Hq, Hkv);
-  B2T_CHECK_LAUNCH("clm_attn_tree_kernel");
-  return 0;
+template <> int LlamaShared<__bf16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) {
+  return launch_gemm(g, s, &clm_gemm_tiles<EP_SWIGLU, __bf16>);
 }
-
-// The bf16 policy of the forward (clm_llama.h)
-struct LlamaBf16 : LlamaOps<__bf16> {
-  static int gemm_rope(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_ROPE, __bf16>); }
-  static int gemm_swiglu(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_SWIGLU, __bf16>); }
-  static int gemm_resid(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_RESID, __bf16>); }
-  static int gemm_head(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_HEAD, __bf16>); }
-  static int attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
-    return launch_attn_bf16(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
-  }
-  static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
-                       int Hkv, int hd, hipStream_t s) {
-    return launch_attn_tree_bf16(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
-  }
-};
-
-}  // namespace
-
-// LlamaShared<__bf16> (clm_llama.h): this unit's launches for the policy of another family (causal_lm_qwen3.hip)
-template <> int LlamaShared<__bf16>::gemm_rope(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_rope(g, s); }
-template <> int LlamaShared<__bf16>::gemm_swiglu(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_swiglu(g, s); }
-template <> int LlamaShared<__bf16>::gemm_resid(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_resid(g, s); }
-template <> int LlamaShared<__bf16>::gemm_head(const ClmGemm& g, hipStream_t s) { return LlamaBf16::gemm_head(g, s); }
+template <> int LlamaShared<__bf16>::gemm_resid(const ClmGemm& g, hipStream_t s) {
+  return launch_gemm(g, s, &clm_gemm_tiles<EP_RESID, __bf16>);
+}
+template <> int LlamaShared<__bf16>::gemm_head(const ClmGemm& g, hipStream_t s) {
+  return launch_gemm(g, s, &clm_gemm_tiles<EP_HEAD, __bf16>);
+}
 template <> int LlamaShared<__bf16>::embed(const int* ids, const E* et, float* resid, int d, long long rows, hipStream_t s) {
-  return LlamaBf16::embed(ids, et, resid, d, rows, s);
+  hipLaunchKernelGGL(clm_llama_embed_kernel<E>, dim3((unsigned)rows), dim3(256), 0, s, ids, et, resid, d);
+  B2T_CHECK_LAUNCH("clm_llama_embed_kernel");
+  return 0;
 }
 template <> int LlamaShared<__bf16>::rmsnorm(const float* x, const int* rowmap, long long n, const E* w, float eps, E* out, int d,
                                                hipStream_t s) {
-  return LlamaBf16::rmsnorm(x, rowmap, n, w, eps, out, d, s);
+  hipLaunchKernelGGL(clm_llama_rmsnorm_kernel<E>, dim3((unsigned)rup(n, ROWPAD)), dim3(256), 0, s, x, rowmap, (int)n, w, eps, out, d);
+  B2T_CHECK_LAUNCH("clm_llama_rmsnorm_kernel");
+  return 0;
 }
 template <> int LlamaShared<__bf16>::attn(const E* qkv, E* out, const int* seq_off, int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
-  return LlamaBf16::attn(qkv, out, seq_off, n_seq, Hq, Hkv, hd, s);
+  const dim3 grid(n_seq, Hq);
+  if (hd == 64) hipLaunchKernelGGL((clm_attn_kernel<64, E>), grid, dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv);
+  else hipLaunchKernelGGL((clm_attn_kernel<128, E>), grid, dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv);   // 64 or 128: clm_llama_check_model
+  B2T_CHECK_LAUNCH("clm_attn_kernel");
+  return 0;
 }
 template <> int LlamaShared<__bf16>::attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start,
                                                  int n_seq, int Hq, int Hkv, int hd, hipStream_t s) {
-  return LlamaBf16::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, Hq, Hkv, hd, s);
+  const dim3 grid(n_seq, Hq);
+  if (hd == 64) hipLaunchKernelGGL((clm_attn_tree_kernel<64, E>), grid, dim3(256), 0, s, qkv, out, seq_off, tok_node, own_start, Hq, Hkv);
+  else hipLaunchKernelGGL((clm_attn_tree_kernel<128, E>), grid, dim3(256), 0, s, qkv, out, seq_off, tok_node, own_start, Hq, Hkv);
+  B2T_CHECK_LAUNCH("clm_attn_tree_kernel");
+  return 0;
 }
 
 }  // namespace b2t
@@ -84,13 +70,13 @@ using namespace b2t;
 extern "C" int b2t_clm_llama_score_bf16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                         int n_seq, float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes,
                                         void* stream) {
-  return llama_score<LlamaBf16>("b2t_clm_llama_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws,
-                                ws_bytes, stream);
+  return llama_score<LlamaPolicy<__bf16>>("b2t_clm_llama_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
+                                          ws, ws_bytes, stream);
 }
 
 extern "C" int b2t_clm_llama_score_tree_bf16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                              int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws,
                                              size_t ws_bytes, void* stream) {
-  return llama_score_tree<LlamaBf16>("b2t_clm_llama_score_tree_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                     tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
+  return llama_score_tree<LlamaPolicy<__bf16>>("b2t_clm_llama_score_tree_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                               tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
 }

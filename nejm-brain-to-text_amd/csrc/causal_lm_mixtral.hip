@@ -30,9 +30,9 @@
 // reads the routing back; both tiles are served through the one tile rule launch_gemm, on a grid sized for S rows.
 //
 // This unit instantiates the two grouped GEMMs (on both tiles) and the kernels of clm_moe.h, in both element types, and nothing
-// else: every other kernel is reached through LlamaShared<E>, the entry-point bodies are clm_llama.h's under MixtralFamily, the
-// cached call is clm_score_tree_cached.  The workspace is the Llama layout with an empty hbuf plus one region behind it (mixtral_layout,
-// clm_moe.h), hence the size functions of its own; the cache's size is the Llama family's.
+// else: every other kernel is reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's
+// under MixtralFamily.  The workspace is the Llama layout with an empty hbuf plus one region behind it (mixtral_layout,
+// clm_moe.h); the cache's size is the Llama family's, which is why this unit exports no cache_kv_bytes.
 #include "clm_moe.h"
 
 namespace b2t {
@@ -47,34 +47,23 @@ struct MixtralPolicy : LlamaShared<El>, MoeOps<El> {
 using MixtralF16 = MixtralPolicy<_Float16>;
 using MixtralBf16 = MixtralPolicy<__bf16>;
 
-// dimensions the two descriptors must have for the sizes of mixtral_layout to mean anything (the full checks are
-// clm_llama_check_model and clm_mixtral_check)
-bool mixtral_dims_ok(const b2t_clm_llama_t* m, const b2t_clm_moe_t* moe) {
-  return m && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-         m->d_model % m->n_heads == 0 && moe_dims_ok(moe);
-}
-
 }  // namespace
 }  // namespace b2t
 
 using namespace b2t;
 
 extern "C" size_t b2t_clm_mixtral_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_tokens, int n_seq) {
-  if (!mixtral_dims_ok(model, moe) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return mixtral_layout(model, moe, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+  return llama_ws_bytes<MixtralFamily>(model, n_tokens, n_seq, moe);
 }
 
 extern "C" size_t b2t_clm_mixtral_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_nodes,
                                                 long long n_tokens, int n_seq) {
-  if (!mixtral_dims_ok(model, moe) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return mixtral_layout(model, moe, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+  return llama_tree_ws_bytes<MixtralFamily>(model, n_nodes, n_tokens, n_seq, moe);
 }
 
 extern "C" size_t b2t_clm_mixtral_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_rows,
                                                        long long n_tokens, int n_seq) {
-  if (!mixtral_dims_ok(model, moe) || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  const size_t tree = mixtral_layout(model, moe, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
-  return clm_cached_state(tree, n_rows, model->n_heads, model->d_model).total;
+  return llama_tree_cached_ws_bytes<MixtralFamily>(model, n_rows, n_tokens, n_seq, moe);
 }
 
 extern "C" int b2t_clm_mixtral_score_f16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
@@ -95,18 +84,9 @@ extern "C" int b2t_clm_mixtral_score_tree_cached_f16(const b2t_clm_llama_t* mode
                                                      int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                      float* scores_out, float* tok_logp_out, long long* n_rows_out,
                                                      int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "b2t_clm_mixtral_score_tree_cached_f16";
-  if (int rc = clm_llama_check_model(model)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  if (int rc = clm_mixtral_check(who, m, moe)) return rc;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads};
-  return clm_score_tree_cached(
-      who, "b2t_clm_mixtral_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-      n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return mixtral_layout(model, moe, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
-        return mixtral_forward<MixtralF16>(m, r, L, base, attn, s, moe);
-      });
+  return llama_score_tree_cached<MixtralF16, MixtralFamily>("b2t_clm_mixtral_score_tree_cached_f16", "b2t_clm_mixtral_score_tree_f16",
+                                                            model, cache, update, ids_host, seq_off_host, n_seq, scores_out,
+                                                            tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, stream, moe);
 }
 
 extern "C" int b2t_clm_mixtral_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,

@@ -32,9 +32,9 @@
 // in checkpoint order (no head_dim_perm); gate / up rows are interleaved as for Llama.
 //
 // This unit instantiates the two epilogues (on both tiles) and the two kernels, in both element types, and nothing else:
-// every other kernel is reached through LlamaShared<E>, the entry-point bodies are clm_llama.h's under Olmo2Family, the cached
-// call is clm_score_tree_cached.  The workspace is the Llama layout plus one fp32 region [padded rows][(Hq + Hkv) hd] behind it
-// (olmo2_layout, clm_olmo2.h), hence the size functions of its own; the cache's size is the Llama family's.
+// every other kernel is reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's under
+// Olmo2Family.  The workspace is the Llama layout plus one fp32 region [padded rows][(Hq + Hkv) hd] behind it (olmo2_layout,
+// clm_olmo2.h); the cache's size is the Llama family's.
 #include "clm_olmo2.h"
 
 namespace b2t {
@@ -48,35 +48,25 @@ struct Olmo2Policy : LlamaShared<El>, Olmo2Ops<El> {
 using Olmo2F16 = Olmo2Policy<_Float16>;
 using Olmo2Bf16 = Olmo2Policy<__bf16>;
 
-// dimensions a descriptor must have for the sizes of olmo2_layout to mean anything (the full check is clm_llama_check_model)
-bool olmo2_dims_ok(const b2t_clm_llama_t* m) {
-  return m && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-         m->d_model % m->n_heads == 0;
-}
-
 }  // namespace
 }  // namespace b2t
 
 using namespace b2t;
 
 extern "C" size_t b2t_clm_olmo2_ws_bytes(const b2t_clm_llama_t* model, long long n_tokens, int n_seq) {
-  if (!olmo2_dims_ok(model) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return olmo2_layout(model, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+  return llama_ws_bytes<Olmo2Family>(model, n_tokens, n_seq);
 }
 
 extern "C" size_t b2t_clm_olmo2_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq) {
-  if (!olmo2_dims_ok(model) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return olmo2_layout(model, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+  return llama_tree_ws_bytes<Olmo2Family>(model, n_nodes, n_tokens, n_seq);
 }
 
 extern "C" size_t b2t_clm_olmo2_cache_kv_bytes(const b2t_clm_llama_t* model, int cap) {
-  return b2t_clm_llama_cache_kv_bytes(model, cap);
+  return llama_cache_kv_bytes<Olmo2Family>(model, cap);
 }
 
 extern "C" size_t b2t_clm_olmo2_tree_cached_ws_bytes(const b2t_clm_llama_t* model, long long n_rows, long long n_tokens, int n_seq) {
-  if (!olmo2_dims_ok(model) || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  const size_t tree = olmo2_layout(model, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
-  return clm_cached_state(tree, n_rows, model->n_heads, model->d_model).total;
+  return llama_tree_cached_ws_bytes<Olmo2Family>(model, n_rows, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_olmo2_score_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
@@ -99,18 +89,9 @@ extern "C" int b2t_clm_olmo2_score_tree_cached_f16(const b2t_clm_llama_t* model,
                                                    const int32_t* seq_off_host, int n_seq, float* scores_out,
                                                    float* tok_logp_out, long long* n_rows_out, int* n_reused_out, void* ws,
                                                    size_t ws_bytes, void* stream) {
-  const char* who = "b2t_clm_olmo2_score_tree_cached_f16";
-  if (int rc = clm_llama_check_model(model)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  if (int rc = clm_olmo2_check(who, m, qk_norm_host)) return rc;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads};
-  return clm_score_tree_cached(
-      who, "b2t_clm_olmo2_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-      n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return olmo2_layout(model, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
-        return olmo2_forward<Olmo2F16>(m, r, L, base, attn, s, qk_norm_host);
-      });
+  return llama_score_tree_cached<Olmo2F16, Olmo2Family>("b2t_clm_olmo2_score_tree_cached_f16", "b2t_clm_olmo2_score_tree_f16", model,
+                                                        cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
+                                                        n_rows_out, n_reused_out, ws, ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_olmo2_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,

@@ -36,7 +36,7 @@
 // This unit instantiates the EP_QKV_F32 epilogue (on both tiles), the rotation kernel and the flat and tree attention at head
 // dim 96, in both element types, and the cached and trunk attention at 96 in fp16 (behind clm_launch_attn_cached of
 // causal_lm_cache.hip, which hands head dim 96 to clm_launch_attn_cached_96 below); every other kernel is reached through
-// LlamaShared<E>, the entry-point bodies are clm_llama.h's under Phi3Family, the cached call is clm_score_tree_cached.  No kernel
+// LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's under Phi3Family.  No kernel
 // here uses scratch (tests/test_clm_phi3_host.py checks it).  The workspace is phi3_layout (clm_phi3.h).
 #include "clm_attn.h"
 #include "clm_phi3.h"
@@ -66,12 +66,6 @@ struct Phi3Policy : LlamaShared<El>, Phi3Ops<El> {
 using Phi3F16 = Phi3Policy<_Float16>;
 using Phi3Bf16 = Phi3Policy<__bf16>;
 
-// dimensions a descriptor pair must have for the sizes of phi3_layout to mean anything (the full check is clm_phi3_check)
-bool phi3_dims_ok(const b2t_clm_llama_t* m, const b2t_clm_phi3_t* p3) {
-  return m && p3 && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-         (p3->head_dim == 64 || p3->head_dim == 96 || p3->head_dim == 128);
-}
-
 }  // namespace
 
 // launch_attn of causal_lm_cache.hip at head dim 96: stage B over the whole cached blocks, then the tree walk
@@ -89,12 +83,8 @@ int clm_launch_attn_cached_96(const ClmCachedAttn& a, const _Float16* qkv, const
 }
 
 int clm_phi3_check(const char* who, const b2t_clm_llama_t* m, const b2t_clm_phi3_t* p3) {
-  B2T_REQUIRE(m, "%s: null model", who);
-  B2T_REQUIRE(p3, "%s: null phi3 descriptor", who);
-  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
-              m->max_pos > 0,
-              "%s: bad dimensions (layers %d, d %d, heads %d, kv heads %d, ffn %d, vocab %d, max_pos %d)", who, m->n_layers,
-              m->d_model, m->n_heads, m->n_kv_heads, m->ffn_dim, m->vocab, m->max_pos);
+  B2T_REQUIRE(!m || p3, "%s: null phi3 descriptor", who);   // behind the null model, in front of the dimensions
+  if (int rc = clm_check_dims(who, m)) return rc;
   const int hd = p3->head_dim, rot = p3->rotary_dims;
   B2T_REQUIRE(hd == 64 || hd == 96 || hd == 128, "%s: unsupported head dim %d (64, 96 or 128)", who, hd);
   B2T_REQUIRE(rot >= 2 && rot <= hd && rot % 2 == 0, "%s: rotary_dims %d is not an even number in [2, head_dim %d]", who, rot, hd);
@@ -102,14 +92,12 @@ int clm_phi3_check(const char* who, const b2t_clm_llama_t* m, const b2t_clm_phi3
   B2T_REQUIRE(m->d_model % 64 == 0 && m->ffn_dim % 64 == 0 && qc % 64 == 0 && qw % 64 == 0,
               "%s: d_model %d, ffn_dim %d, n_heads * head_dim %lld and (n_heads + 2 n_kv_heads) * head_dim %lld must be multiples "
               "of 64", who, m->d_model, m->ffn_dim, qc, qw);
-  B2T_REQUIRE(m->n_heads % m->n_kv_heads == 0, "%s: n_heads %d is not a multiple of n_kv_heads %d", who, m->n_heads, m->n_kv_heads);
-  B2T_REQUIRE(m->rms_eps >= 0.f && m->rms_eps < 1.f, "%s: rms_eps %g outside [0, 1)", who, (double)m->rms_eps);
-  B2T_REQUIRE(m->embed_tokens && m->lm_head && m->final_norm_w && m->rope_cos && m->rope_sin && (m->n_layers == 0 || m->layers_host),
-              "%s: null weight pointer", who);
+  if (int rc = clm_check_gqa(who, *m)) return rc;
+  if (int rc = clm_check_eps(who, *m)) return rc;
+  if (int rc = clm_check_pointers(who, *m)) return rc;
   for (int l = 0; l < m->n_layers; ++l) {
-    const b2t_clm_llama_layer_t& w = m->layers_host[l];
-    B2T_REQUIRE(w.norm1_w && w.norm2_w && w.qkv_w && w.o_w && w.gate_up_w && w.down_w, "%s: null weight pointer in layer %d", who, l);
-    B2T_REQUIRE(!w.qkv_b, "%s: layer %d has q / k / v biases (qkv_b), which Phi-3 does not", who, l);
+    if (int rc = clm_check_layer(who, m->layers_host[l], l)) return rc;
+    B2T_REQUIRE(!m->layers_host[l].qkv_b, "%s: layer %d has q / k / v biases (qkv_b), which Phi-3 does not", who, l);
   }
   return 0;
 }
@@ -119,26 +107,21 @@ int clm_phi3_check(const char* who, const b2t_clm_llama_t* m, const b2t_clm_phi3
 using namespace b2t;
 
 extern "C" size_t b2t_clm_phi3_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_tokens, int n_seq) {
-  if (!phi3_dims_ok(model, phi3) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return phi3_layout(model, phi3, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+  return llama_ws_bytes<Phi3Family>(model, n_tokens, n_seq, phi3);
 }
 
 extern "C" size_t b2t_clm_phi3_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_nodes,
                                              long long n_tokens, int n_seq) {
-  if (!phi3_dims_ok(model, phi3) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return phi3_layout(model, phi3, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+  return llama_tree_ws_bytes<Phi3Family>(model, n_nodes, n_tokens, n_seq, phi3);
 }
 
 extern "C" size_t b2t_clm_phi3_cache_kv_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, int cap) {
-  if (!phi3_dims_ok(model, phi3) || cap < 1 || cap > model->max_pos || model->n_layers < 1) return 0;
-  return (size_t)model->n_layers * (size_t)cap * 2 * (size_t)model->n_kv_heads * (size_t)phi3->head_dim * sizeof(_Float16);
+  return llama_cache_kv_bytes<Phi3Family>(model, cap, phi3);
 }
 
 extern "C" size_t b2t_clm_phi3_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_rows,
                                                     long long n_tokens, int n_seq) {
-  if (!phi3_dims_ok(model, phi3) || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  const size_t tree = phi3_layout(model, phi3, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
-  return clm_cached_state(tree, n_rows, model->n_heads, model->n_heads * phi3->head_dim).total;
+  return llama_tree_cached_ws_bytes<Phi3Family>(model, n_rows, n_tokens, n_seq, phi3);
 }
 
 extern "C" int b2t_clm_phi3_score_f16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
@@ -159,17 +142,9 @@ extern "C" int b2t_clm_phi3_score_tree_cached_f16(const b2t_clm_llama_t* model, 
                                                   int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                   float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
                                                   void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "b2t_clm_phi3_score_tree_cached_f16";
-  if (int rc = clm_phi3_check(who, model, phi3)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, phi3->head_dim};
-  return clm_score_tree_cached(
-      who, "b2t_clm_phi3_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out,
-      n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return phi3_layout(model, phi3, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
-        return phi3_forward<Phi3F16>(m, *phi3, r, L, base, attn, s);
-      });
+  return llama_score_tree_cached<Phi3F16, Phi3Family>("b2t_clm_phi3_score_tree_cached_f16", "b2t_clm_phi3_score_tree_f16", model, cache,
+                                                      update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out,
+                                                      n_reused_out, ws, ws_bytes, stream, phi3);
 }
 
 extern "C" int b2t_clm_phi3_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,

@@ -15,8 +15,8 @@
 //
 // This unit instantiates that one epilogue, on both tiles and for both element types, and nothing else: the forward is
 // llama_forward (clm_llama.h) under a policy with qk_norm set, every other kernel is reached through LlamaShared<E>, the
-// launches causal_lm_llama.hip and causal_lm_llama_bf16.hip export, the cached call is clm_score_tree_cached
-// (clm_internal.h), and the workspace and cache sizes are the Llama size functions'.  For head dim 128 the norm weights are
+// launches causal_lm_llama.hip and causal_lm_llama_bf16.hip define, the three entry-point bodies are clm_llama.h's under
+// LlamaFamily, and the workspace and cache sizes are the Llama size functions'.  For head dim 128 the norm weights are
 // stored in the order of the q / k rows they scale (llm_rescore.head_dim_perm); the mean of squares does not notice.
 #include "clm_llama.h"
 
@@ -68,18 +68,9 @@ extern "C" int b2t_clm_qwen3_score_tree_cached_f16(const b2t_clm_llama_t* model,
                                                    const int32_t* seq_off_host, int n_seq, float* scores_out,
                                                    float* tok_logp_out, long long* n_rows_out, int* n_reused_out, void* ws,
                                                    size_t ws_bytes, void* stream) {
-  const char* who = "b2t_clm_qwen3_score_tree_cached_f16";
-  if (int rc = clm_llama_check_model(model)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  if (int rc = clm_qknorm_check(who, m, qk_norm_host)) return rc;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, m.d_model / m.n_heads};
-  return clm_score_tree_cached(
-      who, "b2t_clm_qwen3_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-      n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return llama_layout(model, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
-        return llama_forward<Qwen3F16>(m, r, L, base, attn, s, qk_norm_host);
-      });
+  return llama_score_tree_cached<Qwen3F16>("b2t_clm_qwen3_score_tree_cached_f16", "b2t_clm_qwen3_score_tree_f16", model, cache, update,
+                                           ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out, n_reused_out, ws,
+                                           ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_qwen3_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,

@@ -1,7 +1,7 @@
 // clm_gemma2.h — the Gemma-2 forward (causal_lm_gemma2.hip's header has the contract and the kernel sequence), written once for
 // both element types like clm_olmo2.h: the three kernels Gemma-2 adds, its workspace layout, gemma2_forward and Gemma2Family,
-// which hands them to the entry-point bodies of clm_llama.h.  A policy P of this forward is LlamaShared<E> (the QKV GEMM with
-// EP_ROPE and the uncapped head GEMM) plus
+// which hands them to the entry-point bodies and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E>
+// (the QKV GEMM with EP_ROPE and the uncapped head GEMM) plus
 //   P::gemm_geglu, P::gemm_f32, P::gemm_head_cap (g, s)   the gate / up GEMM with EP_GEGLU, the o_proj / down GEMM with EP_F32
 //                                                         and the head GEMM with EP_HEAD_CAP
 //   P::embed_scaled, P::rmsnorm1p, P::postnorm1p_add      the launches of the three kernels below
@@ -167,14 +167,18 @@ int gemma2_forward(const b2t_clm_llama_t& m, const b2t_clm_gemma2_t& g2, const C
   return clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, reinterpret_cast<float*>(base + L.logp), r.Mh, s);
 }
 
-// what llama_score / llama_score_tree (clm_llama.h) take from this family; the extra argument is the b2t_clm_gemma2_t
+// what the entry-point bodies and the size rules of clm_llama.h take from this family; the extra argument is the b2t_clm_gemma2_t
 struct Gemma2Family {
-  static int check_model(const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2) { return clm_gemma2_check_model(m, g2); }
+  static int head_dim(const b2t_clm_llama_t&, const b2t_clm_gemma2_t* g2) { return g2->head_dim; }
+  static float attn_cap(const b2t_clm_gemma2_t* g2) { return g2->attn_cap; }
+  static bool dims_ok(const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2) {
+    return llama_dims_ok(m) && g2 && (g2->head_dim == 128 || g2->head_dim == 256);
+  }
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const b2t_clm_gemma2_t* g2) {
     return gemma2_layout(m, g2, rows, hrows, ints);
   }
   template <class P>
-  static int check(const char*, const b2t_clm_llama_t&, const b2t_clm_gemma2_t*) { return 0; }   // check_model has it all
+  static int check(const char*, const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2) { return clm_gemma2_check_model(m, g2); }
   template <class P>
   static int attn(const b2t_clm_llama_t& m, const b2t_clm_gemma2_t* g2, int /*layer*/, const typename P::E* qkv, typename P::E* out,
                   const int* seq_off, int n_seq, hipStream_t s) {

@@ -1,12 +1,13 @@
 // clm_gptoss.h — the gpt-oss forward (causal_lm_gptoss.hip's header has the contract and the kernel sequence), written once for
 // both element types like clm_gemma2.h: the router kernel gpt-oss adds, its workspace layout, one layer's routed MLP
 // (gptoss_mlp: plan, gather and combine are clm_moe.h's kernels and region, unchanged), gptoss_forward and GptOssFamily, which
-// hands them to the entry-point bodies of clm_llama.h.  A policy P of this forward is LlamaShared<E> (the QKV GEMM with bias and
-// rotation, the o_proj GEMM with bias into the residual, the head, embed, RMSNorm) and MoeOps<E> (gather) plus
+// hands them to the entry-point bodies and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E> (the QKV
+// GEMM with bias and rotation, the o_proj GEMM with bias into the residual, the head, embed, RMSNorm), MoeOps<E> (gather) and
+// GptOssOps<E> (below: the router's launch route_oss, and attn_sink / attn_tree_sink (..., sinks, window, s), the flat and the
+// tree attention with a sink and a window, instantiated by the unit that names the policy) plus
 //   P::gemm_experts_glu, P::gemm_experts_f32b (g, s)   the two grouped GEMMs with EP_OSS_GLU and EP_F32_BIAS
-//   P::route_oss                                       the launch of the router kernel below
-//   P::attn, P::attn_tree (..., sinks, window, s)      the flat and the tree attention with a sink and a window
 #pragma once
+#include "clm_attn.h"
 #include "clm_moe.h"
 
 namespace b2t {
@@ -88,6 +89,20 @@ struct GptOssOps {
     hipLaunchKernelGGL(clm_gptoss_route_kernel<El>, dim3((unsigned)rows), dim3(256), 0, s, x, wr, br, d, ne, k, route_e, route_w,
                        route_out);
     B2T_CHECK_LAUNCH("clm_gptoss_route_kernel");
+    return 0;
+  }
+  static int attn_sink(const El* qkv, El* out, const int* seq_off, int n_seq, int Hq, int Hkv, const float* sinks, int window,
+                       hipStream_t s) {
+    hipLaunchKernelGGL((clm_attn_sink_kernel<OSS_HEAD_DIM, El>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, Hq, Hkv, sinks,
+                       window);
+    B2T_CHECK_LAUNCH("clm_attn_sink_kernel");
+    return 0;
+  }
+  static int attn_tree_sink(const El* qkv, El* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
+                            int Hkv, const float* sinks, int window, hipStream_t s) {
+    hipLaunchKernelGGL((clm_attn_tree_sink_kernel<OSS_HEAD_DIM, El>), dim3(n_seq, Hq), dim3(256), 0, s, qkv, out, seq_off, tok_node,
+                       own_start, Hq, Hkv, sinks, window);
+    B2T_CHECK_LAUNCH("clm_attn_tree_sink_kernel");
     return 0;
   }
 };
@@ -199,24 +214,39 @@ int gptoss_forward(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t& g, const Cl
   return clm_head(x16, m.lm_head, m.vocab, d, r, L, base, s, &P::gemm_head);
 }
 
-// what llama_score / llama_score_tree (clm_llama.h) take from this family; the extra argument is the b2t_clm_gptoss_t
-struct GptOssFamily {
-  static int check_model(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) { return clm_gptoss_check_model(m, g); }
-  static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const b2t_clm_gptoss_t* g) {
-    return gptoss_layout(m, g, rows, hrows, ints);
+// the gpt-oss descriptor in a family's extra argument: the argument itself, or the member g of a record that carries more
+inline const b2t_clm_gptoss_t* gptoss_of(const b2t_clm_gptoss_t* g) { return g; }
+template <class X>
+const b2t_clm_gptoss_t* gptoss_of(const X* x) { return x->g; }
+
+// what the entry-point bodies and the size rules of clm_llama.h take from this family; the extra argument is the
+// b2t_clm_gptoss_t, or a record gptoss_of finds it in (causal_lm_gptoss_mx.hip's, whose family takes all but forward from here)
+struct GptOssFamily : LlamaFamilyBase {
+  template <class X>
+  static int head_dim(const b2t_clm_llama_t&, const X* x) { return gptoss_of(x)->head_dim; }
+  template <class X>
+  static bool dims_ok(const b2t_clm_llama_t* m, const X* x) {
+    const b2t_clm_gptoss_t* g = gptoss_of(x);
+    return llama_dims_ok(m) && g && g->head_dim == OSS_HEAD_DIM && g->n_experts >= 1 && g->n_experts <= OSS_MAX_EXPERTS &&
+           g->top_k >= 1 && g->top_k <= MOE_MAX_TOPK && g->top_k <= g->n_experts;
   }
-  template <class P>
-  static int check(const char*, const b2t_clm_llama_t&, const b2t_clm_gptoss_t*) { return 0; }   // check_model has it all
-  template <class P>
-  static int attn(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t* g, int l, const typename P::E* qkv, typename P::E* out,
-                  const int* seq_off, int n_seq, hipStream_t s) {
-    return P::attn(qkv, out, seq_off, n_seq, m.n_heads, m.n_kv_heads, g->layers_host[l].sinks, g->layers_host[l].window, s);
+  template <class X>
+  static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const X* x) {
+    return gptoss_layout(m, gptoss_of(x), rows, hrows, ints);
   }
-  template <class P>
-  static int attn_tree(const b2t_clm_llama_t& m, const b2t_clm_gptoss_t* g, int l, const typename P::E* qkv, typename P::E* out,
-                       const int* seq_off, const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
-    return P::attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, m.n_heads, m.n_kv_heads, g->layers_host[l].sinks,
-                        g->layers_host[l].window, s);
+  template <class P, class X>
+  static int check(const char*, const b2t_clm_llama_t* m, const X* x) { return clm_gptoss_check_model(m, gptoss_of(x)); }
+  template <class P, class X>
+  static int attn(const b2t_clm_llama_t& m, const X* x, int l, const typename P::E* qkv, typename P::E* out, const int* seq_off,
+                  int n_seq, hipStream_t s) {
+    const b2t_clm_gptoss_layer_t& w2 = gptoss_of(x)->layers_host[l];
+    return P::attn_sink(qkv, out, seq_off, n_seq, m.n_heads, m.n_kv_heads, w2.sinks, w2.window, s);
+  }
+  template <class P, class X>
+  static int attn_tree(const b2t_clm_llama_t& m, const X* x, int l, const typename P::E* qkv, typename P::E* out, const int* seq_off,
+                       const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
+    const b2t_clm_gptoss_layer_t& w2 = gptoss_of(x)->layers_host[l];
+    return P::attn_tree_sink(qkv, out, seq_off, tok_node, own_start, n_seq, m.n_heads, m.n_kv_heads, w2.sinks, w2.window, s);
   }
   template <class P, class Attn>
   static int forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,

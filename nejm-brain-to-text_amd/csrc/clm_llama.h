@@ -1,19 +1,31 @@
 // clm_llama.h — the Llama-family forward (causal_lm_llama.hip's header has the contract and the kernel sequence), written once
-// for both element types: the embed and RMSNorm kernels, llama_forward and the bodies of the flat and the tree entry point are
-// templates, on the element type or on a policy P that names it and supplies the launches that differ with it:
+// for both element types and for every family that rides on it: the embed and RMSNorm kernels, llama_forward, the bodies of the
+// flat, the tree and the cached entry point, the size rules and the statements the families' descriptor checks share.
+//
+// A policy P names the element type and supplies the launches that differ with it:
 //   P::E                                        _Float16 or __bf16 (ClmElem, clm_internal.h)
 //   P::gemm_rope, gemm_swiglu, gemm_resid, gemm_head (g, s)   the four GEMMs, each through the one tile rule launch_gemm
-//   P::embed, P::rmsnorm                        the two kernels below (LlamaOps<E>)
+//   P::embed, P::rmsnorm                        the launches of the two kernels below
 //   P::attn, P::attn_tree                       the flat and the tree attention launcher
 //   P::qk_norm                                  whether the QKV GEMM's epilogue norms the q and k heads (Qwen3): llama_forward then
 //                                               hands it the layer's weights from the b2t_clm_qknorm_t array and rms_eps
-// causal_lm_llama.hip holds the fp16 policy and the fp16 entry points (the cached one included), causal_lm_llama_bf16.hip the
-// bf16 policy, every bf16 kernel instantiation and the two bf16 entry points.  causal_lm_qwen3.hip holds the two Qwen3
-// policies: gemm_rope with the epilogue EP_QKNORM_ROPE, instantiated there, and every other launch through LlamaShared<E>.
-// The two entry-point bodies also serve a family with another layer (OLMo-2, clm_olmo2.h; Mixtral, clm_moe.h): their second
-// template argument supplies the layout, the refusals that go with the family's extra argument and the forward (LlamaFamily
-// below by default), and -- through LlamaFamilyBase, or on its own for Gemma-2 (clm_gemma2.h), whose head dim is not
-// d_model / n_heads, and Phi-3 (clm_phi3.h), whose head dim may be 96 -- the model check and the attention launches.
+// The Llama policy is LlamaShared<E> (below; causal_lm_llama.hip defines its members for fp16 and holds the fp16 entry points,
+// causal_lm_llama_bf16.hip the same for bf16, with every bf16 kernel instantiation) plus qk_norm = false; Qwen3's
+// (causal_lm_qwen3.hip) is LlamaShared<E> plus a gemm_rope with the epilogue EP_QKNORM_ROPE, instantiated there.
+//
+// A family Fam is what the bodies and the size rules take beside the policy; x is the family's extra argument, of its own type X
+// (the q / k norm array of Qwen3 and OLMo-2, or a descriptor: b2t_clm_moe_t, b2t_clm_gemma2_t, b2t_clm_phi3_t, b2t_clm_gptoss_t):
+//   Fam::layout(model, rows, hrows, ints, x)    the workspace layout of a forward
+//   Fam::forward<P>(m, run, L, base, attn, s, x)   the forward; attn(layer, qkv, out) enqueues one layer's attention
+//   Fam::attn<P>, Fam::attn_tree<P>(m, x, layer, ...)   the flat and the tree attention of one layer
+//   Fam::head_dim(m, x)                         d_model / n_heads, or the descriptor's field (Gemma-2, Phi-3, gpt-oss)
+//   Fam::attn_cap(x)                            the soft cap on the attention scores: 0, or Gemma-2's
+//   Fam::dims_ok(model, x)                      what the size rules need of the descriptors: llama_dims_ok and the family's term
+//   Fam::check<P>(who, model, x)                every refusal of the descriptors, a null model included, for the entry point `who`
+// LlamaFamilyBase has head_dim, attn_cap, dims_ok, check, attn and attn_tree of a family whose descriptor obeys the Llama rule:
+// the defaults, which a family derives and replaces where it differs.  LlamaFamily is the Llama family's (Qwen3 included:
+// P::qk_norm), Olmo2Family (clm_olmo2.h), MixtralFamily (clm_moe.h), Gemma2Family (clm_gemma2.h), Phi3Family (clm_phi3.h) and
+// GptOssFamily (clm_gptoss.h) the others'.
 #pragma once
 #include <math.h>
 #include <string>
@@ -29,10 +41,45 @@ int clm_llama_check_model(const b2t_clm_llama_t* m);
 // none, and EP_QKNORM_ROPE adds none) are refused; causal_lm_qwen3.hip
 int clm_qknorm_check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_qknorm_t* qkn);
 
-// The launches of the Llama policy for element type E that another family's policy shares (P's list above; Qwen3's and OLMo-2's
-// policies put a QKV GEMM of their own in front of gemm_rope, Mixtral's takes it as it is),
-// so that their kernels are instantiated in one unit: the members are defined in causal_lm_llama.hip for _Float16 and in
-// causal_lm_llama_bf16.hip for __bf16, each forwarding to its unit's policy.
+// The statements every family's descriptor check makes, `pre` being the prefix of its messages (the family's name, or the entry
+// point's for Phi-3); the head-dim set, the multiples-of-64 line and the extras stay with the family, in the family's order.
+inline int clm_check_dims(const char* pre, const b2t_clm_llama_t* m) {
+  B2T_REQUIRE(m, "%s: null model", pre);
+  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 &&
+              m->max_pos > 0,
+              "%s: bad dimensions (layers %d, d %d, heads %d, kv heads %d, ffn %d, vocab %d, max_pos %d)", pre, m->n_layers,
+              m->d_model, m->n_heads, m->n_kv_heads, m->ffn_dim, m->vocab, m->max_pos);
+  return 0;
+}
+inline int clm_check_gqa(const char* pre, const b2t_clm_llama_t& m) {
+  B2T_REQUIRE(m.n_heads % m.n_kv_heads == 0, "%s: n_heads %d is not a multiple of n_kv_heads %d", pre, m.n_heads, m.n_kv_heads);
+  return 0;
+}
+inline int clm_check_eps(const char* pre, const b2t_clm_llama_t& m) {
+  B2T_REQUIRE(m.rms_eps >= 0.f && m.rms_eps < 1.f, "%s: rms_eps %g outside [0, 1)", pre, (double)m.rms_eps);
+  return 0;
+}
+// the model's own pointers; `own`: whether the family's own per-layer array, where it has one, is there
+inline int clm_check_pointers(const char* pre, const b2t_clm_llama_t& m, bool own = true) {
+  B2T_REQUIRE(m.embed_tokens && m.lm_head && m.final_norm_w && m.rope_cos && m.rope_sin &&
+              (m.n_layers == 0 || (m.layers_host && own)), "%s: null weight pointer", pre);
+  return 0;
+}
+// layer l's six matrices and norms (qkv_b may be null: no q / k / v biases); `own`: the family's own pointers of the layer
+inline int clm_check_layer(const char* pre, const b2t_clm_llama_layer_t& w, int l, bool own = true) {
+  B2T_REQUIRE(w.norm1_w && w.norm2_w && w.qkv_w && w.o_w && w.gate_up_w && w.down_w && own, "%s: null weight pointer in layer %d",
+              pre, l);
+  return 0;
+}
+// dimensions a descriptor must have for the sizes of a layout to mean anything (the full check is the family's check)
+inline bool llama_dims_ok(const b2t_clm_llama_t* m) {
+  return m && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->n_kv_heads > 0 && m->ffn_dim > 0 && m->vocab > 0;
+}
+
+// The launches of the Llama policy for element type E, which the other families' policies share (Qwen3's and OLMo-2's put a QKV
+// GEMM of their own in front of gemm_rope, Mixtral's takes it as it is), so that their kernels are instantiated in one unit:
+// the template has no definitions; the members are specialised in causal_lm_llama.hip for _Float16 and in
+// causal_lm_llama_bf16.hip for __bf16, each with its launch.
 template <class El>
 struct LlamaShared {
   using E = El;
@@ -46,19 +93,11 @@ struct LlamaShared {
   static int attn_tree(const E* qkv, E* out, const int* seq_off, const int* tok_node, const int* own_start, int n_seq, int Hq,
                        int Hkv, int hd, hipStream_t s);
 };
-// the specialisations the two units define, declared before any use
-#define B2T_LLAMA_SHARED(EL)                                                                                                  \
-  template <> int LlamaShared<EL>::gemm_rope(const ClmGemm&, hipStream_t);                                                    \
-  template <> int LlamaShared<EL>::gemm_swiglu(const ClmGemm&, hipStream_t);                                                  \
-  template <> int LlamaShared<EL>::gemm_resid(const ClmGemm&, hipStream_t);                                                   \
-  template <> int LlamaShared<EL>::gemm_head(const ClmGemm&, hipStream_t);                                                    \
-  template <> int LlamaShared<EL>::embed(const int*, const EL*, float*, int, long long, hipStream_t);                         \
-  template <> int LlamaShared<EL>::rmsnorm(const float*, const int*, long long, const EL*, float, EL*, int, hipStream_t);     \
-  template <> int LlamaShared<EL>::attn(const EL*, EL*, const int*, int, int, int, int, hipStream_t);                         \
-  template <> int LlamaShared<EL>::attn_tree(const EL*, EL*, const int*, const int*, const int*, int, int, int, int, hipStream_t);
-B2T_LLAMA_SHARED(_Float16)
-B2T_LLAMA_SHARED(__bf16)
-#undef B2T_LLAMA_SHARED
+// the Llama policy of the forward for element type El
+template <class El>
+struct LlamaPolicy : LlamaShared<El> {
+  static constexpr bool qk_norm = false;
+};
 
 namespace {
 
@@ -88,23 +127,6 @@ __global__ __launch_bounds__(256) void clm_llama_rmsnorm_kernel(const float* x, 
   const float rstd = 1.0f / sqrtf(block_sum256(v, red) / d + eps);
   for (int c = threadIdx.x; c < d; c += 256) o[c] = (E)(xr[c] * rstd * (float)w[c]);
 }
-
-// the part of a policy that is the same text for both element types
-template <class El>
-struct LlamaOps {
-  using E = El;
-  static constexpr bool qk_norm = false;
-  static int embed(const int* ids, const E* et, float* resid, int d, long long rows, hipStream_t s) {
-    hipLaunchKernelGGL(clm_llama_embed_kernel<E>, dim3((unsigned)rows), dim3(256), 0, s, ids, et, resid, d);
-    B2T_CHECK_LAUNCH("clm_llama_embed_kernel");
-    return 0;
-  }
-  static int rmsnorm(const float* x, const int* rowmap, long long n, const E* w, float eps, E* out, int d, hipStream_t s) {
-    hipLaunchKernelGGL(clm_llama_rmsnorm_kernel<E>, dim3((unsigned)rup(n, ROWPAD)), dim3(256), 0, s, x, rowmap, (int)n, w, eps, out, d);
-    B2T_CHECK_LAUNCH("clm_llama_rmsnorm_kernel");
-    return 0;
-  }
-};
 
 // Workspace of a forward over `rows` rows with `hrows` head rows and `ints` index entries (2-byte elements either way)
 inline ClmLayout llama_layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints) {
@@ -166,13 +188,18 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
   return llama_forward_mlp<P>(m, r, L, base, attn, s, qkn, mlp);
 }
 
-// What a family whose descriptor obeys the Llama rule hd = d_model / n_heads hands the entry-point bodies beside layout, check
-// and forward: the model check, the head dim and the two attention launches, which are told the layer (gpt-oss, clm_gptoss.h:
-// a sink per head and a window per layer; nobody else looks at it).  Gemma-2 (clm_gemma2.h), whose head dim is a
-// field of its own descriptor and whose attention takes a soft cap, supplies its own.
+// What a family whose descriptor obeys the Llama rule hd = d_model / n_heads hands the bodies and the size rules beside layout
+// and forward (the contract in this file's header): the model check alone as its check, and the two attention launches, which
+// are told the layer (gpt-oss, clm_gptoss.h: a sink per head and a window per layer; nobody else looks at it).
 struct LlamaFamilyBase {
   template <class X>
-  static int check_model(const b2t_clm_llama_t* m, const X*) { return clm_llama_check_model(m); }
+  static int head_dim(const b2t_clm_llama_t& m, const X*) { return m.d_model / m.n_heads; }
+  template <class X>
+  static float attn_cap(const X*) { return 0.f; }
+  template <class X>
+  static bool dims_ok(const b2t_clm_llama_t* m, const X*) { return llama_dims_ok(m) && m->d_model % m->n_heads == 0; }
+  template <class P, class X>
+  static int check(const char*, const b2t_clm_llama_t* m, const X*) { return clm_llama_check_model(m); }
   template <class P, class X>
   static int attn(const b2t_clm_llama_t& m, const X*, int /*layer*/, const typename P::E* qkv, typename P::E* out,
                   const int* seq_off, int n_seq, hipStream_t s) {
@@ -185,15 +212,16 @@ struct LlamaFamilyBase {
   }
 };
 
-// What the two entry-point bodies below take from a family: the workspace layout, the refusals that go with the q / k norm
-// array, and the forward.  This is the Llama family's (Qwen3 included: P::qk_norm); OLMo-2's is Olmo2Family (clm_olmo2.h).
+// The Llama family's (Qwen3 included: P::qk_norm): the Llama layout, the refusals that go with the q / k norm array behind the
+// model check, and llama_forward.
 struct LlamaFamily : LlamaFamilyBase {
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const void* /*extra*/ = nullptr) {
     return llama_layout(m, rows, hrows, ints);   // the q / k norm array changes no size
   }
   template <class P>
-  static int check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_qknorm_t* qkn) {
-    if constexpr (P::qk_norm) return clm_qknorm_check(who, m, qkn);
+  static int check(const char* who, const b2t_clm_llama_t* m, const b2t_clm_qknorm_t* qkn) {
+    if (int rc = clm_llama_check_model(m)) return rc;
+    if constexpr (P::qk_norm) return clm_qknorm_check(who, *m, qkn);
     return 0;
   }
   template <class P, class Attn>
@@ -203,15 +231,13 @@ struct LlamaFamily : LlamaFamilyBase {
   }
 };
 
-// The flat entry point of a policy; `who` is its name.  `extra` is what the family's layout, check and forward take beside the
-// model, of the family's own type X: the q / k norm array (Qwen3, OLMo-2) or a descriptor (Mixtral's b2t_clm_moe_t, clm_moe.h).
+// The flat entry point of a policy and a family; `who` is its name, `extra` the family's extra argument.
 template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
 int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                 float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream, const X* extra = nullptr) {
   using E = typename P::E;
-  if (int rc = Fam::check_model(model, extra)) return rc;
+  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
   const b2t_clm_llama_t& m = *model;
-  if (int rc = Fam::template check<P>(who, m, extra)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
@@ -234,9 +260,8 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
                      int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                      void* stream, const X* extra = nullptr) {
   using E = typename P::E;
-  if (int rc = Fam::check_model(model, extra)) return rc;
+  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
   const b2t_clm_llama_t& m = *model;
-  if (int rc = Fam::template check<P>(who, m, extra)) return rc;
   B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
   if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
   const long long M = seq_off_host[n_seq];
@@ -256,6 +281,48 @@ int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_
   };
   if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
   return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
+}
+
+// The cached entry point of a policy: the family's check, then the family-independent rule (clm_internal.h) over the family's
+// layout and forward; `uncached` names the tree call for callers without a cache.
+template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
+int llama_score_tree_cached(const char* who, const char* uncached, const b2t_clm_llama_t* model, b2t_clm_cache_t* cache, int update,
+                            const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
+                            long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes, void* stream,
+                            const X* extra = nullptr) {
+  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
+  const b2t_clm_llama_t& m = *model;
+  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, Fam::head_dim(m, extra), Fam::attn_cap(extra)};
+  return clm_score_tree_cached(
+      who, uncached, dims, cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out, n_reused_out, ws,
+      ws_bytes, as_stream(stream), [&](long long rows, size_t ints) { return Fam::layout(model, rows, rows, ints, extra); },
+      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
+        return Fam::template forward<P>(m, r, L, base, attn, s, extra);
+      });
+}
+
+// The size rules behind every family's exported size functions: 0 for descriptors or counts no call would accept, else the bytes
+// of the flat, the tree and the cached call's workspace and of a cache's K | V for `cap` positions.  The cached state is sized by
+// n_heads * head_dim, which is d_model only where the Llama rule holds.
+template <class Fam, class X = b2t_clm_qknorm_t>
+size_t llama_ws_bytes(const b2t_clm_llama_t* m, long long n_tokens, int n_seq, const X* x = nullptr) {
+  if (!Fam::dims_ok(m, x) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
+  return Fam::layout(m, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq), x).total;
+}
+template <class Fam, class X = b2t_clm_qknorm_t>
+size_t llama_tree_ws_bytes(const b2t_clm_llama_t* m, long long n_nodes, long long n_tokens, int n_seq, const X* x = nullptr) {
+  if (!Fam::dims_ok(m, x) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
+  return Fam::layout(m, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq), x).total;
+}
+template <class Fam, class X = b2t_clm_qknorm_t>
+size_t llama_cache_kv_bytes(const b2t_clm_llama_t* m, int cap, const X* x = nullptr) {
+  if (!Fam::dims_ok(m, x) || cap < 1 || cap > m->max_pos || m->n_layers < 1) return 0;
+  return (size_t)m->n_layers * (size_t)cap * 2 * (size_t)m->n_kv_heads * (size_t)Fam::head_dim(*m, x) * sizeof(_Float16);
+}
+template <class Fam, class X = b2t_clm_qknorm_t>
+size_t llama_tree_cached_ws_bytes(const b2t_clm_llama_t* m, long long n_rows, long long n_tokens, int n_seq, const X* x = nullptr) {
+  const size_t tree = llama_tree_ws_bytes<Fam>(m, n_rows, n_tokens, n_seq, x);
+  return tree ? clm_cached_state(tree, n_rows, m->n_heads, m->n_heads * Fam::head_dim(*m, x)).total : 0;
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // clm_phi3.h — the Phi-3 forward (causal_lm_phi3.hip's header has the contract and the kernel sequence), written once for both
 // element types like clm_olmo2.h: the one kernel Phi-3 adds, its workspace layout, phi3_forward and Phi3Family, which hands them
-// to the entry-point bodies of clm_llama.h.  A policy P of this forward is LlamaShared<E> (embed, RMSNorm, the SwiGLU, residual
-// and head GEMMs) plus
+// to the entry-point bodies and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E> (embed, RMSNorm, the
+// SwiGLU, residual and head GEMMs) plus
 //   P::gemm_qkv (g, s)                          the QKV GEMM with EP_QKV_F32
 //   P::rope                                     the launch of the kernel below
 //   P::attn, P::attn_tree (..., hd, s)          the flat and the tree attention: head dim 96 here, 64 and 128 through LlamaShared
@@ -109,18 +109,18 @@ int phi3_forward(const b2t_clm_llama_t& m, const b2t_clm_phi3_t& p3, const ClmRu
   return clm_head(x16, m.lm_head, m.vocab, d, r, L, base, s, &P::gemm_head);
 }
 
-// what llama_score / llama_score_tree (clm_llama.h) take from this family; the extra argument is the b2t_clm_phi3_t
-struct Phi3Family {
-  // the model must be there for the bodies to name it; everything else is refused by check, under the entry point's name
-  static int check_model(const b2t_clm_llama_t* m, const b2t_clm_phi3_t*) {
-    B2T_REQUIRE(m, "b2t_clm_phi3: null model");
-    return 0;
+// what the entry-point bodies and the size rules of clm_llama.h take from this family; the extra argument is the b2t_clm_phi3_t.
+// Every refusal is under the entry point's name.
+struct Phi3Family : LlamaFamilyBase {
+  static int head_dim(const b2t_clm_llama_t&, const b2t_clm_phi3_t* p3) { return p3->head_dim; }
+  static bool dims_ok(const b2t_clm_llama_t* m, const b2t_clm_phi3_t* p3) {
+    return llama_dims_ok(m) && p3 && (p3->head_dim == 64 || p3->head_dim == 96 || p3->head_dim == 128);
   }
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const b2t_clm_phi3_t* p3) {
     return phi3_layout(m, p3, rows, hrows, ints);
   }
   template <class P>
-  static int check(const char* who, const b2t_clm_llama_t& m, const b2t_clm_phi3_t* p3) { return clm_phi3_check(who, &m, p3); }
+  static int check(const char* who, const b2t_clm_llama_t* m, const b2t_clm_phi3_t* p3) { return clm_phi3_check(who, m, p3); }
   template <class P>
   static int attn(const b2t_clm_llama_t& m, const b2t_clm_phi3_t* p3, int /*layer*/, const typename P::E* qkv, typename P::E* out,
                   const int* seq_off, int n_seq, hipStream_t s) {
