@@ -597,7 +597,8 @@ int b2t_nbest_convert_to_inputs(const int32_t* ali, const int32_t* a_off, int n,
 
 /* ---- causal LM scoring (the n-best rescoring LLM, language-model-standalone.py:92-162) ------------------------------
  * Scoring-only forward of a pre-LayerNorm OPT decoder (OPTForCausalLM with ReLU, word_embed_proj_dim == hidden_size), csrc/causal_lm.hip
- * (the layer loop and the host pieces every path shares: csrc/clm_internal.h; the attention arithmetic: csrc/clm_attn.h).
+ * (the layer loop, the host pieces every path shares and the bodies of every family's entry points and size functions:
+ * csrc/clm_internal.h; the attention arithmetic: csrc/clm_attn.h).
  * Weights are fp16 DEVICE arrays in this layout (nejm-brain-to-text_amd/llm_rescore.py builds it once at load time):
  *   rows of every nn.Linear weight [N][K] zero-padded to a multiple of 256; K (= d_model or ffn_dim) a multiple of 64;
  *   qkv_w = [q_proj; k_proj; v_proj] rows, qkv_b the three biases; embed_tokens [round_up(vocab, 256)][d] (zero rows beyond
@@ -620,7 +621,9 @@ typedef struct {
   const b2t_clm_layer_t* layers_host;  /* HOST array of n_layers entries (device pointers inside) */
 } b2t_clm_t;
 
-/* Workspace bytes of b2t_clm_score_f16 for n_tokens tokens in n_seq sequences (0 if the sizes are invalid). */
+/* Workspace bytes of b2t_clm_score_f16 for n_tokens tokens in n_seq sequences (0 if the sizes are invalid, or the model is
+ * null or has dimensions no call accepts: one below 1, n_layers < 0, d_model no multiple of n_heads; so for every OPT size
+ * function). */
 size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, int n_seq);
 /* Log-probability of packed sequences: sequence s is ids_host[seq_off_host[s] .. seq_off_host[s+1]) (HOST int32 arrays,
  * seq_off_host[0] = 0, every length 1..max_pos, every id < vocab).  scores_out[s] (fp32, device) = sum over t = 1..n-1 of
@@ -685,8 +688,8 @@ typedef struct {
   int32_t* ids_host;  /* HOST [cap]: the cached chain */
   int cap, n;         /* capacity; positions held -- n is updated by the call */
 } b2t_clm_cache_t;
-/* Bytes of b2t_clm_cache_t.kv for `cap` positions: n_layers * cap * 2 * d_model * 2 (0 if invalid: null model, cap < 1,
- * cap > max_pos, n_layers < 1). */
+/* Bytes of b2t_clm_cache_t.kv for `cap` positions: n_layers * cap * 2 * d_model * 2 (0 if invalid: null model or bad dimensions,
+ * cap < 1, cap > max_pos, n_layers < 1). */
 size_t b2t_clm_cache_kv_bytes(const b2t_clm_t* model, int cap);
 /* HOST function (no GPU): the rule above for a cached chain cache_ids_host[0..cache_n) of capacity cap and a packed list.
  * Every output is optional: *trunk = Tn, *common = P, *reused = R, *n_nodes = the tree plan's nodes, *n_rows = n_nodes - R

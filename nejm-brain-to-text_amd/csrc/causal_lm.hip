@@ -25,8 +25,9 @@
 //
 // The host-side pieces the other paths (causal_lm_tree.hip, causal_lm_cache.hip, causal_lm_llama.hip) reuse -- launch_gemm,
 // the embed / LayerNorm / attention / head launchers, clm_check_model, the list check, the workspace layout and the flat
-// index builder -- have external linkage and are declared in clm_internal.h, which also holds the layer loop (clm_forward)
-// and the body of the flat entry point (clm_score_flat; GPT-2, causal_lm_gpt2.hip, enters it with its own fc1 launcher).
+// index builder -- have external linkage and are declared in clm_internal.h, which also holds the layer loop (clm_forward),
+// this descriptor's family (OptFamily) and the bodies of the entry points and the size rules of every family (GPT-2,
+// causal_lm_gpt2.hip, enters them with a policy of its own for the fc1 launcher).
 // The kernels stay private to this file: the GEMM's template is clm_gemm.h, instantiated here for the four epilogues of this
 // forward; the attention's arithmetic and clm_attn_kernel itself are clm_attn.h's templates (instantiated here in fp16 for
 // head dims 64, 80 and 128, behind clm_launch_attn), and the kernel serves the Llama family's row layout too.
@@ -132,22 +133,15 @@ __global__ __launch_bounds__(64) void clm_seq_sum_kernel(const float* logp, cons
 }  // namespace
 
 int clm_check_model(const b2t_clm_t* m) {
-  B2T_REQUIRE(m, "b2t_clm: null model");
-  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 && m->max_pos > 0,
-              "b2t_clm: bad dimensions (layers %d, d %d, heads %d, ffn %d, vocab %d, max_pos %d)", m->n_layers, m->d_model,
-              m->n_heads, m->ffn_dim, m->vocab, m->max_pos);
-  B2T_REQUIRE(m->d_model % m->n_heads == 0, "b2t_clm: d_model %d is not a multiple of n_heads %d", m->d_model, m->n_heads);
+  const char* pre = "b2t_clm";
+  if (int rc = clm_check_mha_dims(pre, m)) return rc;
   const int hd = m->d_model / m->n_heads;
   B2T_REQUIRE(hd == 64 || hd == 80 || hd == 128, "b2t_clm: unsupported head dim %d (64, 80 or 128)", hd);
-  B2T_REQUIRE(m->d_model % 64 == 0 && m->ffn_dim % 64 == 0, "b2t_clm: d_model %d and ffn_dim %d must be multiples of 64",
-              m->d_model, m->ffn_dim);
+  if (int rc = clm_check_mult64(pre, m->d_model, m->ffn_dim)) return rc;
   B2T_REQUIRE(m->embed_tokens && m->embed_positions && m->final_ln_w && m->final_ln_b && (m->n_layers == 0 || m->layers_host),
               "b2t_clm: null weight pointer");
-  for (int l = 0; l < m->n_layers; ++l) {
-    const b2t_clm_layer_t& w = m->layers_host[l];
-    B2T_REQUIRE(w.ln1_w && w.ln1_b && w.qkv_w && w.qkv_b && w.out_w && w.out_b && w.ln2_w && w.ln2_b && w.fc1_w && w.fc1_b &&
-                w.fc2_w && w.fc2_b, "b2t_clm: null weight pointer in layer %d", l);
-  }
+  for (int l = 0; l < m->n_layers; ++l)
+    if (int rc = clm_check_mha_layer(pre, m->layers_host[l], l)) return rc;
   return 0;
 }
 
@@ -258,12 +252,11 @@ int clm_build_flat_index(const char* what, const int32_t* ids, const int32_t* se
 using namespace b2t;
 
 extern "C" size_t b2t_clm_ws_bytes(const b2t_clm_t* model, long long n_tokens, int n_seq) {
-  if (!model || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return clm_opt_layout(model, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq)).total;
+  return clm_family_ws_bytes<OptFamily>(model, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                  float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  return clm_score_flat("b2t_clm_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws, ws_bytes,
-                        as_stream(stream), &launch_gemm<EP_RELU>);
+  return clm_family_score<OptPolicy, OptFamily>("b2t_clm_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
+                                                ws, ws_bytes, stream);
 }

@@ -173,8 +173,7 @@ int clm_launch_seq_sum_tree_cached(const float* logp, const float* cache_logp, i
 using namespace b2t;
 
 extern "C" size_t b2t_clm_cache_kv_bytes(const b2t_clm_t* model, int cap) {
-  if (!model || cap < 1 || cap > model->max_pos || model->n_layers < 1 || model->d_model < 1) return 0;
-  return (size_t)model->n_layers * (size_t)cap * 2 * (size_t)model->d_model * sizeof(_Float16);
+  return clm_family_cache_kv_bytes<OptFamily>(model, cap);
 }
 
 extern "C" int b2t_clm_cache_plan_host(const int32_t* cache_ids_host, int cache_n, int cap, const int32_t* ids_host,
@@ -200,20 +199,13 @@ extern "C" int b2t_clm_cache_plan_host(const int32_t* cache_ids_host, int cache_
 }
 
 extern "C" size_t b2t_clm_tree_cached_ws_bytes(const b2t_clm_t* model, long long n_rows, long long n_tokens, int n_seq) {
-  if (!model || n_rows < 1 || n_rows > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  const size_t tree = clm_opt_layout(model, n_rows, n_rows, tree_ints(n_rows, n_tokens, n_seq)).total;
-  return clm_cached_state(tree, n_rows, model->n_heads, model->d_model).total;
+  return clm_family_tree_cached_ws_bytes<OptFamily>(model, n_rows, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache, int update, const int32_t* ids_host,
                                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                              long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = clm_check_model(model)) return rc;
-  const b2t_clm_t& m = *model;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_heads, m.d_model / m.n_heads};
-  return clm_score_tree_cached(
-      "b2t_clm_score_tree_cached_f16", "b2t_clm_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq, scores_out,
-      tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return clm_opt_layout(model, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) { return clm_forward(m, r, L, base, attn, s); });
+  return clm_family_score_tree_cached<OptPolicy, OptFamily>("b2t_clm_score_tree_cached_f16", "b2t_clm_score_tree_f16", model, cache,
+                                                            update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
+                                                            n_rows_out, n_reused_out, ws, ws_bytes, stream);
 }

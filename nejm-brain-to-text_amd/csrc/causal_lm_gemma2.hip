@@ -49,7 +49,7 @@
 //
 // This unit instantiates the three GEMM epilogues (on both tiles), the three kernels of clm_gemma2.h and the capped flat and tree
 // attention, in both element types, and the capped cached and trunk attention in fp16; the QKV and the uncapped head GEMM are
-// reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's under Gemma2Family.  The
+// reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_internal.h's under Gemma2Family.  The
 // workspace is gemma2_layout (clm_gemma2.h).
 #include "clm_attn.h"
 #include "clm_gemma2.h"
@@ -137,56 +137,57 @@ int clm_gemma2_check_model(const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2)
 using namespace b2t;
 
 extern "C" size_t b2t_clm_gemma2_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_tokens, int n_seq) {
-  return llama_ws_bytes<Gemma2Family>(model, n_tokens, n_seq, g2);
+  return clm_family_ws_bytes<Gemma2Family>(model, n_tokens, n_seq, g2);
 }
 
 extern "C" size_t b2t_clm_gemma2_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_nodes,
                                                long long n_tokens, int n_seq) {
-  return llama_tree_ws_bytes<Gemma2Family>(model, n_nodes, n_tokens, n_seq, g2);
+  return clm_family_tree_ws_bytes<Gemma2Family>(model, n_nodes, n_tokens, n_seq, g2);
 }
 
 extern "C" size_t b2t_clm_gemma2_cache_kv_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, int cap) {
-  return llama_cache_kv_bytes<Gemma2Family>(model, cap, g2);
+  return clm_family_cache_kv_bytes<Gemma2Family>(model, cap, g2);
 }
 
 extern "C" size_t b2t_clm_gemma2_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, long long n_rows,
                                                       long long n_tokens, int n_seq) {
-  return llama_tree_cached_ws_bytes<Gemma2Family>(model, n_rows, n_tokens, n_seq, g2);
+  return clm_family_tree_cached_ws_bytes<Gemma2Family>(model, n_rows, n_tokens, n_seq, g2);
 }
 
 extern "C" int b2t_clm_gemma2_score_f16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
                                         const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                         size_t ws_bytes, void* stream) {
-  return llama_score<Gemma2F16, Gemma2Family>("b2t_clm_gemma2_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                              tok_logp_out, ws, ws_bytes, stream, g2);
+  return clm_family_score<Gemma2F16, Gemma2Family>("b2t_clm_gemma2_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                   tok_logp_out, ws, ws_bytes, stream, g2);
 }
 
 extern "C" int b2t_clm_gemma2_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
                                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                              long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<Gemma2F16, Gemma2Family>("b2t_clm_gemma2_score_tree_f16", model, ids_host, seq_off_host, n_seq,
-                                                   scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, g2);
+  return clm_family_score_tree<Gemma2F16, Gemma2Family>("b2t_clm_gemma2_score_tree_f16", model, ids_host, seq_off_host, n_seq,
+                                                        scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, g2);
 }
 
 extern "C" int b2t_clm_gemma2_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, b2t_clm_cache_t* cache,
                                                     int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                     float* scores_out, float* tok_logp_out, long long* n_rows_out,
                                                     int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree_cached<Gemma2F16, Gemma2Family>("b2t_clm_gemma2_score_tree_cached_f16", "b2t_clm_gemma2_score_tree_f16", model,
-                                                          cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-                                                          n_rows_out, n_reused_out, ws, ws_bytes, stream, g2);
+  return clm_family_score_tree_cached<Gemma2F16, Gemma2Family>("b2t_clm_gemma2_score_tree_cached_f16",
+                                                               "b2t_clm_gemma2_score_tree_f16", model, cache, update, ids_host,
+                                                               seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out,
+                                                               n_reused_out, ws, ws_bytes, stream, g2);
 }
 
 extern "C" int b2t_clm_gemma2_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
                                          const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                          size_t ws_bytes, void* stream) {
-  return llama_score<Gemma2Bf16, Gemma2Family>("b2t_clm_gemma2_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                               tok_logp_out, ws, ws_bytes, stream, g2);
+  return clm_family_score<Gemma2Bf16, Gemma2Family>("b2t_clm_gemma2_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                    tok_logp_out, ws, ws_bytes, stream, g2);
 }
 
 extern "C" int b2t_clm_gemma2_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_gemma2_t* g2, const int32_t* ids_host,
                                               const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                               long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<Gemma2Bf16, Gemma2Family>("b2t_clm_gemma2_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
-                                                    scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, g2);
+  return clm_family_score_tree<Gemma2Bf16, Gemma2Family>("b2t_clm_gemma2_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
+                                                         scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, g2);
 }

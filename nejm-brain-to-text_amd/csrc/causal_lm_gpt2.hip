@@ -14,15 +14,21 @@
 // result depends on that row alone and on neither the tile nor the batch: flat, tree and cached calls are bit-identical.
 //
 // This unit instantiates that one epilogue in fp16, on both tiles, and nothing else: the forward is clm_forward and the entry
-// points' bodies are clm_score_flat / clm_score_tree / clm_score_tree_cached (clm_internal.h) with this unit's fc1 launcher,
-// which goes through the one tile rule (launch_gemm of causal_lm.hip).  The model is b2t_clm_t, the cache b2t_clm_cache_t, and
-// the sizes are the OPT size functions'.
+// points' bodies are every family's (clm_internal.h) under OptFamily and a policy with this unit's fc1 launcher, which goes
+// through the one tile rule (launch_gemm of causal_lm.hip).  The model is b2t_clm_t, the cache b2t_clm_cache_t, and the sizes
+// are the OPT size functions'.
 #include "clm_gemm.h"
 
 namespace b2t {
 namespace {
 
 int gpt2_fc1(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_GELU>); }
+
+// the policy of OptFamily (clm_internal.h) with gelu_new in the fc1 GEMM's epilogue
+struct Gpt2Policy {
+  using E = _Float16;
+  static constexpr ClmGemmLaunch fc1 = &gpt2_fc1;
+};
 
 }  // namespace
 
@@ -34,29 +40,22 @@ using namespace b2t;
 
 extern "C" int b2t_clm_gpt2_score_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                       float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  return clm_score_flat("b2t_clm_gpt2_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws, ws_bytes,
-                        as_stream(stream), &gpt2_fc1);
+  return clm_family_score<Gpt2Policy, OptFamily>("b2t_clm_gpt2_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                 tok_logp_out, ws, ws_bytes, stream);
 }
 
 extern "C" int b2t_clm_gpt2_score_tree_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                            float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws,
                                            size_t ws_bytes, void* stream) {
-  return clm_score_tree("b2t_clm_gpt2_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-                        n_nodes_out, ws, ws_bytes, as_stream(stream), &gpt2_fc1);
+  return clm_family_score_tree<Gpt2Policy, OptFamily>("b2t_clm_gpt2_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                      tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
 }
 
 extern "C" int b2t_clm_gpt2_score_tree_cached_f16(const b2t_clm_t* model, b2t_clm_cache_t* cache, int update,
                                                   const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                   float* scores_out, float* tok_logp_out, long long* n_rows_out,
                                                   int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = clm_check_model(model)) return rc;
-  const b2t_clm_t& m = *model;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_heads, m.d_model / m.n_heads};
-  return clm_score_tree_cached(
-      "b2t_clm_gpt2_score_tree_cached_f16", "b2t_clm_gpt2_score_tree_f16", dims, cache, update, ids_host, seq_off_host, n_seq,
-      scores_out, tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, as_stream(stream),
-      [&](long long rows, size_t ints) { return clm_opt_layout(model, rows, rows, ints); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
-        return clm_forward(m, r, L, base, attn, s, &gpt2_fc1);
-      });
+  return clm_family_score_tree_cached<Gpt2Policy, OptFamily>("b2t_clm_gpt2_score_tree_cached_f16", "b2t_clm_gpt2_score_tree_f16", model,
+                                                             cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
+                                                             n_rows_out, n_reused_out, ws, ws_bytes, stream);
 }

@@ -36,7 +36,7 @@
 // This unit instantiates the two grouped GEMMs (on both tiles), the router kernel, the plan, gather and combine kernels and the
 // two attention kernels (through GptOssOps<E>, clm_gptoss.h), in both element types where they depend on it, and nothing else:
 // every other kernel is reached through LlamaShared<E>, the flat and the tree entry-point body and the two size rules are
-// clm_llama.h's under GptOssFamily.  There is no cached call: the cached and trunk
+// clm_internal.h's under GptOssFamily.  There is no cached call: the cached and trunk
 // attention kernels have neither sink nor window.
 #include "clm_attn.h"
 #include "clm_gptoss.h"
@@ -88,38 +88,38 @@ int clm_gptoss_check_model(const b2t_clm_llama_t* m, const b2t_clm_gptoss_t* g) 
 using namespace b2t;
 
 extern "C" size_t b2t_clm_gptoss_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_tokens, int n_seq) {
-  return llama_ws_bytes<GptOssFamily>(model, n_tokens, n_seq, oss);
+  return clm_family_ws_bytes<GptOssFamily>(model, n_tokens, n_seq, oss);
 }
 
 extern "C" size_t b2t_clm_gptoss_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, long long n_nodes,
                                                long long n_tokens, int n_seq) {
-  return llama_tree_ws_bytes<GptOssFamily>(model, n_nodes, n_tokens, n_seq, oss);
+  return clm_family_tree_ws_bytes<GptOssFamily>(model, n_nodes, n_tokens, n_seq, oss);
 }
 
 extern "C" int b2t_clm_gptoss_score_f16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
                                         const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                         size_t ws_bytes, void* stream) {
-  return llama_score<GptOssF16, GptOssFamily>("b2t_clm_gptoss_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                              tok_logp_out, ws, ws_bytes, stream, oss);
+  return clm_family_score<GptOssF16, GptOssFamily>("b2t_clm_gptoss_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                   tok_logp_out, ws, ws_bytes, stream, oss);
 }
 
 extern "C" int b2t_clm_gptoss_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
                                              const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                              long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<GptOssF16, GptOssFamily>("b2t_clm_gptoss_score_tree_f16", model, ids_host, seq_off_host, n_seq,
-                                                   scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, oss);
+  return clm_family_score_tree<GptOssF16, GptOssFamily>("b2t_clm_gptoss_score_tree_f16", model, ids_host, seq_off_host, n_seq,
+                                                        scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, oss);
 }
 
 extern "C" int b2t_clm_gptoss_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
                                          const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                          size_t ws_bytes, void* stream) {
-  return llama_score<GptOssBf16, GptOssFamily>("b2t_clm_gptoss_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                               tok_logp_out, ws, ws_bytes, stream, oss);
+  return clm_family_score<GptOssBf16, GptOssFamily>("b2t_clm_gptoss_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                    tok_logp_out, ws, ws_bytes, stream, oss);
 }
 
 extern "C" int b2t_clm_gptoss_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_gptoss_t* oss, const int32_t* ids_host,
                                               const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                               long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<GptOssBf16, GptOssFamily>("b2t_clm_gptoss_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
-                                                    scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, oss);
+  return clm_family_score_tree<GptOssBf16, GptOssFamily>("b2t_clm_gptoss_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
+                                                         scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, oss);
 }

@@ -29,7 +29,7 @@ struct GptOssMxPolicy : LlamaShared<El>, MoeOps<El>, GptOssOps<El> {
   static int gemm_experts_f32b(const ClmGemm& g, hipStream_t s) { return launch_gemm(g, s, &clm_gemm_tiles<EP_F32_BIAS, El, true, true>); }
 };
 
-// what the entry-point bodies of clm_llama.h carry beside the model: the gpt-oss descriptor and the packed experts
+// what the entry-point bodies of clm_internal.h carry beside the model: the gpt-oss descriptor and the packed experts
 struct GptOssMxArg {
   const b2t_clm_gptoss_t* g;
   const b2t_clm_gptoss_mx_t* mx;
@@ -73,7 +73,8 @@ int mx_score(const char* who, const b2t_clm_llama_t* model, const b2t_clm_gptoss
   b2t_clm_llama_t m;
   if (int rc = mx_model(who, model, mx, layers, &m)) return rc;
   const GptOssMxArg x{oss, mx};
-  return llama_score<P, GptOssMxFamily>(who, &m, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws, ws_bytes, stream, &x);
+  return clm_family_score<P, GptOssMxFamily>(who, &m, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws, ws_bytes, stream,
+                                             &x);
 }
 
 template <class P>
@@ -84,8 +85,8 @@ int mx_score_tree(const char* who, const b2t_clm_llama_t* model, const b2t_clm_g
   b2t_clm_llama_t m;
   if (int rc = mx_model(who, model, mx, layers, &m)) return rc;
   const GptOssMxArg x{oss, mx};
-  return llama_score_tree<P, GptOssMxFamily>(who, &m, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_nodes_out, ws,
-                                             ws_bytes, stream, &x);
+  return clm_family_score_tree<P, GptOssMxFamily>(who, &m, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_nodes_out, ws,
+                                                  ws_bytes, stream, &x);
 }
 
 // packed rows to dense ones: a thread expands one piece of eight elements, the GEMM's unit, with the GEMM's function

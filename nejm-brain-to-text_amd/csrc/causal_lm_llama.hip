@@ -27,8 +27,8 @@
 // of 32, and for head dim 128 the q / k rows of each head in the order [0..31, 64..95, 32..63, 96..127] (q . k is invariant
 // under one permutation of both; V and o_proj are untouched).
 //
-// The forward (llama_forward), the bodies of the flat, the tree and the cached entry point, the size rules and the embed /
-// RMSNorm kernels are templates in clm_llama.h, on a per-element-type policy and a family; this unit holds the fp16 launches of
+// The forward (llama_forward) and the embed / RMSNorm kernels are templates in clm_llama.h, the bodies of the flat, the tree and
+// the cached entry point and the size rules in clm_internal.h, on a per-element-type policy and a family; this unit holds the fp16 launches of
 // the Llama policy (LlamaShared<_Float16>: the two GEMM launches of this family through the one tile rule, the OPT paths'
 // residual / head GEMMs and attention launchers, embed and RMSNorm), which every other family's fp16 policy shares, and the
 // model check.  The same forward in bf16 is causal_lm_llama_bf16.hip; Qwen3's, which norms the q and k heads in the QKV GEMM's
@@ -87,40 +87,40 @@ using namespace b2t;
 using LlamaF = LlamaPolicy<_Float16>;
 
 extern "C" size_t b2t_clm_llama_ws_bytes(const b2t_clm_llama_t* model, long long n_tokens, int n_seq) {
-  return llama_ws_bytes<LlamaFamily>(model, n_tokens, n_seq);
+  return clm_family_ws_bytes<LlamaFamily>(model, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_llama_score_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                        int n_seq, float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes,
                                        void* stream) {
-  return llama_score<LlamaF>("b2t_clm_llama_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws,
-                             ws_bytes, stream);
+  return clm_family_score<LlamaF, LlamaFamily>("b2t_clm_llama_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                               tok_logp_out, ws, ws_bytes, stream);
 }
 
 extern "C" size_t b2t_clm_llama_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq) {
-  return llama_tree_ws_bytes<LlamaFamily>(model, n_nodes, n_tokens, n_seq);
+  return clm_family_tree_ws_bytes<LlamaFamily>(model, n_nodes, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_llama_score_tree_f16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                             int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws,
                                             size_t ws_bytes, void* stream) {
-  return llama_score_tree<LlamaF>("b2t_clm_llama_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-                                  n_nodes_out, ws, ws_bytes, stream);
+  return clm_family_score_tree<LlamaF, LlamaFamily>("b2t_clm_llama_score_tree_f16", model, ids_host, seq_off_host, n_seq,
+                                                    scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
 }
 
 extern "C" size_t b2t_clm_llama_cache_kv_bytes(const b2t_clm_llama_t* model, int cap) {
-  return llama_cache_kv_bytes<LlamaFamily>(model, cap);
+  return clm_family_cache_kv_bytes<LlamaFamily>(model, cap);
 }
 
 extern "C" size_t b2t_clm_llama_tree_cached_ws_bytes(const b2t_clm_llama_t* model, long long n_rows, long long n_tokens, int n_seq) {
-  return llama_tree_cached_ws_bytes<LlamaFamily>(model, n_rows, n_tokens, n_seq);
+  return clm_family_tree_cached_ws_bytes<LlamaFamily>(model, n_rows, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_llama_score_tree_cached_f16(const b2t_clm_llama_t* model, b2t_clm_cache_t* cache, int update,
                                                    const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                    float* scores_out, float* tok_logp_out, long long* n_rows_out,
                                                    int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree_cached<LlamaF>("b2t_clm_llama_score_tree_cached_f16", "b2t_clm_llama_score_tree_f16", model, cache, update,
-                                         ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out, n_reused_out, ws,
-                                         ws_bytes, stream);
+  return clm_family_score_tree_cached<LlamaF, LlamaFamily>("b2t_clm_llama_score_tree_cached_f16", "b2t_clm_llama_score_tree_f16",
+                                                           model, cache, update, ids_host, seq_off_host, n_seq, scores_out,
+                                                           tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, stream);
 }

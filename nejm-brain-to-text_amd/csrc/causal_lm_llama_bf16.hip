@@ -70,13 +70,14 @@ using namespace b2t;
 extern "C" int b2t_clm_llama_score_bf16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                         int n_seq, float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes,
                                         void* stream) {
-  return llama_score<LlamaPolicy<__bf16>>("b2t_clm_llama_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-                                          ws, ws_bytes, stream);
+  return clm_family_score<LlamaPolicy<__bf16>, LlamaFamily>("b2t_clm_llama_score_bf16", model, ids_host, seq_off_host, n_seq,
+                                                            scores_out, tok_logp_out, ws, ws_bytes, stream);
 }
 
 extern "C" int b2t_clm_llama_score_tree_bf16(const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
                                              int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws,
                                              size_t ws_bytes, void* stream) {
-  return llama_score_tree<LlamaPolicy<__bf16>>("b2t_clm_llama_score_tree_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                               tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
+  return clm_family_score_tree<LlamaPolicy<__bf16>, LlamaFamily>("b2t_clm_llama_score_tree_bf16", model, ids_host, seq_off_host,
+                                                                 n_seq, scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes,
+                                                                 stream);
 }

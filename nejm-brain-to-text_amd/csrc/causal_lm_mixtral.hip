@@ -30,7 +30,7 @@
 // reads the routing back; both tiles are served through the one tile rule launch_gemm, on a grid sized for S rows.
 //
 // This unit instantiates the two grouped GEMMs (on both tiles) and the kernels of clm_moe.h, in both element types, and nothing
-// else: every other kernel is reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's
+// else: every other kernel is reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_internal.h's
 // under MixtralFamily.  The workspace is the Llama layout with an empty hbuf plus one region behind it (mixtral_layout,
 // clm_moe.h); the cache's size is the Llama family's, which is why this unit exports no cache_kv_bytes.
 #include "clm_moe.h"
@@ -53,52 +53,53 @@ using MixtralBf16 = MixtralPolicy<__bf16>;
 using namespace b2t;
 
 extern "C" size_t b2t_clm_mixtral_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_tokens, int n_seq) {
-  return llama_ws_bytes<MixtralFamily>(model, n_tokens, n_seq, moe);
+  return clm_family_ws_bytes<MixtralFamily>(model, n_tokens, n_seq, moe);
 }
 
 extern "C" size_t b2t_clm_mixtral_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_nodes,
                                                 long long n_tokens, int n_seq) {
-  return llama_tree_ws_bytes<MixtralFamily>(model, n_nodes, n_tokens, n_seq, moe);
+  return clm_family_tree_ws_bytes<MixtralFamily>(model, n_nodes, n_tokens, n_seq, moe);
 }
 
 extern "C" size_t b2t_clm_mixtral_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, long long n_rows,
                                                        long long n_tokens, int n_seq) {
-  return llama_tree_cached_ws_bytes<MixtralFamily>(model, n_rows, n_tokens, n_seq, moe);
+  return clm_family_tree_cached_ws_bytes<MixtralFamily>(model, n_rows, n_tokens, n_seq, moe);
 }
 
 extern "C" int b2t_clm_mixtral_score_f16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
                                          const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                          size_t ws_bytes, void* stream) {
-  return llama_score<MixtralF16, MixtralFamily>("b2t_clm_mixtral_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                                tok_logp_out, ws, ws_bytes, stream, moe);
+  return clm_family_score<MixtralF16, MixtralFamily>("b2t_clm_mixtral_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                     tok_logp_out, ws, ws_bytes, stream, moe);
 }
 
 extern "C" int b2t_clm_mixtral_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
                                               const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                               long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<MixtralF16, MixtralFamily>("b2t_clm_mixtral_score_tree_f16", model, ids_host, seq_off_host, n_seq,
-                                                     scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, moe);
+  return clm_family_score_tree<MixtralF16, MixtralFamily>("b2t_clm_mixtral_score_tree_f16", model, ids_host, seq_off_host, n_seq,
+                                                          scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, moe);
 }
 
 extern "C" int b2t_clm_mixtral_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, b2t_clm_cache_t* cache,
                                                      int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                      float* scores_out, float* tok_logp_out, long long* n_rows_out,
                                                      int* n_reused_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree_cached<MixtralF16, MixtralFamily>("b2t_clm_mixtral_score_tree_cached_f16", "b2t_clm_mixtral_score_tree_f16",
-                                                            model, cache, update, ids_host, seq_off_host, n_seq, scores_out,
-                                                            tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, stream, moe);
+  return clm_family_score_tree_cached<MixtralF16, MixtralFamily>("b2t_clm_mixtral_score_tree_cached_f16",
+                                                                 "b2t_clm_mixtral_score_tree_f16", model, cache, update, ids_host,
+                                                                 seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out,
+                                                                 n_reused_out, ws, ws_bytes, stream, moe);
 }
 
 extern "C" int b2t_clm_mixtral_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
                                           const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                           size_t ws_bytes, void* stream) {
-  return llama_score<MixtralBf16, MixtralFamily>("b2t_clm_mixtral_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                                 tok_logp_out, ws, ws_bytes, stream, moe);
+  return clm_family_score<MixtralBf16, MixtralFamily>("b2t_clm_mixtral_score_bf16", model, ids_host, seq_off_host, n_seq,
+                                                      scores_out, tok_logp_out, ws, ws_bytes, stream, moe);
 }
 
 extern "C" int b2t_clm_mixtral_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_moe_t* moe, const int32_t* ids_host,
                                                const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                                long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<MixtralBf16, MixtralFamily>("b2t_clm_mixtral_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
-                                                      scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, moe);
+  return clm_family_score_tree<MixtralBf16, MixtralFamily>("b2t_clm_mixtral_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
+                                                           scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, moe);
 }

@@ -32,7 +32,7 @@
 // in checkpoint order (no head_dim_perm); gate / up rows are interleaved as for Llama.
 //
 // This unit instantiates the two epilogues (on both tiles) and the two kernels, in both element types, and nothing else:
-// every other kernel is reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's under
+// every other kernel is reached through LlamaShared<E>, the three entry-point bodies and the size rules are clm_internal.h's under
 // Olmo2Family.  The workspace is the Llama layout plus one fp32 region [padded rows][(Hq + Hkv) hd] behind it (olmo2_layout,
 // clm_olmo2.h); the cache's size is the Llama family's.
 #include "clm_olmo2.h"
@@ -54,34 +54,34 @@ using Olmo2Bf16 = Olmo2Policy<__bf16>;
 using namespace b2t;
 
 extern "C" size_t b2t_clm_olmo2_ws_bytes(const b2t_clm_llama_t* model, long long n_tokens, int n_seq) {
-  return llama_ws_bytes<Olmo2Family>(model, n_tokens, n_seq);
+  return clm_family_ws_bytes<Olmo2Family>(model, n_tokens, n_seq);
 }
 
 extern "C" size_t b2t_clm_olmo2_tree_ws_bytes(const b2t_clm_llama_t* model, long long n_nodes, long long n_tokens, int n_seq) {
-  return llama_tree_ws_bytes<Olmo2Family>(model, n_nodes, n_tokens, n_seq);
+  return clm_family_tree_ws_bytes<Olmo2Family>(model, n_nodes, n_tokens, n_seq);
 }
 
 extern "C" size_t b2t_clm_olmo2_cache_kv_bytes(const b2t_clm_llama_t* model, int cap) {
-  return llama_cache_kv_bytes<Olmo2Family>(model, cap);
+  return clm_family_cache_kv_bytes<Olmo2Family>(model, cap);
 }
 
 extern "C" size_t b2t_clm_olmo2_tree_cached_ws_bytes(const b2t_clm_llama_t* model, long long n_rows, long long n_tokens, int n_seq) {
-  return llama_tree_cached_ws_bytes<Olmo2Family>(model, n_rows, n_tokens, n_seq);
+  return clm_family_tree_cached_ws_bytes<Olmo2Family>(model, n_rows, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_olmo2_score_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                        const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                        float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score<Olmo2F16, Olmo2Family>("b2t_clm_olmo2_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                            tok_logp_out, ws, ws_bytes, stream, qk_norm_host);
+  return clm_family_score<Olmo2F16, Olmo2Family>("b2t_clm_olmo2_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                 tok_logp_out, ws, ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_olmo2_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                             const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                             float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                                             void* stream) {
-  return llama_score_tree<Olmo2F16, Olmo2Family>("b2t_clm_olmo2_score_tree_f16", model, ids_host, seq_off_host, n_seq,
-                                                 scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
+  return clm_family_score_tree<Olmo2F16, Olmo2Family>("b2t_clm_olmo2_score_tree_f16", model, ids_host, seq_off_host, n_seq,
+                                                      scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_olmo2_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
@@ -89,22 +89,23 @@ extern "C" int b2t_clm_olmo2_score_tree_cached_f16(const b2t_clm_llama_t* model,
                                                    const int32_t* seq_off_host, int n_seq, float* scores_out,
                                                    float* tok_logp_out, long long* n_rows_out, int* n_reused_out, void* ws,
                                                    size_t ws_bytes, void* stream) {
-  return llama_score_tree_cached<Olmo2F16, Olmo2Family>("b2t_clm_olmo2_score_tree_cached_f16", "b2t_clm_olmo2_score_tree_f16", model,
-                                                        cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-                                                        n_rows_out, n_reused_out, ws, ws_bytes, stream, qk_norm_host);
+  return clm_family_score_tree_cached<Olmo2F16, Olmo2Family>("b2t_clm_olmo2_score_tree_cached_f16", "b2t_clm_olmo2_score_tree_f16",
+                                                             model, cache, update, ids_host, seq_off_host, n_seq, scores_out,
+                                                             tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, stream,
+                                                             qk_norm_host);
 }
 
 extern "C" int b2t_clm_olmo2_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                         const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                         float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score<Olmo2Bf16, Olmo2Family>("b2t_clm_olmo2_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                             tok_logp_out, ws, ws_bytes, stream, qk_norm_host);
+  return clm_family_score<Olmo2Bf16, Olmo2Family>("b2t_clm_olmo2_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                  tok_logp_out, ws, ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_olmo2_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                              const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                              float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                                              void* stream) {
-  return llama_score_tree<Olmo2Bf16, Olmo2Family>("b2t_clm_olmo2_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
-                                                  scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
+  return clm_family_score_tree<Olmo2Bf16, Olmo2Family>("b2t_clm_olmo2_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
+                                                       scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
 }

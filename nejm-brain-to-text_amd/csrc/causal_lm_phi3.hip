@@ -36,7 +36,7 @@
 // This unit instantiates the EP_QKV_F32 epilogue (on both tiles), the rotation kernel and the flat and tree attention at head
 // dim 96, in both element types, and the cached and trunk attention at 96 in fp16 (behind clm_launch_attn_cached of
 // causal_lm_cache.hip, which hands head dim 96 to clm_launch_attn_cached_96 below); every other kernel is reached through
-// LlamaShared<E>, the three entry-point bodies and the size rules are clm_llama.h's under Phi3Family.  No kernel
+// LlamaShared<E>, the three entry-point bodies and the size rules are clm_internal.h's under Phi3Family.  No kernel
 // here uses scratch (tests/test_clm_phi3_host.py checks it).  The workspace is phi3_layout (clm_phi3.h).
 #include "clm_attn.h"
 #include "clm_phi3.h"
@@ -107,56 +107,56 @@ int clm_phi3_check(const char* who, const b2t_clm_llama_t* m, const b2t_clm_phi3
 using namespace b2t;
 
 extern "C" size_t b2t_clm_phi3_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_tokens, int n_seq) {
-  return llama_ws_bytes<Phi3Family>(model, n_tokens, n_seq, phi3);
+  return clm_family_ws_bytes<Phi3Family>(model, n_tokens, n_seq, phi3);
 }
 
 extern "C" size_t b2t_clm_phi3_tree_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_nodes,
                                              long long n_tokens, int n_seq) {
-  return llama_tree_ws_bytes<Phi3Family>(model, n_nodes, n_tokens, n_seq, phi3);
+  return clm_family_tree_ws_bytes<Phi3Family>(model, n_nodes, n_tokens, n_seq, phi3);
 }
 
 extern "C" size_t b2t_clm_phi3_cache_kv_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, int cap) {
-  return llama_cache_kv_bytes<Phi3Family>(model, cap, phi3);
+  return clm_family_cache_kv_bytes<Phi3Family>(model, cap, phi3);
 }
 
 extern "C" size_t b2t_clm_phi3_tree_cached_ws_bytes(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, long long n_rows,
                                                     long long n_tokens, int n_seq) {
-  return llama_tree_cached_ws_bytes<Phi3Family>(model, n_rows, n_tokens, n_seq, phi3);
+  return clm_family_tree_cached_ws_bytes<Phi3Family>(model, n_rows, n_tokens, n_seq, phi3);
 }
 
 extern "C" int b2t_clm_phi3_score_f16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
                                       const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                       size_t ws_bytes, void* stream) {
-  return llama_score<Phi3F16, Phi3Family>("b2t_clm_phi3_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-                                          ws, ws_bytes, stream, phi3);
+  return clm_family_score<Phi3F16, Phi3Family>("b2t_clm_phi3_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                               tok_logp_out, ws, ws_bytes, stream, phi3);
 }
 
 extern "C" int b2t_clm_phi3_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
                                            const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                            long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<Phi3F16, Phi3Family>("b2t_clm_phi3_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                               tok_logp_out, n_nodes_out, ws, ws_bytes, stream, phi3);
+  return clm_family_score_tree<Phi3F16, Phi3Family>("b2t_clm_phi3_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                    tok_logp_out, n_nodes_out, ws, ws_bytes, stream, phi3);
 }
 
 extern "C" int b2t_clm_phi3_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, b2t_clm_cache_t* cache,
                                                   int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                                   float* scores_out, float* tok_logp_out, long long* n_rows_out, int* n_reused_out,
                                                   void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree_cached<Phi3F16, Phi3Family>("b2t_clm_phi3_score_tree_cached_f16", "b2t_clm_phi3_score_tree_f16", model, cache,
-                                                      update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out,
-                                                      n_reused_out, ws, ws_bytes, stream, phi3);
+  return clm_family_score_tree_cached<Phi3F16, Phi3Family>("b2t_clm_phi3_score_tree_cached_f16", "b2t_clm_phi3_score_tree_f16",
+                                                           model, cache, update, ids_host, seq_off_host, n_seq, scores_out,
+                                                           tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, stream, phi3);
 }
 
 extern "C" int b2t_clm_phi3_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
                                        const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out, void* ws,
                                        size_t ws_bytes, void* stream) {
-  return llama_score<Phi3Bf16, Phi3Family>("b2t_clm_phi3_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out,
-                                           ws, ws_bytes, stream, phi3);
+  return clm_family_score<Phi3Bf16, Phi3Family>("b2t_clm_phi3_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                tok_logp_out, ws, ws_bytes, stream, phi3);
 }
 
 extern "C" int b2t_clm_phi3_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_phi3_t* phi3, const int32_t* ids_host,
                                             const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
                                             long long* n_nodes_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score_tree<Phi3Bf16, Phi3Family>("b2t_clm_phi3_score_tree_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                                tok_logp_out, n_nodes_out, ws, ws_bytes, stream, phi3);
+  return clm_family_score_tree<Phi3Bf16, Phi3Family>("b2t_clm_phi3_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
+                                                     scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, phi3);
 }

@@ -15,7 +15,7 @@
 //
 // This unit instantiates that one epilogue, on both tiles and for both element types, and nothing else: the forward is
 // llama_forward (clm_llama.h) under a policy with qk_norm set, every other kernel is reached through LlamaShared<E>, the
-// launches causal_lm_llama.hip and causal_lm_llama_bf16.hip define, the three entry-point bodies are clm_llama.h's under
+// launches causal_lm_llama.hip and causal_lm_llama_bf16.hip define, the three entry-point bodies are clm_internal.h's under
 // LlamaFamily, and the workspace and cache sizes are the Llama size functions'.  For head dim 128 the norm weights are
 // stored in the order of the q / k rows they scale (llm_rescore.head_dim_perm); the mean of squares does not notice.
 #include "clm_llama.h"
@@ -51,16 +51,16 @@ using namespace b2t;
 extern "C" int b2t_clm_qwen3_score_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                        const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                        float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score<Qwen3F16>("b2t_clm_qwen3_score_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws,
-                               ws_bytes, stream, qk_norm_host);
+  return clm_family_score<Qwen3F16, LlamaFamily>("b2t_clm_qwen3_score_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                 tok_logp_out, ws, ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_qwen3_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                             const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                             float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                                             void* stream) {
-  return llama_score_tree<Qwen3F16>("b2t_clm_qwen3_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                    tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
+  return clm_family_score_tree<Qwen3F16, LlamaFamily>("b2t_clm_qwen3_score_tree_f16", model, ids_host, seq_off_host, n_seq,
+                                                      scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_qwen3_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
@@ -68,22 +68,23 @@ extern "C" int b2t_clm_qwen3_score_tree_cached_f16(const b2t_clm_llama_t* model,
                                                    const int32_t* seq_off_host, int n_seq, float* scores_out,
                                                    float* tok_logp_out, long long* n_rows_out, int* n_reused_out, void* ws,
                                                    size_t ws_bytes, void* stream) {
-  return llama_score_tree_cached<Qwen3F16>("b2t_clm_qwen3_score_tree_cached_f16", "b2t_clm_qwen3_score_tree_f16", model, cache, update,
-                                           ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out, n_reused_out, ws,
-                                           ws_bytes, stream, qk_norm_host);
+  return clm_family_score_tree_cached<Qwen3F16, LlamaFamily>("b2t_clm_qwen3_score_tree_cached_f16", "b2t_clm_qwen3_score_tree_f16",
+                                                             model, cache, update, ids_host, seq_off_host, n_seq, scores_out,
+                                                             tok_logp_out, n_rows_out, n_reused_out, ws, ws_bytes, stream,
+                                                             qk_norm_host);
 }
 
 extern "C" int b2t_clm_qwen3_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                         const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                         float* tok_logp_out, void* ws, size_t ws_bytes, void* stream) {
-  return llama_score<Qwen3Bf16>("b2t_clm_qwen3_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, ws,
-                                ws_bytes, stream, qk_norm_host);
+  return clm_family_score<Qwen3Bf16, LlamaFamily>("b2t_clm_qwen3_score_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                  tok_logp_out, ws, ws_bytes, stream, qk_norm_host);
 }
 
 extern "C" int b2t_clm_qwen3_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
                                              const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
                                              float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                                              void* stream) {
-  return llama_score_tree<Qwen3Bf16>("b2t_clm_qwen3_score_tree_bf16", model, ids_host, seq_off_host, n_seq, scores_out,
-                                     tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
+  return clm_family_score_tree<Qwen3Bf16, LlamaFamily>("b2t_clm_qwen3_score_tree_bf16", model, ids_host, seq_off_host, n_seq,
+                                                       scores_out, tok_logp_out, n_nodes_out, ws, ws_bytes, stream, qk_norm_host);
 }

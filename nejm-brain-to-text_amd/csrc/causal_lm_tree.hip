@@ -162,13 +162,12 @@ extern "C" int b2t_clm_tree_plan_host(const int32_t* ids_host, const int32_t* se
 }
 
 extern "C" size_t b2t_clm_tree_ws_bytes(const b2t_clm_t* model, long long n_nodes, long long n_tokens, int n_seq) {
-  if (!model || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return clm_opt_layout(model, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq)).total;
+  return clm_family_tree_ws_bytes<OptFamily>(model, n_nodes, n_tokens, n_seq);
 }
 
 extern "C" int b2t_clm_score_tree_f16(const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
                                       float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
                                       void* stream) {
-  return clm_score_tree("b2t_clm_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_nodes_out, ws,
-                        ws_bytes, as_stream(stream), &launch_gemm<EP_RELU>);
+  return clm_family_score_tree<OptPolicy, OptFamily>("b2t_clm_score_tree_f16", model, ids_host, seq_off_host, n_seq, scores_out,
+                                                     tok_logp_out, n_nodes_out, ws, ws_bytes, stream);
 }

@@ -1,6 +1,6 @@
 // clm_gemma2.h — the Gemma-2 forward (causal_lm_gemma2.hip's header has the contract and the kernel sequence), written once for
 // both element types like clm_olmo2.h: the three kernels Gemma-2 adds, its workspace layout, gemma2_forward and Gemma2Family,
-// which hands them to the entry-point bodies and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E>
+// which hands them to the entry-point bodies and the size rules of clm_internal.h.  A policy P of this forward is LlamaShared<E>
 // (the QKV GEMM with EP_ROPE and the uncapped head GEMM) plus
 //   P::gemm_geglu, P::gemm_f32, P::gemm_head_cap (g, s)   the gate / up GEMM with EP_GEGLU, the o_proj / down GEMM with EP_F32
 //                                                         and the head GEMM with EP_HEAD_CAP
@@ -167,8 +167,11 @@ int gemma2_forward(const b2t_clm_llama_t& m, const b2t_clm_gemma2_t& g2, const C
   return clm_launch_head_combine(g.pmax, g.psum, g.tlogit, g.ncg, reinterpret_cast<float*>(base + L.logp), r.Mh, s);
 }
 
-// what the entry-point bodies and the size rules of clm_llama.h take from this family; the extra argument is the b2t_clm_gemma2_t
+// what the entry-point bodies and the size rules of clm_internal.h take from this family; the extra argument is the b2t_clm_gemma2_t
 struct Gemma2Family {
+  using Model = b2t_clm_llama_t;
+  using Extra = b2t_clm_gemma2_t;
+  static int kv_heads(const b2t_clm_llama_t& m) { return m.n_kv_heads; }
   static int head_dim(const b2t_clm_llama_t&, const b2t_clm_gemma2_t* g2) { return g2->head_dim; }
   static float attn_cap(const b2t_clm_gemma2_t* g2) { return g2->attn_cap; }
   static bool dims_ok(const b2t_clm_llama_t* m, const b2t_clm_gemma2_t* g2) {

@@ -1,7 +1,7 @@
 // clm_gptoss.h — the gpt-oss forward (causal_lm_gptoss.hip's header has the contract and the kernel sequence), written once for
 // both element types like clm_gemma2.h: the router kernel gpt-oss adds, its workspace layout, one layer's routed MLP
 // (gptoss_mlp: plan, gather and combine are clm_moe.h's kernels and region, unchanged), gptoss_forward and GptOssFamily, which
-// hands them to the entry-point bodies and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E> (the QKV
+// hands them to the entry-point bodies and the size rules of clm_internal.h.  A policy P of this forward is LlamaShared<E> (the QKV
 // GEMM with bias and rotation, the o_proj GEMM with bias into the residual, the head, embed, RMSNorm), MoeOps<E> (gather) and
 // GptOssOps<E> (below: the router's launch route_oss, and attn_sink / attn_tree_sink (..., sinks, window, s), the flat and the
 // tree attention with a sink and a window, instantiated by the unit that names the policy) plus
@@ -219,7 +219,7 @@ inline const b2t_clm_gptoss_t* gptoss_of(const b2t_clm_gptoss_t* g) { return g; 
 template <class X>
 const b2t_clm_gptoss_t* gptoss_of(const X* x) { return x->g; }
 
-// what the entry-point bodies and the size rules of clm_llama.h take from this family; the extra argument is the
+// what the entry-point bodies and the size rules of clm_internal.h take from this family; the extra argument is the
 // b2t_clm_gptoss_t, or a record gptoss_of finds it in (causal_lm_gptoss_mx.hip's, whose family takes all but forward from here)
 struct GptOssFamily : LlamaFamilyBase {
   template <class X>

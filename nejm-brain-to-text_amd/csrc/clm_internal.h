@@ -1,17 +1,11 @@
-// clm_internal.h — what the units of the causal-LM forward share (the four fp16 units named below; causal_lm_llama_bf16.hip,
-// the Llama family in bf16, uses the element-type trait ClmElem, ClmGemm, the tile rule, the head and the index builders;
-// causal_lm_qwen3.hip, Qwen3 in both formats, the same and clm_score_tree_cached; causal_lm_gpt2.hip, GPT-2, the OPT forward
-// and entry-point bodies below with its own fc1 GEMM; causal_lm_neox.hip, GPT-NeoX, the launchers, the head, the index builders
-// and clm_score_tree_cached around a forward of its own; causal_lm_olmo2.hip and causal_lm_mixtral.hip, the Llama family's
-// entry-point bodies around a layer of their own).  causal_lm.hip (the flat OPT path) defines the tile rule,
-// the embed / LayerNorm / head / sum launchers, the flat attention kernel behind clm_launch_attn, the workspace layout, the
-// list check and the flat index builder; causal_lm_tree.hip (the shared-prefix tree path) the plan, the tree index builder
-// and the tree attention kernel behind clm_launch_attn_tree; causal_lm_cache.hip (the tree path behind a context cache) and
-// causal_lm_llama.hip (the Llama family, flat, tree and cached) use them.  All attention launchers serve both families: OPT's
-// row q[d] | k[d] | v[d] is the Llama row q[Hq * D] | k[Hkv * D] | v[Hkv * D] with Hkv = Hq.  The kernels stay private to their
-// files (the flat and tree attention kernels and their arithmetic are clm_attn.h's templates, the GEMM's clm_gemm.h's);
-// these are their fp16 launchers, so each is instantiated once.  clm_forward, the OPT layer loop of the flat, tree and cached entry points, and clm_score_tree_cached, the
-// cached entry point of both families behind their model checks, are at the end.
+// clm_internal.h — what the units of the causal-LM forward share, for every family and both element types: the epilogue names
+// and the GEMM's arguments, the declarations of the launchers, the layout, the list check, the plan and the index builders that
+// causal_lm.hip, causal_lm_tree.hip and causal_lm_cache.hip define, the family-independent body of a cached call
+// (clm_score_tree_cached), and at the end the family contract with the bodies of the flat, the tree and the cached entry point and
+// the size rules that every family's exported functions are one call of.  The OPT forward (clm_forward) and its family are
+// here too; GPT-NeoX's is in its unit, the Llama-derived families' are in clm_llama.h and the headers beside it.  This header
+// holds no kernel: kernels stay private to their units (the attention's templates are clm_attn.h's, the GEMM's clm_gemm.h's).  All attention launchers
+// serve every family: OPT's row q[d] | k[d] | v[d] is the Llama row q[Hq * D] | k[Hkv * D] | v[Hkv * D] with Hkv = Hq.
 #pragma once
 #include <math.h>
 #include <string>
@@ -124,6 +118,32 @@ int clm_launch_seq_sum(const float* logp, const int* seq_off, const int* head_of
                        hipStream_t s);
 // dimensions, head dim and weight pointers of a model descriptor (0, or an error with the message set)
 int clm_check_model(const b2t_clm_t* m);
+// The statements the checks of the two descriptors with one head count share (M: b2t_clm_t, clm_check_model, or b2t_clm_neox_t,
+// causal_lm_neox.hip), `pre` being the prefix of their messages; the head-dim set, the extras and the order stay with the check.
+template <class M>
+int clm_check_mha_dims(const char* pre, const M* m) {
+  B2T_REQUIRE(m, "%s: null model", pre);
+  B2T_REQUIRE(m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 && m->max_pos > 0,
+              "%s: bad dimensions (layers %d, d %d, heads %d, ffn %d, vocab %d, max_pos %d)", pre, m->n_layers, m->d_model,
+              m->n_heads, m->ffn_dim, m->vocab, m->max_pos);
+  B2T_REQUIRE(m->d_model % m->n_heads == 0, "%s: d_model %d is not a multiple of n_heads %d", pre, m->d_model, m->n_heads);
+  return 0;
+}
+inline int clm_check_mult64(const char* pre, int d_model, int ffn_dim) {
+  B2T_REQUIRE(d_model % 64 == 0 && ffn_dim % 64 == 0, "%s: d_model %d and ffn_dim %d must be multiples of 64", pre, d_model, ffn_dim);
+  return 0;
+}
+// layer l's twelve pointers
+inline int clm_check_mha_layer(const char* pre, const b2t_clm_layer_t& w, int l) {
+  B2T_REQUIRE(w.ln1_w && w.ln1_b && w.qkv_w && w.qkv_b && w.out_w && w.out_b && w.ln2_w && w.ln2_b && w.fc1_w && w.fc1_b &&
+              w.fc2_w && w.fc2_b, "%s: null weight pointer in layer %d", pre, l);
+  return 0;
+}
+// dimensions such a descriptor must have for the sizes of its layout to mean anything (the full check is the family's check)
+template <class M>
+bool clm_mha_dims_ok(const M* m) {
+  return m && m->n_layers >= 0 && m->d_model > 0 && m->n_heads > 0 && m->ffn_dim > 0 && m->vocab > 0 && m->d_model % m->n_heads == 0;
+}
 
 // ---- sizes ----
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -212,12 +232,11 @@ inline int clm_head(const void* x16, const void* W, int vocab, int d, const ClmR
 }
 
 // The pre-LN OPT forward over r.rows rows up to the per-row log-probs logp[r.Mh] (base + L.logp); attn(layer, qkv, out)
-// enqueues one layer's attention from qkv ([rows][3d]) into out ([rows][d]).  `fc1` launches the fc1 GEMM with the family's
-// activation in its epilogue: OPT's ReLU (the default), or GPT-2's gelu_new (causal_lm_gpt2.hip) -- the families differ in
+// enqueues one layer's attention from qkv ([rows][3d]) into out ([rows][d]).  `fc1` launches the fc1 GEMM with the policy's
+// activation in its epilogue: OPT's ReLU (OptPolicy, below), or GPT-2's gelu_new (causal_lm_gpt2.hip) -- the two differ in
 // nothing else behind the loader.
 template <class Attn>
-int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
-                ClmGemmLaunch fc1 = &launch_gemm<EP_RELU>) {
+int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s, ClmGemmLaunch fc1) {
   const int d = m.d_model, hd = d / m.n_heads, F = m.ffn_dim, M = (int)r.rows;
   float* resid = reinterpret_cast<float*>(base + L.resid);
   _Float16* x16 = reinterpret_cast<_Float16*>(base + L.x16);
@@ -247,56 +266,6 @@ int clm_forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* b
   if (r.Mh <= 0) return 0;
   if (int rc = clm_launch_layernorm(resid, r.d_src, r.Mh, H16(m.final_ln_w), H16(m.final_ln_b), x16, d, s)) return rc;
   return clm_head(x16, H16(m.embed_tokens), m.vocab, d, r, L, base, s);   // the head is tied to embed_tokens
-}
-
-// What the flat and the tree entry point of this forward do behind their names (b2t_clm_score_f16 / b2t_clm_score_tree_f16, and
-// GPT-2's twins with their own fc1): the checks, the index build, the layout, the forward and the sums.  `who` is the entry
-// point's name in every message.
-inline int clm_score_flat(const char* who, const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
-                          float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, hipStream_t s, ClmGemmLaunch fc1) {
-  if (int rc = clm_check_model(model)) return rc;
-  const b2t_clm_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  const ClmLayout L = clm_opt_layout(model, M, M - n_seq, flat_ints(M, n_seq));
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  char* base = static_cast<char*>(ws);
-  ClmFlatIndex ix;
-  const std::string upload = std::string(who) + " upload";
-  if (int rc = clm_build_flat_index(upload.c_str(), ids_host, seq_off_host, n_seq, reinterpret_cast<int*>(base + L.ints), s, &ix))
-    return rc;
-  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
-    return clm_launch_attn(qkv, out, ix.d_soff, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
-  };
-  if (int rc = clm_forward(m, ix.run, L, base, attn, s, fc1)) return rc;
-  return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
-}
-
-inline int clm_score_tree(const char* who, const b2t_clm_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
-                          float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes, hipStream_t s,
-                          ClmGemmLaunch fc1) {
-  if (int rc = clm_check_model(model)) return rc;
-  const b2t_clm_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);
-  const long long Mn = plan.Mn;
-  if (n_nodes_out) *n_nodes_out = Mn;
-  const ClmLayout L = clm_opt_layout(model, Mn, Mn, tree_ints(Mn, M, n_seq));
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  char* base = static_cast<char*>(ws);
-  ClmTreeIndex ix;
-  const std::string upload = std::string(who) + " upload";
-  if (int rc = clm_build_tree_index(upload.c_str(), ids_host, seq_off_host, n_seq, plan, 0, reinterpret_cast<int*>(base + L.ints),
-                                    s, &ix))
-    return rc;
-  auto attn = [&](int, const _Float16* qkv, _Float16* out) {
-    return clm_launch_attn_tree(qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
-  };
-  if (int rc = clm_forward(m, ix.run, L, base, attn, s, fc1)) return rc;
-  return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
 }
 
 // ---- the context cache (causal_lm_cache.hip) ----
@@ -399,5 +368,171 @@ int clm_score_tree_cached(const char* who, const char* uncached, const ClmCacheD
   }
   return 0;
 }
+
+// ---- the entry points and the size rules of every family ----
+// A policy P names the element type and supplies the launches that differ with it:
+//   P::E                                        _Float16 or __bf16 (ClmElem)
+// and whatever the family's forward asks of it: the Llama-derived families' policies are described in clm_llama.h; the two
+// policies over OptFamily (below) have P::fc1, the launch of the fc1 GEMM with the activation in its epilogue.
+//
+// A family Fam is what the bodies and the size rules take beside the policy; x is the family's extra argument, of its own type X
+// (the q / k norm array of Qwen3 and OLMo-2, or a descriptor: b2t_clm_moe_t, b2t_clm_gemma2_t, b2t_clm_phi3_t, b2t_clm_gptoss_t;
+// a family without one ignores a null const void*):
+//   Fam::Model                                  the descriptor: b2t_clm_t, b2t_clm_neox_t or b2t_clm_llama_t.  The bodies and the
+//                                               rules read its n_layers, n_heads, vocab and max_pos themselves
+//   Fam::Extra                                  the type X of a call that passes no extra argument
+//   Fam::kv_heads(m)                            the K / V heads: n_kv_heads, or n_heads where the descriptor has one head count
+//   Fam::layout(model, rows, hrows, ints, x)    the workspace layout of a forward
+//   Fam::forward<P>(m, run, L, base, attn, s, x)   the forward; attn(layer, qkv, out) enqueues one layer's attention
+//   Fam::attn<P>, Fam::attn_tree<P>(m, x, layer, ...)   the flat and the tree attention of one layer
+//   Fam::head_dim(m, x)                         d_model / n_heads, or the descriptor's field (Gemma-2, Phi-3, gpt-oss)
+//   Fam::attn_cap(x)                            the soft cap on the attention scores: 0, or Gemma-2's
+//   Fam::dims_ok(model, x)                      what the size rules need of the descriptors: every field they divide by or size a
+//                                               buffer with is vouched for here (llama_dims_ok or clm_mha_dims_ok and the family's term)
+//   Fam::check<P>(who, model, x)                every refusal of the descriptors, a null model included, for the entry point `who`
+// ClmMhaFamily (below) has everything but Model, layout, forward and check for a descriptor with one head count and hd = d_model /
+// n_heads: OptFamily (OPT and GPT-2, below) and NeoxFamily (causal_lm_neox.hip) derive it.  LlamaFamilyBase (clm_llama.h) has the
+// same for a b2t_clm_llama_t that obeys the Llama rule: the defaults, which a family derives and replaces where it differs.
+// LlamaFamily is the Llama family's (Qwen3 included: P::qk_norm), Olmo2Family (clm_olmo2.h), MixtralFamily (clm_moe.h),
+// Gemma2Family (clm_gemma2.h), Phi3Family (clm_phi3.h) and GptOssFamily (clm_gptoss.h) the others'.
+
+// The flat entry point of a policy and a family; `who` is its name in every message, `extra` the family's extra argument.
+template <class P, class Fam, class X = typename Fam::Extra>
+int clm_family_score(const char* who, const typename Fam::Model* model, const int32_t* ids_host, const int32_t* seq_off_host,
+                     int n_seq, float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream,
+                     const X* extra = nullptr) {
+  using E = typename P::E;
+  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
+  const typename Fam::Model& m = *model;
+  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
+  const long long M = seq_off_host[n_seq];
+  const ClmLayout L = Fam::layout(model, M, M - n_seq, flat_ints(M, n_seq), extra);
+  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
+  const hipStream_t s = as_stream(stream);
+  char* base = static_cast<char*>(ws);
+  ClmFlatIndex ix;
+  if (int rc = clm_build_flat_index((std::string(who) + " upload").c_str(), ids_host, seq_off_host, n_seq,
+                                    reinterpret_cast<int*>(base + L.ints), s, &ix))
+    return rc;
+  auto attn = [&](int l, const E* qkv, E* out) { return Fam::template attn<P>(m, extra, l, qkv, out, ix.d_soff, n_seq, s); };
+  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
+  return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
+}
+
+// The tree entry point of a policy and a family.
+template <class P, class Fam, class X = typename Fam::Extra>
+int clm_family_score_tree(const char* who, const typename Fam::Model* model, const int32_t* ids_host, const int32_t* seq_off_host,
+                          int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
+                          void* stream, const X* extra = nullptr) {
+  using E = typename P::E;
+  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
+  const typename Fam::Model& m = *model;
+  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
+  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
+  const long long M = seq_off_host[n_seq];
+  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);   // a node's position (learned or rotary) is its depth
+  const long long Mn = plan.Mn;
+  if (n_nodes_out) *n_nodes_out = Mn;
+  const ClmLayout L = Fam::layout(model, Mn, Mn, tree_ints(Mn, M, n_seq), extra);
+  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
+  const hipStream_t s = as_stream(stream);
+  char* base = static_cast<char*>(ws);
+  ClmTreeIndex ix;
+  if (int rc = clm_build_tree_index((std::string(who) + " upload").c_str(), ids_host, seq_off_host, n_seq, plan, 0,
+                                    reinterpret_cast<int*>(base + L.ints), s, &ix))
+    return rc;
+  auto attn = [&](int l, const E* qkv, E* out) {
+    return Fam::template attn_tree<P>(m, extra, l, qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, s);
+  };
+  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
+  return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
+}
+
+// The cached entry point of a policy and a family: the family's check, then the family-independent rule (clm_score_tree_cached)
+// over the family's layout and forward; `uncached` names the tree call for callers without a cache.
+template <class P, class Fam, class X = typename Fam::Extra>
+int clm_family_score_tree_cached(const char* who, const char* uncached, const typename Fam::Model* model, b2t_clm_cache_t* cache,
+                                 int update, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                 float* tok_logp_out, long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes,
+                                 void* stream, const X* extra = nullptr) {
+  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
+  const typename Fam::Model& m = *model;
+  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, Fam::kv_heads(m), Fam::head_dim(m, extra), Fam::attn_cap(extra)};
+  return clm_score_tree_cached(
+      who, uncached, dims, cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out, n_reused_out, ws,
+      ws_bytes, as_stream(stream), [&](long long rows, size_t ints) { return Fam::layout(model, rows, rows, ints, extra); },
+      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
+        return Fam::template forward<P>(m, r, L, base, attn, s, extra);
+      });
+}
+
+// The size rules behind every family's exported size functions: 0 for descriptors or counts no call would accept, else the bytes
+// of the flat, the tree and the cached call's workspace and of a cache's K | V for `cap` positions.  The cached state is sized by
+// n_heads * head_dim, which is d_model only where hd = d_model / n_heads.
+template <class Fam, class X = typename Fam::Extra>
+size_t clm_family_ws_bytes(const typename Fam::Model* m, long long n_tokens, int n_seq, const X* x = nullptr) {
+  if (!Fam::dims_ok(m, x) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
+  return Fam::layout(m, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq), x).total;
+}
+template <class Fam, class X = typename Fam::Extra>
+size_t clm_family_tree_ws_bytes(const typename Fam::Model* m, long long n_nodes, long long n_tokens, int n_seq, const X* x = nullptr) {
+  if (!Fam::dims_ok(m, x) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
+  return Fam::layout(m, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq), x).total;
+}
+template <class Fam, class X = typename Fam::Extra>
+size_t clm_family_cache_kv_bytes(const typename Fam::Model* m, int cap, const X* x = nullptr) {
+  if (!Fam::dims_ok(m, x) || cap < 1 || cap > m->max_pos || m->n_layers < 1) return 0;
+  return (size_t)m->n_layers * (size_t)cap * 2 * (size_t)Fam::kv_heads(*m) * (size_t)Fam::head_dim(*m, x) * sizeof(_Float16);
+}
+template <class Fam, class X = typename Fam::Extra>
+size_t clm_family_tree_cached_ws_bytes(const typename Fam::Model* m, long long n_rows, long long n_tokens, int n_seq,
+                                       const X* x = nullptr) {
+  const size_t tree = clm_family_tree_ws_bytes<Fam>(m, n_rows, n_tokens, n_seq, x);
+  return tree ? clm_cached_state(tree, n_rows, m->n_heads, m->n_heads * Fam::head_dim(*m, x)).total : 0;
+}
+
+// What the families of a descriptor with one head count and hd = d_model / n_heads (M: b2t_clm_t or b2t_clm_neox_t) hand the
+// bodies and the size rules beside Model, layout, forward and check: no extra argument, and the OPT paths' two fp16 attention
+// launches with Hkv = Hq.
+struct ClmMhaFamily {
+  using Extra = void;
+  template <class M>
+  static int kv_heads(const M& m) { return m.n_heads; }
+  template <class M>
+  static int head_dim(const M& m, const void*) { return m.d_model / m.n_heads; }
+  static float attn_cap(const void*) { return 0.f; }
+  template <class M>
+  static bool dims_ok(const M* m, const void*) { return clm_mha_dims_ok(m); }
+  template <class P, class M>
+  static int attn(const M& m, const void*, int /*layer*/, const _Float16* qkv, _Float16* out, const int* seq_off, int n_seq,
+                  hipStream_t s) {
+    return clm_launch_attn(qkv, out, seq_off, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
+  }
+  template <class P, class M>
+  static int attn_tree(const M& m, const void*, int /*layer*/, const _Float16* qkv, _Float16* out, const int* seq_off,
+                       const int* tok_node, const int* own_start, int n_seq, hipStream_t s) {
+    return clm_launch_attn_tree(qkv, out, seq_off, tok_node, own_start, n_seq, m.n_heads, m.n_heads, m.d_model / m.n_heads, s);
+  }
+};
+
+// The family of b2t_clm_t: clm_opt_layout, clm_check_model (its messages say "b2t_clm:", not the entry point's name) and
+// clm_forward with the policy's fc1.  OptPolicy is OPT's (ReLU); GPT-2's is causal_lm_gpt2.hip's.
+struct OptFamily : ClmMhaFamily {
+  using Model = b2t_clm_t;
+  static ClmLayout layout(const b2t_clm_t* m, long long rows, long long hrows, size_t ints, const void*) {
+    return clm_opt_layout(m, rows, hrows, ints);
+  }
+  template <class P>
+  static int check(const char*, const b2t_clm_t* m, const void*) { return clm_check_model(m); }
+  template <class P, class Attn>
+  static int forward(const b2t_clm_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s, const void*) {
+    return clm_forward(m, r, L, base, attn, s, P::fc1);
+  }
+};
+struct OptPolicy {
+  using E = _Float16;
+  static constexpr ClmGemmLaunch fc1 = &launch_gemm<EP_RELU>;
+};
 
 }  // namespace b2t

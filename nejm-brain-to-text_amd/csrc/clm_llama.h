@@ -1,9 +1,9 @@
 // clm_llama.h — the Llama-family forward (causal_lm_llama.hip's header has the contract and the kernel sequence), written once
-// for both element types and for every family that rides on it: the embed and RMSNorm kernels, llama_forward, the bodies of the
-// flat, the tree and the cached entry point, the size rules and the statements the families' descriptor checks share.
+// for both element types and for every family that rides on it: the embed and RMSNorm kernels, llama_forward, the Llama family
+// and the defaults of the families that derive it, and the statements the families' descriptor checks share.  The bodies of the
+// entry points, the size rules and the family contract are clm_internal.h's, for every family.
 //
-// A policy P names the element type and supplies the launches that differ with it:
-//   P::E                                        _Float16 or __bf16 (ClmElem, clm_internal.h)
+// What a forward of this header asks of its policy P beside P::E:
 //   P::gemm_rope, gemm_swiglu, gemm_resid, gemm_head (g, s)   the four GEMMs, each through the one tile rule launch_gemm
 //   P::embed, P::rmsnorm                        the launches of the two kernels below
 //   P::attn, P::attn_tree                       the flat and the tree attention launcher
@@ -12,20 +12,6 @@
 // The Llama policy is LlamaShared<E> (below; causal_lm_llama.hip defines its members for fp16 and holds the fp16 entry points,
 // causal_lm_llama_bf16.hip the same for bf16, with every bf16 kernel instantiation) plus qk_norm = false; Qwen3's
 // (causal_lm_qwen3.hip) is LlamaShared<E> plus a gemm_rope with the epilogue EP_QKNORM_ROPE, instantiated there.
-//
-// A family Fam is what the bodies and the size rules take beside the policy; x is the family's extra argument, of its own type X
-// (the q / k norm array of Qwen3 and OLMo-2, or a descriptor: b2t_clm_moe_t, b2t_clm_gemma2_t, b2t_clm_phi3_t, b2t_clm_gptoss_t):
-//   Fam::layout(model, rows, hrows, ints, x)    the workspace layout of a forward
-//   Fam::forward<P>(m, run, L, base, attn, s, x)   the forward; attn(layer, qkv, out) enqueues one layer's attention
-//   Fam::attn<P>, Fam::attn_tree<P>(m, x, layer, ...)   the flat and the tree attention of one layer
-//   Fam::head_dim(m, x)                         d_model / n_heads, or the descriptor's field (Gemma-2, Phi-3, gpt-oss)
-//   Fam::attn_cap(x)                            the soft cap on the attention scores: 0, or Gemma-2's
-//   Fam::dims_ok(model, x)                      what the size rules need of the descriptors: llama_dims_ok and the family's term
-//   Fam::check<P>(who, model, x)                every refusal of the descriptors, a null model included, for the entry point `who`
-// LlamaFamilyBase has head_dim, attn_cap, dims_ok, check, attn and attn_tree of a family whose descriptor obeys the Llama rule:
-// the defaults, which a family derives and replaces where it differs.  LlamaFamily is the Llama family's (Qwen3 included:
-// P::qk_norm), Olmo2Family (clm_olmo2.h), MixtralFamily (clm_moe.h), Gemma2Family (clm_gemma2.h), Phi3Family (clm_phi3.h) and
-// GptOssFamily (clm_gptoss.h) the others'.
 #pragma once
 #include <math.h>
 #include <string>
@@ -189,9 +175,12 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
 }
 
 // What a family whose descriptor obeys the Llama rule hd = d_model / n_heads hands the bodies and the size rules beside layout
-// and forward (the contract in this file's header): the model check alone as its check, and the two attention launches, which
+// and forward (the contract in clm_internal.h): the model check alone as its check, and the two attention launches, which
 // are told the layer (gpt-oss, clm_gptoss.h: a sink per head and a window per layer; nobody else looks at it).
 struct LlamaFamilyBase {
+  using Model = b2t_clm_llama_t;
+  using Extra = b2t_clm_qknorm_t;
+  static int kv_heads(const b2t_clm_llama_t& m) { return m.n_kv_heads; }
   template <class X>
   static int head_dim(const b2t_clm_llama_t& m, const X*) { return m.d_model / m.n_heads; }
   template <class X>
@@ -230,100 +219,6 @@ struct LlamaFamily : LlamaFamilyBase {
     return llama_forward<P>(m, r, L, base, attn, s, qkn);
   }
 };
-
-// The flat entry point of a policy and a family; `who` is its name, `extra` the family's extra argument.
-template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
-int llama_score(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
-                float* scores_out, float* tok_logp_out, void* ws, size_t ws_bytes, void* stream, const X* extra = nullptr) {
-  using E = typename P::E;
-  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  const ClmLayout L = Fam::layout(model, M, M - n_seq, flat_ints(M, n_seq), extra);
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  const hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  ClmFlatIndex ix;
-  if (int rc = clm_build_flat_index((std::string(who) + " upload").c_str(), ids_host, seq_off_host, n_seq,
-                                    reinterpret_cast<int*>(base + L.ints), s, &ix))
-    return rc;
-  auto attn = [&](int l, const E* qkv, E* out) { return Fam::template attn<P>(m, extra, l, qkv, out, ix.d_soff, n_seq, s); };
-  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
-  return clm_launch_seq_sum(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hoff, scores_out, tok_logp_out, n_seq, s);
-}
-
-// The tree entry point of a policy.
-template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
-int llama_score_tree(const char* who, const b2t_clm_llama_t* model, const int32_t* ids_host, const int32_t* seq_off_host,
-                     int n_seq, float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
-                     void* stream, const X* extra = nullptr) {
-  using E = typename P::E;
-  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  B2T_REQUIRE(ids_host && seq_off_host && scores_out && ws, "%s: null argument", who);
-  if (int rc = clm_check_lists(who, ids_host, seq_off_host, n_seq, m.vocab, m.max_pos)) return rc;
-  const long long M = seq_off_host[n_seq];
-  ClmTreePlan& plan = clm_plan_tree(ids_host, seq_off_host, n_seq);   // a node's rotary position is its depth, node_pos
-  const long long Mn = plan.Mn;
-  if (n_nodes_out) *n_nodes_out = Mn;
-  const ClmLayout L = Fam::layout(model, Mn, Mn, tree_ints(Mn, M, n_seq), extra);
-  B2T_REQUIRE(ws_bytes >= L.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
-  const hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  ClmTreeIndex ix;
-  if (int rc = clm_build_tree_index((std::string(who) + " upload").c_str(), ids_host, seq_off_host, n_seq, plan, 0,
-                                    reinterpret_cast<int*>(base + L.ints), s, &ix))
-    return rc;
-  auto attn = [&](int l, const E* qkv, E* out) {
-    return Fam::template attn_tree<P>(m, extra, l, qkv, out, ix.d_soff, ix.d_node, ix.d_own, n_seq, s);
-  };
-  if (int rc = Fam::template forward<P>(m, ix.run, L, base, attn, s, extra)) return rc;
-  return clm_launch_seq_sum_tree(reinterpret_cast<float*>(base + L.logp), ix.d_soff, ix.d_hrow, scores_out, tok_logp_out, n_seq, s);
-}
-
-// The cached entry point of a policy: the family's check, then the family-independent rule (clm_internal.h) over the family's
-// layout and forward; `uncached` names the tree call for callers without a cache.
-template <class P, class Fam = LlamaFamily, class X = b2t_clm_qknorm_t>
-int llama_score_tree_cached(const char* who, const char* uncached, const b2t_clm_llama_t* model, b2t_clm_cache_t* cache, int update,
-                            const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out, float* tok_logp_out,
-                            long long* n_rows_out, int* n_reused_out, void* ws, size_t ws_bytes, void* stream,
-                            const X* extra = nullptr) {
-  if (int rc = Fam::template check<P>(who, model, extra)) return rc;
-  const b2t_clm_llama_t& m = *model;
-  const ClmCacheDims dims{m.vocab, m.max_pos, m.n_heads, m.n_kv_heads, Fam::head_dim(m, extra), Fam::attn_cap(extra)};
-  return clm_score_tree_cached(
-      who, uncached, dims, cache, update, ids_host, seq_off_host, n_seq, scores_out, tok_logp_out, n_rows_out, n_reused_out, ws,
-      ws_bytes, as_stream(stream), [&](long long rows, size_t ints) { return Fam::layout(model, rows, rows, ints, extra); },
-      [&](const ClmRun& r, const ClmLayout& L, char* base, auto&& attn, hipStream_t s) {
-        return Fam::template forward<P>(m, r, L, base, attn, s, extra);
-      });
-}
-
-// The size rules behind every family's exported size functions: 0 for descriptors or counts no call would accept, else the bytes
-// of the flat, the tree and the cached call's workspace and of a cache's K | V for `cap` positions.  The cached state is sized by
-// n_heads * head_dim, which is d_model only where the Llama rule holds.
-template <class Fam, class X = b2t_clm_qknorm_t>
-size_t llama_ws_bytes(const b2t_clm_llama_t* m, long long n_tokens, int n_seq, const X* x = nullptr) {
-  if (!Fam::dims_ok(m, x) || n_tokens < 1 || n_seq < 1 || n_seq > n_tokens) return 0;
-  return Fam::layout(m, n_tokens, n_tokens - n_seq, flat_ints(n_tokens, n_seq), x).total;
-}
-template <class Fam, class X = b2t_clm_qknorm_t>
-size_t llama_tree_ws_bytes(const b2t_clm_llama_t* m, long long n_nodes, long long n_tokens, int n_seq, const X* x = nullptr) {
-  if (!Fam::dims_ok(m, x) || n_nodes < 1 || n_nodes > n_tokens || n_seq < 1 || n_seq > n_tokens) return 0;
-  return Fam::layout(m, n_nodes, n_nodes, tree_ints(n_nodes, n_tokens, n_seq), x).total;
-}
-template <class Fam, class X = b2t_clm_qknorm_t>
-size_t llama_cache_kv_bytes(const b2t_clm_llama_t* m, int cap, const X* x = nullptr) {
-  if (!Fam::dims_ok(m, x) || cap < 1 || cap > m->max_pos || m->n_layers < 1) return 0;
-  return (size_t)m->n_layers * (size_t)cap * 2 * (size_t)m->n_kv_heads * (size_t)Fam::head_dim(*m, x) * sizeof(_Float16);
-}
-template <class Fam, class X = b2t_clm_qknorm_t>
-size_t llama_tree_cached_ws_bytes(const b2t_clm_llama_t* m, long long n_rows, long long n_tokens, int n_seq, const X* x = nullptr) {
-  const size_t tree = llama_tree_ws_bytes<Fam>(m, n_rows, n_tokens, n_seq, x);
-  return tree ? clm_cached_state(tree, n_rows, m->n_heads, m->n_heads * Fam::head_dim(*m, x)).total : 0;
-}
 
 }  // namespace
 }  // namespace b2t

@@ -1,7 +1,7 @@
 // clm_moe.h — the routed-experts MLP of a sparse mixture-of-experts layer (Mixtral; causal_lm_mixtral.hip's header has the
 // contract), written once for both element types: the four small kernels around the grouped GEMM, the workspace region, the
 // launches of one layer's MLP (moe_mlp) and MixtralFamily, which hands layout, refusals and forward to the entry-point bodies
-// and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E> (everything the Llama layer launches) plus
+// and the size rules of clm_internal.h.  A policy P of this forward is LlamaShared<E> (everything the Llama layer launches) plus
 //   P::gemm_experts_swiglu, P::gemm_experts_f32 (g, s)   the two grouped GEMMs, each through the one tile rule launch_gemm
 //   P::route, P::gather                                   the launches of the two kernels below that depend on E (MoeOps<E>)
 //
@@ -247,7 +247,7 @@ inline int clm_mixtral_check(const char* who, const b2t_clm_llama_t& m, const b2
   return 0;
 }
 
-// what the entry-point bodies and the size rules of clm_llama.h take from this family
+// what the entry-point bodies and the size rules of clm_internal.h take from this family
 struct MixtralFamily : LlamaFamilyBase {
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const b2t_clm_moe_t* moe) {
     return mixtral_layout(m, moe, rows, hrows, ints);

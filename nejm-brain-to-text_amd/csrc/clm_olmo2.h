@@ -1,6 +1,6 @@
 // clm_olmo2.h — the OLMo-2 forward (causal_lm_olmo2.hip's header has the contract and the kernel sequence), written once for
 // both element types like clm_llama.h: the two kernels OLMo-2 adds, its workspace layout, olmo2_forward and Olmo2Family, which
-// hands them to the entry-point bodies and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E> (embed,
+// hands them to the entry-point bodies and the size rules of clm_internal.h.  A policy P of this forward is LlamaShared<E> (embed,
 // the final RMSNorm, the SwiGLU and head GEMMs, the attention launchers) plus
 //   P::gemm_qkv, P::gemm_f32 (g, s)             the QKV GEMM with EP_QKV_F32 and the o_proj / down GEMM with EP_F32
 //   P::qknorm_rope, P::postnorm_add             the launches of the two kernels below
@@ -153,7 +153,7 @@ inline int clm_olmo2_check(const char* who, const b2t_clm_llama_t& m, const b2t_
   return 0;
 }
 
-// what the entry-point bodies and the size rules of clm_llama.h take from this family
+// what the entry-point bodies and the size rules of clm_internal.h take from this family
 struct Olmo2Family : LlamaFamilyBase {
   static ClmLayout layout(const b2t_clm_llama_t* m, long long rows, long long hrows, size_t ints, const void* /*extra*/ = nullptr) {
     return olmo2_layout(m, rows, hrows, ints);

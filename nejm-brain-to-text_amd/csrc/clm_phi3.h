@@ -1,6 +1,6 @@
 // clm_phi3.h — the Phi-3 forward (causal_lm_phi3.hip's header has the contract and the kernel sequence), written once for both
 // element types like clm_olmo2.h: the one kernel Phi-3 adds, its workspace layout, phi3_forward and Phi3Family, which hands them
-// to the entry-point bodies and the size rules of clm_llama.h.  A policy P of this forward is LlamaShared<E> (embed, RMSNorm, the
+// to the entry-point bodies and the size rules of clm_internal.h.  A policy P of this forward is LlamaShared<E> (embed, RMSNorm, the
 // SwiGLU, residual and head GEMMs) plus
 //   P::gemm_qkv (g, s)                          the QKV GEMM with EP_QKV_F32
 //   P::rope                                     the launch of the kernel below
@@ -109,7 +109,7 @@ int phi3_forward(const b2t_clm_llama_t& m, const b2t_clm_phi3_t& p3, const ClmRu
   return clm_head(x16, m.lm_head, m.vocab, d, r, L, base, s, &P::gemm_head);
 }
 
-// what the entry-point bodies and the size rules of clm_llama.h take from this family; the extra argument is the b2t_clm_phi3_t.
+// what the entry-point bodies and the size rules of clm_internal.h take from this family; the extra argument is the b2t_clm_phi3_t.
 // Every refusal is under the entry point's name.
 struct Phi3Family : LlamaFamilyBase {
   static int head_dim(const b2t_clm_llama_t&, const b2t_clm_phi3_t* p3) { return p3->head_dim; }

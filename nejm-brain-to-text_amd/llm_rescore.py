@@ -348,19 +348,28 @@ def load_opt_arrays(model_dir: str) -> Tuple[dict, Dict[str, "object"]]:
 class _Scorer:
     """What OptScorer and LlamaScorer share: packing and validating the ids, growing the workspace, the outputs, the context
     cache and the `score` / `token_logprobs` / `eval` surface.  A subclass builds its descriptor (`desc`, with `device`,
-    `share_prefixes`, `last_stats` and `_ws` = None), calls `_alloc_cache`, and supplies `_cache_kv_bytes`, `_sizes` and
-    `_score`: its library calls on the path "flat", "tree" or "cached"."""
+    `share_prefixes`, `last_stats` and `_ws` = None) and calls `_alloc_cache`; the names and the leading arguments of its library
+    calls on the path "flat", "tree" or "cached" (`_cache_kv_bytes`, `_sizes`, `_score`) follow from the class data below."""
     _cache = None
-    _WS_BYTES = ""    # the family's flat sizing call, for the message of a refused size
     _NO_CACHE = ""    # the ValueError of use_cache=True on a scorer without a context cache
     _CONTEXT_CACHE = True   # False: the family has no cached call, and refuses context_cache_tokens > 0 itself
+    _SIZES = ""       # the family's size functions: _SIZES + ws_bytes / tree_ws_bytes / cache_kv_bytes / tree_cached_ws_bytes
+    _size_args = ()   # what the workspace size functions take between the model and the sizes (Mixtral: its MoE descriptor)
+    _CACHE_SIZES = None   # where the cache is another family's (Mixtral: Llama's), that family's _SIZES: its cache_kv_bytes takes
+    #                       the model alone.  None: _SIZES + cache_kv_bytes, with _size_args
+    _ENTRY = None     # the entry points: _ENTRY + score_<suffix> / score_tree_<suffix> / score_tree_cached_f16.  None:
+    #                   b2t_clm_<_family>_, from the instance's _family
+    _qk = ()          # what the entry points take between the model and the lists (or the cache)
+    _suffix = "f16"   # the compute dtype in the entry points' names
 
     def eval(self):   # the reference calls model.eval(); scoring has no training mode
         return self
 
     def _cache_kv_bytes(self, lib, cap):
         """Bytes of the cache's K / V for `cap` positions by the family's library call (0: cap outside [1, max_pos])."""
-        raise NotImplementedError
+        import ctypes as C
+        prefix, args = (self._SIZES, self._size_args) if self._CACHE_SIZES is None else (self._CACHE_SIZES, ())
+        return getattr(lib, prefix + "cache_kv_bytes")(C.byref(self.desc), *args, cap)
 
     def _alloc_cache(self, context_cache_tokens):
         """context_cache_tokens > 0: the caller-owned b2t_clm_cache_t of that many positions, on the scorer's device."""
@@ -399,11 +408,32 @@ class _Scorer:
 
     def _sizes(self, lib, path, ids, off):
         """(rows computed, positions reused, workspace bytes) of a call on `path` for the packed ids / offsets."""
-        raise NotImplementedError
+        import ctypes as C
+        desc, M, n_seq = (C.byref(self.desc),) + tuple(self._size_args), len(ids), len(off) - 1
+        if path == "cached":
+            plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
+            return plan["rows"], plan["reused"], getattr(lib, self._SIZES + "tree_cached_ws_bytes")(*desc, plan["rows"], M, n_seq)
+        if path == "tree":
+            nodes = tree_plan(ids, off)[2]
+            return nodes, 0, getattr(lib, self._SIZES + "tree_ws_bytes")(*desc, nodes, M, n_seq)
+        return M, 0, getattr(lib, self._SIZES + "ws_bytes")(*desc, M, n_seq)
 
     def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
         """The library call of `path`; every array argument is an address (tok may be None)."""
-        raise NotImplementedError
+        import ctypes as C
+        import b2t_native as N
+        desc = C.byref(self.desc)
+        pre = (self._ENTRY or f"b2t_clm_{self._family}_") + "score_"
+        if path == "cached":
+            name = pre + "tree_cached_f16"
+            N.check(getattr(lib, name)(desc, *self._qk, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq,
+                                       scores, tok, None, None, ws, ws_bytes, stream), name)
+        elif path == "tree":
+            name = pre + "tree_" + self._suffix
+            N.check(getattr(lib, name)(desc, *self._qk, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream), name)
+        else:
+            name = pre + self._suffix
+            N.check(getattr(lib, name)(desc, *self._qk, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
 
     def _run(self, ids_list, want_tokens: bool, share_prefixes: Optional[bool] = None, use_cache: Optional[bool] = None,
              update_cache: bool = True):
@@ -431,7 +461,7 @@ class _Scorer:
         path = "cached" if cached else "tree" if tree else "flat"
         nodes, reused, need = self._sizes(lib, path, ids, off)
         if need == 0:
-            raise RuntimeError(f"{self._WS_BYTES}: invalid sizes: {N.last_error()}")
+            raise RuntimeError(f"{self._SIZES}ws_bytes: invalid sizes: {N.last_error()}")
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         scores = torch.empty(len(seqs), dtype=torch.float32, device=self.device)
@@ -477,9 +507,9 @@ class OptScorer(_Scorer):
     useful; results stay bit-identical.  Per call `use_cache` = None (the scorer's setting) | True | False; after a cached
     call `last_stats` = {"tokens", "nodes": rows computed, "reused": positions taken from the cache}."""
 
-    _WS_BYTES = "b2t_clm_ws_bytes"
     _NO_CACHE = "use_cache=True on a scorer built without context_cache_tokens"
-    _ENTRY = "b2t_clm_"   # the family's entry points: _ENTRY + score_f16 / score_tree_f16 / score_tree_cached_f16
+    _SIZES = "b2t_clm_"   # GPT-2's too
+    _ENTRY = "b2t_clm_"
     _dtype_of = staticmethod(lambda dtype: opt_dtype(dtype))
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
@@ -501,36 +531,6 @@ class OptScorer(_Scorer):
                               self.w["final_ln_w"].data_ptr(), self.w["final_ln_b"].data_ptr(), self._layers)
         self._ws = None
         self._alloc_cache(context_cache_tokens)
-
-    def _cache_kv_bytes(self, lib, cap):
-        import ctypes as C
-        return lib.b2t_clm_cache_kv_bytes(C.byref(self.desc), cap)
-
-    def _sizes(self, lib, path, ids, off):
-        import ctypes as C
-        desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
-        if path == "cached":
-            plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
-            return plan["rows"], plan["reused"], lib.b2t_clm_tree_cached_ws_bytes(desc, plan["rows"], M, n_seq)
-        if path == "tree":
-            nodes = tree_plan(ids, off)[2]
-            return nodes, 0, lib.b2t_clm_tree_ws_bytes(desc, nodes, M, n_seq)
-        return M, 0, lib.b2t_clm_ws_bytes(desc, M, n_seq)
-
-    def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
-        import ctypes as C
-        import b2t_native as N
-        desc = C.byref(self.desc)
-        if path == "cached":
-            name = self._ENTRY + "score_tree_cached_f16"
-            N.check(getattr(lib, name)(desc, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq, scores, tok, None,
-                                       None, ws, ws_bytes, stream), name)
-        elif path == "tree":
-            name = self._ENTRY + "score_tree_f16"
-            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream), name)
-        else:
-            name = self._ENTRY + "score_f16"
-            N.check(getattr(lib, name)(desc, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
 
 
 # ---- the compute dtype ----------------------------------------------------------------------------------------------------
@@ -837,9 +837,8 @@ class NeoxScorer(_Scorer):
     _tree_f16 / _tree_cached_f16 (csrc/causal_lm_neox.hip): partial rotary positions in the QKV GEMM's epilogue, the erf (or
     tanh) GELU in the fc1 GEMM's, the parallel residual.  A cached position costs n_layers * 4 * d_model bytes.  fp16 only."""
 
-    _WS_BYTES = "b2t_clm_neox_ws_bytes"
     _NO_CACHE = "use_cache=True on a scorer built without context_cache_tokens"
-    _ENTRY = "b2t_clm_neox_"
+    _SIZES = _ENTRY = "b2t_clm_neox_"
 
     def __init__(self, dims: dict, arrays: Dict[str, "object"], device="cuda", share_prefixes: bool = False,
                  context_cache_tokens: int = 0, dtype=None):
@@ -865,23 +864,6 @@ class NeoxScorer(_Scorer):
                                   self.w["rope_cos"].data_ptr(), self.w["rope_sin"].data_ptr(), self._layers)
         self._ws = None
         self._alloc_cache(context_cache_tokens)
-
-    def _cache_kv_bytes(self, lib, cap):
-        import ctypes as C
-        return lib.b2t_clm_neox_cache_kv_bytes(C.byref(self.desc), cap)
-
-    def _sizes(self, lib, path, ids, off):
-        import ctypes as C
-        desc, M, n_seq = C.byref(self.desc), len(ids), len(off) - 1
-        if path == "cached":
-            plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
-            return plan["rows"], plan["reused"], lib.b2t_clm_neox_tree_cached_ws_bytes(desc, plan["rows"], M, n_seq)
-        if path == "tree":
-            nodes = tree_plan(ids, off)[2]
-            return nodes, 0, lib.b2t_clm_neox_tree_ws_bytes(desc, nodes, M, n_seq)
-        return M, 0, lib.b2t_clm_neox_ws_bytes(desc, M, n_seq)
-
-    _score = OptScorer._score   # the OPT twins' argument lists under this family's _ENTRY
 
 
 # ---- the Llama family (HF LlamaForCausalLM, MistralForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM) ---------------------
@@ -1184,12 +1166,8 @@ class LlamaScorer(_Scorer):
     Arrays that hold layers.<i>.q_norm_w / k_norm_w (a Qwen3 layout) make the scorer take the b2t_clm_qwen3_* entry points, which
     norm every q and k head in the QKV GEMM's epilogue, on all those paths; sizes and the cache are the Llama calls'."""
 
-    _WS_BYTES = "b2t_clm_llama_ws_bytes"
-    _SIZES = "b2t_clm_llama_"   # the family's size functions: _SIZES + ws_bytes / tree_ws_bytes / cache_kv_bytes / tree_cached_ws_bytes
+    _SIZES = "b2t_clm_llama_"
     _NO_CACHE = "use_cache=True on a scorer built without a context cache (context_cache_tokens)"
-    _size_args = ()   # what the family's workspace size functions take between the model and the sizes (Mixtral: its MoE descriptor)
-    _CACHE_SIZES = None   # where the cache is another family's (Mixtral: Llama's), that family's _SIZES: its cache_kv_bytes takes
-    #                       the model alone.  None: _SIZES + cache_kv_bytes, with _size_args
     _OWN_ARRAYS = ()      # suffixes of the arrays that _point copies itself (they are not in the compute dtype)
 
     # A family is a subclass with class data and two hooks.  The constructor runs, in this order: _describe (which raises the
@@ -1255,38 +1233,6 @@ class LlamaScorer(_Scorer):
             raise ValueError(f"LlamaScorer: the context cache (context_cache_tokens > 0) lives in GPU memory; device "
                              f"{torch.device(device)} has none")
 
-    def _cache_kv_bytes(self, lib, cap):
-        import ctypes as C
-        prefix, args = (self._SIZES, self._size_args) if self._CACHE_SIZES is None else (self._CACHE_SIZES, ())
-        return getattr(lib, prefix + "cache_kv_bytes")(C.byref(self.desc), *args, cap)
-
-    def _sizes(self, lib, path, ids, off):
-        import ctypes as C
-        desc, M, n_seq = (C.byref(self.desc),) + tuple(self._size_args), len(ids), len(off) - 1
-        if path == "cached":
-            plan = cache_plan(self._cache_ids[:self._cache.n], self._cache.cap, ids, off)
-            return plan["rows"], plan["reused"], getattr(lib, self._SIZES + "tree_cached_ws_bytes")(*desc, plan["rows"], M, n_seq)
-        if path == "tree":
-            nodes = tree_plan(ids, off)[2]
-            return nodes, 0, getattr(lib, self._SIZES + "tree_ws_bytes")(*desc, nodes, M, n_seq)
-        return M, 0, getattr(lib, self._SIZES + "ws_bytes")(*desc, M, n_seq)
-
-    def _score(self, lib, path, update_cache, ids, off, n_seq, scores, tok, ws, ws_bytes, stream):
-        import ctypes as C
-        import b2t_native as N
-        desc = C.byref(self.desc)
-        pre = f"b2t_clm_{self._family}_score_"
-        if path == "cached":
-            name = pre + "tree_cached_f16"
-            N.check(getattr(lib, name)(desc, *self._qk, C.byref(self._cache), 1 if update_cache else 0, ids, off, n_seq,
-                                       scores, tok, None, None, ws, ws_bytes, stream), name)
-        elif path == "tree":
-            name = pre + "tree_" + self._suffix
-            N.check(getattr(lib, name)(desc, *self._qk, ids, off, n_seq, scores, tok, None, ws, ws_bytes, stream), name)
-        else:
-            name = pre + self._suffix
-            N.check(getattr(lib, name)(desc, *self._qk, ids, off, n_seq, scores, tok, ws, ws_bytes, stream), name)
-
 
 # ---- OLMo-2 (HF Olmo2ForCausalLM): whole-row q / k norms and a post-norm layer ---------------------------------------------
 OLMO2_HEAD_DIMS = (64, 128)
@@ -1345,7 +1291,6 @@ class Olmo2Scorer(LlamaScorer):
     per-layer q / k norm weights of olmo2_device_layout, and whose workspace sizes are the b2t_clm_olmo2_* size functions'
     (the Llama workspace plus an fp32 region for the rows the two norms read)."""
 
-    _WS_BYTES = "b2t_clm_olmo2_ws_bytes"
     _SIZES = "b2t_clm_olmo2_"
 
     def _describe(self, dims, arrays, dtype, context_cache_tokens):
@@ -1439,7 +1384,6 @@ class MixtralScorer(LlamaScorer):
     workspace sizes are the b2t_clm_mixtral_* size functions' (the Llama workspace plus the routing and the sorted rows); the
     cache's size is the Llama family's."""
 
-    _WS_BYTES = "b2t_clm_mixtral_ws_bytes"
     _SIZES = "b2t_clm_mixtral_"
     _CACHE_SIZES = "b2t_clm_llama_"
 
@@ -1557,7 +1501,6 @@ class Gemma2Scorer(LlamaScorer):
     compute dtype, the two feed-forward norms per layer), and whose sizes, the cache's included, are the b2t_clm_gemma2_* size
     functions'."""
 
-    _WS_BYTES = "b2t_clm_gemma2_ws_bytes"
     _SIZES = "b2t_clm_gemma2_"
 
     def _describe(self, dims, arrays, dtype, context_cache_tokens):
@@ -1696,7 +1639,6 @@ class Phi3Scorer(LlamaScorer):
     b2t_clm_phi3_t of phi3_dims (head dim, rotary dims), and whose sizes, the cache's included, are the b2t_clm_phi3_* size
     functions'."""
 
-    _WS_BYTES = "b2t_clm_phi3_ws_bytes"
     _SIZES = "b2t_clm_phi3_"
 
     def _describe(self, dims, arrays, dtype, context_cache_tokens):
@@ -1955,7 +1897,6 @@ class GptOssScorer(LlamaScorer):
     b2t_clm_gptoss_t of gptoss_device_layout's arrays, and whose workspace sizes are the b2t_clm_gptoss_* size functions'.  There
     is no context cache for this family: context_cache_tokens > 0 raises ValueError."""
 
-    _WS_BYTES = "b2t_clm_gptoss_ws_bytes"
     _SIZES = "b2t_clm_gptoss_"
     _CONTEXT_CACHE = False
     _OWN_ARRAYS = (".sinks",)   # fp32 in either compute dtype

@@ -141,7 +141,6 @@ def test_python_surface(tmp_path):
     for name in ("cache_len", "cache_ids", "cache_reset", "_alloc_cache"):
         assert getattr(R.LlamaScorer, name) is getattr(R._Scorer, name) is getattr(R.OptScorer, name), name
     assert isinstance(R._Scorer.cache_len, property) and isinstance(R._Scorer.cache_ids, property)
-    assert R.LlamaScorer._cache_kv_bytes is not R.OptScorer._cache_kv_bytes
     assert "context cache" in R.LlamaScorer._NO_CACHE
 
     model, cfg = tiny_model("llama", n_layers=1)
@@ -163,6 +162,29 @@ def test_python_surface(tmp_path):
             sc.token_logprobs([[2, 3]], use_cache=True)
     with pytest.raises(ValueError, match="context_cache_tokens < 0"):
         R.LlamaScorer(dims, dict(lay), "cpu", False, -1)
+    # the two classes size their cache through different library functions, each one the library has
+    import torch
+    import b2t_native as N
+    lib = N.load()
+
+    class Names:
+        def __init__(self):
+            self.seen = []
+
+        def __getattr__(self, name):
+            self.seen.append(name)
+            return getattr(lib, name)
+
+    odims = dict(n_layers=0, d_model=64, n_heads=1, ffn_dim=64, vocab=8, max_pos=16)
+    oarr = {k: torch.zeros(n, 64, dtype=torch.float16) for k, n in (("embed_tokens", 8), ("embed_positions", 18))}
+    oarr.update({k: torch.zeros(64, dtype=torch.float16) for k in ("final_ln_w", "final_ln_b")})
+    asked = {}
+    for sc in (R.LlamaScorer(dims, dict(lay), "cpu"), R.OptScorer(odims, oarr, "cpu")):
+        names = Names()
+        sc._cache_kv_bytes(names, 8)
+        assert len(names.seen) == 1 and hasattr(lib, names.seen[0]), names.seen
+        asked[type(sc)] = names.seen[0]
+    assert asked == {R.LlamaScorer: "b2t_clm_llama_cache_kv_bytes", R.OptScorer: "b2t_clm_cache_kv_bytes"}
     # build_scorer refuses before it reads the weights: a directory with nothing but config.json
     bare = tmp_path / "bare"
     bare.mkdir()
