@@ -401,8 +401,17 @@ int b2t_lm_prologue_f32(const float* logits, const float* log_priors, float blan
  * Outputs, sorted best first (slots beyond the live beam: hyp_len = -1):
  *   hyps [U][second_beam][max_len] token ids, hyp_len [U][second_beam], score = LogAdd(s, ns), vscore = Viterbi
  *   score, times [U][second_beam][max_len] (frame of each token on the Viterbi path; may be NULL).  Only the first
- *   hyp_len entries of a hyps / times row are written; the rest keeps whatever the buffer held.
- * max_nodes bounds the trie (<= second_beam new nodes per frame); b2t_beam_overflowed reports exhaustion. */
+ *   hyp_len entries of a hyps / times row are written; the rest keeps whatever the buffer held.  A hypothesis of
+ *   probability zero (score and vscore at the log-zero sentinel -FLT_MAX or below; such prefixes fill up a list that
+ *   has fewer live ones) has no Viterbi path: the contents of its times row are unspecified.
+ *   An utterance consumes min(lens[u], T) frames of the call (0: its state and outputs are what they were before).
+ * Overflow contract.  max_nodes bounds the trie (<= second_beam new nodes per frame) and max_len the length of a
+ * hypothesis.  An utterance's overflow flag is set when a frame needs a trie node beyond max_nodes, or when a prefix
+ * that survives a frame is longer than max_len; b2t_beam_overflowed returns 1 if any utterance's flag is set.  The
+ * outputs of a flagged utterance are invalid from then on (hyp_len may exceed max_len, prefixes may be wrong), but
+ * every write stays in bounds: hyps / times rows are clipped at max_len, no node id >= max_nodes is used as an index,
+ * and the other utterances of the batch are unaffected.  The flag is sticky across calls; b2t_beam_reset clears it
+ * (and may give the same block a new max_len / max_nodes layout that fits in it). */
 size_t b2t_beam_state_bytes(int max_len, int max_nodes);
 int b2t_beam_reset(void* state, int U, int max_len, int max_nodes, void* stream);
 int b2t_prefix_beam_search_f32(const float* logp, const int32_t* lens, int U, int T, int C, int first_beam,

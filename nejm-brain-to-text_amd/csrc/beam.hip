@@ -308,18 +308,22 @@ __global__ __launch_bounds__(1024) void prefix_beam_kernel(const float* __restri
     const int nb = s_nb, cur = s_cur, at = s_abs;
     BT(0)
     // ---- 1. first beam: top-K classes of the frame (one wave; ties -> lowest class id) --------------
+    // K DISTINCT classes, like topk / a stable argsort: a chosen lane is marked taken, not overwritten with -inf, so on a
+    // frame with fewer than K finite log-probs the -inf classes follow in index order and no class (and no padding lane
+    // tid >= C) is chosen twice.  Order: (not taken, value descending, lane ascending); K <= C real lanes always exist.
     if (tid < 64) {
-      float v = tid < C ? lp_u[(long long)f * C + tid] : -INFINITY;
+      const float v = tid < C ? lp_u[(long long)f * C + tid] : -INFINITY;
+      int taken = tid < C ? 0 : 1;
       cp[tid] = v;
       for (int k = 0; k < K; ++k) {
-        float best = v; int bi = tid;
+        float best = v; int bi = tid, bt = taken;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-          const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-          if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+          const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o), ot = __shfl_xor(bt, o);
+          if (ot < bt || (ot == bt && (ob > best || (ob == best && oi < bi)))) { best = ob; bi = oi; bt = ot; }
         }
         if (tid == 0) { tk_id[k] = bi; tk_p[k] = best; }
-        if (tid == bi) v = -INFINITY;
+        if (tid == bi) taken = 1;
       }
     }
     if (tid < nb) {
@@ -352,6 +356,7 @@ __global__ __launch_bounds__(1024) void prefix_beam_kernel(const float* __restri
       if (slot == 0) {                                   // prefix h stays
         node = h_node[h];
         const int last = h_tok[h];
+        bool rep = false; float prep = NEGMAX, pext = NEGMAX;
         for (int k = 0; k < K; ++k) {
           const int c = tk_id[k]; const float p = tk_p[k];
           if (c == blank) {                              // case 0: *a + blank => *a
@@ -361,32 +366,37 @@ __global__ __launch_bounds__(1024) void prefix_beam_kernel(const float* __restri
             valid = 1;
           } else if (h_dep[h] > 0 && c == last) {        // case 1: *a + a => *a
             ns_ = log_add(ns_, h_ns[h] + p);
-            if (vns_ < h_vns[h] + p) {
-              vns_ = h_vns[h] + p;
-              if (ctp_ < p) { ctp_ = p; tn = TSrc{(short)h, 1, 2}; }
-            }
+            rep = true; prep = p;
             valid = 1;
           }
         }
-        if (h_dep[h] > 0) {                              // extension of the parent prefix that lands on h
-          const int hp = h_pidx[h];
-          if (hp >= 0) {
-            for (int k = 0; k < K; ++k) {
-              if (tk_id[k] != last || last == blank) continue;
-              const float p = tk_p[k];
-              float add, vc; TSrc src;
-              if (h_dep[hp] > 0 && last == h_tok[hp]) {  // case 2: *a(blank) + a => *aa
-                add = h_s[hp] + p; vc = h_vs[hp] + p; src = TSrc{(short)hp, 0, 1};
-              } else {                                   // case 3: *a + b => *ab
-                add = h_score[hp] + p; vc = h_vit[hp] + p;
-                src = TSrc{(short)hp, (char)(h_vs[hp] > h_vns[hp] ? 0 : 1), 1};
-              }
-              ns_ = log_add(ns_, add);
-              if (vns_ < vc) { vns_ = vc; ctp_ = p; tn = src; }
-              valid = 1;
+        bool ext = false; float vc = NEGMAX; TSrc src{0, 0, 3};
+        const int hp = h_dep[h] > 0 ? h_pidx[h] : -1;    // extension of the parent prefix that lands on h
+        if (hp >= 0) {
+          for (int k = 0; k < K; ++k) {
+            if (tk_id[k] != last || last == blank) continue;
+            const float p = tk_p[k];
+            float add;
+            if (h_dep[hp] > 0 && last == h_tok[hp]) {    // case 2: *a(blank) + a => *aa
+              add = h_s[hp] + p; vc = h_vs[hp] + p; src = TSrc{(short)hp, 0, 1};
+            } else {                                     // case 3: *a + b => *ab
+              add = h_score[hp] + p; vc = h_vit[hp] + p;
+              src = TSrc{(short)hp, (char)(h_vs[hp] > h_vns[hp] ? 0 : 1), 1};
             }
+            ns_ = log_add(ns_, add);
+            ext = true; pext = p;
+            valid = 1;
           }
         }
+        // Viterbi part of v_ns: the two contributions (both with the class `last`, so the same p) are applied in BEAM order
+        // like the reference's walk over its hypotheses (the oracle fixes that walk to beam order).  The order shows: the
+        // first one sets cur_token_prob = p, after which a better repeat (case 1) raises v_ns but keeps the times vector.
+        if (ext && hp < h && vns_ < vc) { vns_ = vc; ctp_ = pext; tn = src; }
+        if (rep && vns_ < h_vns[h] + prep) {
+          vns_ = h_vns[h] + prep;
+          if (ctp_ < prep) { ctp_ = prep; tn = TSrc{(short)h, 1, 2}; }
+        }
+        if (ext && hp > h && vns_ < vc) { vns_ = vc; ctp_ = pext; tn = src; }
       } else {                                           // prefix h extended by class c (new prefix)
         const int c = tk_id[slot - 1]; const float p = tk_p[slot - 1];
         if (c != blank) {
@@ -519,6 +529,7 @@ __global__ __launch_bounds__(1024) void prefix_beam_kernel(const float* __restri
         h_node[tid] = n; h_par[tid] = par[n]; h_tok[tid] = tok[n]; h_dep[tid] = dep[n];
         h_s[tid] = hb.fl[0 * BMAX + tid]; h_ns[tid] = hb.fl[1 * BMAX + tid]; h_vs[tid] = hb.fl[2 * BMAX + tid];
         h_vns[tid] = hb.fl[3 * BMAX + tid]; h_ctp[tid] = hb.fl[4 * BMAX + tid];
+        if (h_dep[tid] > L) hdr[4] = 1;   // a surviving prefix longer than max_len: its hyps / times rows are clipped, so flag it
       }
     }
     __syncthreads();
@@ -664,7 +675,8 @@ extern "C" int b2t_prefix_beam_search_lex_f32(const float* logp, const int32_t* 
   return 0;
 }
 
-// 1 if any utterance's trie overflowed max_nodes / max_len (results invalid); synchronises the stream.
+// 1 if any utterance's trie overflowed max_nodes, or a surviving prefix grew past max_len (results invalid; b2t.h states
+// the contract); synchronises the stream.
 extern "C" int b2t_beam_overflowed(const void* state, int U, int max_len, int max_nodes, int* flag_host, void* stream) {
   B2T_REQUIRE(state && flag_host, "beam_overflowed: null");
   BeamLayout lay(max_nodes, max_len);

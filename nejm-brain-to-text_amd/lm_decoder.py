@@ -125,7 +125,9 @@ def process_blank(s: str) -> str:
 
 class BrainSpeechDecoder:
     """Decode()/Reset()/FinishDecoding()/DecodedSomething()/result() as in brain_speech_decoder.h:112-124.
-    Decode() may be called repeatedly with consecutive chunks of log-probabilities (streaming)."""
+    Decode() may be called repeatedly with consecutive chunks of log-probabilities (streaming).  max_len bounds the tokens
+    of a hypothesis (and, times the second beam, the prefix trie): Decode() raises RuntimeError when the searcher reports that
+    either was exhausted; Reset() makes the decoder usable again."""
 
     def __init__(self, resource: DecodeResource, opts: DecodeOptions, device="cuda:0", max_len=1024):
         self.res, self.opts = resource, opts
@@ -224,6 +226,14 @@ class BrainSpeechDecoder:
                     ops._p(d["child"]), ops._p(d["logp"]), ops._p(d["bow"]), ops._p(d["suffix"]), ops._p(d["nstate"]), lm.V,
                     lm.start_state, lm.eos if self.opts.lm_eos else -1, float(self.opts.lm_alpha), float(self.opts.lm_beta),
                     float(lm.unk_logp), ops._p(lms), ops._stream()), "b2t_prefix_beam_search_lm_f32")
+            flag = C.c_int(0)
+            N.check(N.load().b2t_beam_overflowed(ops._p(self.state), 1, self.max_len, self.max_nodes, C.byref(flag),
+                                                 ops._stream()), "b2t_beam_overflowed")
+        if flag.value:
+            self._result = []
+            raise RuntimeError(f"prefix beam search: a capacity was exhausted (max_len = {self.max_len} tokens per hypothesis, "
+                               f"max_nodes = {self.max_nodes}); results are invalid -- Reset(), or construct "
+                               "BrainSpeechDecoder with a larger max_len")
         self._out = (hyps.cpu().numpy()[0], hl.cpu().numpy()[0], sc.cpu().numpy()[0], vs.cpu().numpy()[0],
                      tm.cpu().numpy()[0], lms.cpu().numpy()[0])
         self._update_result()
