@@ -1223,6 +1223,71 @@ int (b2t_clm_gptoss_mx_score_tree_bf16)(const b2t_clm_llama_t* model, const b2t_
 int b2t_clm_mxfp4_unpack_f16(const void* q, const void* s, long long rows, int K, void* out, void* stream);
 int b2t_clm_mxfp4_unpack_bf16(const void* q, const void* s, long long rows, int K, void* out, void* stream);
 
+/* ---- the Llama family with the projections kept in block-scaled FP8 (csrc/causal_lm_llama_fp8.hip) ---------------------------
+ * The fine-grained FP8 spelling of a checkpoint (HF FineGrainedFP8Config; the Qwen3-*-FP8 line): every quantised linear is a
+ * matrix of OCP e4m3fn codes [N][K], one byte a weight, beside an fp32 weight_scale_inv [N / bn][K / bk]; element (n, k) has the
+ * value E(f32(code) * scale[n / bn][k / bk]): the code widened exactly, one fp32 multiplication rounded to nearest even with
+ * subnormal products kept, one conversion to the call's element type E rounded to nearest even with subnormal results kept --
+ * what the loader's dequantise-then-cast (llm_rescore.fp8_dequant(...).to(dtype)) puts into qkv_w, o_w, gate_up_w and down_w.
+ * These calls keep the four projections of every layer so in device memory and unpack in the tile GEMM: where the dense tile
+ * loads 16 bytes of B, the packed one loads the 8 bytes and the one scale that hold the same eight elements, expands them in
+ * registers and writes the dense tile's LDS image.  From there on the kernel is the dense one, the k order and the epilogues
+ * included, so scores and token log-probs are BYTE-IDENTICAL to the b2t_clm_llama_* / b2t_clm_qwen3_* call on the expanded
+ * model, on both tiles (B2T_CLM_GEMM_256).  This is not an FP8 matrix multiplication: activations are never quantised.
+ * The model is the Llama section's, except that every layer's qkv_w, o_w, gate_up_w and down_w must be NULL (a caller holds one
+ * form of the projections, not both); embedding, head, norms and qkv_b stay 16-bit.  fp8 describes the packed form: block_k =
+ * bk, a multiple of 64 that divides d_model and ffn_dim, and layers_host, a HOST array of n_layers records with DEVICE
+ * pointers inside, in the rows of the dense matrices (the same row permutations, rows padded to 256):
+ *   qkv_q     uint8 [round_up((Hq + 2 Hkv) hd, 256)][d]    qkv_s     fp32 [rows / 32][d / bk]
+ *   o_q       uint8 [round_up(d, 256)][Hq hd]              o_s       fp32 [rows / 32][Hq hd / bk]
+ *   gate_up_q uint8 [round_up(2 F, 256)][d]                gate_up_s fp32 [rows / 32][d / bk]
+ *   down_q    uint8 [round_up(d, 256)][F]                  down_s    fp32 [rows / 32][F / bk]
+ * The code arrays are 8-byte aligned, the scale arrays 4-byte.
+ * A scale row serves 32 consecutive stored rows: the loader expands the checkpoint's block rows to that grain, which the row
+ * permutations respect when bn is a multiple of 32.  Padding rows hold code 0 and scale 0.  The codes 0x7F and 0xFF (NaN), a
+ * scale that is not finite and a value that is not finite in E have no defined result: the loader refuses them by name.
+ * qk_norm_host selects the model: NULL is Llama / Mistral / Qwen2 (EP_ROPE, with or without qkv_b), an array is Qwen3's, whose
+ * QKV epilogue norms every q and k head (the Qwen3 section's rules).  The five score calls have the Llama twins' argument lists
+ * with qk_norm_host and fp8 after the model, their outputs, their workspace and cache (the size functions are the twins':
+ * b2t_clm_llama_ws_bytes / _tree_ws_bytes / _cache_kv_bytes / _tree_cached_ws_bytes) and their refusals; they also refuse, before
+ * any launch, a null fp8, a null layers_host or pointer inside it, a layer whose qkv_w, o_w, gate_up_w or down_w is not NULL,
+ * and a block_k that is not a multiple of 64 or does not divide d_model and ffn_dim.
+ * b2t_clm_fp8_unpack_f16 / _bf16 write rows packed rows of K elements (q [rows][K] codes, s fp32 [ceil(rows / 32)][K / block_k],
+ * DEVICE; block_k a multiple of 64 that divides K) to the dense out [rows][K] through the same device function as the
+ * GEMM: a public utility, and the way to test the expansion exhaustively. */
+typedef struct {
+  const void *qkv_q, *qkv_s;           /* uint8 [round_up((Hq + 2 Hkv) hd, 256)][d], fp32 [rows / 32][d / block_k] */
+  const void *o_q, *o_s;               /* uint8 [round_up(d, 256)][Hq hd], fp32 [rows / 32][Hq hd / block_k] */
+  const void *gate_up_q, *gate_up_s;   /* uint8 [round_up(2 F, 256)][d], fp32 [rows / 32][d / block_k] */
+  const void *down_q, *down_s;         /* uint8 [round_up(d, 256)][F], fp32 [rows / 32][F / block_k] */
+} b2t_clm_llama_fp8_layer_t;
+typedef struct {
+  int block_k;                                    /* columns of a scale block: a multiple of 64 that divides d_model and ffn_dim */
+  const b2t_clm_llama_fp8_layer_t* layers_host;   /* HOST array of n_layers entries (device pointers inside) */
+} b2t_clm_llama_fp8_t;
+
+int b2t_clm_llama_fp8_score_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const b2t_clm_llama_fp8_t* fp8,
+                                const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_llama_fp8_score_tree_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
+                                     const b2t_clm_llama_fp8_t* fp8, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                     float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
+                                     void* stream);
+int b2t_clm_llama_fp8_score_tree_cached_f16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
+                                            const b2t_clm_llama_fp8_t* fp8, b2t_clm_cache_t* cache, int update,
+                                            const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                            float* tok_logp_out, long long* n_rows_out, int* n_reused_out, void* ws,
+                                            size_t ws_bytes, void* stream);
+int b2t_clm_llama_fp8_score_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host, const b2t_clm_llama_fp8_t* fp8,
+                                 const int32_t* ids_host, const int32_t* seq_off_host, int n_seq, float* scores_out,
+                                 float* tok_logp_out, void* ws, size_t ws_bytes, void* stream);
+int b2t_clm_llama_fp8_score_tree_bf16(const b2t_clm_llama_t* model, const b2t_clm_qknorm_t* qk_norm_host,
+                                      const b2t_clm_llama_fp8_t* fp8, const int32_t* ids_host, const int32_t* seq_off_host, int n_seq,
+                                      float* scores_out, float* tok_logp_out, long long* n_nodes_out, void* ws, size_t ws_bytes,
+                                      void* stream);
+int b2t_clm_fp8_unpack_f16(const void* q, const void* s, long long rows, int K, int block_k, void* out, void* stream);
+int b2t_clm_fp8_unpack_bf16(const void* q, const void* s, long long rows, int K, int block_k, void* out, void* stream);
+
 /* ---- the same scoring for GPT-NeoX (csrc/causal_lm_neox.hip) ---------------------------------------------------------------
  * HF GPTNeoXForCausalLM with head dim 64 or 128: of the Pythia suite 70M, 160M, 410M, 1.4B, 6.9B and 12B (not pythia-2.8b,
  * head dim 80, pythia-1b, 256, or GPT-NeoX-20B, 96: refused).  The layer is OPT's -- LayerNorm with eps 1e-5,

@@ -165,6 +165,16 @@ class ClmGptOssMx(C.Structure):
     _fields_ = [(n, VP) for n in ("gate_up_q", "gate_up_s", "down_q", "down_s")]
 
 
+class ClmLlamaFp8Layer(C.Structure):
+    """Mirror of b2t_clm_llama_fp8_layer_t (include/b2t.h): one layer's four projections kept in FP8, codes and fp32 scales."""
+    _fields_ = [(n, VP) for n in ("qkv_q", "qkv_s", "o_q", "o_s", "gate_up_q", "gate_up_s", "down_q", "down_s")]
+
+
+class ClmLlamaFp8(C.Structure):
+    """Mirror of b2t_clm_llama_fp8_t (include/b2t.h): the packed projections of a Llama-family model beside its b2t_clm_llama_t."""
+    _fields_ = [("block_k", C.c_int), ("layers_host", C.POINTER(ClmLlamaFp8Layer))]
+
+
 class ClmQkNorm(C.Structure):
     """Mirror of b2t_clm_qknorm_t (include/b2t.h): device weights [hd] of one Qwen3 layer's q and k RMSNorm."""
     _fields_ = [("q_norm_w", VP), ("k_norm_w", VP)]
@@ -341,6 +351,13 @@ for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16"):
     _SIGNATURES["b2t_clm_gptoss_mx_" + _t] = (_res, _args[:2] + [C.POINTER(ClmGptOssMx)] + _args[2:])
 for _t in ("f16", "bf16"):
     _SIGNATURES["b2t_clm_mxfp4_unpack_" + _t] = (C.c_int, [VP, VP, LL, C.c_int, VP, VP])
+# the Llama family with the projections kept in FP8: the Qwen3 twin's list (the q / k norm array may be null) with the packed
+# descriptor behind it (the size functions are the Llama twins'), and the unpack utility
+for _t in ("score_f16", "score_tree_f16", "score_bf16", "score_tree_bf16", "score_tree_cached_f16"):
+    _res, _args = _SIGNATURES["b2t_clm_qwen3_" + _t]
+    _SIGNATURES["b2t_clm_llama_fp8_" + _t] = (_res, _args[:2] + [C.POINTER(ClmLlamaFp8)] + _args[2:])
+for _t in ("f16", "bf16"):
+    _SIGNATURES["b2t_clm_fp8_unpack_" + _t] = (C.c_int, [VP, VP, LL, C.c_int, C.c_int, VP, VP])
 # GPT-NeoX: the OPT twin's list on its own model struct (same cache)
 for _t in ("ws_bytes", "tree_ws_bytes", "cache_kv_bytes", "tree_cached_ws_bytes", "score_f16", "score_tree_f16",
            "score_tree_cached_f16"):

@@ -12,7 +12,9 @@
 // Gemma-2 adds (EP_GEGLU: gelu_new where SwiGLU has silu; EP_HEAD_CAP: the fused head on soft-capped logits) in both,
 // causal_lm_phi3.hip EP_QKV_F32 again in both (Phi-3's rotation reads the fp32 q | k columns in a kernel of its own),
 // causal_lm_gptoss.hip the two gpt-oss adds to the grouped tile (EP_OSS_GLU, EP_F32_BIAS: per-expert biases) in both,
-// causal_lm_gptoss_mx.hip those two on the packed form of the grouped tile (clm_gemm_grouped_mx_kernel: B in MXFP4).  Which
+// causal_lm_gptoss_mx.hip those two on the packed form of the grouped tile (clm_gemm_grouped_mx_kernel: B in MXFP4),
+// causal_lm_llama_fp8.hip the Llama and Qwen3 layers' four on the packed form of the plain tile (clm_gemm_fp8_kernel: B in
+// block-scaled FP8) in both.  Which
 // tile a GEMM gets is decided in one place, launch_gemm of causal_lm.hip, for either element type; clm_gemm_tiles below only
 // launches it.
 #pragma once
@@ -114,27 +116,61 @@ __device__ __forceinline__ uint4 mxfp4_unpack8<__bf16>(unsigned q, unsigned sb) 
   return r;
 }
 
+// FP8 -> E: the eight values of 8 bytes of OCP e4m3fn codes (element i is byte i; q.x holds elements 0..3) times the block's
+// fp32 scale s, as eight E in element order -- the uint4 that the dense path loads from a matrix of (E)((float)code * s).  Two
+// roundings, in the loader's order (llm_rescore.fp8_dequant, then the cast): the code widened to fp32 (exact, the e4m3
+// subnormals included), one fp32 multiplication rounded to nearest even with subnormal products kept, one conversion to E
+// rounded to nearest even with subnormal results kept (this target never flushes either).  Codes 0x7F and 0xFF (NaN) have no
+// defined result: the loader refuses them; a product that is not finite in E is refused there too.  The one definition: the
+// packed plain tile below and b2t_clm_fp8_unpack_f16 / _bf16 (causal_lm_llama_fp8.hip) call it.
+template <class E>
+__device__ __forceinline__ uint4 fp8_unpack8(uint2 q, float s) {
+  typedef E e2 __attribute__((ext_vector_type(2)));
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  const f2 v[4] = {__builtin_amdgcn_cvt_pk_f32_fp8((int)q.x, false), __builtin_amdgcn_cvt_pk_f32_fp8((int)q.x, true),
+                   __builtin_amdgcn_cvt_pk_f32_fp8((int)q.y, false), __builtin_amdgcn_cvt_pk_f32_fp8((int)q.y, true)};
+  uint4 r;
+  unsigned* o = &r.x;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    e2 p;
+    p[0] = (E)(v[i][0] * s); p[1] = (E)(v[i][1] * s);
+    o[i] = __builtin_bit_cast(unsigned, p);
+  }
+  return r;
+}
+
+// how a tile reads its B operand: 16-bit elements, MXFP4 (the grouped tile alone) or block-scaled FP8 (the plain tile alone)
+enum { PK_DENSE = 0, PK_MXFP4 = 1, PK_FP8 = 2 };
+
 // BM x BN block tile, WGM x WGN waves, each wave (BM / WGM) x 64 = FM x 2 fragments of 32 x 32.  E is the element type of
 // A, B, bias and out16 (ClmElem, clm_internal.h).  This is the body of both kernels below.  GROUPED (routed experts,
 // clm_moe.h): B is a stack of matrices b_stride elements apart and the rows of A are sorted by matrix in segments of whole
 // 256-row blocks, so a tile of either size lies in one segment; it takes its matrix from blk_expert[m0 / 128] and returns, the
 // whole workgroup alike and before any barrier, where that is negative (a block no row was routed to).  Nothing else
-// differs: the k order and the arithmetic of an output element are those of the plain tile.  MX (with GROUPED: gpt-oss experts
-// kept in MXFP4) reads B packed: g.B holds K / 2 bytes of nibbles a row and g.b_scale K / 32 scale bytes a row, in the rows and
+// differs: the k order and the arithmetic of an output element are those of the plain tile.  PK selects the form of B: PK_DENSE,
+// 16-bit elements.  PK_MXFP4 (with GROUPED: gpt-oss experts kept in MXFP4) reads B packed: g.B holds K / 2 bytes of nibbles a row and g.b_scale K / 32 scale bytes a row, in the rows and
 // the strides (b_stride, in elements) of the dense stack.  A thread fetches, where the dense tile fetches 16 bytes of B, the 4
 // bytes that hold the same eight elements and their block's scale byte -- a thread's piece never crosses a row's end or a
 // block of 32 -- and unpacks them (mxfp4_unpack8) into the uint4 the dense tile would have loaded, on its way into the same LDS
 // layout: from the LDS reads on the kernel is the dense one, operand bits and k order included.  The unpacking of tile kt + 1 is
 // spread over the last three of tile kt's four MFMA steps, so that its VALU work issues under the matrix pipe and not, with every
 // wave of the workgroup at once, between the k loop's last MFMA and the barrier (in the last tile it expands stale registers,
-// which nothing reads).
-template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16, bool GROUPED = false, bool MX = false>
+// which nothing reads).  PK_FP8 (without GROUPED: the Llama family's projections kept in block-scaled FP8) does the same with one
+// byte an element: g.B holds K e4m3fn codes a row in the rows of the dense matrix, g.b_scale fp32 [rows / 32][K / b_block_k], the
+// scale of every 32 stored rows and b_block_k columns (a multiple of CK, so a k tile lies in one block column, and a thread's
+// four pieces, RS rows apart, in block rows RS / 32 apart).  A thread fetches the 8 bytes that hold the dense piece's eight
+// elements and their block's scale, and fp8_unpack8 makes the dense uint4 of them under the same MFMA steps.
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16, bool GROUPED = false, int PK = PK_DENSE>
 __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
-  static_assert(!MX || GROUPED, "the packed B operand is the grouped tile's");
+  static_assert(PK != PK_MXFP4 || GROUPED, "the MXFP4 B operand is the grouped tile's");
+  static_assert(PK != PK_FP8 || !GROUPED, "the FP8 B operand is the plain tile's");
+  constexpr bool MX = PK == PK_MXFP4, F8 = PK == PK_FP8;
   using vec8 = typename ClmElem<E>::v8;
   constexpr int T = 64 * WGM * WGN, WTM = BM / WGM, WTN = BN / WGN, FM = WTM / 32, FN = WTN / 32, RS = T / 8;
   static_assert(WTN == 64, "the head epilogue reduces over 64-column wave slices");
   static_assert(BM * 8 == 4 * T && BN * 8 == 4 * T, "four 16-byte loads per operand and thread per k tile");
+  static_assert(RS % 32 == 0, "a thread's four pieces of B are whole scale rows of 32 apart");
   extern __shared__ __attribute__((aligned(16))) unsigned char clm_lds[];
   E* As = reinterpret_cast<E*>(clm_lds);
   E* Bs = As + 2 * BM * CPITCH;
@@ -164,6 +200,14 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
   const unsigned char* bs = static_cast<const unsigned char*>(g.b_scale);
   unsigned rq0, rq1, rq2, rq3, rs0, rs1, rs2, rs3;
 #define CLM_FETCH_MX(rq, rs, e) rq = *reinterpret_cast<const unsigned*>(bq + ((e) >> 1)); rs = bs[(e) >> 5];
+  // FP8: element e of B is byte e; the scales of the thread's first piece are row f8s, of piece i the row i * RS / 32 below
+  // it, nkb = K / b_block_k to a row; f8kb is the block column of the k tile being fetched, f8in that tile's place in it
+  const int nkb = F8 ? K / g.b_block_k : 0, f8tiles = F8 ? g.b_block_k / CK : 1;
+  const float* f8s = static_cast<const float*>(g.b_scale) + (long long)((n0 + (tid >> 3)) >> 5) * nkb;
+  int f8kb = 0, f8in = 0;
+  uint2 rf0, rf1, rf2, rf3;
+  float rc0, rc1, rc2, rc3;
+#define CLM_FETCH_F8(rf, rc, i, k0) rf = *reinterpret_cast<const uint2*>(bq + boff + (i) * rstep + (k0)); rc = f8s[(i) * (RS / 32) * nkb + f8kb];
   // an empty statement that keeps an unpacked piece where it was computed: without it the compiler moves the unpacking, whose
   // results only the stash reads, behind the k tile's last MFMA
 #define CLM_PIN(r) asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
@@ -173,6 +217,8 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
   if constexpr (MX) {                                                                                                   \
     CLM_FETCH_MX(rq0, rs0, boff + (k0)) CLM_FETCH_MX(rq1, rs1, boff + rstep + (k0))                                     \
     CLM_FETCH_MX(rq2, rs2, boff + 2 * rstep + (k0)) CLM_FETCH_MX(rq3, rs3, boff + 3 * rstep + (k0))                     \
+  } else if constexpr (F8) {                                                                                            \
+    CLM_FETCH_F8(rf0, rc0, 0, k0) CLM_FETCH_F8(rf1, rc1, 1, k0) CLM_FETCH_F8(rf2, rc2, 2, k0) CLM_FETCH_F8(rf3, rc3, 3, k0) \
   } else {                                                                                                              \
   rb0 = *reinterpret_cast<const uint4*>(bg + (k0)); rb1 = *reinterpret_cast<const uint4*>(bg + rstep + (k0));             \
   rb2 = *reinterpret_cast<const uint4*>(bg + 2 * rstep + (k0)); rb3 = *reinterpret_cast<const uint4*>(bg + 3 * rstep + (k0)); }
@@ -195,10 +241,17 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
     rb0 = mxfp4_unpack8<E>(rq0, rs0); rb1 = mxfp4_unpack8<E>(rq1, rs1);
     rb2 = mxfp4_unpack8<E>(rq2, rs2); rb3 = mxfp4_unpack8<E>(rq3, rs3);
   }
+  if constexpr (F8) {
+    rb0 = fp8_unpack8<E>(rf0, rc0); rb1 = fp8_unpack8<E>(rf1, rc1);
+    rb2 = fp8_unpack8<E>(rf2, rc2); rb3 = fp8_unpack8<E>(rf3, rc3);
+  }
   CLM_STASH(0)
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
+    if constexpr (F8) {   // the block column of tile kt + 1
+      if (++f8in == f8tiles) { f8in = 0; ++f8kb; }
+    }
     if (kt + 1 < nk) { CLM_FETCH((kt + 1) * CK) }
     const E* ap = As + cur * BM * CPITCH + (wm * WTM + li) * CPITCH + 8 * hh;
     const E* bp = Bs + cur * BN * CPITCH + (wn * WTN + li) * CPITCH + 8 * hh;
@@ -218,12 +271,18 @@ __device__ __forceinline__ void clm_gemm_tile(const ClmGemm& g) {
         if (kk == 32) { rb1 = mxfp4_unpack8<E>(rq1, rs1); CLM_PIN(rb1) }
         if (kk == 48) { rb2 = mxfp4_unpack8<E>(rq2, rs2); CLM_PIN(rb2) rb3 = mxfp4_unpack8<E>(rq3, rs3); CLM_PIN(rb3) }
       }
+      if constexpr (F8) {   // the same places
+        if (kk == 16) { rb0 = fp8_unpack8<E>(rf0, rc0); CLM_PIN(rb0) }
+        if (kk == 32) { rb1 = fp8_unpack8<E>(rf1, rc1); CLM_PIN(rb1) }
+        if (kk == 48) { rb2 = fp8_unpack8<E>(rf2, rc2); CLM_PIN(rb2) rb3 = fp8_unpack8<E>(rf3, rc3); CLM_PIN(rb3) }
+      }
     }
     if (kt + 1 < nk) { CLM_STASH(cur ^ 1) }
     __syncthreads();
   }
 #undef CLM_FETCH
 #undef CLM_FETCH_MX
+#undef CLM_FETCH_F8
 #undef CLM_PIN
 #undef CLM_STASH
   // epilogue: C/D layout of the 32x32 MFMAs: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
@@ -474,12 +533,19 @@ __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_grouped_kernel(ClmGem
 // the grouped tile over experts kept in MXFP4 (ClmGemm::b_scale)
 template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16>
 __global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_grouped_mx_kernel(ClmGemm g) {
-  clm_gemm_tile<BM, BN, WGM, WGN, EP, E, true, true>(g);
+  clm_gemm_tile<BM, BN, WGM, WGN, EP, E, true, PK_MXFP4>(g);
 }
 
-template <int BM, int BN, int WGM, int WGN, int EP, class E, bool GROUPED, bool MX = false>
+// the plain tile over a matrix kept in block-scaled FP8 (ClmGemm::b_scale, b_block_k)
+template <int BM, int BN, int WGM, int WGN, int EP, class E = _Float16>
+__global__ __launch_bounds__(64 * WGM * WGN) void clm_gemm_fp8_kernel(ClmGemm g) {
+  clm_gemm_tile<BM, BN, WGM, WGN, EP, E, false, PK_FP8>(g);
+}
+
+template <int BM, int BN, int WGM, int WGN, int EP, class E, bool GROUPED, int PK = PK_DENSE>
 constexpr auto clm_gemm_entry() {
-  if constexpr (MX) return &clm_gemm_grouped_mx_kernel<BM, BN, WGM, WGN, EP, E>;
+  if constexpr (PK == PK_MXFP4) return &clm_gemm_grouped_mx_kernel<BM, BN, WGM, WGN, EP, E>;
+  else if constexpr (PK == PK_FP8) return &clm_gemm_fp8_kernel<BM, BN, WGM, WGN, EP, E>;
   else if constexpr (GROUPED) return &clm_gemm_grouped_kernel<BM, BN, WGM, WGN, EP, E>;
   else return &clm_gemm_kernel<BM, BN, WGM, WGN, EP, E>;
 }
@@ -487,18 +553,18 @@ constexpr auto clm_gemm_entry() {
 constexpr size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * CPITCH * 2; }   // 2-byte elements
 
 // The launch of one GEMM on the tile the rule chose (ClmGemmTiles of clm_internal.h); GROUPED launches the grouped kernel on
-// the same grid (M is then the sorted rows S, a multiple of 256), MX the packed grouped one.
-template <int EP, class E = _Float16, bool GROUPED = false, bool MX = false>
+// the same grid (M is then the sorted rows S, a multiple of 256), PK the packed form of either.
+template <int EP, class E = _Float16, bool GROUPED = false, int PK = PK_DENSE>
 int clm_gemm_tiles(const ClmGemm& g, hipStream_t s, bool use256) {
   if (use256) {   // one 8-wave workgroup per CU
-    const auto kern = clm_gemm_entry<256, 256, 2, 4, EP, E, GROUPED, MX>();
+    const auto kern = clm_gemm_entry<256, 256, 2, 4, EP, E, GROUPED, PK>();
     const int m256 = (g.M + 255) / 256, n256 = (g.N + 255) / 256;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(256, 256));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(256, 256));
     hipLaunchKernelGGL(kern, dim3(m256 * n256), dim3(512), lds_bytes(256, 256), s, g);
   } else {
-    const auto kern = clm_gemm_entry<128, 128, 2, 2, EP, E, GROUPED, MX>();
+    const auto kern = clm_gemm_entry<128, 128, 2, 2, EP, E, GROUPED, PK>();
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(128, 128));
     B2T_REQUIRE(attr == hipSuccess, "b2t_clm_score_f16: %zu bytes of LDS refused", lds_bytes(128, 128));

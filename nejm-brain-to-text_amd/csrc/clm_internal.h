@@ -88,6 +88,9 @@ struct ClmGemm {
   float glu_limit;                          // EP_OSS_GLU: the clamp on gate (from above) and up (both sides), > 0
   // the packed grouped kernel only (clm_gemm_grouped_mx_kernel): B is MXFP4 nibbles, K / 2 bytes a row, low nibble first
   const void* b_scale;                      // E8M0 scale bytes, K / 32 a row, in the rows and strides of B
+  // the packed plain kernel only (clm_gemm_fp8_kernel): B is e4m3fn codes, K bytes a row, and b_scale fp32
+  // [round_up(N, 256) / 32][K / b_block_k], the scale of 32 stored rows by b_block_k columns
+  int b_block_k;                            // a multiple of 64 that divides K
 };
 
 // The tile rule (B2T_CLM_GEMM_256) lives in one definition, causal_lm.hip: it picks the tile and hands the launch to `tiles`,

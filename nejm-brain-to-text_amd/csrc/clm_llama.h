@@ -123,9 +123,11 @@ inline ClmLayout llama_layout(const b2t_clm_llama_t* m, long long rows, long lon
 // The forward over r.rows rows up to the per-row log-probs logp[Mh]; attn(layer, qkv, out) enqueues one layer's attention,
 // mlp(layer, x16, resid) one layer's MLP: resid += MLP(x16), x16 being E(RMSNorm(resid; norm2_w)) with its padding rows zero.
 // qkn is the per-layer q / k norm weights of a policy with qk_norm (checked by clm_qknorm_check), unused otherwise.
+// f8 (causal_lm_llama_fp8.hip, whose policy's GEMMs read B packed): the scales of the projections kept in FP8, the codes being
+// where the dense matrices are; null for every other caller.
 template <class P, class Attn, class Mlp>
 int llama_forward_mlp(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
-                      const b2t_clm_qknorm_t* qkn, Mlp&& mlp) {
+                      const b2t_clm_qknorm_t* qkn, Mlp&& mlp, const b2t_clm_llama_fp8_t* f8 = nullptr) {
   using E = typename P::E;
   const int d = m.d_model, Hq = m.n_heads, Hkv = m.n_kv_heads, hd = d / Hq, qw = (Hq + 2 * Hkv) * hd;
   const long long rows = r.rows;
@@ -142,10 +144,12 @@ int llama_forward_mlp(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout
     g.qscale = 1.0f / sqrtf((float)hd); g.qcols = Hq * hd;
     g.pos = r.d_pos; g.rope_cos = m.rope_cos; g.rope_sin = m.rope_sin; g.rope_cols = (Hq + Hkv) * hd; g.hd = hd;
     if constexpr (P::qk_norm) { g.qnorm_w = qkn[l].q_norm_w; g.knorm_w = qkn[l].k_norm_w; g.rms_eps = m.rms_eps; }
+    if (f8) { g.b_scale = f8->layers_host[l].qkv_s; g.b_block_k = f8->block_k; }
     if (int rc = P::gemm_rope(g, s)) return rc;
     if (int rc = attn(l, qkv, x16)) return rc;
     g = ClmGemm{};
     g.A = x16; g.B = w.o_w; g.M = (int)rows; g.N = d; g.K = d; g.resid = resid; g.ldo = d;
+    if (f8) { g.b_scale = f8->layers_host[l].o_s; g.b_block_k = f8->block_k; }
     if (int rc = P::gemm_resid(g, s)) return rc;
     if (int rc = P::rmsnorm(resid, nullptr, rows, W(w.norm2_w), m.rms_eps, x16, d, s)) return rc;
     if (int rc = mlp(l, x16, resid)) return rc;
@@ -158,7 +162,7 @@ int llama_forward_mlp(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout
 // The forward with the family's dense SwiGLU MLP: gate / up GEMM (EP_SWIGLU), down GEMM into the residual.
 template <class P, class Attn>
 int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L, char* base, Attn&& attn, hipStream_t s,
-                  const b2t_clm_qknorm_t* qkn = nullptr) {
+                  const b2t_clm_qknorm_t* qkn = nullptr, const b2t_clm_llama_fp8_t* f8 = nullptr) {
   using E = typename P::E;
   const int d = m.d_model, F = m.ffn_dim;
   E* hb = reinterpret_cast<E*>(base + L.hbuf);
@@ -166,12 +170,14 @@ int llama_forward(const b2t_clm_llama_t& m, const ClmRun& r, const ClmLayout& L,
     const b2t_clm_llama_layer_t& w = m.layers_host[l];
     ClmGemm g{};
     g.A = x16; g.B = w.gate_up_w; g.M = (int)r.rows; g.N = 2 * F; g.K = d; g.out16 = hb; g.ldo = F;
+    if (f8) { g.b_scale = f8->layers_host[l].gate_up_s; g.b_block_k = f8->block_k; }
     if (int rc = P::gemm_swiglu(g, s)) return rc;
     g = ClmGemm{};
     g.A = hb; g.B = w.down_w; g.M = (int)r.rows; g.N = d; g.K = F; g.resid = resid; g.ldo = d;
+    if (f8) { g.b_scale = f8->layers_host[l].down_s; g.b_block_k = f8->block_k; }
     return P::gemm_resid(g, s);
   };
-  return llama_forward_mlp<P>(m, r, L, base, attn, s, qkn, mlp);
+  return llama_forward_mlp<P>(m, r, L, base, attn, s, qkn, mlp, f8);
 }
 
 // What a family whose descriptor obeys the Llama rule hd = d_model / n_heads hands the bodies and the size rules beside layout

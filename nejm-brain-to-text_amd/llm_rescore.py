@@ -1105,11 +1105,16 @@ def llama_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=Non
     head_dim_perm like the q and k rows they scale; q / k / v biases are then refused.
     dtype=torch.bfloat16 (clm_dtype's spellings) makes the weights bf16 in the same layout: a bf16 checkpoint's values are
     kept exactly, an fp32 or fp16 one is rounded to nearest even."""
-    import torch
     wdt = clm_dtype(dtype)
     sd = dict(state)
+    return _llama_layout(sd, dims, inv_freq, wdt, reader(sd, wdt))
+
+
+def _llama_layout(sd: dict, dims: dict, inv_freq: np.ndarray, wdt, get) -> Dict[str, "object"]:
+    """llama_device_layout's body over the reader `get`: llama_fp8_device_layout hands it one that yields the packed matrices'
+    codes, which take the same row permutations and the same padding."""
+    import torch
     Hq, Hkv, hd = dims["n_heads"], dims["n_kv_heads"], dims["d_model"] // dims["n_heads"]
-    get = reader(sd, wdt)
     out = _trunk(sd, get, dims, inv_freq)
     dev = out["embed_tokens"].device
     qperm = torch.from_numpy(qkv_row_perm(Hq, Hkv, hd)).to(dev)
@@ -1232,6 +1237,237 @@ class LlamaScorer(_Scorer):
         if int(context_cache_tokens) > 0 and torch.device(device).type != "cuda":
             raise ValueError(f"LlamaScorer: the context cache (context_cache_tokens > 0) lives in GPU memory; device "
                              f"{torch.device(device)} has none")
+
+
+# ---- the fine-grained FP8 spelling of a Llama-family checkpoint (HF FineGrainedFP8Config; Qwen3-*-FP8) ---------------------
+LINEAR_WEIGHTS = ("dense", "fp8")   # build_scorer's linear_weights: expanded to the compute dtype, or kept as the checkpoint has them
+# the four GEMMs of a layer and the checkpoint's linears behind each: a group is wholly packed or wholly plain
+_FP8_GROUPS = (("qkv", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")), ("o", ("self_attn.o_proj",)),
+               ("gate_up", ("mlp.gate_proj", "mlp.up_proj")), ("down", ("mlp.down_proj",)))
+_FP8_FIELDS = tuple(g + t for g, _ in _FP8_GROUPS for t in ("_q", "_s"))   # b2t_clm_llama_fp8_layer_t
+FP8_ROWS = 32   # stored rows a scale row of the packed layout serves: the row permutations move rows in chunks of 32
+
+
+def fp8_block(cfg: dict) -> Optional[Tuple[int, int]]:
+    """The block [bn, bk] of a config.json whose quantization_config is the fine-grained FP8 spelling (quant_method "fp8", fmt
+    absent or "e4m3", weight_block_size [bn, bk]); None for a checkpoint without a quantization_config, and for gpt-oss's own
+    "mxfp4".  activation_scheme is ignored: this scorer quantises no activation.  Refused, by name and before any weight is
+    read: every other quant_method, every other fmt, FP8 without weight_block_size (per-tensor or per-channel), a block whose
+    rows are no multiple of 32 or whose columns no multiple of 64 (with the numbers), and FP8 for a model_type outside the
+    Llama row of FAMILIES."""
+    qc = cfg.get("quantization_config")
+    if not qc:
+        return None
+    qm, mt = qc.get("quant_method"), cfg.get("model_type")
+    if qm == "mxfp4" and mt == "gpt_oss":
+        return None
+    if qm != "fp8":
+        raise ValueError(f"quantization_config: quant_method {qm!r} is not supported ('fp8' with weight_block_size for "
+                         f"{', '.join(LLAMA_MODEL_TYPES)}; 'mxfp4' for gpt_oss)")
+    fmt = qc.get("fmt")
+    if fmt not in (None, "e4m3"):
+        raise ValueError(f"quantization_config: fmt {fmt!r} is not supported (e4m3 only)")
+    wbs = qc.get("weight_block_size")
+    if not isinstance(wbs, (list, tuple)) or len(wbs) != 2:
+        raise ValueError(f"quantization_config: weight_block_size {wbs!r} is not supported ([rows, columns]; per-tensor and "
+                         f"per-channel FP8 are not built)")
+    bn, bk = int(wbs[0]), int(wbs[1])
+    if bn < 1 or bk < 1 or bn % FP8_ROWS or bk % 64:
+        raise ValueError(f"quantization_config: weight_block_size [{bn}, {bk}] is not supported (rows a multiple of {FP8_ROWS}, the "
+                         f"grain of the stored row order; columns a multiple of 64, the GEMM's k tile)")
+    if mt not in LLAMA_MODEL_TYPES:
+        raise ValueError(f"quantization_config: FP8 checkpoints are read for {', '.join(LLAMA_MODEL_TYPES)} only, not model_type {mt!r}")
+    return bn, bk
+
+
+def fp8_dequant(q, s, bn: int, bk: int, name: str = "fp8"):
+    """fp32 [N][K] of e4m3fn codes q [N][K] (torch.float8_e4m3fn, or the same bytes as uint8) and fp32 scales s [N / bn][K / bk]:
+    f32(q[n][k]) * s[n / bn][k / bk], one fp32 multiplication (round to nearest even, subnormals kept) of the exactly widened
+    code -- HF's Fp8Dequantize rule.  The one host definition of the expansion: the caller casts the result."""
+    import torch
+    if q.dtype == torch.uint8:
+        q = q.view(torch.float8_e4m3fn)
+    if q.dtype != torch.float8_e4m3fn or q.dim() != 2:
+        raise ValueError(f"{name}: codes {q.dtype} {tuple(q.shape)} must be a float8_e4m3fn matrix")
+    N, K = q.shape
+    if N % bn or K % bk:
+        raise ValueError(f"{name}: shape {N} x {K} is not a multiple of the block [{bn}, {bk}]")
+    if tuple(s.shape) != (N // bn, K // bk):
+        raise ValueError(f"{name}: scales {tuple(s.shape)} do not go with codes {N} x {K} in blocks of [{bn}, {bk}] "
+                         f"(expected {(N // bn, K // bk)})")
+    return (q.float().reshape(N // bn, bn, K // bk, bk) * s.float()[:, None, :, None]).reshape(N, K)
+
+
+def _fp8_groups(sd: dict, n_layers: int) -> Tuple[bool, ...]:
+    """Which of a layer's four GEMMs (_FP8_GROUPS) the checkpoint holds packed: a linear is packed iff its weight_scale_inv is
+    there.  Refused by tensor name: a group with only some of its linears packed, and a layer that differs from layer 0."""
+    first = None
+    for i in range(n_layers):
+        p = f"model.layers.{i}."
+        flags = []
+        for _, names in _FP8_GROUPS:
+            has = [p + n + ".weight_scale_inv" in sd for n in names]
+            if any(has) and not all(has):
+                lack = p + names[has.index(False)] + ".weight_scale_inv"
+                raise ValueError(f"checkpoint lacks {lack} while {p + names[has.index(True)]} is packed: the linears of one GEMM "
+                                 f"({' | '.join(names)}) are all FP8 or all plain")
+            flags.append(all(has))
+        if first is None:
+            first = tuple(flags)
+        elif tuple(flags) != first:
+            g, on = [(ns[0], a) for (_, ns), a, b in zip(_FP8_GROUPS, flags, first) if a != b][0]
+            raise ValueError(f"{p}{g} is {'FP8' if on else 'plain'} and model.layers.0.{g} is not: the layers of one checkpoint "
+                             f"must agree")
+    return first or (False,) * len(_FP8_GROUPS)
+
+
+def _fp8_linear(sd: dict, name: str, bn: int, bk: int, wdt):
+    """The packed linear `name` (.weight float8_e4m3fn [N][K], .weight_scale_inv fp32 [N / bn][K / bk]) expanded and cast:
+    fp8_dequant(...).to(wdt).  Refused by tensor name: a weight that is not float8_e4m3fn, an N or K the block does not divide
+    (with the numbers), scales of another shape, a NaN code (0x7F, 0xFF), a scale that is not finite, and a value that is not
+    finite in wdt (448 s > 65504 in fp16)."""
+    import torch
+    q, s = sd[name + ".weight"].detach(), sd[name + ".weight_scale_inv"].detach()
+    if q.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{name}.weight is {q.dtype} beside a weight_scale_inv, expected torch.float8_e4m3fn")
+    if ((q.view(torch.uint8) & 0x7F) == 0x7F).any():
+        raise ValueError(f"{name}.weight: a NaN code (0x7F or 0xFF)")
+    if not torch.isfinite(s.float()).all():
+        raise ValueError(f"{name}.weight_scale_inv: a scale is not finite")
+    w = fp8_dequant(q, s, bn, bk, name + ".weight").to(wdt)
+    if not torch.isfinite(w).all():
+        raise ValueError(f"{name}.weight / weight_scale_inv: a value is not finite in {wdt}")
+    return w
+
+
+def _fp8_names(sd: dict, n_layers: int, groups: Tuple[bool, ...]) -> List[str]:
+    """The packed linears' names (without .weight), after refusing every other weight_scale_inv and every float8 tensor that
+    has none: embedding, head, norms and biases stay 16-bit, as they are published."""
+    import torch
+    names = [f"model.layers.{i}.{n}" for i in range(n_layers) for (_, ns), on in zip(_FP8_GROUPS, groups) if on for n in ns]
+    known = set(names)
+    for k, v in sd.items():
+        if k.endswith(".weight_scale_inv") and k[:-len(".weight_scale_inv")] not in known:
+            raise ValueError(f"{k}: only the layers' q / k / v / o / gate / up / down projections may be FP8 (a packed head or "
+                             f"embedding is not built)")
+        if getattr(v, "dtype", None) in (torch.float8_e4m3fn, torch.float8_e5m2) and not (k.endswith(".weight") and k[:-len(".weight")] in known):
+            raise ValueError(f"{k} is {v.dtype} without a weight_scale_inv beside it")
+    return names
+
+
+def fp8_dense_state(state: dict, dims: dict, block: Tuple[int, int], dtype=None) -> Dict[str, "object"]:
+    """The plain state dict of an FP8 one: every packed linear's .weight replaced by fp8_dequant(...).to(dtype) and its
+    .weight_scale_inv dropped, everything else as it is -- what llama_device_layout then reads as any other checkpoint."""
+    wdt = clm_dtype(dtype)
+    sd = dict(state)
+    for name in _fp8_names(sd, dims["n_layers"], _fp8_groups(sd, dims["n_layers"])):
+        sd[name + ".weight"] = _fp8_linear(sd, name, block[0], block[1], wdt)
+        del sd[name + ".weight_scale_inv"]
+    return sd
+
+
+def llama_fp8_device_layout(state: dict, dims: dict, inv_freq: np.ndarray, dtype=None, block: Tuple[int, int] = (128, 128)) -> Dict[str, "object"]:
+    """llama_device_layout for build_scorer(..., linear_weights="fp8"): every tensor but the four matrices of a layer is that
+    layout's, made by the same code, and in place of qkv_w / o_w / gate_up_w / down_w the layers have the checkpoint's FP8 form
+    as the kernels of csrc/causal_lm_llama_fp8.hip read it (b2t_clm_llama_fp8_layer_t), for a checkpoint in blocks of block =
+    [bn, bk] (fp8_block): <g>_q uint8 [rows padded to 256][K], the e4m3fn codes under the row permutation and the zero padding of
+    <g>_w, and <g>_s fp32 [rows padded / 32][K / bk], the scale of every 32 stored rows -- the checkpoint's block rows expanded to
+    that grain, which qkv_row_perm and gate_up_row_perm respect because they move rows in chunks of 32 and bn is a multiple
+    of 32.  Padding rows have code 0 and scale 0.  The bytes are permuted by row and padded, never expanded: one byte a weight
+    and 4 / (32 bk) for the scales, here and on the device.  fp8_dequant(q, s, 32, bk).to(dtype) of these arrays is the <g>_w of
+    llama_device_layout on fp8_dense_state(state) to the byte.
+    Every refusal of the dense reading (_fp8_groups, _fp8_linear) is made here too, with the same message; a checkpoint that
+    holds one of the four GEMMs plain is refused by that projection's name."""
+    import torch
+    wdt = clm_dtype(dtype)
+    sd = dict(state)
+    bn, bk = block
+    groups = _fp8_groups(sd, dims["n_layers"])
+    if not all(groups):
+        plain = [f"model.layers.0.{ns[0]}" for (_, ns), on in zip(_FP8_GROUPS, groups) if not on]
+        raise ValueError(f"linear_weights='fp8': the checkpoint lacks {plain[0]}.weight_scale_inv (the packed layout needs all four "
+                         f"GEMMs of a layer in FP8; use linear_weights='dense')")
+    names = _fp8_names(sd, dims["n_layers"], groups)
+    for n in names:
+        _fp8_linear(sd, n, bn, bk, wdt)   # the refusals alone, in the dense reading's order; the expansion is dropped
+    packed = {n + ".weight" for n in names}
+    plain = reader(sd, wdt)
+
+    def shaped(name, t, shape):
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t.contiguous()
+
+    def codes(name, shape, to=None):
+        return shaped(name, plain.raw(name).view(torch.uint8), shape) if name in packed else plain(name, shape, to)
+    codes.raw = plain.raw
+
+    def scales(name, shape, to=None):   # a packed matrix's scale per row: [N][K / bk]
+        if name not in packed:
+            return plain(name, shape, to)
+        return shaped(name, plain.raw(name + "_scale_inv").float().repeat_interleave(bn, 0), (shape[0], shape[1] // bk))
+    out = _llama_layout(sd, dims, inv_freq, wdt, codes)
+    Hq, Hkv, hd = dims["n_heads"], dims["n_kv_heads"], dims["d_model"] // dims["n_heads"]
+    dev = out["embed_tokens"].device
+    qperm = torch.from_numpy(qkv_row_perm(Hq, Hkv, hd)).to(dev)
+    gperm = torch.from_numpy(gate_up_row_perm(dims["ffn_dim"])).to(dev)
+    for i in range(dims["n_layers"]):
+        S = _layer(scales, f"model.layers.{i}.", dims, hd, qperm, gperm)
+        for g, _ in _FP8_GROUPS:
+            rows = S[g + "_w"]
+            s = rows[::FP8_ROWS].contiguous()
+            if not torch.equal(s.repeat_interleave(FP8_ROWS, 0), rows):
+                raise ValueError(f"layers.{i}.{g}: 32 consecutive stored rows do not share one scale (block rows {bn})")
+            out[f"layers.{i}.{g}_q"] = out.pop(f"layers.{i}.{g}_w")
+            out[f"layers.{i}.{g}_s"] = s
+    return out
+
+
+class Fp8LlamaScorer(LlamaScorer):
+    """A LlamaScorer that keeps the four projections of every layer in block-scaled FP8 on the device (build_scorer(...,
+    linear_weights="fp8"), for a Llama / Mistral / Qwen2 / Qwen3 checkpoint in the fine-grained FP8 spelling): `w` holds
+    llama_fp8_device_layout's layers.<i>.{qkv,o,gate_up,down}_q (uint8 codes) and _s (fp32 scales) and no qkv_w / o_w / gate_up_w /
+    down_w (the model descriptor's are NULL); the calls are b2t_clm_llama_fp8_score_f16 / _tree_f16 / _tree_cached_f16 / _bf16 /
+    _tree_bf16 (csrc/causal_lm_llama_fp8.hip) with the q / k norm array (Qwen3) or NULL and the b2t_clm_llama_fp8_t of those
+    tensors, which unpack in the tile GEMM.  Activations are never quantised.  Scores, token log-probs and last_stats are the
+    LlamaScorer's of the same checkpoint to the byte; workspace, context cache and their size functions are the same."""
+
+    _OWN_ARRAYS = tuple("." + f for f in _FP8_FIELDS)
+
+    def _describe(self, dims, arrays, dtype, context_cache_tokens):
+        import b2t_native as N
+        super()._describe(dims, arrays, dtype, context_cache_tokens)
+        n = dims["n_layers"]
+        if n > 0 and ("layers.0.qkv_q" not in arrays or "layers.0.qkv_w" in arrays):
+            raise KeyError("Fp8LlamaScorer: the arrays lack layers.<i>.qkv_q / qkv_s / ... / down_s or hold qkv_w beside them "
+                           "(llama_fp8_device_layout makes them)")
+        ks = {"qkv": dims["d_model"], "o": dims["d_model"], "gate_up": dims["d_model"], "down": dims["ffn_dim"]}
+        bks = {K // arrays[f"layers.0.{g}_s"].shape[1] for g, K in ks.items()} if n > 0 else {128}
+        if len(bks) != 1:
+            raise ValueError(f"Fp8LlamaScorer: the scale arrays disagree on the block's columns ({sorted(bks)})")
+        self.block_k = bks.pop()
+        self._fp8_layers = (N.ClmLlamaFp8Layer * max(1, n))()
+        self._fp8 = N.ClmLlamaFp8(self.block_k, self._fp8_layers)
+        qkn = self._qk[0] if self._qk else None   # Qwen3's array, or NULL
+        self._family, self._qk = "llama_fp8", (qkn, self._fp8)
+
+    def _point(self, arrays):
+        import torch
+        super()._point(arrays)
+        for k, v in arrays.items():
+            if k.endswith(self._OWN_ARRAYS):
+                want = torch.uint8 if k.endswith("_q") else torch.float32
+                if v.dtype != want:
+                    raise ValueError(f"Fp8LlamaScorer: {k} is {v.dtype}, expected {want}")
+                self.w[k] = v.to(self.device).contiguous()
+        for i in range(self.dims["n_layers"]):
+            for f in _FP8_FIELDS:
+                setattr(self._fp8_layers[i], f, self.w[f"layers.{i}.{f}"].data_ptr())
+
+    def weight_bytes(self) -> int:
+        """bytes of the packed projections held: per layer the sum over the four GEMMs of rows_padded K + 4 (rows_padded / 32)
+        (K / block_k)"""
+        return sum(v.numel() * v.element_size() for k, v in self.w.items() if k.endswith(self._OWN_ARRAYS))
 
 
 # ---- OLMo-2 (HF Olmo2ForCausalLM): whole-row q / k norms and a post-norm layer ---------------------------------------------
@@ -2017,11 +2253,24 @@ _FAMILY_ROWS = (
 FAMILIES = {mt: fam for fam in _FAMILY_ROWS for mt in fam.model_types}   # by config.json's model_type
 
 
-def _family_for(fam: Family, expert_weights: str) -> Family:
-    """The family's row for build_scorer's expert_weights: itself for "dense"; for "mxfp4" gpt-oss with the packed layout and
-    scorer, any other family refused.  Reads no weight."""
+def _family_for(fam: Family, expert_weights: str, linear_weights: str = "dense", cfg: Optional[dict] = None) -> Family:
+    """The family's row for build_scorer's expert_weights and linear_weights: itself for "dense"; for "mxfp4" gpt-oss with the
+    packed layout and scorer, any other family refused; for "fp8" the Llama row with the packed layout and scorer, any other
+    family and a checkpoint whose config.json (cfg) has no FP8 quantization_config refused.  Reads no weight."""
     if expert_weights not in EXPERT_WEIGHTS:
         raise ValueError(f"expert_weights {expert_weights!r} is not one of {EXPERT_WEIGHTS}")
+    if linear_weights not in LINEAR_WEIGHTS:
+        raise ValueError(f"linear_weights {linear_weights!r} is not one of {LINEAR_WEIGHTS}")
+    if linear_weights == "fp8":
+        if fam.scorer is not LlamaScorer:
+            raise ValueError(f"linear_weights='fp8' is for {', '.join(LLAMA_MODEL_TYPES)} checkpoints in the fine-grained FP8 "
+                             f"spelling; model_type {fam.model_types[0]!r} has no packed form")
+        if expert_weights != "dense":
+            raise ValueError(f"expert_weights={expert_weights!r} with linear_weights='fp8': model_type {fam.model_types[0]!r} has no experts")
+        if fp8_block(cfg or {}) is None:
+            raise ValueError("linear_weights='fp8': the checkpoint's config.json has no FP8 quantization_config (quantising a plain "
+                             "checkpoint is not built: use linear_weights='dense')")
+        return fam._replace(layout=llama_fp8_device_layout, scorer=Fp8LlamaScorer)
     if expert_weights == "dense":
         return fam
     if fam.scorer is not GptOssScorer:
@@ -2038,11 +2287,17 @@ def _load_arrays(fam: Family, model_dir: str, max_positions: Optional[int] = Non
         return dims, fam.layout(_load_state_dict(model_dir), dims, *([fam.rope(cfg)] if fam.rope else []))
     dims = fam.dims(cfg, max_positions)
     wdt = fam.dtype(dtype, cfg)
-    return dims, fam.layout(_load_state_dict(model_dir), dims, fam.rope(cfg), wdt)
+    block = fp8_block(cfg)   # the fine-grained FP8 spelling: kept packed, or expanded into the plain spelling first
+    if fam.layout is llama_fp8_device_layout:
+        return dims, fam.layout(_load_state_dict(model_dir), dims, fam.rope(cfg), wdt, block)
+    sd = _load_state_dict(model_dir)
+    if block is not None:
+        sd = fp8_dense_state(sd, dims, block, wdt)
+    return dims, fam.layout(sd, dims, fam.rope(cfg), wdt)
 
 
 def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_cache_tokens=0, max_positions=None, *,
-                 expert_weights="dense", dtype=None):
+                 linear_weights="dense", expert_weights="dense", dtype=None):
     """The scorer of the checkpoint in model_dir by config.json's model_type: the row of FAMILIES that serves it (the one
     list of the supported families: OPT, GPT-2, GPT-NeoX / Pythia, Llama / Mistral / Qwen2 / Qwen3, OLMo-2, Mixtral, Gemma-2,
     Phi-3 / Phi-4, gpt-oss, each with its scorer class).  Anything else ("olmo", "olmo3", "gemma", "gemma3", "qwen3_moe", "phi",
@@ -2055,14 +2310,25 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
     expert_weights (by keyword, like dtype behind it): "dense" (the default) expands a gpt-oss checkpoint's MXFP4 experts to the compute dtype, four times their
     published size; "mxfp4" keeps them packed in host and device memory and unpacks them in the grouped GEMM (GptOssMxScorer:
     the same scores to the byte).  "mxfp4" for another family, or for a gpt-oss checkpoint in the plain spelling (by the name of
-    the _blocks tensor it lacks), is refused before any weight is expanded."""
+    the _blocks tensor it lacks), is refused before any weight is expanded.
+    A Llama / Mistral / Qwen2 / Qwen3 checkpoint in the fine-grained FP8 spelling (config.json's quantization_config with
+    quant_method "fp8", fmt "e4m3" or none, weight_block_size [bn, bk], bn a multiple of 32 and bk of 64; every quantised linear
+    a float8_e4m3fn weight beside an fp32 weight_scale_inv; activation_scheme is ignored, for this scorer quantises no
+    activation) is read by fp8_block / fp8_dequant.  linear_weights (by keyword): "dense" (the default) expands it into the
+    compute dtype, dequantise then cast as HF does, into the layout of any other checkpoint; "fp8" keeps the four projections
+    of every layer packed in host and device memory, one byte a weight plus the scales, and unpacks them in the tile GEMM
+    (Fp8LlamaScorer: the same scores to the byte, weight_bytes() the bytes held).  Every other quant_method or fmt, a block the
+    kernels cannot follow, "fp8" for another family or for a checkpoint without the FP8 quantization_config, and "fp8" with
+    bfloat16 and a context cache are refused before any weight is read; a NaN code, a scale or a value that is not finite in the
+    compute dtype, a shape the block does not divide and a half-packed GEMM are refused by the tensor's name."""
     cfg = load_config(model_dir)
     mt = cfg.get("model_type", "opt")
     fam = FAMILIES.get(mt)
     if fam is None:
         raise ValueError(f"model_type {mt!r} is not supported (opt, gpt2, gpt_neox, {', '.join(LLAMA_MODEL_TYPES)}, gemma2, phi3, "
                          f"gpt_oss, olmo2, mixtral)")
-    fam = _family_for(fam, expert_weights)
+    fp8_block(cfg)   # refuses the quantization_configs that nothing here reads
+    fam = _family_for(fam, expert_weights, linear_weights, cfg)
     # every refusal that needs no weight, before the weights are read
     if not fam.scorer._CONTEXT_CACHE:
         gptoss_check_cache(context_cache_tokens)
@@ -2075,16 +2341,17 @@ def build_scorer(model_dir: str, device="cuda", share_prefixes=False, context_ca
 
 
 def build_opt(model_name="facebook/opt-6.7b", cache_dir=None, device="cuda", share_prefixes=False, context_cache_tokens=0,
-              max_positions=None, *, expert_weights="dense", dtype=None):
+              max_positions=None, *, linear_weights="dense", expert_weights="dense", dtype=None):
     """(scorer, tokenizer) from a local checkpoint; weights converted once into the device layout (fp16, or bf16 for a
     LlamaScorer's checkpoint with dtype="bfloat16" or, saved in bfloat16, dtype="auto").  The scorer is build_scorer's: its
     docstring lists the families.
     share_prefixes=True makes the scorer compute each distinct candidate prefix (the decoding context included) once;
     context_cache_tokens > 0 also keeps the context's keys / values / log-probs across calls (either scorer; GPU memory).
-    expert_weights="mxfp4" keeps a gpt-oss checkpoint's experts packed (build_scorer)."""
+    expert_weights="mxfp4" keeps a gpt-oss checkpoint's experts packed, linear_weights="fp8" the projections of a Llama-family
+    checkpoint in the fine-grained FP8 spelling (build_scorer)."""
     model_dir = resolve_model_dir(model_name, cache_dir)
     scorer = build_scorer(model_dir, device, share_prefixes, context_cache_tokens, max_positions, expert_weights=expert_weights,
-                          dtype=dtype)
+                          linear_weights=linear_weights, dtype=dtype)
     from transformers import AutoTokenizer
     tok = AutoTokenizer.from_pretrained(model_dir, local_files_only=True)
     tok.padding_side = "right"

@@ -86,6 +86,15 @@ much of the grouped GEMMs is padding.  `--experts mxfp4` makes the experts an MX
 them packed (b2t_clm_gptoss_mx_score_bf16 / _tree_bf16), alternating with the dense scorer of the same checkpoint.
 
   python tools/bench_llm_rescore.py --arch gptoss --lists 5 --cands 5|20|100 [--list nbest --context 64] [--experts mxfp4]
+
+`--arch llama|qwen3 --weights fp8` measures what keeping the projections packed costs: one synthetic checkpoint in the fine-grained
+FP8 spelling (weight_block_size [128, 128]; random non-NaN e4m3 codes, scales spread over three octaves) at the chosen shape,
+through the dense scorer (the checkpoint expanded into --dtype) and through the Fp8LlamaScorer that unpacks in the tile GEMM
+(linear_weights="fp8"), flat and tree of each alternating list by list under the protocol of --arch olmo2.  The line has both
+scorers' times, their ratio per list, whether the packed scores were the dense scorer's bytes, and the bytes of the four
+projections in either form (weight_bytes).  No HF model is built.
+
+  python tools/bench_llm_rescore.py --arch llama|qwen3 --weights fp8 --layers 8 --lists 5 --cands 5|20|100 [--dtype bfloat16]
 """
 import argparse
 import json
@@ -139,6 +148,9 @@ def main():
     ap.add_argument("--experts", choices=("dense", "mxfp4"), default="dense",
                     help="--arch gptoss: mxfp4 makes the experts an MXFP4 checkpoint's and runs the scorer that keeps them packed "
                          "(expert_weights='mxfp4') beside the dense scorer of the same checkpoint")
+    ap.add_argument("--weights", choices=("dense", "fp8"), default="dense",
+                    help="--arch llama / qwen3: fp8 makes the checkpoint a fine-grained FP8 one and runs the scorer that keeps its "
+                         "projections packed (linear_weights='fp8') beside the dense scorer of the same checkpoint")
     ap.add_argument("--cands", type=int, default=100)
     ap.add_argument("--lists", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -181,6 +193,10 @@ def main():
         return main_olmo2(a)
     if a.arch == "gpt2":
         return main_gpt2(a)
+    if a.weights == "fp8":
+        if a.arch not in ("llama", "qwen3") or a.session:
+            ap.error("--weights fp8 needs --arch llama or qwen3 and has no --session")
+        return main_fp8(a)
     if a.arch != "opt":
         return main_llama(a)
     import torch
@@ -307,6 +323,58 @@ def main_llama(a):
     hd = d // H
     flop_tok = 2 * (L * (d * (H + 2 * Hkv) * hd + d * d + 3 * d * ffn) + d * V)
     return against_hf(a, sc, model, calls, rng, flop_tok, {"kv_heads": Hkv})
+
+
+def main_fp8(a, block=(128, 128)):
+    """--arch llama / qwen3 --weights fp8: a checkpoint in the fine-grained FP8 spelling at the chosen shape -- every linear of
+    every layer uniform random non-NaN e4m3 codes with one scale 2^U(-14.5, -11.5) a block, which gives weights of about the
+    usual 1 / sqrt(K) spread at K = 4096; embedding, head and norms random in --dtype -- through the dense LlamaScorer of its
+    expansion and the Fp8LlamaScorer of its bytes, under the protocol of --arch olmo2."""
+    import torch
+    import llm_rescore as R
+    torch.manual_seed(0)
+    dt = R.clm_dtype(a.dtype)
+    d, H, Hkv, ffn, V, L = a.d, a.heads, a.kv_heads, a.ffn, a.vocab, a.layers
+    hd, dev, (bn, bk) = d // H, "cuda", block
+    rng = np.random.default_rng(0)
+    cfg = dict(model_type=a.arch, hidden_size=d, num_attention_heads=H, num_key_value_heads=Hkv, intermediate_size=ffn, vocab_size=V,
+               num_hidden_layers=L, max_position_embeddings=2048, rms_norm_eps=1e-6, tie_word_embeddings=False, rope_theta=1000000.0,
+               quantization_config={"quant_method": "fp8", "fmt": "e4m3", "weight_block_size": list(block), "activation_scheme": "dynamic"})
+    assert R.fp8_block(cfg) == block
+    rn = lambda *s, std: (torch.randn(*s, device=dev) * std).to(dt)
+    nw = lambda n: (1 + 0.2 * torch.randn(n, device=dev)).to(dt)
+    ok = torch.tensor([c for c in range(256) if c & 0x7F != 0x7F], dtype=torch.uint8, device=dev)
+    st = {"model.embed_tokens.weight": rn(V, d, std=2.0 / d ** 0.5), "lm_head.weight": rn(V, d, std=2.0 / d ** 0.5), "model.norm.weight": nw(d)}
+    for l in range(L):
+        p = f"model.layers.{l}."
+        st[p + "input_layernorm.weight"], st[p + "post_attention_layernorm.weight"] = nw(d), nw(d)
+        if a.arch == "qwen3":
+            st[p + "self_attn.q_norm.weight"], st[p + "self_attn.k_norm.weight"] = nw(hd), nw(hd)
+        for n, (o, i) in {"self_attn.q_proj": (H * hd, d), "self_attn.k_proj": (Hkv * hd, d), "self_attn.v_proj": (Hkv * hd, d),
+                          "self_attn.o_proj": (d, H * hd), "mlp.gate_proj": (ffn, d), "mlp.up_proj": (ffn, d), "mlp.down_proj": (d, ffn)}.items():
+            st[p + n + ".weight"] = ok[torch.randint(0, 254, (o, i), device=dev)].view(torch.float8_e4m3fn)
+            st[p + n + ".weight_scale_inv"] = torch.exp2(-14.5 + 3 * torch.rand(o // bn, i // bk, device=dev))
+    dims, inv = R.llama_dims(cfg), R.rope_inv_freq(cfg)
+    scs = {"dense": R.LlamaScorer(dims, R.llama_device_layout(R.fp8_dense_state(st, dims, block, dt), dims, inv, dtype=dt), dev, dtype=dt),
+           "fp8": R.Fp8LlamaScorer(dims, R.llama_fp8_device_layout(st, dims, inv, dt, block), dev, dtype=dt)}
+    del st
+    torch.cuda.empty_cache()
+    dense_bytes = sum(v.numel() * v.element_size() for k, v in scs["dense"].w.items() if k.endswith(("qkv_w", "o_w", "gate_up_w", "down_w")))
+    lists, ntok, nodes, same, per, stat = alternate(a, rng, V, scs, ("dense", "fp8"))
+    ratio = lambda t: [round(o / l, 4) for o, l in zip(per["fp8", t], per["dense", t])]
+    with torch.inference_mode():
+        equal = all(scs["fp8"].score(l, share_prefixes=t).tobytes() == scs["dense"].score(l, share_prefixes=t).tobytes()
+                    for l in lists for t in (False, True))
+        finite = bool(np.isfinite(scs["dense"].score(lists[0])).all())
+    print(json.dumps({"bench": "llm_rescore_fp8", "arch": a.arch, "dtype": a.dtype, "layers": L, "d": d, "heads": H, "kv_heads": Hkv,
+                      "ffn": ffn, "vocab": V, "block": list(block), "cands": a.cands, "list": a.list, "context": a.context,
+                      "lists": len(lists), "reps": max(1, a.reps), "tokens": float(np.mean(ntok)), "nodes": float(np.mean(nodes)),
+                      "dense_flat_ms": stat(("dense", False)), "fp8_flat_ms": stat(("fp8", False)),
+                      "dense_tree_ms": stat(("dense", True)), "fp8_tree_ms": stat(("fp8", True)),
+                      "fp8_over_dense_flat": {"median": round(float(np.median(ratio(False))), 4), "per_list": ratio(False)},
+                      "fp8_over_dense_tree": {"median": round(float(np.median(ratio(True))), 4), "per_list": ratio(True)},
+                      "flat_tree_bit_identical": bool(same), "fp8_scores_are_dense_bytes": bool(equal), "scores_finite": finite,
+                      "dense_weight_bytes": dense_bytes, "fp8_weight_bytes": scs["fp8"].weight_bytes()}))
 
 
 def main_gpt2(a):
